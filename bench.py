@@ -25,6 +25,11 @@ extra `pcie_inclusive_traj_per_s`).  Rank 0 prints ONE JSON line.
 solve.  Named extras in the same line: `overlapped_traj_per_s` (consecutive batches on two handles/streams, the
 steady-state serving rate), `pcie_inclusive_traj_per_s`, `yield` (converged / problems) and, for N > 1,
 `gather_ms_per_step` (host-side time of the final gather inside a step).
+
+A plain run sets up, warms up, times the steps and prints the line; `roofline` then prices this run's kernel time with the
+committed counter summaries under profiles/.  `--full` adds everything that takes runs of its own: the CPU baseline, the
+PCIe-inclusive and overlapped extras, the live rocprofv3 --pmc passes and, for config 2, the other configs (`other_configs`).
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs) for output-by-output comparison of two builds.
 """
 import argparse
 import json
@@ -73,6 +78,25 @@ def workload(P, g, cfg, B, first):
     if cfg == 4:
         return model, bx, sp, P.astrobee_se3_batch(B, first)
     return model, bx, sp, P.astrobee_manifold_batch(B, first)
+
+
+DUMP_BYTES = 64 * 10**6
+
+
+def dump_outputs(d, solver, st):
+    """What a caller of the timed path receives from its last step -- X [B,N,n], U [B,N,m] (gusto_get_traj) and the
+    per-problem status (gusto_get_status) -- as float64 DIR/<name>.npy.  Above DUMP_BYTES in all, a fixed seeded sample of
+    the problems; problem_index.npy names the rows written either way."""
+    X, U = solver.traj()
+    arrays = dict(X=X, U=U, **st)
+    B = X.shape[0]
+    per_problem = 8 * (sum(a[0].size for a in arrays.values()) + 1)
+    k = min(B, (DUMP_BYTES - 4096) // per_problem)      # (4096: the .npy headers)
+    idx = np.arange(B) if k == B else np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+    arrays["problem_index"] = np.arange(B)
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a[idx], dtype=np.float64))
 
 
 def usable_cores():
@@ -368,13 +392,18 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"),
                     help="weak: every rank its own batch; strong: the config's batch split over the ranks")
     ap.add_argument("--batch", type=int, default=0, help="override the config's batch size")
+    ap.add_argument("--full", action="store_true", help="also the measurements beyond the headline: CPU baseline, PCIe-inclusive and "
+                    "overlapped extras, live rocprofv3 --pmc passes, the other configs (the --no-* options below trim a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's trajectories "
+                    "and status as DIR/<name>.npy (float64; N > 1 ranks: rank 0's shard)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="0 = the config's sample per usable host core (10-30 s)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the in-process lines of configs 3 / 4 / 5 (other_configs)")
     ap.add_argument("--no-live-traffic", action="store_true", help="skip the two child rocprofv3 --pmc passes (roofline.traffic then "
                     "comes from the committed summary under profiles/)")
     ap.add_argument("--no-extras", action="store_true", help="skip the PCIe-inclusive and overlapped extras (profiling runs: "
-                    "every launch of the kernel is then one serial step, so rocprofv3's average is the step's)")
+                    "every launch of the kernel is then one serial step, so rocprofv3's average is the step's); a run without "
+                    "--full skips them too")
     ap.add_argument("--overlap", type=int, default=1,
                     help="batches in flight: consecutive steps alternate between this many handles/streams, so the "
                          "slowest problems of one batch overlap the start of the next (1 = strictly serial steps)")
@@ -384,6 +413,7 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
                     help="torch.distributed backend of a multi-rank run (nccl = RCCL; gloo: ranks sharing one GPU in tests)")
     args = ap.parse_args()
+    extras = args.full and not args.no_extras
     cfg = CONFIGS[args.config]
     trajopt = args.algo == "trajopt"
     if trajopt:
@@ -509,6 +539,8 @@ def main():
     solver = solvers[(args.steps - 1) % D]
 
     st = solver.status()
+    if args.dump_outputs and rank == 0:     # before the extras below re-solve on this handle
+        dump_outputs(args.dump_outputs, solver, st)
     n_conv, n_succ = int(st["converged"].sum()), int(st["successful"].sum())
     scp_iters, ipm_iters = int(st["iterations"].sum()), int(st["ipm_iters"].sum())
     tot = torch.tensor([float(n_conv), float(n_succ), float(scp_iters), float(ipm_iters), float(B)], device=cdev,
@@ -523,7 +555,7 @@ def main():
     # named extras, outside the timed region, rank 0's GPU only:
     # (a) SURVEY.md 8(d): host buffers in, trajectories out (H2D + solve + D2H), median of 5
     pcie = []
-    for _ in range(0 if args.no_extras else 5):
+    for _ in range(5 if extras else 0):
         t1 = time.perf_counter()
         solver.set_problems(x0, glo, ghi, tf)
         solver.solve(TO_MAX if trajopt else MAX_ITER)
@@ -532,7 +564,7 @@ def main():
     pcie_s = float(np.median(pcie)) if pcie else float("nan")
     # (b) two batches in flight on two handles/streams (the tail of one batch overlaps the head of the next)
     overlapped = None
-    if D == 1 and dist is None and not args.no_extras and not trajopt:
+    if D == 1 and dist is None and extras and not trajopt:
         s2 = [solver, mk()]
         K2 = 12
         for i in range(2):
@@ -562,7 +594,7 @@ def main():
         b_kkt, b_lin = algorithmic_bytes(n, m + (n if trajopt else 0), N_KNOTS)   # (TrajOpt: the n defect variables of a knot are controls)
         alg_bytes = b_kkt * ipm_iters + b_lin * scp_iters      # this rank, one launch
         achieved = alg_bytes / (avg_ms * 1e-3) / 1e9
-        # HBM traffic of one solve.  PMC counters need their own rocprofv3 --pmc passes: the default single-GPU run makes
+        # HBM traffic of one solve.  PMC counters need their own rocprofv3 --pmc passes: a single-GPU --full run makes
         # them itself after the timed region (two child passes of tools/pmc_probe.py on the same seeded batch: live_pmc);
         # otherwise, or if that fails, the figure is read from the latest committed summary of the same workload
         traffic, traffic_src, valu_flops, traffic_live = None, None, None, None
@@ -576,7 +608,7 @@ def main():
             pmc_t, src_t = committed_pmc("trajopt")
             if pmc_t:
                 traffic, traffic_src = pmc_t.get("traffic_bytes_per_launch"), src_t + " (separate rocprofv3 --pmc passes, not this run)"
-        if (full_batch or (trajopt and args.config == 2 and B == 1024)) and dist is None and not args.no_extras and not args.no_live_traffic:
+        if (full_batch or (trajopt and args.config == 2 and B == 1024)) and dist is None and extras and not args.no_live_traffic:
             traffic_live = live_pmc(args.config, algo="trajopt" if trajopt else "gusto")
             if traffic_live:
                 traffic_live["committed_traffic_bytes_per_launch"] = traffic
@@ -584,7 +616,7 @@ def main():
                 traffic_src = ("live: two child rocprofv3 --pmc passes (FETCH_SIZE x 2, WRITE_SIZE; KiB) of tools/pmc_probe.py in this run, "
                                "one launch of the same seeded batch")
         others = None
-        if args.config == 2 and not args.batch and dist is None and not args.no_extras and not trajopt and not args.no_other_configs:
+        if args.config == 2 and not args.batch and dist is None and extras and not trajopt and not args.no_other_configs:
             try:
                 others = other_configs(P, g, torch, dev_ord, live=not args.no_live_traffic)
             except Exception as e:      # the headline line must come out whatever happens to the side measurements
@@ -633,10 +665,10 @@ def main():
             "solve + get_traj (host), median of 5, one GPU", "overlapped_traj_per_s": overlapped,
             "gathered_problems_per_step": gathered[0] if dist is not None else None, "gather_error": gather_err[0],
             "gather_ms_per_step": (1e3 * gather_total / args.steps) if dist is not None else None,
-            # BASELINE.json configs 3 / 4 / 5 in the same run (3 serial steps each, after the timed region)
+            # BASELINE.json configs 3 / 4 / 5 in the same --full run (3 serial steps each, after the timed region)
             "other_configs": others,
         }
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             threads = usable_cores()
             n_sample = args.cpu_sample or (({2: 768, 4: 16}[args.config]) if trajopt else cfg["cpu_per_core"] * max(2, threads))
             out["cpu_baseline"] = cpu_baseline(P, g, args.config, n_sample, threads, B, args.algo)

@@ -7,12 +7,12 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err
-timeout 300 python bench.py --overlap 2 --steps 60 --no-cpu-baseline > $OUT/bench_overlap2.json 2>> $OUT/bench.err
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+timeout 300 python bench.py --full --overlap 2 --steps 60 --no-cpu-baseline > $OUT/bench_overlap2.json 2>> $OUT/bench.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python bench.py --steps 20 --no-cpu-baseline --no-extras > $OUT/stats.log 2>&1
 : > $OUT/configs.jsonl
 for c in 2 3 4 5; do   # every BASELINE config through the contract harness itself
-  timeout 900 python bench.py --config $c --steps 8 --warmup 2 --no-extras >> $OUT/configs.jsonl 2>> $OUT/bench.err
+  timeout 900 python bench.py --full --config $c --steps 8 --warmup 2 --no-extras >> $OUT/configs.jsonl 2>> $OUT/bench.err
 done
 for c in 4 5; do   # kernel stats of BASELINE configs 4 and 5 (astrobeeSE3 B=8192, manifold B=2048)
   m=$((c - 2))
@@ -34,7 +34,7 @@ for w in "3 gusto" "4 gusto" "5 gusto" "2 trajopt"; do
 done
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c3 -o stats -- python bench.py --config 3 --steps 4 --warmup 1 --no-extras --no-cpu-baseline > $OUT/stats_c3.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_trajopt -o stats -- python bench.py --algo trajopt --steps 6 --warmup 1 --no-extras --no-cpu-baseline > $OUT/stats_trajopt.log 2>&1
-timeout 600 python bench.py --algo trajopt > $OUT/bench_trajopt.json 2>> $OUT/bench.err
+timeout 600 python bench.py --full --algo trajopt > $OUT/bench_trajopt.json 2>> $OUT/bench.err
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" \
            "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" \
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA" \
