@@ -1,16 +1,18 @@
-"""Independent numpy restatement of the convex subproblem of ONE GuSTO trip for dubins_car, astrobeeSE3 and
-astrobeeSE3manifold, written straight from the reference's model files -- NOT through the oracle's row list:
+"""Independent numpy restatement of the convex subproblem of ONE GuSTO trip for all four models, written straight from
+the reference's model files -- NOT through the oracle's row list:
 
-  dynamics f            dubins_car.jl:161-165, astrobee_se3.jl:180-190 (+ quat_functions.jl:253-257),
+  dynamics f            freeflyer_se2.jl:182-206, dubins_car.jl:161-165, astrobee_se3.jl:180-190 (+ quat_functions.jl:253-257),
                         astrobee_se3_manifold.jl:231-246
   Jacobians A, B        complex-step derivatives of f (no hand-written Jacobian table is shared with the oracle)
   trapezoid rows        dubins_car.jl:134-146, astrobee_se3_manifold.jl:169-195
-  constraint registry   dubins_car.jl:184-226, astrobee_se3.jl:322-379, astrobee_se3_manifold.jl:533-608
+  constraint registry   freeflyer_se2.jl:338-390, dubins_car.jl:184-226, astrobee_se3.jl:322-379, astrobee_se3_manifold.jl:533-608
   row functions         dynamics.jl:56-81, astrobee_se3.jl:244-263,282-305,308-311, astrobee_se3_manifold.jl:308-340,481-504
   penalisation          scp_gusto.jl:253-314 (incl. the +-eps pair of the convex_state_eq category, :297-311)
-  signed distance       sphere vs AABB / sphere vs sphere in 3-D (stands in for BulletCollision.distance)
+  signed distance       sphere vs AABB / sphere vs sphere in 3-D, disc vs AABB / disc in the plane for the freeflyer
+                        (stands in for BulletCollision.distance)
 
-The subproblem is handed to scipy SLSQP in its full slack form (variables X, U and one slack per penalised row)."""
+subproblem_rows states the rows; solve_subproblem hands them to scipy SLSQP in the full slack form (variables X, U and one
+slack per penalised row); np_kkt.certify checks a candidate point against them."""
 import numpy as np
 import scipy.optimize as so
 
@@ -73,6 +75,24 @@ class AstrobeeSE3Manifold(Astrobee):
         return np.concatenate([v, F / Astrobee.mass, qd, wd])
 
 
+class FreeflyerSE2:
+    """freeflyer_se2.jl:15-21,160-214 with robot/freeflyer.jl:28-62; state (r, theta, v, omega), control (F, M).  Its registry
+    (freeflyer_se2.jl:338-390) has the penalised velocity rows, the trust region and the BODY obstacle rows (a disc of radius r
+    against the keep-out components in the plane); the arm component (freeflyer.jl:55-57) enters trust_region_ratio_gusto only --
+    ncsi_arm_obstacle_avoidance_constraints_convexified is written but not registered."""
+    n, m = 6, 3
+    mass, J = 0.5 * (15.36 + 18.08), 0.184
+    r, clearance = 0.157, 0.05
+    v_max, w_max = 0.2, 20 * PI / 180
+    a_max, al_max = 2 * 0.185 / (0.5 * (15.36 + 18.08)), 0.593 / (0.184 / 6.43)
+    Delta0, eps = 3.0, 1e-2
+    has_tr = True
+
+    @staticmethod
+    def f(x, u):
+        return np.concatenate([x[3:6], u[0:2] / FreeflyerSE2.mass, u[2:3] / FreeflyerSE2.J])
+
+
 def jac(model, x, u):
     """complex-step Jacobians of f"""
     n, m, h = model.n, model.m, 1e-30
@@ -86,35 +106,49 @@ def jac(model, x, u):
     return A, B
 
 
-# ---- signed distance of a sphere of radius r centred at c (3-D) -----------------------------------------------------
+# ---- signed distance of a sphere (a disc in 2-D) of radius r centred at c ---------------------------------------------
 def sd_box(c, lo, hi, r):
+    d = len(c)
+    lo, hi = np.asarray(lo)[:d], np.asarray(hi)[:d]
     e = np.where(c < lo, c - lo, np.where(c > hi, c - hi, 0.0))
     if np.any(e != 0):
-        d = np.linalg.norm(e)
-        return d - r, e / d
+        dist = np.linalg.norm(e)
+        return dist - r, e / dist
     a, b = c - lo, hi - c          # inside: nearest face
     i = int(np.argmin(np.concatenate([a, b])))
-    nh = np.zeros(3)
-    if i < 3:
+    nh = np.zeros(d)
+    if i < d:
         nh[i] = -1.0
         return -a[i] - r, nh
-    nh[i - 3] = 1.0
-    return -b[i - 3] - r, nh
+    nh[i - d] = 1.0
+    return -b[i - d] - r, nh
 
 
 def sd_sphere(c, cs, rs, r):
-    v = c - cs
+    v = c - np.asarray(cs)[:len(c)]
     d = np.linalg.norm(v)
     return d - rs - r, v / d
 
 
-def solve_subproblem(model, N, tf, x_init, goal_lo, goal_hi, Xp, Up, Delta, omega, boxes=(), spheres=(), maxiter=400):
-    """One trip's convex subproblem (scp_gusto.jl:178-314) by SLSQP.  Returns X, U, objective (unscaled)."""
+def subproblem_rows(model, N, tf, x_init, goal_lo, goal_hi, Xp, Up, Delta, omega, toggle=None, boxes=(), spheres=()):
+    """The rows of one trip's convex subproblem (scp_gusto.jl:178-314) around (Xp, Up), on z = [x_0, u_0, x_1, u_1, ...]:
+
+      E z = e                         init, trapezoid collocation, point-goal rows (dense E)
+      hard[j](z) <= 0                 entries (fn, scale, kind): kind "goal" for BoxGoal rows, "hard" for the rest; `scale` > 0
+                                      states the row in the units the certificate (np_kkt.py) measures it in -- the
+                                      acceleration / control bounds relative to their limit, the hard half of the manifold's
+                                      +-eps pair scaled by kappa like the penalised rows.  SLSQP sees the rows unscaled.
+      kappa (w g_i(z) - off_i) <= s_i, s_i >= 0    penalised rows: entries (fn, w, off) of `pen`, tags in `pen_tag`
+      minimise kappa sum_k wt_k |u_k|^2 + sum_i s_i,  kappa = 1 / max(1, omega), wt = trapezoid weights
+
+    Every fn maps z to (value, (indices, gradient)).  `toggle` is the obstacle toggle distance (default Delta / 8 + clearance,
+    what scp_gusto.jl:76 sets)."""
     n, m = model.n, model.m
     nz = n + m
     dt = tf / (N - 1)
     kappa = 1.0 / max(1.0, omega)
-    toggle = Delta / 8 + model.clearance
+    if toggle is None:
+        toggle = Delta / 8 + model.clearance
     nzN = nz * N
     ix = lambda k, i: nz * k + i
     iu = lambda k, i: nz * k + n + i
@@ -141,7 +175,7 @@ def solve_subproblem(model, N, tf, x_init, goal_lo, goal_hi, Xp, Up, Delta, omeg
     E, e = np.array(rows), np.array(rhs, float)
 
     # ---- inequality rows as (value, gradient) callables of z; hard: g <= 0; penalised: kappa (w g - off) <= s ------
-    hard, pen = [], []          # entries: (fun(z) -> (val, sparse grad dict), weight, off)
+    hard, pen, pen_tag = [], [], []
 
     def quad(idx, coef, c0):     # sum coef_i z_i^2 + c0
         idx, coef = np.array(idx), np.array(coef, float)
@@ -155,20 +189,27 @@ def solve_subproblem(model, N, tf, x_init, goal_lo, goal_hi, Xp, Up, Delta, omeg
         idx, ctr = np.array(idx), np.array(ctr, float)
         return lambda z: (float(np.sum((z[idx] - ctr) ** 2)), (idx, 2 * (z[idx] - ctr)))
 
+    def add_pen(tag, fn, wt, off):
+        pen.append((fn, wt, off)); pen_tag.append(tag)
+
+    comps = [("b", b) for b in (boxes if boxes is not None else ())] + \
+            [("s", s) for s in (spheres if spheres is not None else ())]
     for k in range(N):
         if model is Dubins:
             for i in range(n):      # csi_max/min_bound_constraints (dynamics.jl:56-64): penalised
-                pen.append((lin_([ix(k, i)], [1.0], -model.x_max[i]), omega, 0.0))
+                add_pen(("x_max", k, i), lin_([ix(k, i)], [1.0], -model.x_max[i]), omega, 0.0)
             for i in range(n):
-                pen.append((lin_([ix(k, i)], [-1.0], -model.x_max[i]), omega, 0.0))
+                add_pen(("x_min", k, i), lin_([ix(k, i)], [-1.0], -model.x_max[i]), omega, 0.0)
             if k < N - 1:           # cci_max/min_bound_constraints (dynamics.jl:73-81): hard, k = 1..N-1
-                hard.append(lin_([iu(k, 0)], [1.0], -model.u_max))
-                hard.append(lin_([iu(k, 0)], [-1.0], -model.u_max))
+                hard.append((lin_([iu(k, 0)], [1.0], -model.u_max), 1 / model.u_max, "hard"))
+                hard.append((lin_([iu(k, 0)], [-1.0], -model.u_max), 1 / model.u_max, "hard"))
             continue
         man = model is AstrobeeSE3Manifold
-        iw = 10 if man else 9
+        se2 = model is FreeflyerSE2
+        iv, nv = 3, (2 if se2 else 3)                     # velocity block
+        iw, nw = (5, 1) if se2 else ((10, 3) if man else (9, 3))
         if model.has_tr:            # stri_state_trust_region: omega * ||x - xp||^2 - Delta <= s
-            pen.append((quad_about([ix(k, i) for i in range(n)], Xp[k]), omega, Delta))
+            add_pen(("tr", k), quad_about([ix(k, i) for i in range(n)], Xp[k]), omega, Delta)
         if man:
             qp = Xp[k, 6:10]
             qn = np.linalg.norm(qp)
@@ -176,30 +217,45 @@ def solve_subproblem(model, N, tf, x_init, goal_lo, goal_hi, Xp, Up, Delta, omeg
             #   j = 1:  -w h - eps <= -s1   (s1 >= 0 is minimised, so this is the HARD bound w h + eps >= 0)
             #   j = 2:   w h - eps <=  s2   (the L1 penalty on h > eps / w)
             hfun = lin_([ix(k, 6 + j) for j in range(4)], qp / qn, qn - np.sum(qp * qp) / qn - 1.0)
-            hard.append((lambda z, hf=hfun: (lambda v, g: (-(omega * v) - model.eps, (g[0], -omega * g[1])))(*hf(z))))
-            pen.append((hfun, omega, model.eps))
-            pen.append((lin_([ix(k, 6)], [-1.0], 0.0), omega, 0.0))           # csi_orientation_sign: -qw
-        pen.append((quad([ix(k, 3 + j) for j in range(3)], [1.0] * 3, -model.v_max ** 2), omega, 0.0))
-        pen.append((quad([ix(k, iw + j) for j in range(3)], [1.0] * 3, -model.w_max ** 2), omega, 0.0))
-        r0 = Xp[k, 0:3]
-        comps = [("b", b) for b in boxes] + [("s", s) for s in spheres]
-        for kind, o in comps:       # ncsi_obstacle_avoidance_signed_distance_convexified
+            hard.append(((lambda z, hf=hfun: (lambda v, g: (-(omega * v) - model.eps, (g[0], -omega * g[1])))(*hf(z))),
+                         kappa, "hard"))
+            add_pen(("qnorm", k), hfun, omega, model.eps)
+            add_pen(("qw", k), lin_([ix(k, 6)], [-1.0], 0.0), omega, 0.0)           # csi_orientation_sign: -qw
+        add_pen(("v", k), quad([ix(k, iv + j) for j in range(nv)], [1.0] * nv, -model.v_max ** 2), omega, 0.0)
+        add_pen(("w", k), quad([ix(k, iw + j) for j in range(nw)], [1.0] * nw, -model.w_max ** 2), omega, 0.0)
+        d_ws = 2 if se2 else 3      # workspace: the plane for the freeflyer (its obstacles are AABBs / spheres seen as discs)
+        r0 = Xp[k, 0:d_ws]
+        for i, (kind, o) in enumerate(comps):       # ncsi_*_obstacle_avoidance_..._convexified, body component
             d, nh = sd_box(r0, o[0:3], o[3:6], model.r) if kind == "b" else sd_sphere(r0, o[0:3], o[3], model.r)
             if d < toggle:
-                pen.append((lin_([ix(k, j) for j in range(3)], -nh, model.clearance - d + nh @ r0), omega, 0.0))
+                add_pen(("obs", k, i), lin_([ix(k, j) for j in range(d_ws)], -nh, model.clearance - d + nh @ r0), omega, 0.0)
         if k < N - 1:               # cci_translational/angular_accel_bound: hard, k = 1..N-1
-            hard.append(quad([iu(k, j) for j in range(3)], [1 / model.mass ** 2] * 3, -model.a_max ** 2))
-            hard.append(quad([iu(k, 3 + j) for j in range(3)], [1 / model.J ** 2] * 3, -model.al_max ** 2))
+            nf, im, nm = (2, 2, 1) if se2 else (3, 3, 3)
+            hard.append((quad([iu(k, j) for j in range(nf)], [1 / model.mass ** 2] * nf, -model.a_max ** 2),
+                         1 / model.a_max ** 2, "hard"))
+            hard.append((quad([iu(k, im + j) for j in range(nm)], [1 / model.J ** 2] * nm, -model.al_max ** 2),
+                         1 / model.al_max ** 2, "hard"))
     for i in range(n):              # csbci_goal_constraints (BoxGoal): hard
         if goal_lo[i] != goal_hi[i]:
             if np.isfinite(goal_hi[i]):
-                hard.append(lin_([ix(N - 1, i)], [1.0], -goal_hi[i]))
+                hard.append((lin_([ix(N - 1, i)], [1.0], -goal_hi[i]), 1.0, "goal"))
             if np.isfinite(goal_lo[i]):
-                hard.append(lin_([ix(N - 1, i)], [-1.0], goal_lo[i]))
+                hard.append((lin_([ix(N - 1, i)], [-1.0], goal_lo[i]), 1.0, "goal"))
 
-    ns = len(pen)
-    w = np.full(N, dt); w[0] = w[-1] = 0.5 * dt
+    wt = np.full(N, dt); wt[0] = wt[-1] = 0.5 * dt
     uidx = np.array([[iu(k, j) for j in range(m)] for k in range(N)])
+    return dict(n=n, m=m, N=N, nzN=nzN, kappa=kappa, omega=omega, E=E, e=e, hard=hard, pen=pen, pen_tag=pen_tag,
+                wt=wt, uidx=uidx)
+
+
+def solve_subproblem(model, N, tf, x_init, goal_lo, goal_hi, Xp, Up, Delta, omega, boxes=(), spheres=(), maxiter=400,
+                     toggle=None):
+    """One trip's convex subproblem (subproblem_rows) by SLSQP in its full slack form.  Returns X, U, objective (unscaled)."""
+    R = subproblem_rows(model, N, tf, x_init, goal_lo, goal_hi, Xp, Up, Delta, omega, toggle, boxes, spheres)
+    n, m, nzN, kappa, E, e = R["n"], R["m"], R["nzN"], R["kappa"], R["E"], R["e"]
+    pen, hard = R["pen"], [h[0] for h in R["hard"]]
+    ns = len(pen)
+    w, uidx = R["wt"], R["uidx"]
 
     def obj(z):
         return kappa * float(np.sum(w[:, None] * z[uidx] ** 2)) + float(z[nzN:].sum())
@@ -232,6 +288,6 @@ def solve_subproblem(model, N, tf, x_init, goal_lo, goal_hi, Xp, Up, Delta, omeg
                       constraints=[{"type": "eq", "fun": lambda z: Epad @ z - e, "jac": lambda z: Epad},
                                    {"type": "ineq", "fun": ineq, "jac": ineq_jac}],
                       bounds=[(None, None)] * nzN + [(0, None)] * ns, options={"ftol": 1e-15, "maxiter": maxiter})
-    Z = res.x[:nzN].reshape(N, nz)
-    return dict(X=Z[:, :n], U=Z[:, n:], obj=res.fun / kappa, res=res, n_pen=ns, n_hard=len(hard),
+    Z = res.x[:nzN].reshape(N, n + m)
+    return dict(X=Z[:, :n], U=Z[:, n:], obj=res.fun / kappa, res=res, n_pen=ns, n_hard=len(hard), rows=R,
                 eq_violation=float(np.abs(Epad @ res.x - e).max()), ineq_min=float(ineq(res.x).min()))

@@ -55,11 +55,21 @@ def test_manifold_against_independent_slsqp(b, omega):
     assert s["n_pen"] == 6 * (4 + 12 + 2)       # per knot: quat-norm, -qw, v, w + every obstacle (toggle = 125 m)
 
 
+@pytest.mark.parametrize("omega,Delta", [(1.0, 3.0), (10.0, 0.05)])
+def test_freeflyer_against_independent_slsqp(omega, Delta):
+    """np_models.FreeflyerSE2 (the body disc against the table slabs and the notebook boxes, the trust region, the velocity rows,
+    the hard acceleration rows) pinned by the oracle's optimum"""
+    x0, glo, ghi, tf = P.freeflyer_batch(2)
+    x0[0] = P.FREEFLYER_X_INIT
+    s = _compare(go.FREEFLYER_SE2, M.FreeflyerSE2, 10, (x0, glo, ghi, tf), 0, P.freeflyer_env(), None, Delta, omega)
+    assert s["n_hard"] == 2 * 9
+
+
 def test_complex_step_jacobians_match_the_oracle_tables():
-    """the hand-written Jacobian tables of the oracle (astrobee_se3.jl:206-233, astrobee_se3_manifold.jl:248-296)
+    """the hand-written Jacobian tables of the oracle (freeflyer_se2.jl:208-221, astrobee_se3.jl:206-233, astrobee_se3_manifold.jl:248-296)
     against complex-step derivatives of the independently written f"""
     rng = np.random.default_rng(5)
-    for mid, model in ((go.DUBINS_CAR, M.Dubins), (go.ASTROBEE_SE3, M.AstrobeeSE3), (go.ASTROBEE_SE3_MANIFOLD, M.AstrobeeSE3Manifold)):
+    for mid, model in ((go.FREEFLYER_SE2, M.FreeflyerSE2), (go.DUBINS_CAR, M.Dubins), (go.ASTROBEE_SE3, M.AstrobeeSE3), (go.ASTROBEE_SE3_MANIFOLD, M.AstrobeeSE3Manifold)):
         o = go.Oracle(mid, 8)
         for _ in range(4):
             x, u = rng.uniform(-0.6, 0.6, model.n), rng.uniform(-0.6, 0.6, model.m)
