@@ -106,7 +106,11 @@ int gusto_default_ipm_opts(gusto_ipm_opts* o);
 int gusto_model_dims(int model_id, int* x_dim, int* u_dim);
 
 /* SCPProblem(TOP) for a batch (types.jl:256-259): allocates all device memory for up to batch_cap problems of
- * N knots and hist_cap SCP iterations of history.  device = HIP device ordinal. */
+ * N knots and hist_cap SCP iterations of history.  device = HIP device ordinal.
+ * Horizons: 3 <= N <= 256 is accepted here, but a problem's workgroup keeps its KKT blocks in the 160 KiB LDS of a CU, which
+ * bounds N per model: FreeflyerSE2 256, DubinsCar 256, AstrobeeSE3 200, AstrobeeSE3Manifold 182.  A larger N is refused with
+ * GUSTO_ERR_ARG ("does not fit the 160 KiB LDS") by the first gusto_solve / gusto_solve_async / gusto_subproblem, which
+ * launches nothing (tests/horizons.py holds the table, tests/test_boundary.py checks it against the layout). */
 int gusto_create(gusto_handle* h, int model_id, int N, int batch_cap, int hist_cap, int device);
 int gusto_destroy(gusto_handle h);
 const char* gusto_last_error(gusto_handle h);
@@ -261,7 +265,10 @@ typedef struct {
     int max_penalty_iteration, max_convex_iteration, max_trust_iteration;
 } gusto_trajopt_params;
 int gusto_default_trajopt_params(int model_id, gusto_trajopt_params* tp);
-/* SCPProblem(TOP) + SCPParam_TrajOpt(model) for a batch; hist_cap >= 2 * max_penalty * max_convex * max_trust + 8 entries */
+/* SCPProblem(TOP) + SCPParam_TrajOpt(model) for a batch; hist_cap >= 2 * max_penalty * max_convex * max_trust + 8 entries.
+ * Horizons as for gusto_create, with the TrajOpt kernel's larger LDS layout (the defect variables): FreeflyerSE2 N <= 256,
+ * AstrobeeSE3 N <= 157, AstrobeeSE3Manifold N <= 139.  A larger N is refused with GUSTO_ERR_ARG ("does not fit the 160 KiB
+ * LDS") by the first gusto_solve_trajopt / gusto_solve_trajopt_async / gusto_subproblem_trajopt, which launches nothing. */
 int gusto_create_trajopt(gusto_handle* h, int model_id, int N, int batch_cap, int hist_cap, int device);
 int gusto_set_trajopt_params(gusto_handle h, const gusto_trajopt_params* tp);
 /* the whole three-loop schedule (penalty mu x k, convex iterations, trust region s x tau+-) for every problem of the batch;

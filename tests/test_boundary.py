@@ -223,3 +223,32 @@ def test_chain_kernel_layouts(tmp_path):
             assert acc & mk == 0
             acc |= mk
         assert acc == (1 << 64) - 1
+
+
+def test_horizon_limits_of_the_lds_layouts(tmp_path):
+    """tests/horizons.py against the layouts the launches size their LDS by (make_lds_layout<MODEL>(N), tests/c/lds_limits.hip):
+    every N from 3 up to a kernel's limit fits the 160 KiB of a CU, every N above it does not -- a layout change that moves any
+    limit fails here, so the table, the header's statement and the GPU tests at the limits (tests/test_gpu_horizons.py) move with it."""
+    import json, subprocess
+    import horizons as HZ
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path / "lds_limits")
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
+                           "-I" + os.path.join(ROOT, "gusto.jl_amd", "csrc"), os.path.join(ROOT, "tests", "c", "lds_limits.hip"), "-o", exe],
+                          stderr=subprocess.DEVNULL)
+    d = {int(k): v for k, v in json.loads(subprocess.check_output([exe]).decode()).items()}
+    Ns = list(range(HZ.N_MIN, HZ.N_MAX + 1))
+    assert sorted(d) == list(range(7)) and all(len(v) == len(Ns) for v in d.values())
+    for internal, limit in list(HZ.GUSTO.items()) + [(HZ.TRAJOPT_INTERNAL[m], lim) for m, lim in HZ.TRAJOPT.items()]:
+        fits = [N for N, b in zip(Ns, d[internal]) if b <= HZ.LDS_BYTES]
+        assert fits == list(range(HZ.N_MIN, limit + 1)), (internal, limit, max(fits))
+    # the header states the same numbers at gusto_create / gusto_create_trajopt
+    hdr = open(os.path.join(ROOT, "include", "gusto_hip.h")).read()
+    names = {g.FREEFLYER_SE2: "FreeflyerSE2", g.DUBINS_CAR: "DubinsCar", g.ASTROBEE_SE3: "AstrobeeSE3",
+             g.ASTROBEE_SE3_MANIFOLD: "AstrobeeSE3Manifold"}
+    for fn, table in (("int gusto_create(", HZ.GUSTO), ("int gusto_create_trajopt(", HZ.TRAJOPT)):
+        doc = hdr[hdr.rindex("/*", 0, hdr.index(fn)):hdr.index(fn)]
+        for m, lim in table.items():
+            assert re.search(r"\b%s (N <= )?%d\b" % (names[m], lim), doc), (fn, names[m], lim)

@@ -70,14 +70,15 @@ def obj_gate(model, c):
 
 
 def oracle_trips(model, N, boxes, spheres, prob, max_iter=30):
-    """(Xp, Up, Delta, omega) of the first, second, middle and last trip of an oracle SCP run"""
+    """(Xp, Up, Delta, omega) of the first, second, middle and last trip of an oracle SCP run; an empty list for a run that stops
+    before its first trip (SubproblemFailed at the first subproblem: dubins_car at N = 3, where no control reaches the goal)"""
     o = go.Oracle(model, N, boxes=boxes, spheres=spheres)
     o.set_trace(max_iter + 2)
     o.set_problem(*prob)
     r = o.solve(max_iter)
     tr = o.trace()
     T = len(tr)
-    return [(tr[t]["Xp"], tr[t]["Up"], r["Delta"][t], r["omega"][t]) for t in sorted({0, 1, T // 2, T - 1}) if t < T]
+    return [(tr[t]["Xp"], tr[t]["Up"], r["Delta"][t], r["omega"][t]) for t in sorted({0, 1, T // 2, T - 1}) if 0 <= t < T]
 
 
 def _calibration_points(model):
@@ -296,3 +297,17 @@ def test_mean_complementarity_stop_leaves_one_pair_high():
     cs = K.certify(s["rows"], s["X"], s["U"])
     assert cs["comp"] < 1e-9 and cs["stat"] < 1e-6, (cs["comp"], cs["stat"])
     assert 0 < r["obj"] - s["obj"] <= c["n_pairs"] * K.STOP_MU, (r["obj"], s["obj"])
+
+
+def test_oracle_trips_of_a_run_that_fails_its_first_subproblem():
+    """dubins_car at N = 3: no control reaches the goal in two steps, so the oracle's first subproblem is infeasible (SubproblemFailed
+    with no trip traced) -- oracle_trips returns no trips instead of failing on the empty trace"""
+    x0, glo, ghi, tf = batch(go.DUBINS_CAR, 2)
+    for b in range(2):
+        prob = (x0[b], glo[b], ghi[b], tf[b])
+        o = go.Oracle(go.DUBINS_CAR, 3)
+        o.set_problem(*prob)
+        r = o.solve(30)
+        assert r["stop_reason"] == 2 and r["iterations"] == 0
+        assert oracle_trips(go.DUBINS_CAR, 3, None, None, prob) == []
+    assert len(oracle_trips(go.DUBINS_CAR, 4, None, None, (x0[0], glo[0], ghi[0], tf[0]))) == 4
