@@ -351,13 +351,9 @@ template <int MODEL, bool ONE> struct LdsC {
     static constexpr int KDS = (KDW > NZ * (NZ + 1) / 2) ? KDW : NZ * (NZ + 1) / 2;
     static constexpr bool PHICL_LDS = n <= 8 && !PHI_FROM_K;
 };
-// The KKT solve as two Riccati segments joined by a coarse LQR stage (round 6; seg.hpp).
-//   GUSTO_SEG2   (off): both chains interleaved in ONE wave, freeflyerSE2 -- parity-green and slower (profiles/r06_two_chains.txt)
+// The KKT solve as Riccati segments joined by coarse LQR stages (round 6; segw.hpp).
 //   GUSTO_SEG_W2 (on):  a WAVE PER CHAIN for the matrix-core kernels (astrobeeSE3, astrobeeSE3manifold): scp_kernel_w2, launched for
-//                       batches that leave half of the SIMDs idle (launch.hpp: seg_w2_wanted)
-#ifndef GUSTO_SEG2
-#define GUSTO_SEG2 0
-#endif
+//                       batches that leave SIMDs without a wave (launch.hpp: launch_scp)
 #ifndef GUSTO_SEG_W2
 #ifdef GUSTO_STRICT_SYNC   // (the check build's ordering points are workgroup barriers: one wave per workgroup only)
 #define GUSTO_SEG_W2 0
@@ -365,11 +361,9 @@ template <int MODEL, bool ONE> struct LdsC {
 #define GUSTO_SEG_W2 1
 #endif
 #endif
-#define GUSTO_SEG_ANY (GUSTO_SEG2 || GUSTO_SEG_W2)
 #ifndef GUSTO_SEG_MIN_N
 #define GUSTO_SEG_MIN_N 4       // stages per chain at least (a chain of two or three stages is barely controllable)
 #endif
-__host__ __device__ constexpr int seg_split(int N) { return N >> 1; }   // two chains: A = stages 0 .. s-1, B = s .. N-1 (one stage longer for odd N)
 template <int MODEL> constexpr bool seg2_big() { return GUSTO_SEG_W2 && MT<MODEL>::MFMA && MT<MODEL>::SWEEP_CALL && MT<MODEL>::NDEF == 0; }
 // LDS block of the segmented solve of these kernels, behind everything else (offsets relative to LdsLayout::seg).  NCH chains
 // (= waves per problem, 2 or 4): chain c covers the stages seg_lo(c) .. seg_lo(c + 1) - 1, interface j sits between chain j and

@@ -776,7 +776,7 @@ template <int MODEL> GD bool costate_adjoint_rt(const gusto_model_params& mp, do
 // of their record.
 // (NOPP: no P | Pi records -- the costates come from the adjoint recursion; a template parameter, chosen at run time by the
 // caller, so that the stage loop holds no branch around its stores)
-// SEG (round 6, seg.hpp): the sweep over the stages kHi .. kLo of ONE chain of a split horizon.  A chain in front of an interface
+// SEG (round 6, segw.hpp): the sweep over the stages kHi .. kLo of ONE chain of a split horizon.  A chain in front of an interface
 // (isA) starts from P = 0, Pi = I -- its end state adjoined as a terminal equality; the last chain (kHi = N - 1) starts as the sweep
 // always did.  Every chain leaves the P, Pi in front of its first stage and its Gd in the segmented solve's LDS block (offsets oP,
 // oPi, oGd from the base of the dynamic LDS; oGd < 0: sGd), and a chain with kLo > 0 does not write record kLo - 1, which belongs to

@@ -49,7 +49,7 @@ struct gusto_handle_s {
     int lds_bytes = 0, per_cu = 0;   // ... its dynamic LDS per workgroup and workgroups per CU (gusto_dev_launch_info)
     int sched_init[gusto::SQ_WORDS] = {0};   // initial scheduler words of a launch (host side of an async copy)
     bool have_problems = false, have_shoot = false;
-    int decomposition = 0;         // gusto_set_decomposition: 0 auto, 1 a wave per problem, 2 a lane per problem (lane.hpp)
+    int decomposition = 0;         // gusto_set_decomposition: 0 auto, 1 a wave per problem, 3 / 4 two / four waves per problem (2: reserved, refused)
     int waves = 0;                 // waves per problem of the GuSTO kernel (0 = one per 64 knots; development builds: GUSTO_DEV_WAVES)
     // gusto_set_active: the problems the next gusto_solve calls iterate (n_active < 0: all of them); d_active = the mask [B]
     // (gusto_shoot reads it), d_active + batch_cap = the list of active problems (the hand-out order of the launch)

@@ -2228,7 +2228,7 @@ GD StepOut step_phase(BLK& K, const RowCtx<MODEL>& ctx, const RowState& rs, int 
         double hdx[ADJ ? n : 1];
 #pragma unroll
         for (int i = 0; i < (ADJ ? n : 1); i++) hdx[i] = 0;
-        OpStep<NP, RowState, ADJ> op{rs, dxs, dus, pass, mu_t, tau, gAx, gAu, gBx, gBu, &pre, hdx};
+        OpStep<NP, ADJ> op{rs, dxs, dus, pass, mu_t, tau, gAx, gAu, gBx, gBu, &pre, hdx};
         ctx.tick(0);
 #if GUSTO_SEG_W2
         if constexpr (NCH > 0) {
@@ -2278,7 +2278,7 @@ GD StepOut step_phase(BLK& K, const RowCtx<MODEL>& ctx, const RowState& rs, int 
     }
     K.sync();
     // (adjoint costates: nu_1 is known after the sweep; adjoint_sweep_1w_call closes with this block.  Two waves per problem, CLOSE =
-    // false: the helper wave's costate pass runs beside this phase and closes itself -- seg.hpp: segw_helper)
+    // false: the helper wave's costate pass runs beside this phase and closes itself -- segw.hpp: segw_helper)
     if constexpr (CLOSE)
     if (!(ADJ && adj_rt) && k == 0 && (pass == 1 || ncomp == 0)) costate_close_x1<MODEL>(K, hdt, gxs);
     return StepOut{l_amax, l_c0, l_c1, l_c2};
@@ -2538,15 +2538,8 @@ __device__ __noinline__ ResidOut resid_phase_call(typename BLK::Args a, RowScal 
     return resid_phase<MODEL, BLK, NCH>(K, ctx, rs, k, act, hdt, wk, alpha_prev, gusto_dyn_lds + C::misc + 32);
 }
 
-// The KKT solve as Riccati segments joined by coarse LQR stages (round 6).  seg.hpp (-DGUSTO_SEG2=1, off): two chains interleaved
-// in ONE wave, freeflyerSE2 -- parity-green, slower: the sequential phases are ISSUE-bound, not latency-bound
-// (profiles/r06_two_chains.txt).  segw.hpp (on): a WAVE per chain, the matrix-core kernels.
+// The KKT solve as Riccati segments joined by coarse LQR stages (round 6): a WAVE per chain, the matrix-core kernels (segw.hpp).
 }  // namespace gusto
-#if GUSTO_SEG2
-#include "seg.hpp"
-#else
-namespace gusto { template <int MODEL> constexpr bool seg2_model() { return false; } }
-#endif
 #if GUSTO_SEG_W2
 #include "segw.hpp"
 #endif
@@ -2573,11 +2566,8 @@ template <int MODEL, class BLK, int NCH = 0> GD void ipm_solve(BLK& K, double De
     double* mug = K.misc + 32;   // goal multipliers (state-index space)
     double* mugn = K.misc + 48;  // ... of the current Newton step
     // the horizon split into Riccati segments: NCH chains, a wave each (segw.hpp: scp_kernel_w2, the matrix-core kernels; launch_scp
-    // starts it for N >= NCH GUSTO_SEG_MIN_N only), or two chains in the one wave (seg.hpp: A = stages 0 .. seg_s - 1, B = seg_s .. N - 1)
+    // starts it for N >= NCH GUSTO_SEG_MIN_N only)
     constexpr bool SEGB = seg2_big<MODEL>() && BLK::ONE && NCH > 0;
-    constexpr bool SEG = (seg2_model<MODEL>() && BLK::ONE) || SEGB;
-    [[maybe_unused]] const bool seg = SEG && (SEGB || N >= 2 * GUSTO_SEG_MIN_N);
-    [[maybe_unused]] const int seg_s = seg_split(N);
 #if GUSTO_SEG_W2
     if constexpr (SEGB) segw_open<MODEL, NCH>(K);
 #endif
@@ -2705,6 +2695,8 @@ template <int MODEL, class BLK, int NCH = 0> GD void ipm_solve(BLK& K, double De
             K.sync();
         }
         // (4) factorise
+        // (seg_done here and swp below stay runtime flags: as `if constexpr (SEGB) ... else` hipcc emits different code for the
+        // kernels of these units, and no such variant has been measured)
         bool seg_done = false;
         [[maybe_unused]] bool seg_fail = false;
 #if GUSTO_SEG_W2
@@ -2718,17 +2710,6 @@ template <int MODEL, class BLK, int NCH = 0> GD void ipm_solve(BLK& K, double De
             GUSTO_REFRESH_K();
             seg_done = true;
             if (*fail != 0.0) { if constexpr (NCH == 4) segw_join(); segw_join(); break; }   // (the barriers of the waves stay paired)
-        }
-#endif
-#if GUSTO_SEG2
-        if constexpr (SEG && !SEGB) {
-            if (seg) {
-                factor_sweep_pg2s<MODEL>(SweepView<MODEL>::make(K), fail, pf, seg_s);
-                pf.tick(PF_FACTOR);
-                GUSTO_REFRESH_K();
-                seg_coarse_factor<MODEL>(K, fail);
-                seg_done = true;
-            }
         }
 #endif
         if (!seg_done) {
@@ -2825,8 +2806,8 @@ template <int MODEL, class BLK, int NCH = 0> GD void ipm_solve(BLK& K, double De
             }
             K.sync();
             pf.tick(PF_RHS);
-            // the two vector sweeps of this right-hand side and the phase between them: the chains' waves side by side (segw.hpp), two
-            // chains in the one wave (seg.hpp), or the sequential recursion
+            // the two vector sweeps of this right-hand side and the phase between them: the chains' waves side by side (segw.hpp) or
+            // the sequential recursion
             bool swp = false;
 #if GUSTO_SEG_W2
             if constexpr (SEGB) {
@@ -2843,19 +2824,6 @@ template <int MODEL, class BLK, int NCH = 0> GD void ipm_solve(BLK& K, double De
                 pf.tick(PF_MID);
                 segw_post<MODEL, NCH>(K, SEGW_FWD); forward_sweep_seg_call<MODEL, NCH>(K.args()); segw_join();
                 swp = true;
-            }
-#endif
-#if GUSTO_SEG2
-            if constexpr (SEG && !SEGB) {
-                if (seg) {
-                    backward_sweep_seg<MODEL>(SweepView<MODEL>::make(K), seg_s);
-                    pf.tick(PF_BACK);
-                    GUSTO_REFRESH_K();
-                    mid_phase_seg<MODEL>(K, k, act, hdt, seg_s, mugn, &pf);
-                    pf.tick(PF_MID);
-                    forward_sweep_seg<MODEL>(SweepView<MODEL>::make(K), seg_s);
-                    swp = true;
-                }
             }
 #endif
             if (!swp) {
@@ -2884,14 +2852,7 @@ template <int MODEL, class BLK, int NCH = 0> GD void ipm_solve(BLK& K, double De
             else
 #endif
             if constexpr (T::SWEEP_CALL) so = step_phase_call<MODEL, BLK>(K.args(), RowScal{kappa, omega, Delta}, k, act, pass, ncomp, hdt, tau, mu_t, &pf);
-            else {
-                // (segmented solve: the costates of chain A's knots hang on dlam, those of chain B's on mu_g)
-                const double* mult = mugn;
-#if GUSTO_SEG2
-                if constexpr (SEG && !SEGB) mult = (seg && k < seg_s) ? (const double*)(K.misc + (SegC<MODEL>::LAM - BLK::C::misc)) : mult;
-#endif
-                so = step_phase<MODEL>(K, ctx, rs, k, act, pass, ncomp, hdt, tau, mu_t, mult, gxs);
-            }
+            else so = step_phase<MODEL>(K, ctx, rs, k, act, pass, ncomp, hdt, tau, mu_t, mugn, gxs);
             if constexpr (costate_adjoint<MODEL>() && BLK::ONE)
                 if (adj_now && (pass == 1 || ncomp == 0)) adjoint_sweep_1w_call<MODEL>(K.args(), hdt);
             (void)adj_now;

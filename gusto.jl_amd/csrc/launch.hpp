@@ -7,11 +7,6 @@
 
 #include "handle.hpp"
 #include "scp.hpp"
-// the lane-per-problem kernel of dubins_car (lane.hpp: parity-green, 4.3x slower than the wave kernel at config 3) is built only
-// with -DGUSTO_WITH_LANE; without it gusto_set_decomposition(GUSTO_DECOMP_LANE) is refused
-#ifdef GUSTO_WITH_LANE
-#include "lane.hpp"
-#endif
 
 using namespace gusto;
 
@@ -188,64 +183,6 @@ template <int MODEL> static int launch_scp(gusto_handle h, int mode, int max_ite
     h->pending = true;   // completed by gusto_finish (handle.hpp)
     return GUSTO_OK;
 }
-
-#ifdef GUSTO_WITH_LANE
-// Which decomposition a GuSTO solve of this handle runs (models that have the lane-per-problem kernel, lane.hpp): the
-// caller's choice (gusto_set_decomposition), else GUSTO_DEV_LANE=0/1, else a wave per problem -- measured on MI355X
-// (profiles/r04_lane_vs_wave.txt) the lane kernel is the slower one at every batch size of BASELINE.json: an interior point
-// iteration of 64 problems issues ~170 k instructions (0.33 ms on an idle GPU) and a wave runs as long as the longest of
-// its 64 problems (813 iterations + trips in the config-3 batch, against 80 on average), DESIGN.md section 3
-static inline bool lane_decomposition(gusto_handle h) {
-    if (h->decomposition == 1) return false;
-    if (h->decomposition == 2) return true;
-    if (const char* e = dev_env("GUSTO_DEV_LANE")) return atoi(e) != 0;   // (development builds)
-    return false;
-}
-// One lane per problem (lane.hpp): ceil(B / lanes per wave) one-wave workgroups, each with its own block of the lane
-// workspace; no device-side scheduler (every problem is resident from the start, a lane runs its problem to the end)
-template <int MODEL> static int launch_lane(gusto_handle h, int mode, int max_iter, int force) {
-    using Y = LaneLay<MODEL>;
-    KParams P;
-    int rc = fill_params<MODEL>(h, P, h->B);
-    if (rc) return rc;
-    if (h->n_active >= 0) { h->err = "gusto_set_active: not with a lane per problem (gusto_set_decomposition)"; return GUSTO_ERR_STATE; }
-    P.mode = mode; P.max_iter = max_iter; P.force = force;
-    int cus = 0;
-    HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
-    // lanes per wave: 64 unless the batch is too small to give every SIMD a wave (then fewer problems per wave: the
-    // instruction stream of a wave costs the same for 16 problems as for 64)
-    int lpw = 64;
-    if (const char* e = dev_env("GUSTO_DEV_LANES_PER_WAVE")) lpw = std::max(1, std::min(64, atoi(e)));
-    else while (lpw > 8 && (h->B + lpw - 1) / lpw < 4 * std::max(1, cus)) lpw >>= 1;
-    // persistent lanes: at most the waves the GPU keeps resident (one per SIMD at this kernel's register budget); a lane that
-    // finishes takes the next problem of the batch (lane.hpp)
-    int per_cu = 0;
-    HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&lane_kernel<MODEL>), 64, 0));
-    int nw = std::min((h->B + lpw - 1) / lpw, std::max(1, per_cu) * std::max(1, cus));
-    if (const char* e = dev_env("GUSTO_DEV_SLOTS")) nw = std::max(1, std::min(nw, atoi(e)));
-    const size_t need = (size_t)nw * (size_t)h->N * (size_t)(Y::EK * 64);
-    if (need > h->ws_doubles) {
-        if (h->d_ws) hipFree(h->d_ws);
-        h->d_ws = nullptr; h->ws_doubles = 0;
-        HIPCHK(h, dalloc(&h->d_ws, need));
-        h->ws_doubles = need;
-    }
-    P.ws = h->d_ws;
-    h->slots = nw; h->lds_bytes = 0; h->per_cu = per_cu;
-    memset(h->sched_init, 0, sizeof(h->sched_init));
-    h->sched_init[SQ_HEAD_A] = std::min(h->B, nw * lpw);   // the problems handed out at launch: the counter's start
-    HIPCHK(h, hipMemcpyAsync(h->d_queue, h->sched_init, SQ_WORDS * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    P.queue = h->d_queue;
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(lane_kernel<MODEL>, dim3(nw), dim3(64), 0, h->stream, P, lpw);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    h->sched_err = 0;
-    HIPCHK(h, gusto_fetch_sched_err(h));
-    h->pending = true;
-    return GUSTO_OK;
-}
-#endif   // GUSTO_WITH_LANE
 
 // TrajOpt: every problem of the batch through trajopt_kernel (scp.hpp); mode 1 = one subproblem per problem (parity hook)
 template <int MODEL> static int launch_trajopt(gusto_handle h, int mode, int max_iter) {

@@ -8,7 +8,7 @@
 //     equality, multiplier lam = the costate behind the interface -- the machinery the goal rows already use: Pi starts as I, and the
 //     chain's "Gd" is its compliance d(end state) / d lam.
 // A chain then is the affine map (y, lam) -> (front costate, end state) = (P y + Pi lam + p, Pi' y - Gd lam + th), and two neighbours
-// MERGE into one chain of the same form (seg.hpp's coarse stage; cf. the associative LQR elements of parallel-in-time Riccati
+// MERGE into one chain of the same form (a coarse LQR stage; cf. the associative LQR elements of parallel-in-time Riccati
 // solvers).  With A in front of B, Ta = (I + P_B Gd_A)^-1, Sig = Gd_A Ta (symmetric), Pa = Ta P_B:
 //       P = P_A + Pi_A Pa Pi_A',   Pi = Pi_A Ta Pi_B,   Gd = Gd_B + Pi_B' Sig Pi_B,
 //       p = p_A + Pi_A (Pa th_A + Ta ph),   th = th_B + Pi_B' (Ta' th_A - Sig ph),          ph = p_B - lam0
@@ -458,7 +458,7 @@ template <int MODEL, int NCH> GD void segw_rows_step_helper(Blk<MODEL, true>& B,
 #pragma unroll
     for (int i = 0; i < WS; i++) dxs[i] = act ? B.dXs[k * n + i] : 0.0;   // (the main wave's step phase has stored the primal step)
     RowPre<0> pre;
-    OpStep<0, RowState, false> op{rs, dxs, dus, pass, mu_t, tau, gAx, gAu, gBx, gBu, &pre, nullptr};
+    OpStep<0, false> op{rs, dxs, dus, pass, mu_t, tau, gAx, gAu, gBx, gBu, &pre, nullptr};
     visit_obs_rows<MODEL>(ctx, xs, op, ctx.mask & seg_obs_share(rank, nshare));
     const int o = sb + SB::sPG2(hi) + k;
     L[o] = op.amax.an; L[o + 64] = op.amax.ad; L[o + 128] = op.c0; L[o + 192] = op.c1; L[o + 256] = op.c2;

@@ -36,7 +36,7 @@ end
 # with gusto_solve_async so the GPUs run concurrently; the results come back in problem order.
 # gusto_set_decomposition (include/gusto_hip.h): how a solve maps problems to the GPU.  AUTO picks by batch size -- for astrobeeSE3 /
 # astrobeeSE3manifold two or four wavefronts per problem (a wave per Riccati chain of the horizon) while the batch leaves SIMDs idle.
-const GUSTO_DECOMP_AUTO, GUSTO_DECOMP_WAVE, GUSTO_DECOMP_LANE, GUSTO_DECOMP_WAVE2, GUSTO_DECOMP_WAVE4 = Cint(0), Cint(1), Cint(2), Cint(3), Cint(4)
+const GUSTO_DECOMP_AUTO, GUSTO_DECOMP_WAVE, GUSTO_DECOMP_LANE, GUSTO_DECOMP_WAVE2, GUSTO_DECOMP_WAVE4 = Cint(0), Cint(1), Cint(2), Cint(3), Cint(4)   # (LANE: reserved, refused)
 
 function solve_SCP_batch!(TOSs::Vector, TOPs::Vector, init_method=init_traj_straightline; max_iter=30, force=false, device=0, devices=nothing,
                           decomposition=GUSTO_DECOMP_AUTO)

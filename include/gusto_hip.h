@@ -139,13 +139,8 @@ int gusto_set_env_batch(gusto_handle h, int B, const int* n_box, const double* b
 int gusto_set_schedule(gusto_handle h, int probe_iters, int min_batch);
 /* How a gusto_solve maps problems to the GPU (new; affects time only -- both kernels run scp_gusto.jl:49-176 on the same
  * subproblem, scp_gusto.jl:178-314, to the same tolerances).  WAVE: one wavefront per problem, lane k = knot k, the
- * Newton system staged in LDS (every model).  LANE: one LANE per problem, 64 problems per wavefront, the Riccati recursion
- * in that lane's registers and its per-knot data streamed through HBM in a [wave][knot][entry][lane] layout -- built for
- * dubins_car (BASELINE.json configs[2]: n = 3, N = 30, batches of 65 536, where a wave per problem leaves 34 of 64 lanes
- * idle and spends its time on 3 x 3 blocks); other models ignore the setting.  AUTO (default) = WAVE: as measured on MI355X
- * the LANE kernel is correct (same trips, statuses and trajectories to 1e-12) but slower at the BASELINE batch sizes, because a
- * wavefront runs as long as the longest of its 64 problems.  The scheduler of gusto_set_schedule belongs
- * to the WAVE kernel.
+ * Newton system staged in LDS (every model).  LANE (one lane per problem) is reserved and refused with GUSTO_ERR_ARG: that kernel
+ * was measured slower at every batch size and is not in the library; the value keeps its number.
  * WAVE2 / WAVE4 (round 6; astrobeeSE3 and astrobeeSE3manifold, N <= 64): two or four wavefronts per problem -- the horizon split into
  * as many Riccati chains, a wave each, joined by coarse LQR stages, and each knot's obstacle rows shared between the waves
  * (csrc/segw.hpp).  For batches that leave SIMDs without a wave: AUTO takes WAVE4 up to six problems per CU, WAVE2 up to sixteen
@@ -179,7 +174,7 @@ int gusto_solve_async(gusto_handle h, int max_iter, int force);
  * iterate, NULL = all again (the state after gusto_set_problems).  The reference's drivers loop per problem --
  * solve_SCPshooting! takes another SCP iteration and another shooting attempt only `while !SCPS.converged &&
  * SCPS.iterations < max_iter` (src/traj_opt.jl:23) -- and a batch needs that condition per problem: an inactive problem
- * keeps its trajectory, histories and counters untouched.  Not for TrajOpt handles nor the lane-per-problem decomposition. */
+ * keeps its trajectory, histories and counters untouched.  Not for TrajOpt handles. */
 int gusto_set_active(gusto_handle h, const int* active);
 int gusto_wait(gusto_handle h);
 /* GPU time of the last gusto_solve, measured with HIP events on the stream the kernel ran on */

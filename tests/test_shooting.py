@@ -323,12 +323,15 @@ def test_inactive_problems_are_left_untouched():
         assert np.array_equal(st2[key], st3[key]), key
     for key in h2:
         assert np.array_equal(np.asarray(h2[key]), np.asarray(h3[key]), equal_nan=True), key
-    lane = g.BatchSolver(g.DUBINS_CAR, 30, 8)
-    lane.set_problems(*P.dubins_batch(8))
-    try:
-        lane.set_decomposition(2)            # (the lane-per-problem kernel: only in -DGUSTO_WITH_LANE builds)
-    except g.GustoError:
-        return
-    lane.set_active(np.ones(8, bool))
+    d = g.BatchSolver(g.DUBINS_CAR, 30, 8)
+    d.set_problems(*P.dubins_batch(8))
     with pytest.raises(g.GustoError):
-        lane.solve(2)
+        d.set_decomposition(2)               # (GUSTO_DECOMP_LANE: reserved, refused)
+    d.set_active(np.ones(8, bool))           # ... and the handle goes on with the decomposition it had
+    d.solve(2)
+    ref = g.BatchSolver(g.DUBINS_CAR, 30, 8)
+    ref.set_problems(*P.dubins_batch(8))
+    ref.solve(2)
+    # (not every problem takes a trip: the batch holds subproblems that are infeasible at trip 0, common.hpp: IPM_DIVERGED)
+    assert (d.status()["iterations"] > 0).any() and np.array_equal(d.status()["iterations"], ref.status()["iterations"])
+    assert all(np.array_equal(a, b) for a, b in zip(d.traj(), ref.traj()))
