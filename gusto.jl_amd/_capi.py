@@ -27,6 +27,8 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_set_trust_state", "gusto_subproblem", "gusto_default_shoot_opts", "gusto_shoot", "gusto_get_shoot",
            "gusto_default_trajopt_params", "gusto_create_trajopt", "gusto_set_trajopt_params", "gusto_solve_trajopt", "gusto_solve_trajopt_async",
            "gusto_get_trajopt_history", "gusto_subproblem_trajopt",
+           "gusto_default_verify_opts", "gusto_verify", "gusto_get_verify", "gusto_interpolate", "gusto_get_dense",
+           "gusto_last_verify_ms",
            "gusto_dev_get_prof", "gusto_dev_launch_info"]
 
 
@@ -51,6 +53,20 @@ class IpmOpts(C.Structure):
 
 class ShootOpts(C.Structure):
     _fields_ = [("substeps", C.c_int), ("max_newton", C.c_int), ("ftol", C.c_double), ("no_group_pass", C.c_int)]
+
+
+class VerifyOpts(C.Structure):
+    _fields_ = [("dt_min", C.c_double), ("nstep", C.c_int), ("nstep_cap", C.c_int), ("dense_collision", C.c_int)]
+
+
+VERIFY_FIELDS = (("collision_free", np.int32), ("first_knot", np.int32), ("first_dist", np.float64),
+                 ("min_dist_knots", np.float64), ("dyn_defect_l1", np.float64), ("min_dist_dense", np.float64),
+                 ("min_dense_sample", np.int32), ("max_gap", np.float64))
+
+
+class VerifyReport(C.Structure):
+    """gusto_verify_report: caller-owned arrays [B]"""
+    _fields_ = [(k, C.c_void_p) for k, _ in VERIFY_FIELDS]
 
 
 class TrajOptParams(C.Structure):
@@ -84,7 +100,7 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(_ROOT, "include"), "-fPIC",
              "-Wno-unused-value", "-Wno-pass-failed"]
-    units = ["gusto_hip", "shoot", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
+    units = ["gusto_hip", "shoot", "verify", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
     bdir = os.path.join(_HERE, "build")
     os.makedirs(bdir, exist_ok=True)
 
@@ -152,6 +168,12 @@ def lib():
         L.gusto_shoot.argtypes = [vp, vp, C.POINTER(ShootOpts)]
         L.gusto_get_shoot.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.gusto_subproblem.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.gusto_default_verify_opts.argtypes = [C.POINTER(VerifyOpts)]
+        L.gusto_verify.argtypes = [vp, vp, vp, C.POINTER(VerifyOpts)]
+        L.gusto_get_verify.argtypes = [vp, C.POINTER(VerifyReport)]
+        L.gusto_interpolate.argtypes = [vp, vp, vp, C.POINTER(VerifyOpts), C.POINTER(ci)]
+        L.gusto_get_dense.argtypes = [vp, vp, vp, vp]
+        L.gusto_last_verify_ms.argtypes = [vp, C.POINTER(C.c_double)]
         L.gusto_default_trajopt_params.argtypes = [ci, C.POINTER(TrajOptParams)]
         L.gusto_create_trajopt.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci]
         L.gusto_set_trajopt_params.argtypes = [vp, C.POINTER(TrajOptParams)]
@@ -182,6 +204,12 @@ def default_trajopt_params(model):
 def default_ipm_opts():
     o = IpmOpts()
     lib().gusto_default_ipm_opts(C.byref(o))
+    return o
+
+
+def default_verify_opts():
+    o = VerifyOpts()
+    lib().gusto_default_verify_opts(C.byref(o))
     return o
 
 
@@ -412,6 +440,52 @@ class BatchSolver:
                                          X.ctypes.data, U.ctypes.data), "get_shoot")
         return dict(status=st, newton_iters=it, resid=res, p0=pp, X=X, U=U)
 
+    def _verify_args(self, X, U, opts):
+        if (X is None) != (U is None):
+            raise ValueError("verify / interpolate: X and U are given together or not at all")
+        o = default_verify_opts()
+        for k, v in opts.items():
+            if k not in ("dt_min", "nstep", "nstep_cap", "dense_collision"):
+                raise TypeError(f"unknown verify option {k!r}")
+            setattr(o, k, float(v) if k == "dt_min" else int(v))
+        Xa = None if X is None else _arr(X).reshape(self.B, self.N, self.n)
+        Ua = None if U is None else _arr(U).reshape(self.B, self.N, self.m)
+        return Xa, Ua, o
+
+    def get_verify(self):
+        """gusto_get_verify: the report of the last verify() / interpolate() as a dict of [B] arrays."""
+        out = {k: np.zeros(self.B, dtype=t) for k, t in VERIFY_FIELDS}
+        rep = VerifyReport(**{k: v.ctypes.data for k, v in out.items()})
+        self._chk(self.L.gusto_get_verify(self.h, C.byref(rep)), "get_verify")
+        out["collision_free"] = out["collision_free"].astype(bool)
+        return out
+
+    def verify(self, X=None, U=None, **opts):
+        """gusto_verify + gusto_get_verify: collision check at the knots, forward-Euler defect, RK4 roll-out between the knots
+        (dense minimum distance, gap at the knots) of X, U (default: the handle's trajectories, left as they are).
+        opts: dt_min, nstep, nstep_cap, dense_collision (gusto_verify_opts)."""
+        Xa, Ua, o = self._verify_args(X, U, opts)
+        self._chk(self.L.gusto_verify(self.h, None if Xa is None else Xa.ctypes.data, None if Ua is None else Ua.ctypes.data,
+                                      C.byref(o)), "verify")
+        return self.get_verify()
+
+    def interpolate(self, X=None, U=None, **opts):
+        """gusto_interpolate + gusto_get_dense: (nfull [B], Xfull [B, nfull_max, n], Ufull [B, nfull_max - 1, m]); rows behind
+        nfull[b] are zeros.  get_verify() then holds the report of the same pass."""
+        Xa, Ua, o = self._verify_args(X, U, opts)
+        nf = C.c_int()
+        self._chk(self.L.gusto_interpolate(self.h, None if Xa is None else Xa.ctypes.data,
+                                           None if Ua is None else Ua.ctypes.data, C.byref(o), C.byref(nf)), "interpolate")
+        nfull = np.zeros(self.B, dtype=np.int32)
+        Xf, Uf = np.zeros((self.B, nf.value, self.n)), np.zeros((self.B, nf.value - 1, self.m))
+        self._chk(self.L.gusto_get_dense(self.h, nfull.ctypes.data, Xf.ctypes.data, Uf.ctypes.data), "get_dense")
+        return nfull, Xf, Uf
+
+    def last_verify_ms(self):
+        ms = C.c_double()
+        self._chk(self.L.gusto_last_verify_ms(self.h, C.byref(ms)), "last_verify_ms")
+        return ms.value
+
     def subproblem(self, Xp, Up, Delta, omega, toggle):
         B = self.B
         Xp, Up = _arr(Xp).reshape(B, self.N, self.n), _arr(Up).reshape(B, self.N, self.m)
@@ -473,3 +547,8 @@ class TrajOptSolver(BatchSolver):
 
     def shoot(self, *a, **k):
         raise GustoError("TrajOptSolver: shooting belongs to the GuSTO path")
+
+    def verify(self, *a, **k):
+        raise GustoError("TrajOptSolver: verify / interpolate are not supported on TrajOpt handles (gusto_verify answers GUSTO_ERR_ARG)")
+
+    interpolate = verify

@@ -164,6 +164,9 @@ int gusto_destroy(gusto_handle h) {
                     h->d_to_mu, h->d_to_xtol, h->d_to_ftol, h->d_to_ctol, h->d_Upub, h->d_env, h->d_gX, h->d_gU, h->d_active};
     for (void* p : ptrs) if (p) hipFree(p);
     for (void* p : {(void*)h->d_shX, (void*)h->d_shU, (void*)h->d_shP, (void*)h->d_shP0, (void*)h->d_shRes, (void*)h->d_shSt, (void*)h->d_shIt, (void*)h->d_shList, (void*)h->d_shXt, (void*)h->d_shUt}) if (p) hipFree(p);
+    for (void* p : {(void*)h->d_vI, (void*)h->d_vD, (void*)h->d_vX, (void*)h->d_vU, (void*)h->d_vXf, (void*)h->d_vUf}) if (p) hipFree(p);
+    if (h->ev_v0) hipEventDestroy(h->ev_v0);
+    if (h->ev_v1) hipEventDestroy(h->ev_v1);
     if (h->d_order) hipFree(h->d_order);
     if (h->d_queue) hipFree(h->d_queue);
     if (h->d_sched_ord) hipFree(h->d_sched_ord);
@@ -341,7 +344,7 @@ static int set_problems_impl(gusto_handle h, int B, const double* x_init, const 
     }
     int rc = do_init(h, X0 == nullptr);
     if (rc) return rc;
-    h->have_problems = true; h->have_shoot = false;
+    h->have_problems = true; h->have_shoot = false; h->have_verify = false; h->have_dense = false;
     h->n_active = -1;   // (gusto_set_active belongs to the problems it was set for)
     return GUSTO_OK;
 }

@@ -64,6 +64,15 @@ struct gusto_handle_s {
     double *d_shX = nullptr, *d_shU = nullptr, *d_shP = nullptr, *d_shP0 = nullptr, *d_shRes = nullptr;
     double *d_shXt = nullptr, *d_shUt = nullptr;   // knot-major staging of the shooting trajectories ([N][n][B])
     int *d_shSt = nullptr, *d_shIt = nullptr, *d_shList = nullptr;
+    // post-solve verification (verify.hip): the report ([4][batch_cap] ints: collision_free, first_knot, min_dense_sample, nfull;
+    // [5][batch_cap] doubles: first_dist, min_dist_knots, dyn_defect_l1, min_dist_dense, max_gap), copies of a caller's X / U,
+    // the dense trajectories of gusto_interpolate ([batch_cap][dense_rows][n], [batch_cap][dense_rows - 1][m]), its own events
+    int* d_vI = nullptr;
+    double *d_vD = nullptr, *d_vX = nullptr, *d_vU = nullptr, *d_vXf = nullptr, *d_vUf = nullptr;
+    int dense_rows = 0;
+    bool have_verify = false, have_dense = false;
+    hipEvent_t ev_v0 = nullptr, ev_v1 = nullptr;
+    double last_verify_ms = 0.0;
     std::string err;
 };
 

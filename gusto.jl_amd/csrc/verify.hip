@@ -1,0 +1,349 @@
+// verify.hip -- batched post-solve verification: interpolate_traj, dynamics_constraint_satisfaction and
+// verify_collision_free of the two Astrobee model files, for every problem of a batch and every model of the library.
+//   interpolate_traj                   src/dynamics/astrobee_se3_manifold.jl:1011-1042, astrobee_se3.jl:495-527
+//   dynamics_constraint_satisfaction   astrobee_se3_manifold.jl:1044-1055, astrobee_se3.jl:529-540
+//   verify_collision_free              astrobee_se3_manifold.jl:1057-1077, astrobee_se3.jl:542-560
+// One WORKGROUP per problem, 64 ceil(N / 64) lanes, lane k = knot k and the interval k -> k + 1.  A lane evaluates the signed
+// distances of its knot, the forward-Euler defect of its interval and rolls its interval out: Nstep = ceil(dt / dt_min)
+// classical RK4 steps of dt / Nstep from X[:,k] under the held control U[:,k] (every interval restarts from its knot, as the
+// reference does).  The per-problem numbers are reductions over the lanes -- DPP / v_readlane inside a wave, LDS across the
+// waves (common.hpp: block_reduce) -- in a fixed order and without atomics: a problem's report is the same bit for bit
+// whatever batch it sits in.  Dynamics: Dyn<MODEL>::f; distances: signed_distance<WS> at the workspace location the solver
+// uses (the first WS states plus the component offset, every component of mp.n_robot_comp), obstacle tables read through
+// the constant address space with a wave-uniform index (models.hpp), shared (gusto_set_env) or per problem
+// (gusto_set_env_batch).
+// verify_collision_free looks at the KNOTS only and returns the first hit of its loop nest, obstacle-major: a lane keeps the
+// first (component, obstacle) pair that penetrates at its knot, the key (component n_obs + obstacle) N + knot orders the
+// hits of all lanes as the reference's loops would meet them (components outermost, as in trust_region_ratio_gusto; the
+// reference's function has rb_idx = 1 only).  What the reference lacks -- the smallest distance over ALL dense samples, the
+// sample it occurs at and the gap between the end of a rolled-out interval and the next knot (the value its
+// `Xfull[:,istart] = X[:,k]` overwrites) -- is reported next to it.
+// Stores of the dense trajectory: lane k owns the Nstep n consecutive doubles of its interval, Nstep n doubles away from its
+// neighbour's -- a cache line per lane per store if written directly.  The samples of DENSE_TILE substeps are staged in LDS
+// ([lane][substep][i]) and copied out by the whole workgroup, consecutive threads to consecutive addresses inside each
+// lane's DENSE_TILE n doubles; the held controls are copied straight from U (thread e writes double e of the problem).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "handle.hpp"
+#include "models.hpp"
+
+using namespace gusto;
+
+namespace {
+
+constexpr int DENSE_TILE = 4;      // substeps staged in LDS per copy-out: 4 n doubles per lane (26.6 KB for N <= 64, n = 13)
+constexpr int NO_HIT = 1 << 30;    // (keys stay below 2 * 64 * 256)
+
+struct VerifyArgs {
+    const double *X, *U;           // [B][N][n], [B][N][m]: the handle's trajectories or the caller's copies
+    const int* active;             // gusto_set_active: null = every problem, else the mask [B]
+    double dt_min;
+    int nstep, dense_collision;
+    int nfull_max;                 // rows per problem of Xfull (dense output only)
+    int *collision_free, *first_knot, *min_dense_sample, *nfull;
+    double *first_dist, *min_dist_knots, *dyn_defect_l1, *min_dist_dense, *max_gap;
+    double *Xfull, *Ufull;         // [B][nfull_max][n], [B][nfull_max - 1][m]
+};
+
+// smallest signed distance of the robot at state x over components and obstacles; with `hit`: the first penetrating pair in
+// loop order (its ordinal and distance)
+template <int MODEL> GD double min_distance(const KParams& P, const Env& E, const double* x, int* hit, double* hit_d) {
+    using T = MT<MODEL>;
+    double dmin = INFINITY;
+    for (int c = 0; c < P.mp.n_robot_comp; c++)
+        for (int i = 0; i < E.n_obs; i++) {
+            double nh[T::WS];
+            const double d = signed_distance<T::WS>(P, E, c, x, i, nh);
+            dmin = fmin(dmin, d);
+            if (hit && d < 0 && *hit == NO_HIT) { *hit = c * E.n_obs + i; *hit_d = d; }
+        }
+    return dmin;
+}
+
+template <int MODEL, bool DENSE> __global__ void __launch_bounds__(256) verify_kernel(const KParams P, const VerifyArgs V) {
+    using T = MT<MODEL>;
+    constexpr int n = T::n, m = T::m;
+    extern __shared__ double stage[];   // DENSE: [lanes][DENSE_TILE][n]
+    __shared__ double sred[8];
+    const int b = blockIdx.x, k = threadIdx.x, N = P.N, nt = blockDim.x;
+    if (V.active && !V.active[b]) return;   // (the whole workgroup: an inactive problem's report is left as it is)
+    const double dt = P.tf[b] / (N - 1);
+    const int nstep = V.nstep > 0 ? V.nstep : (int)ceil(dt / V.dt_min);   // (the host has checked 1 <= nstep <= nstep_cap)
+    const int nfull = nstep * (N - 1) + 1;
+    if (DENSE && nfull > V.nfull_max) return;
+    const double h = dt / nstep;
+    const double* X = V.X + (size_t)b * N * n;
+    const double* U = V.U + (size_t)b * N * m;
+    const bool knot = k < N, ival = k < N - 1;
+    double x[n], xn[n], u[m];
+#pragma unroll
+    for (int i = 0; i < n; i++) { x[i] = knot ? X[k * n + i] : 0.0; xn[i] = ival ? X[(k + 1) * n + i] : 0.0; }
+#pragma unroll
+    for (int i = 0; i < m; i++) u[i] = knot ? U[k * m + i] : 0.0;
+    const Env E = problem_env(P, b);
+
+    // verify_collision_free: the knots
+    double dk = INFINITY, hit_d = 0.0;
+    int hit = NO_HIT;
+    if constexpr (T::HAS_OBS) {
+        if (knot) {
+            dk = min_distance<MODEL>(P, E, x, &hit, &hit_d);
+            if (hit != NO_HIT) hit = hit * N + k;
+        }
+    }
+    // dynamics_constraint_satisfaction: the forward-Euler defect of the interval
+    double defect = 0.0;
+    if (ival) {
+        double f[n];
+        Dyn<MODEL>::f(P.mp, x, u, f);
+#pragma unroll
+        for (int i = 0; i < n; i++) defect += fabs((xn[i] - x[i]) / dt - f[i]);
+    }
+    // interpolate_traj: the interval from its knot, zero-order hold of u
+    double dd = INFINITY, gap = 0.0;
+    int di = -1;
+    double* Xf = DENSE ? V.Xfull + (size_t)b * V.nfull_max * n : nullptr;
+    for (int s0 = 0; s0 < nstep; s0 += DENSE_TILE) {
+        const int cnt = min(DENSE_TILE, nstep - s0);
+        for (int s = s0; s < s0 + cnt; s++) {
+            const bool samp = ival || (k == N - 1 && s == 0);   // (the last dense sample is the last knot)
+            if constexpr (T::HAS_OBS) {
+                if (samp && V.dense_collision) {
+                    const double d = min_distance<MODEL>(P, E, x, nullptr, nullptr);
+                    if (d < dd) { dd = d; di = k * nstep + s; }
+                }
+            }
+            if constexpr (DENSE) {
+                if (samp)
+#pragma unroll
+                    for (int i = 0; i < n; i++) stage[(k * DENSE_TILE + (s - s0)) * n + i] = x[i];
+            }
+            if (ival) {
+                double k1[n], k2[n], k3[n], k4[n], w[n];
+                Dyn<MODEL>::f(P.mp, x, u, k1);
+#pragma unroll
+                for (int i = 0; i < n; i++) w[i] = x[i] + 0.5 * h * k1[i];
+                Dyn<MODEL>::f(P.mp, w, u, k2);
+#pragma unroll
+                for (int i = 0; i < n; i++) w[i] = x[i] + 0.5 * h * k2[i];
+                Dyn<MODEL>::f(P.mp, w, u, k3);
+#pragma unroll
+                for (int i = 0; i < n; i++) w[i] = x[i] + h * k3[i];
+                Dyn<MODEL>::f(P.mp, w, u, k4);
+#pragma unroll
+                for (int i = 0; i < n; i++) x[i] = x[i] + 1.0 / 6.0 * h * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
+            }
+        }
+        if constexpr (DENSE) {
+            __syncthreads();
+            for (int e = k; e < nt * DENSE_TILE * n; e += nt) {
+                const int kk = e / (DENSE_TILE * n), r = e % (DENSE_TILE * n);
+                const int rows = kk < N - 1 ? cnt : ((kk == N - 1 && s0 == 0) ? 1 : 0);
+                if (r / n < rows) Xf[((size_t)kk * nstep + s0) * n + r] = stage[e];
+            }
+            __syncthreads();
+        }
+    }
+    if (ival) {
+#pragma unroll
+        for (int i = 0; i < n; i++) gap = nanmax(gap, fabs(x[i] - xn[i]));
+    }
+    if constexpr (DENSE) {   // held controls, and zeros behind the problem's own samples
+        double* Uf = V.Ufull + (size_t)b * (V.nfull_max - 1) * m;
+        for (int e = k; e < (nfull - 1) * m; e += nt) Uf[e] = U[(e / m / nstep) * m + e % m];
+        for (int e = (nfull - 1) * m + k; e < (V.nfull_max - 1) * m; e += nt) Uf[e] = 0.0;
+        for (int e = nfull * n + k; e < V.nfull_max * n; e += nt) Xf[e] = 0.0;
+    }
+
+    const double dk_all = block_reduce(dk, OpMin(), sred);
+    const int first = (int)block_reduce((double)hit, OpMin(), sred);
+    const double def_all = block_reduce(defect, OpSum(), sred);
+    const double dd_all = block_reduce(dd, OpMin(), sred);
+    const int di_all = (int)block_reduce((di >= 0 && dd == dd_all) ? (double)di : (double)NO_HIT, OpMin(), sred);
+    const double gap_all = block_reduce(gap, OpNanMax(), sred);
+    if (first != NO_HIT && hit == first) V.first_dist[b] = hit_d;   // (one lane: keys are distinct)
+    if (k == 0) {
+        V.collision_free[b] = first == NO_HIT;
+        V.first_knot[b] = first == NO_HIT ? 0 : first % N + 1;
+        if (first == NO_HIT) V.first_dist[b] = 0.0;
+        V.min_dist_knots[b] = dk_all;
+        V.dyn_defect_l1[b] = def_all;
+        V.min_dist_dense[b] = dd_all;
+        V.min_dense_sample[b] = di_all == NO_HIT ? -1 : di_all;
+        V.max_gap[b] = gap_all;
+        if (DENSE) V.nfull[b] = nfull;
+    }
+}
+
+template <int MODEL> int launch_verify(gusto_handle h, const KParams& P, const VerifyArgs& V, bool dense) {
+    const int nt = 64 * ((h->N + 63) / 64);
+    if (dense) {
+        const size_t lds = sizeof(double) * nt * DENSE_TILE * MT<MODEL>::n;
+        auto kern = &verify_kernel<MODEL, true>;
+        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, dim3(h->B), dim3(nt), lds, h->stream, P, V);
+    } else {
+        hipLaunchKernelGGL((verify_kernel<MODEL, false>), dim3(h->B), dim3(nt), 0, h->stream, P, V);
+    }
+    HIPCHK(h, hipGetLastError());
+    return GUSTO_OK;
+}
+
+int verify_impl(gusto_handle h, const double* X, const double* U, const gusto_verify_opts* opts, bool dense, int* nfull_max, const char* who) {
+    if (!h) return GUSTO_ERR_ARG;
+    const std::string w(who);
+    if (h->trajopt) { h->err = w + ": TrajOpt handle (its controls carry the defect variables; not supported)"; return GUSTO_ERR_ARG; }
+    if (!h->have_problems) { h->err = w + ": call gusto_set_problems first"; return GUSTO_ERR_STATE; }
+    if ((X == nullptr) != (U == nullptr)) { h->err = w + ": X and U are given together or not at all"; return GUSTO_ERR_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    { int rc = gusto_finish(h); if (rc) return rc; }
+    gusto_verify_opts o;
+    gusto_default_verify_opts(&o);
+    if (opts) o = *opts;
+    if (o.nstep < 0 || o.nstep_cap < 1 || (o.nstep == 0 && !(o.dt_min > 0)) || (o.dense_collision != 0 && o.dense_collision != 1)) {
+        h->err = w + ": bad options";
+        return GUSTO_ERR_ARG;
+    }
+    const size_t B = h->B, Bc = h->batch_cap, N = h->N, n = h->n, m = h->m;
+    const bool has_obs = h->model != GUSTO_DUBINS_CAR;
+    if (has_obs && h->d_env && h->env_B != h->B) {
+        h->err = w + ": gusto_set_env_batch was called with a different number of problems than gusto_set_problems";
+        return GUSTO_ERR_STATE;
+    }
+    // Nstep of every problem: never clamped
+    int nstep_max = o.nstep;
+    if (o.nstep == 0) {
+        std::vector<double> tf(B);
+        HIPCHK(h, hipMemcpyAsync(tf.data(), h->d_tf, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (size_t b = 0; b < B; b++) {
+            const double q = ceil(tf[b] / (double)(N - 1) / o.dt_min);
+            if (!(q >= 1 && q <= (double)o.nstep_cap)) {
+                h->err = w + ": problem " + std::to_string(b) + " needs ceil(dt / dt_min) = " + std::to_string(q) + " substeps, outside 1 .. nstep_cap";
+                return GUSTO_ERR_ARG;
+            }
+            nstep_max = std::max(nstep_max, (int)q);
+        }
+    } else if (o.nstep > o.nstep_cap) {
+        h->err = w + ": nstep above nstep_cap";
+        return GUSTO_ERR_ARG;
+    }
+    if (!h->d_vI) {
+        HIPCHK(h, dalloc(&h->d_vI, 4 * Bc)); HIPCHK(h, dalloc(&h->d_vD, 5 * Bc));
+        HIPCHK(h, hipMemsetAsync(h->d_vI, 0, sizeof(int) * 4 * Bc, h->stream));
+        HIPCHK(h, hipMemsetAsync(h->d_vD, 0, sizeof(double) * 5 * Bc, h->stream));
+        HIPCHK(h, hipEventCreate(&h->ev_v0)); HIPCHK(h, hipEventCreate(&h->ev_v1));
+    }
+    VerifyArgs V{};
+    V.X = h->d_X; V.U = h->d_U;
+    if (X) {   // the caller's trajectories: copies of their own, the handle's stay as they are
+        if (!h->d_vX) { HIPCHK(h, dalloc(&h->d_vX, Bc * N * n)); HIPCHK(h, dalloc(&h->d_vU, Bc * N * m)); }
+        HIPCHK(h, hipMemcpyAsync(h->d_vX, X, sizeof(double) * B * N * n, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_vU, U, sizeof(double) * B * N * m, hipMemcpyHostToDevice, h->stream));
+        V.X = h->d_vX; V.U = h->d_vU;
+    }
+    V.active = h->n_active >= 0 ? h->d_active : nullptr;
+    V.dt_min = o.dt_min; V.nstep = o.nstep; V.dense_collision = o.dense_collision;
+    V.collision_free = h->d_vI; V.first_knot = h->d_vI + Bc; V.min_dense_sample = h->d_vI + 2 * Bc; V.nfull = h->d_vI + 3 * Bc;
+    V.first_dist = h->d_vD; V.min_dist_knots = h->d_vD + Bc; V.dyn_defect_l1 = h->d_vD + 2 * Bc; V.min_dist_dense = h->d_vD + 3 * Bc;
+    V.max_gap = h->d_vD + 4 * Bc;
+    if (dense) {
+        const int nf = nstep_max * (int)(N - 1) + 1;
+        if (nf != h->dense_rows) {   // another layout: a new buffer, zeros everywhere
+            if (h->d_vXf) hipFree(h->d_vXf);
+            if (h->d_vUf) hipFree(h->d_vUf);
+            h->d_vXf = h->d_vUf = nullptr; h->dense_rows = 0; h->have_dense = false;
+            HIPCHK(h, dalloc(&h->d_vXf, Bc * nf * n)); HIPCHK(h, dalloc(&h->d_vUf, Bc * (nf - 1) * m));
+            HIPCHK(h, hipMemsetAsync(h->d_vXf, 0, sizeof(double) * Bc * nf * n, h->stream));
+            HIPCHK(h, hipMemsetAsync(h->d_vUf, 0, sizeof(double) * Bc * (nf - 1) * m, h->stream));
+            HIPCHK(h, hipMemsetAsync(V.nfull, 0, sizeof(int) * Bc, h->stream));
+            h->dense_rows = nf;
+        }
+        V.nfull_max = nf; V.Xfull = h->d_vXf; V.Ufull = h->d_vUf;
+    }
+    KParams P;
+    memset(&P, 0, sizeof(P));
+    P.N = h->N; P.B = h->B; P.mp = h->mp; P.tf = h->d_tf;
+    if (has_obs) {
+        P.box = h->d_box; P.sph = h->d_sph;
+        if (h->d_env) { P.n_obs = h->n_obs_max; P.env = h->d_env; }
+        else { P.n_box = h->n_box; P.n_sph = h->n_sph; P.n_obs = h->n_box + h->n_sph; }
+    }
+    HIPCHK(h, hipEventRecord(h->ev_v0, h->stream));
+    int rc = GUSTO_ERR_ARG;
+    switch (h->model) {
+    case GUSTO_FREEFLYER_SE2: rc = launch_verify<GUSTO_FREEFLYER_SE2>(h, P, V, dense); break;
+    case GUSTO_DUBINS_CAR: rc = launch_verify<GUSTO_DUBINS_CAR>(h, P, V, dense); break;
+    case GUSTO_ASTROBEE_SE3: rc = launch_verify<GUSTO_ASTROBEE_SE3>(h, P, V, dense); break;
+    case GUSTO_ASTROBEE_SE3_MANIFOLD: rc = launch_verify<GUSTO_ASTROBEE_SE3_MANIFOLD>(h, P, V, dense); break;
+    }
+    if (rc) return rc;
+    HIPCHK(h, hipEventRecord(h->ev_v1, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev_v0, h->ev_v1));
+    h->last_verify_ms = ms;
+    h->have_verify = true;
+    if (dense) { h->have_dense = true; if (nfull_max) *nfull_max = V.nfull_max; }
+    return GUSTO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gusto_default_verify_opts(gusto_verify_opts* o) {
+    if (!o) return GUSTO_ERR_ARG;
+    o->dt_min = 0.1;           // interpolate_traj(traj, SCPP, dt_min=0.1)
+    o->nstep = 0; o->nstep_cap = 64; o->dense_collision = 1;
+    return GUSTO_OK;
+}
+
+int gusto_verify(gusto_handle h, const double* X, const double* U, const gusto_verify_opts* o) {
+    return verify_impl(h, X, U, o, false, nullptr, "gusto_verify");
+}
+
+int gusto_interpolate(gusto_handle h, const double* X, const double* U, const gusto_verify_opts* o, int* nfull_max) {
+    return verify_impl(h, X, U, o, true, nfull_max, "gusto_interpolate");
+}
+
+int gusto_get_verify(gusto_handle h, gusto_verify_report* out) {
+    if (h) { int rcw = gusto_finish(h); if (rcw) return rcw; }
+    if (!h || !out) return GUSTO_ERR_ARG;
+    if (!h->have_verify) { h->err = "gusto_get_verify: call gusto_verify first"; return GUSTO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t B = h->B, Bc = h->batch_cap;
+#define CPV(dst, src) if (dst) HIPCHK(h, hipMemcpy(dst, src, sizeof(*(dst)) * B, hipMemcpyDeviceToHost))
+    CPV(out->collision_free, h->d_vI); CPV(out->first_knot, h->d_vI + Bc); CPV(out->min_dense_sample, h->d_vI + 2 * Bc);
+    CPV(out->first_dist, h->d_vD); CPV(out->min_dist_knots, h->d_vD + Bc); CPV(out->dyn_defect_l1, h->d_vD + 2 * Bc);
+    CPV(out->min_dist_dense, h->d_vD + 3 * Bc); CPV(out->max_gap, h->d_vD + 4 * Bc);
+#undef CPV
+    return GUSTO_OK;
+}
+
+int gusto_get_dense(gusto_handle h, int* nfull, double* Xfull, double* Ufull) {
+    if (h) { int rcw = gusto_finish(h); if (rcw) return rcw; }
+    if (!h) return GUSTO_ERR_ARG;
+    if (!h->have_dense) { h->err = "gusto_get_dense: call gusto_interpolate first"; return GUSTO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t B = h->B, Bc = h->batch_cap, nf = h->dense_rows;
+    if (nfull) HIPCHK(h, hipMemcpy(nfull, h->d_vI + 3 * Bc, sizeof(int) * B, hipMemcpyDeviceToHost));
+    if (Xfull) HIPCHK(h, hipMemcpy(Xfull, h->d_vXf, sizeof(double) * B * nf * h->n, hipMemcpyDeviceToHost));
+    if (Ufull) HIPCHK(h, hipMemcpy(Ufull, h->d_vUf, sizeof(double) * B * (nf - 1) * h->m, hipMemcpyDeviceToHost));
+    return GUSTO_OK;
+}
+
+int gusto_last_verify_ms(gusto_handle h, double* ms) {
+    if (!h || !ms) return GUSTO_ERR_ARG;
+    if (!h->have_verify) { h->err = "gusto_last_verify_ms: call gusto_verify first"; return GUSTO_ERR_STATE; }
+    *ms = h->last_verify_ms;
+    return GUSTO_OK;
+}
+
+}  // extern "C"

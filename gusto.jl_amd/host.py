@@ -524,6 +524,54 @@ def solve_SCPshooting_batch(TOSs, TOPs, solve_method=None, init_method=init_traj
 
 
 # ---- batch API (new: the reference has no batch mode) --------------------------------------------------------------
+# ---- post-solve checks of the Astrobee model files on the device (csrc/verify.hip) --------------------------------
+def _verify_handle(traj, SCPP, device=0):
+    """A one-problem handle that holds `traj` as its trajectory: the model, robot scalars and Workspace of SCPP."""
+    model = SCPP.PD.model
+    n, N = model.x_dim, SCPP.N
+    if traj.X.shape != (n, N):
+        raise ValueError("traj does not have the problem's x_dim x N")
+    env = SCPP.PD.env
+    bs = BatchSolver(model.model_id, N, 1, hist_cap=8, device=device, boxes=env.boxes, spheres=env.spheres,
+                     scp_params=SCPP.scp_params, model_params=SCPP.model_params)
+    lo, hi = _goal_bounds(SCPP.PD.goal_set, n, SCPP.tf_guess)
+    bs.set_problems(SCPP.PD.x_init[None], lo[None], hi[None], [traj.Tf], traj.X.T[None].copy(), traj.U.T[None].copy())
+    return bs
+
+
+def interpolate_traj(traj, SCPP, dt_min=0.1):
+    """astrobee_se3_manifold.jl:1011-1042: the trajectory at Nstep = ceil(dt / dt_min) RK4 samples per knot interval, every
+    interval restarted from its knot under the held control; a Trajectory with X x_dim x Nfull, U u_dim x (Nfull - 1)."""
+    bs = _verify_handle(traj, SCPP)
+    try:
+        nfull, Xf, Uf = bs.interpolate(dt_min=dt_min, nstep_cap=max(64, int(np.ceil(traj.dt / dt_min))))
+    finally:
+        bs.close()
+    out = Trajectory(Xf[0, :nfull[0]].T.copy(), Uf[0, :nfull[0] - 1].T.copy(), traj.Tf)
+    return out
+
+
+def verify_collision_free(traj, SCPP):
+    """astrobee_se3_manifold.jl:1057-1077: (free, k, dist) -- the first knot (1-based) whose signed distance is negative, in
+    the reference's obstacle-major order; (True, 0, 0.0) for a free trajectory."""
+    bs = _verify_handle(traj, SCPP)
+    try:
+        r = bs.verify(nstep=1, dense_collision=0)
+    finally:
+        bs.close()
+    return bool(r["collision_free"][0]), int(r["first_knot"][0]), float(r["first_dist"][0])
+
+
+def dynamics_constraint_satisfaction(traj, SCPP):
+    """astrobee_se3_manifold.jl:1044-1055: sum_k |(x_{k+1} - x_k) / dt - f(x_k, u_k)|_1."""
+    bs = _verify_handle(traj, SCPP)
+    try:
+        r = bs.verify(nstep=1, dense_collision=0)
+    finally:
+        bs.close()
+    return float(r["dyn_defect_l1"][0])
+
+
 def shard_bounds(B, world_size, rank):
     """Contiguous block of ceil(B/G) problems per rank; the tail rank may get fewer."""
     per = -(-B // world_size)
@@ -532,8 +580,12 @@ def shard_bounds(B, world_size, rank):
 
 
 def solve_SCP_batch(TOSs, TOPs, solve_method=None, init_method=init_traj_straightline, solver="hip", max_iter=30,
-                    force=False, device=0, devices=None, decomposition=0):
+                    force=False, device=0, devices=None, decomposition=0, verify=False):
     """All TOPs must share model and N (each may bring its own environment); one gusto_solve covers the whole list.
+
+    `verify` (GuSTO handles only): one gusto_verify per shard after its solve; every SCPS then carries `verify`, the dict of its
+    problem's report (collision_free, first_knot, first_dist, min_dist_knots, dyn_defect_l1, min_dist_dense, min_dense_sample,
+    max_gap).  A dict of gusto_verify_opts fields instead of True sets them.  Without it the solutions are what they were.
 
     `decomposition` (gusto_set_decomposition; GuSTO handles only): 0 = the library's choice by batch size -- for the 12/13-state
     models two or four wavefronts per problem while the batch leaves SIMDs idle --, 1 one wave per problem, 3 / 4 two / four.
@@ -544,6 +596,8 @@ def solve_SCP_batch(TOSs, TOPs, solve_method=None, init_method=init_traj_straigh
     if solve_method not in (None, solve_gusto_hip, solve_trajopt_hip):
         raise NotImplementedError("solve_SCP_batch! runs the batched kernels: solve_method must be solve_gusto_hip or solve_trajopt_hip")
     trajopt = solve_method is solve_trajopt_hip
+    if verify and trajopt:
+        raise NotImplementedError("solve_SCP_batch!: verify is not available for TrajOpt handles")
     if len(TOSs) != len(TOPs) or not TOPs:
         raise ValueError("solve_SCP_batch!: need as many solutions as problems, at least one")
     TOP0 = TOPs[0]
@@ -601,10 +655,13 @@ def solve_SCP_batch(TOSs, TOPs, solve_method=None, init_method=init_traj_straigh
         bs.wait()
         snap = _fetch(bs, None if gathered is None else (gathered[0][b0:b1], gathered[1][b0:b1]))
         per = bs.last_solve_ms() * 1e-3 / (b1 - b0)
+        rep = bs.verify(**(verify if isinstance(verify, dict) else {})) if verify else None
         for b in range(b0, b1):
             SCPP = SCPProblem(TOPs[b])
             SCPS = SCPSolution(SCPP, inits[b])
             (_fill_trajopt_solution if trajopt else _fill_solution)(SCPS, SCPP, snap, b - b0, per)
+            if rep is not None:
+                SCPS.verify = {k: v[b - b0].item() for k, v in rep.items()}
             TOSs[b].traj, TOSs[b].SCPS = SCPS.traj, SCPS
             out[b] = SCPS
     return out

@@ -377,3 +377,55 @@ function solve_trajopt_batch!(TOSs::Vector, TOPs::Vector, init_method=init_traj_
   end
   nothing
 end
+
+# ---- post-solve verification on the GPU (gusto_verify / gusto_interpolate, csrc/verify.hip) ---------------------------------
+# interpolate_traj, dynamics_constraint_satisfaction and verify_collision_free of the Astrobee model files
+# (astrobee_se3_manifold.jl:1011-1077) for every problem of a handle, plus the smallest distance over the dense samples and
+# the gap between a rolled-out interval and its next knot.  GuSTO handles only (TrajOpt handles answer GUSTO_ERR_ARG).
+struct GustoVerifyOpts      # gusto_verify_opts
+  dt_min::Cdouble; nstep::Cint; nstep_cap::Cint; dense_collision::Cint
+end
+mutable struct GustoVerifyReport      # gusto_verify_report
+  collision_free::Ptr{Cint}; first_knot::Ptr{Cint}
+  first_dist::Ptr{Cdouble}; min_dist_knots::Ptr{Cdouble}; dyn_defect_l1::Ptr{Cdouble}; min_dist_dense::Ptr{Cdouble}
+  min_dense_sample::Ptr{Cint}
+  max_gap::Ptr{Cdouble}
+end
+
+# the report of B problems of handle h as a NamedTuple of vectors; X [n,N,B], U [m,N,B] or nothing = the handle's own trajectories
+function verify_batch!(h::Ptr{Cvoid}, B::Integer, X=nothing, U=nothing; dt_min=0.1, nstep=0, nstep_cap=64, dense_collision=true)
+  Xp = X === nothing ? Ptr{Cdouble}(C_NULL) : pointer(X); Up = U === nothing ? Ptr{Cdouble}(C_NULL) : pointer(U)
+  GC.@preserve X U gusto_check(ccall((:gusto_verify, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{GustoVerifyOpts}),
+                    h, Xp, Up, GustoVerifyOpts(dt_min, nstep, nstep_cap, dense_collision ? 1 : 0)), h, "verify")
+  free, knot, sample = zeros(Cint, B), zeros(Cint, B), zeros(Cint, B)
+  dist, dknots, defect, ddense, gap = zeros(B), zeros(B), zeros(B), zeros(B), zeros(B)
+  GC.@preserve free knot sample dist dknots defect ddense gap begin
+    rep = GustoVerifyReport(pointer(free), pointer(knot), pointer(dist), pointer(dknots), pointer(defect), pointer(ddense),
+                            pointer(sample), pointer(gap))
+    gusto_check(ccall((:gusto_get_verify, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoVerifyReport}), h, rep), h, "get_verify")
+  end
+  (collision_free = free .!= 0, first_knot = Int.(knot), first_dist = dist, min_dist_knots = dknots, dyn_defect_l1 = defect,
+   min_dist_dense = ddense, min_dense_sample = Int.(sample), max_gap = gap)
+end
+
+# interpolate_traj(traj, SCPP, dt_min) on the handle that solved SCPS (solve_gusto_hip!): the Trajectory at Nstep RK4 samples per interval
+function interpolate_traj_hip(traj::Trajectory, SCPS::SCPSolution, dt_min=0.1)
+  h = get(GUSTO_HANDLES, SCPS, C_NULL)
+  h == C_NULL && error("interpolate_traj_hip: run solve_gusto_hip! on this SCPSolution first")
+  n, N = size(traj.X); m = size(traj.U, 1)
+  X, U = Float64.(traj.X), Float64.(traj.U)
+  nmax = Ref{Cint}(0)
+  gusto_check(ccall((:gusto_interpolate, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{GustoVerifyOpts}, Ref{Cint}),
+                    h, X, U, GustoVerifyOpts(dt_min, 0, max(64, ceil(Int, traj.dt / dt_min)), 1), nmax), h, "interpolate")
+  nfull, Xf, Uf = zeros(Cint, 1), zeros(n, nmax[]), zeros(m, nmax[] - 1)
+  gusto_check(ccall((:gusto_get_dense, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}), h, nfull, Xf, Uf), h, "get_dense")
+  Trajectory(Xf[:, 1:nfull[1]], Uf[:, 1:nfull[1]-1], traj.Tf)
+end
+
+# verify_collision_free(traj, SCPP) on the handle that solved SCPS: (free, k, dist) as the reference returns them
+function verify_collision_free_hip(traj::Trajectory, SCPS::SCPSolution)
+  h = get(GUSTO_HANDLES, SCPS, C_NULL)
+  h == C_NULL && error("verify_collision_free_hip: run solve_gusto_hip! on this SCPSolution first")
+  r = verify_batch!(h, 1, Float64.(traj.X), Float64.(traj.U); nstep=1, dense_collision=false)
+  r.collision_free[1], r.first_knot[1], r.first_dist[1]
+end

@@ -238,6 +238,51 @@ int gusto_shoot(gusto_handle h, const double* p0, const gusto_shoot_opts* opts);
  * U [B][N][m] the recovered trajectory of the :Optimal problems (shooting.jl:26-36).  Any pointer may be NULL. */
 int gusto_get_shoot(gusto_handle h, int* status, int* newton_iters, double* resid, double* p0, double* X, double* U);
 
+/* Post-solve verification of every problem of the batch (csrc/verify.hip): interpolate_traj, dynamics_constraint_satisfaction
+ * and verify_collision_free of the Astrobee model files (astrobee_se3_manifold.jl:1011-1077, astrobee_se3.jl:495-560), for all
+ * four models.  X [B][N][x_dim], U [B][N][u_dim]: host trajectories to check, or NULL, NULL = the handle's current ones (SCPS.traj);
+ * neither call changes the handle's trajectories, status or histories.  Honours the keep-out sets of gusto_set_env / _batch and
+ * gusto_set_active (an inactive problem's report is left as the last call wrote it).  Runs on the handle's stream, after any
+ * pending gusto_solve_async; timed with events of its own (gusto_last_solve_ms keeps its value).
+ * Roll-out: every interval k -> k+1 restarts from X[:,k], holds U[:,k] and takes Nstep_b classical RK4 steps of dt_b / Nstep_b,
+ * Nstep_b = nstep if nstep > 0, else ceil(dt_b / dt_min), dt_b = tf_b / (N - 1).  An Nstep_b above nstep_cap (or below 1) is
+ * GUSTO_ERR_ARG for the whole call: the count is never clamped.  The dense trajectory has Nstep_b (N - 1) + 1 samples, the last
+ * one X[:,N].  dense_collision = 0 skips the distances at the dense samples (min_dist_dense = +inf, min_dense_sample = -1).
+ * TrajOpt handles answer GUSTO_ERR_ARG: their device-side controls carry the defect variables; not supported here. */
+typedef struct {
+    double dt_min;        /* interpolate_traj(traj, SCPP, dt_min=0.1) */
+    int nstep;            /* > 0: this many substeps for every problem; 0 (default): ceil(dt / dt_min) */
+    int nstep_cap;        /* default 64 */
+    int dense_collision;  /* default 1 */
+} gusto_verify_opts;
+int gusto_default_verify_opts(gusto_verify_opts* o);
+int gusto_verify(gusto_handle h, const double* X, const double* U, const gusto_verify_opts* o);
+/* Caller-owned arrays [B]; any pointer may be NULL.
+ * collision_free, first_knot, first_dist: verify_collision_free as written -- knots only, `dist < 0` on the raw signed distance
+ *   (clearance is read there and unused), the first hit in the reference's obstacle-major loop order (obstacle, then knot; robot
+ *   components outermost); first_knot is 1-based, and 0 with first_dist 0.0 when the trajectory is free.
+ * min_dist_knots: smallest signed distance over knots, obstacles and robot components.
+ * dyn_defect_l1: sum_k |(x_{k+1} - x_k) / dt - f(x_k, u_k)|_1, dynamics_constraint_satisfaction (forward Euler, as written).
+ * min_dist_dense, min_dense_sample: smallest signed distance over all dense samples and the 0-based sample it occurs at (the
+ *   first one on a tie); not in the reference.
+ * max_gap: max_k |xhat_{k+1} - X[:,k+1]|_inf, xhat_{k+1} the end of the roll-out of interval k (the value interpolate_traj
+ *   overwrites with the knot).
+ * DubinsCar (no keep-out set), or an empty one: the distances are +inf, collision_free 1, min_dense_sample -1. */
+typedef struct {
+    int *collision_free, *first_knot;
+    double *first_dist, *min_dist_knots, *dyn_defect_l1, *min_dist_dense;
+    int *min_dense_sample;
+    double *max_gap;
+} gusto_verify_report;
+int gusto_get_verify(gusto_handle h, gusto_verify_report* out);
+/* gusto_verify that also keeps the dense trajectories on the device: nfull_max (may be NULL) receives the row count of the
+ * buffers, the largest Nstep_b (N - 1) + 1 of the batch.  gusto_get_dense copies them out: nfull [B], Xfull [B][nfull_max][x_dim],
+ * Ufull [B][nfull_max - 1][u_dim] (the held controls); the rows behind nfull[b] (Ufull: nfull[b] - 1) are zeros.  Only this call
+ * allocates the dense buffers.  GPU time of the last gusto_verify / gusto_interpolate kernel: gusto_last_verify_ms. */
+int gusto_interpolate(gusto_handle h, const double* X, const double* U, const gusto_verify_opts* o, int* nfull_max);
+int gusto_get_dense(gusto_handle h, int* nfull, double* Xfull, double* Ufull);
+int gusto_last_verify_ms(gusto_handle h, double* ms);
+
 /* One convex subproblem per problem (what scp_gusto.jl:82-104 builds and solves in one trip), linearised at
  * (Xp,Up)[b] with the given Delta/omega/obstacle_toggle_distance[b].  Used by the parity tests.
  * Outputs: Xn,Un [B][N][.], obj [B] (JuMP.objective_value), status [B] (GUSTO_SOLVER_*), iters [B]. */
