@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libgusto_hip.so")
 MAXN, MAXM = 13, 6
 
 FREEFLYER_SE2, DUBINS_CAR, ASTROBEE_SE3, ASTROBEE_SE3_MANIFOLD = 0, 1, 2, 3
-MODEL_DIMS = {0: (6, 3), 1: (3, 1), 2: (12, 6), 3: (13, 6)}
+MODEL_DIMS = {0: (6, 3), 1: (3, 1), 2: (12, 6), 3: (13, 6)}   # (x_dim, u_dim): lib() checks it against gusto_model_dims
 SCP_STATUS = {0: "NA", 1: "OK", 2: "InaccurateModel", 3: "ViolatesConstraints", 4: "TrustRegionViolated"}
 SOLVER_STATUS = {0: "NA", 1: "OPTIMAL", 2: "ALMOST_LOCALLY_SOLVED", 3: "FAILED"}
 STOP_REASON = {0: "MaxIter", 1: "Converged", 2: "SubproblemFailed", 3: "OmegaMaxExceeded", 4: "HistoryFull"}
@@ -181,6 +181,10 @@ def lib():
         L.gusto_solve_trajopt_async.argtypes = [vp, ci]
         L.gusto_get_trajopt_history.argtypes = [vp, C.POINTER(TrajOptHistory)]
         L.gusto_subproblem_trajopt.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        n, m = ci(), ci()
+        for model, dims in MODEL_DIMS.items():   # the library's model table (csrc/handle.hpp) is the source
+            if L.gusto_model_dims(model, C.byref(n), C.byref(m)) or (n.value, m.value) != dims:
+                raise RuntimeError(f"MODEL_DIMS[{model}] = {dims}, libgusto_hip.so says {(n.value, m.value)}")
         _lib = L
     return _lib
 
@@ -215,6 +219,18 @@ def default_verify_opts():
 
 def _arr(a, dtype=np.float64):
     return np.ascontiguousarray(np.asarray(a, dtype=dtype))
+
+
+class _View:
+    """__cuda_array_interface__ v2 of a float64 device array: lets torch wrap a raw device pointer without a copy"""
+
+    def __init__(self, ptr, shape):
+        self.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(int(ptr), False), version=2)
+
+
+def _dev_view(ptr, shape, device):
+    import torch
+    return torch.as_tensor(_View(ptr, shape), device=torch.device("cuda", device))
 
 
 class GustoError(RuntimeError):
@@ -351,17 +367,10 @@ class BatchSolver:
     def traj_dev(self):
         """gusto_get_traj_dev as zero-copy torch views of the handle's HBM buffers: X [B,N,n], U [B,N,m] (valid until
         the next set_problems / solve on this handle).  For device-side consumers, e.g. the RCCL gather."""
-        import torch
         px, pu = C.c_void_p(), C.c_void_p()
         self._chk(self.L.gusto_get_traj_dev(self.h, C.byref(px), C.byref(pu)), "get_traj_dev")
-
-        class _View:       # __cuda_array_interface__ v2: lets torch wrap a raw device pointer without a copy
-            def __init__(self, ptr, shape):
-                self.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(int(ptr), False), version=2)
-
-        dev = torch.device("cuda", self.device)
-        return (torch.as_tensor(_View(px.value, (self.B, self.N, self.n)), device=dev),
-                torch.as_tensor(_View(pu.value, (self.B, self.N, self.m)), device=dev))
+        return (_dev_view(px.value, (self.B, self.N, self.n), self.device),
+                _dev_view(pu.value, (self.B, self.N, self.m), self.device))
 
     def gather_peer(self, sources, host=True):
         """gusto_gather_peer: the shards of `sources` (BatchSolvers, one per GPU, solves possibly still in flight) onto this
@@ -378,15 +387,8 @@ class BatchSolver:
         assert bt.value == Bt
         if host:
             return X, U
-        import torch
-
-        class _View:
-            def __init__(self, ptr, shape):
-                self.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(int(ptr), False), version=2)
-
-        dev = torch.device("cuda", self.device)
-        return (torch.as_tensor(_View(px.value, (Bt, self.N, self.n)), device=dev),
-                torch.as_tensor(_View(pu.value, (Bt, self.N, self.m)), device=dev))
+        return (_dev_view(px.value, (Bt, self.N, self.n), self.device),
+                _dev_view(pu.value, (Bt, self.N, self.m), self.device))
 
     def status(self):
         a = [np.zeros(self.B, dtype=np.int32) for _ in range(5)]

@@ -19,13 +19,10 @@ thread_local std::string g_err;
 extern "C" {
 
 int gusto_model_dims(int model, int* n, int* m) {
-    switch (model) {
-    case GUSTO_FREEFLYER_SE2: *n = 6; *m = 3; return GUSTO_OK;
-    case GUSTO_DUBINS_CAR: *n = 3; *m = 1; return GUSTO_OK;
-    case GUSTO_ASTROBEE_SE3: *n = 12; *m = 6; return GUSTO_OK;
-    case GUSTO_ASTROBEE_SE3_MANIFOLD: *n = 13; *m = 6; return GUSTO_OK;
-    }
-    return GUSTO_ERR_ARG;
+    const ModelInfo* mi = model_info(model);
+    if (!mi) return GUSTO_ERR_ARG;
+    *n = mi->n; *m = mi->m;
+    return GUSTO_OK;
 }
 
 int gusto_default_params(int model, gusto_scp_params* sp, gusto_model_params* mp) {
@@ -100,7 +97,7 @@ static int create_impl(gusto_handle* out, int model, int N, int batch_cap, int h
         g_err = "gusto_create: no usable HIP device (libgusto_hip has no CPU fallback)";
         return GUSTO_ERR_NO_DEVICE;
     }
-    if (trajopt && model != GUSTO_FREEFLYER_SE2 && model != GUSTO_ASTROBEE_SE3 && model != GUSTO_ASTROBEE_SE3_MANIFOLD) {
+    if (trajopt && model_info(model)->trajopt_variant < 0) {
         g_err = "gusto_create_trajopt: FreeflyerSE2, AstrobeeSE3 and AstrobeeSE3Manifold have a TrajOpt variant";
         return GUSTO_ERR_ARG;
     }
@@ -109,8 +106,7 @@ static int create_impl(gusto_handle* out, int model, int N, int batch_cap, int h
     h->model_pub = model; h->m_pub = m; h->trajopt = trajopt;
     gusto_default_params(model, &h->sp, &h->mp);
     if (trajopt) {   // internal variant: controls (u, d), d = the n defect variables of a knot
-        h->model = model == GUSTO_FREEFLYER_SE2 ? gusto::GUSTO_TO_FREEFLYER_SE2
-                 : (model == GUSTO_ASTROBEE_SE3 ? gusto::GUSTO_TO_ASTROBEE_SE3 : gusto::GUSTO_TO_ASTROBEE_SE3_MANIFOLD);
+        h->model = model_info(model)->trajopt_variant;
         h->m = m = m + n;
         gusto_default_trajopt_params(model, &h->tp);
     }
@@ -119,24 +115,21 @@ static int create_impl(gusto_handle* out, int model, int N, int batch_cap, int h
     HIPCHK(h, hipSetDevice(device));
     HIPCHK(h, hipStreamCreate(&h->stream));
     h->own_stream = true;
-    HIPCHK(h, hipEventCreate(&h->ev0));
-    HIPCHK(h, hipEventCreate(&h->ev1));
+    HIPCHK(h, h->ev0.create());
+    HIPCHK(h, h->ev1.create());
     const size_t B = batch_cap, H = hist_cap;
-    HIPCHK(h, dalloc(&h->d_X, B * N * n)); HIPCHK(h, dalloc(&h->d_U, B * N * m));
-    HIPCHK(h, dalloc(&h->d_xinit, B * n)); HIPCHK(h, dalloc(&h->d_glo, B * n)); HIPCHK(h, dalloc(&h->d_ghi, B * n));
-    HIPCHK(h, dalloc(&h->d_tf, B));
-    HIPCHK(h, dalloc(&h->d_sti, B * ST_NI)); HIPCHK(h, dalloc(&h->d_std, B * SD_ND));
-    HIPCHK(h, dalloc(&h->d_Jt, B * H)); HIPCHK(h, dalloc(&h->d_Jf, B * H)); HIPCHK(h, dalloc(&h->d_conv, B * H));
-    HIPCHK(h, dalloc(&h->d_Delta, B * H)); HIPCHK(h, dalloc(&h->d_omega, B * H)); HIPCHK(h, dalloc(&h->d_rho, B * H));
-    HIPCHK(h, dalloc(&h->d_acc, B * H)); HIPCHK(h, dalloc(&h->d_scp, B * H)); HIPCHK(h, dalloc(&h->d_sol, B * H));
-    HIPCHK(h, dalloc(&h->d_tr, B * H)); HIPCHK(h, dalloc(&h->d_cvx, B * H)); HIPCHK(h, dalloc(&h->d_ipm, B * H));
-    HIPCHK(h, dalloc(&h->d_subD, B)); HIPCHK(h, dalloc(&h->d_subW, B)); HIPCHK(h, dalloc(&h->d_subT, B));
-    HIPCHK(h, dalloc(&h->d_subX, B * N * n)); HIPCHK(h, dalloc(&h->d_subU, B * N * m)); HIPCHK(h, dalloc(&h->d_subObj, B));
-    HIPCHK(h, dalloc(&h->d_subSt, B)); HIPCHK(h, dalloc(&h->d_subIt, B));
-    HIPCHK(h, dalloc(&h->d_box, 1)); HIPCHK(h, dalloc(&h->d_sph, 1));
+    HIPCHK(h, h->d_X.alloc(B * N * n)); HIPCHK(h, h->d_U.alloc(B * N * m));
+    HIPCHK(h, h->d_xinit.alloc(B * n)); HIPCHK(h, h->d_glo.alloc(B * n)); HIPCHK(h, h->d_ghi.alloc(B * n));
+    HIPCHK(h, h->d_tf.alloc(B));
+    HIPCHK(h, h->d_sti.alloc(B * ST_NI)); HIPCHK(h, h->d_std.alloc(B * SD_ND));
+    for (auto* b : {&h->d_Jt, &h->d_Jf, &h->d_conv, &h->d_Delta, &h->d_omega, &h->d_rho}) HIPCHK(h, b->alloc(B * H));
+    for (auto* b : {&h->d_acc, &h->d_scp, &h->d_sol, &h->d_tr, &h->d_cvx, &h->d_ipm}) HIPCHK(h, b->alloc(B * H));
+    HIPCHK(h, h->d_subD.alloc(B)); HIPCHK(h, h->d_subW.alloc(B)); HIPCHK(h, h->d_subT.alloc(B));
+    HIPCHK(h, h->d_subX.alloc(B * N * n)); HIPCHK(h, h->d_subU.alloc(B * N * m)); HIPCHK(h, h->d_subObj.alloc(B));
+    HIPCHK(h, h->d_subSt.alloc(B)); HIPCHK(h, h->d_subIt.alloc(B));
+    HIPCHK(h, h->d_box.alloc(1)); HIPCHK(h, h->d_sph.alloc(1));
     if (trajopt) {
-        HIPCHK(h, dalloc(&h->d_to_mu, B * H)); HIPCHK(h, dalloc(&h->d_to_xtol, B * H));
-        HIPCHK(h, dalloc(&h->d_to_ftol, B * H)); HIPCHK(h, dalloc(&h->d_to_ctol, B * H));
+        for (auto* b : {&h->d_to_mu, &h->d_to_xtol, &h->d_to_ftol, &h->d_to_ctol}) HIPCHK(h, b->alloc(B * H));
     }
     return GUSTO_OK;
 }
@@ -147,7 +140,7 @@ int gusto_create_trajopt(gusto_handle* out, int model, int N, int batch_cap, int
     return create_impl(out, model, N, batch_cap, hist_cap, device, true);
 }
 int gusto_default_trajopt_params(int model, gusto_trajopt_params* tp) {   // freeflyer_se2.jl:49-64, astrobee_se3.jl:50-65, astrobee_se3_manifold.jl:56-70
-    if (!tp || (model != GUSTO_FREEFLYER_SE2 && model != GUSTO_ASTROBEE_SE3 && model != GUSTO_ASTROBEE_SE3_MANIFOLD)) return GUSTO_ERR_ARG;
+    if (!tp || !model_info(model) || model_info(model)->trajopt_variant < 0) return GUSTO_ERR_ARG;
     memset(tp, 0, sizeof(*tp));
     tp->mu0 = 1.0; tp->c = 10.0; tp->tau_plus = 2.0; tp->tau_minus = 0.5; tp->k = 5.0; tp->ftol = 0.01; tp->ctol = 0.01;
     tp->max_penalty_iteration = 5; tp->max_convex_iteration = 5; tp->max_trust_iteration = 5;
@@ -158,32 +151,8 @@ int gusto_default_trajopt_params(int model, gusto_trajopt_params* tp) {   // fre
 int gusto_destroy(gusto_handle h) {
     if (!h) return GUSTO_ERR_ARG;
     hipSetDevice(h->device);
-    void* ptrs[] = {h->d_X, h->d_U, h->d_xinit, h->d_glo, h->d_ghi, h->d_tf, h->d_sti, h->d_std, h->d_Jt, h->d_Jf, h->d_conv,
-                    h->d_Delta, h->d_omega, h->d_rho, h->d_acc, h->d_scp, h->d_sol, h->d_tr, h->d_cvx, h->d_ipm, h->d_ws,
-                    h->d_prof, h->d_subD, h->d_subW, h->d_subT, h->d_subX, h->d_subU, h->d_subObj, h->d_subSt, h->d_subIt, h->d_box, h->d_sph,
-                    h->d_to_mu, h->d_to_xtol, h->d_to_ftol, h->d_to_ctol, h->d_Upub, h->d_env, h->d_gX, h->d_gU, h->d_active};
-    for (void* p : ptrs) if (p) hipFree(p);
-    for (void* p : {(void*)h->d_shX, (void*)h->d_shU, (void*)h->d_shP, (void*)h->d_shP0, (void*)h->d_shRes, (void*)h->d_shSt, (void*)h->d_shIt, (void*)h->d_shList, (void*)h->d_shXt, (void*)h->d_shUt}) if (p) hipFree(p);
-    for (void* p : {(void*)h->d_vI, (void*)h->d_vD, (void*)h->d_vX, (void*)h->d_vU, (void*)h->d_vXf, (void*)h->d_vUf}) if (p) hipFree(p);
-    if (h->ev_v0) hipEventDestroy(h->ev_v0);
-    if (h->ev_v1) hipEventDestroy(h->ev_v1);
-    if (h->d_order) hipFree(h->d_order);
-    if (h->d_queue) hipFree(h->d_queue);
-    if (h->d_sched_ord) hipFree(h->d_sched_ord);
-    if (h->h_sched_err) hipHostFree(h->h_sched_err);
-    if (h->ev_gather) hipEventDestroy(h->ev_gather);
-    if (h->ev0) hipEventDestroy(h->ev0);
-    if (h->ev1) hipEventDestroy(h->ev1);
-    if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
     delete h;
     return GUSTO_OK;
-}
-
-// every setter first completes an enqueued solve (gusto_solve_async) on the handle's own device; a latched scheduler error
-// is not the setter's business (handle.hpp: it is surfaced by the getters and the solves until gusto_set_problems)
-static int setter_enter(gusto_handle h) {
-    HIPCHK(h, hipSetDevice(h->device));
-    return gusto_complete(h);
 }
 
 int gusto_set_params(gusto_handle h, const gusto_scp_params* sp, const gusto_model_params* mp) {
@@ -230,11 +199,10 @@ int gusto_set_env(gusto_handle h, int n_box, const double* box, int n_sph, const
     if (!h || n_box < 0 || n_sph < 0 || (n_box && !box) || (n_sph && !sph)) return GUSTO_ERR_ARG;
     if (n_box + n_sph > 64) { h->err = "gusto_set_env: at most 64 keep-out components"; return GUSTO_ERR_ARG; }
     { int rc = setter_enter(h); if (rc) return rc; }
-    hipFree(h->d_box); hipFree(h->d_sph);
-    h->d_box = h->d_sph = nullptr;
-    if (h->d_env) { hipFree(h->d_env); h->d_env = nullptr; }   // back to one keep-out set for the whole batch
+    h->d_box.reset(); h->d_sph.reset();
+    h->d_env.reset();   // back to one keep-out set for the whole batch
     h->env_B = 0; h->n_obs_max = 0;
-    HIPCHK(h, dalloc(&h->d_box, (size_t)6 * n_box)); HIPCHK(h, dalloc(&h->d_sph, (size_t)4 * n_sph));
+    HIPCHK(h, h->d_box.alloc((size_t)6 * n_box)); HIPCHK(h, h->d_sph.alloc((size_t)4 * n_sph));
     if (n_box) HIPCHK(h, hipMemcpy(h->d_box, box, sizeof(double) * 6 * n_box, hipMemcpyHostToDevice));
     if (n_sph) HIPCHK(h, hipMemcpy(h->d_sph, sph, sizeof(double) * 4 * n_sph, hipMemcpyHostToDevice));
     h->n_box = n_box; h->n_sph = n_sph;
@@ -264,11 +232,9 @@ int gusto_set_env_batch(gusto_handle h, int B, const int* n_box, const double* b
     }
     if ((tb && !box) || (ts && !sph)) return GUSTO_ERR_ARG;
     { int rc = setter_enter(h); if (rc) return rc; }
-    hipFree(h->d_box); hipFree(h->d_sph);
-    h->d_box = h->d_sph = nullptr;
-    if (h->d_env) { hipFree(h->d_env); h->d_env = nullptr; }
+    h->d_box.reset(); h->d_sph.reset(); h->d_env.reset();
     h->env_B = 0; h->n_obs_max = 0; h->n_box = 0; h->n_sph = 0;
-    HIPCHK(h, dalloc(&h->d_box, 6 * tb)); HIPCHK(h, dalloc(&h->d_sph, 4 * ts)); HIPCHK(h, dalloc(&h->d_env, (size_t)4 * B));
+    HIPCHK(h, h->d_box.alloc(6 * tb)); HIPCHK(h, h->d_sph.alloc(4 * ts)); HIPCHK(h, h->d_env.alloc((size_t)4 * B));
     if (tb) HIPCHK(h, hipMemcpy(h->d_box, box, sizeof(double) * 6 * tb, hipMemcpyHostToDevice));
     if (ts) HIPCHK(h, hipMemcpy(h->d_sph, sph, sizeof(double) * 4 * ts, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->d_env, rec.data(), sizeof(int) * rec.size(), hipMemcpyHostToDevice));
@@ -278,26 +244,17 @@ int gusto_set_env_batch(gusto_handle h, int B, const int* n_box, const double* b
 
 }  // extern "C"
 
+// the launches of every internal model id (handle.hpp: ModelOps, one object per model_<id>.hip)
+static const ModelOps& (*const MODEL_OPS[])() = {model_ops<0>, model_ops<1>, model_ops<2>, model_ops<3>, model_ops<4>, model_ops<5>, model_ops<6>};
+
 static int do_init(gusto_handle h, bool straight) {
-    switch (h->model) {
-    case 0: return gusto_launch_init_m0(h, straight);
-    case 1: return gusto_launch_init_m1(h, straight);
-    case 2: return gusto_launch_init_m2(h, straight);
-    case 3: return gusto_launch_init_m3(h, straight);
-    case 4: return gusto_launch_init_m4(h, straight);
-    case 5: return gusto_launch_init_m5(h, straight);
-    case 6: return gusto_launch_init_m6(h, straight);
-    }
-    return GUSTO_ERR_ARG;
+    const auto f = MODEL_OPS[h->model]().init;
+    return f ? f(h, straight) : GUSTO_ERR_ARG;
 }
 static int do_trajopt(gusto_handle h, int mode, int max_iter) {
-    switch (h->model) {
-    case 4: return gusto_launch_trajopt_m4(h, mode, max_iter);
-    case 5: return gusto_launch_trajopt_m5(h, mode, max_iter);
-    case 6: return gusto_launch_trajopt_m6(h, mode, max_iter);
-    }
-    h->err = "not a TrajOpt handle (gusto_create_trajopt)";
-    return GUSTO_ERR_STATE;
+    const auto f = MODEL_OPS[h->model]().trajopt;
+    if (!f) { h->err = "not a TrajOpt handle (gusto_create_trajopt)"; return GUSTO_ERR_STATE; }
+    return f(h, mode, max_iter);
 }
 // U between the caller (u_dim columns) and the device (TrajOpt handles keep u | defect per knot: m columns)
 static hipError_t copy_U(gusto_handle h, double* dst, const double* src, bool to_device, hipMemcpyKind kind) {
@@ -312,13 +269,20 @@ static hipError_t copy_U(gusto_handle h, double* dst, const double* src, bool to
 }
 static int do_scp(gusto_handle h, int mode, int max_iter, int force) {
     if (h->trajopt) { h->err = "TrajOpt handle: use gusto_solve_trajopt / gusto_subproblem_trajopt"; return GUSTO_ERR_STATE; }
-    switch (h->model) {
-    case 0: return gusto_launch_scp_m0(h, mode, max_iter, force);
-    case 1: return gusto_launch_scp_m1(h, mode, max_iter, force);
-    case 2: return gusto_launch_scp_m2(h, mode, max_iter, force);
-    case 3: return gusto_launch_scp_m3(h, mode, max_iter, force);
-    }
-    return GUSTO_ERR_ARG;
+    const auto f = MODEL_OPS[h->model]().scp;
+    return f ? f(h, mode, max_iter, force) : GUSTO_ERR_ARG;
+}
+// the status words of every problem, [B][ST_NI]
+static int fetch_status(gusto_handle h, std::vector<int>& st) {
+    st.resize((size_t)h->B * ST_NI);
+    HIPCHK(h, hipMemcpy(st.data(), h->d_sti, sizeof(int) * st.size(), hipMemcpyDeviceToHost));
+    return GUSTO_OK;
+}
+// a history array [B][hist_cap] of the handle into the caller's rows of Ho entries (null dst: not asked for)
+template <class T> static int copy_hist(gusto_handle h, T* dst, const T* src, size_t Ho) {
+    const size_t H = h->hist_cap;
+    if (dst) HIPCHK(h, hipMemcpy2D(dst, sizeof(T) * Ho, src, sizeof(T) * H, sizeof(T) * H, h->B, hipMemcpyDeviceToHost));
+    return GUSTO_OK;
 }
 
 extern "C" {
@@ -392,7 +356,7 @@ int gusto_set_active(gusto_handle h, const int* active) {
         buf[b] = active[b] != 0;
         if (active[b]) buf[(size_t)h->batch_cap + na++] = b;
     }
-    if (!h->d_active) HIPCHK(h, dalloc(&h->d_active, (size_t)2 * h->batch_cap));
+    HIPCHK(h, h->d_active.alloc((size_t)2 * h->batch_cap));
     HIPCHK(h, hipMemcpy(h->d_active, buf.data(), sizeof(int) * buf.size(), hipMemcpyHostToDevice));
     h->n_active = na;
     return GUSTO_OK;
@@ -423,7 +387,7 @@ int gusto_dev_launch_info(gusto_handle h, int* slots, int* lds_bytes, int* per_c
 
 int gusto_dev_workspace_bytes(gusto_handle h, long long* bytes) {
     if (!h || !bytes) return GUSTO_ERR_ARG;
-    *bytes = (long long)(h->ws_doubles * sizeof(double));
+    *bytes = (long long)(h->d_ws.count() * sizeof(double));
     return GUSTO_OK;
 }
 
@@ -435,9 +399,7 @@ int gusto_last_solve_ms(gusto_handle h, double* ms) {
 }
 
 int gusto_get_traj(gusto_handle h, double* X, double* U) {
-    if (h) { int rcw = gusto_finish(h); if (rcw) return rcw; }
-    if (!h || !h->have_problems) return GUSTO_ERR_STATE;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = getter_enter(h, true)) return rc;
     if (X) HIPCHK(h, hipMemcpy(X, h->d_X, sizeof(double) * h->B * h->N * h->n, hipMemcpyDeviceToHost));
     if (U) {
         HIPCHK(h, copy_U(h, U, h->d_U, false, hipMemcpyDeviceToHost));
@@ -453,7 +415,7 @@ int gusto_get_traj_dev(gusto_handle h, const double** X, const double** U) {
     if (U) {
         if (h->trajopt) {   // device rows are (u | defect), pitch u_dim + x_dim: hand out a compact [B][N][u_dim] copy
             HIPCHK(h, hipSetDevice(h->device));
-            if (!h->d_Upub) HIPCHK(h, dalloc(&h->d_Upub, (size_t)h->batch_cap * h->N * h->m_pub));
+            HIPCHK(h, h->d_Upub.alloc((size_t)h->batch_cap * h->N * h->m_pub));
             HIPCHK(h, copy_U(h, h->d_Upub, h->d_U, false, hipMemcpyDeviceToDevice));
             HIPCHK(h, hipStreamSynchronize(h->stream));
             *U = h->d_Upub;
@@ -486,13 +448,7 @@ int gusto_gather_peer(gusto_handle dst, int n_src, const gusto_handle* src, cons
     for (int i = 0; i < n_src; i++) dst_is_src = dst_is_src || src[i] == dst;
     if (!dst_is_src) { int rc = gusto_finish(dst); if (rc) return rc; }
     const size_t N = dst->N, n = dst->n, mp = dst->m_pub;
-    if (tot > dst->gather_cap) {
-        if (dst->d_gX) hipFree(dst->d_gX);
-        if (dst->d_gU) hipFree(dst->d_gU);
-        dst->d_gX = dst->d_gU = nullptr; dst->gather_cap = 0;
-        HIPCHK(dst, dalloc(&dst->d_gX, tot * N * n)); HIPCHK(dst, dalloc(&dst->d_gU, tot * N * mp));
-        dst->gather_cap = tot;
-    }
+    HIPCHK(dst, dst->d_gX.ensure(tot * N * n)); HIPCHK(dst, dst->d_gU.ensure(tot * N * mp));
     // Every shard's copy is enqueued on ITS OWN handle's stream, right behind that shard's solve: no host-side wait for any
     // solve before the first copy is queued, and the copies of different sources run side by side -- one xGMI link per source
     // GPU, the direct fan-in of SURVEY.md 8(e) with all links busy -- instead of one after the other on dst's stream.
@@ -509,13 +465,13 @@ int gusto_gather_peer(gusto_handle dst, int n_src, const gusto_handle* src, cons
         }
         const double* su = q->d_U;
         if (q->trajopt) {     // (device rows are (u | defect): compact them on the source GPU first, on the same stream)
-            if (!q->d_Upub) HIPCHK(q, dalloc(&q->d_Upub, (size_t)q->batch_cap * q->N * q->m_pub));
+            HIPCHK(q, q->d_Upub.alloc((size_t)q->batch_cap * q->N * q->m_pub));
             HIPCHK(q, copy_U(q, q->d_Upub, q->d_U, false, hipMemcpyDeviceToDevice));
             su = q->d_Upub;
         }
         HIPCHK(q, hipMemcpyPeerAsync(dst->d_gX + at * N * n, dst->device, q->d_X, q->device, sizeof(double) * q->B * N * n, q->stream));
         HIPCHK(q, hipMemcpyPeerAsync(dst->d_gU + at * N * mp, dst->device, su, q->device, sizeof(double) * q->B * N * mp, q->stream));
-        if (!q->ev_gather) HIPCHK(q, hipEventCreateWithFlags(&q->ev_gather, hipEventDisableTiming));
+        HIPCHK(q, q->ev_gather.create(hipEventDisableTiming));
         HIPCHK(q, hipEventRecord(q->ev_gather, q->stream));
         at += q->B;
     }
@@ -541,11 +497,9 @@ int gusto_gather_peer(gusto_handle dst, int n_src, const gusto_handle* src, cons
 }
 
 int gusto_get_status(gusto_handle h, int* iterations, int* converged, int* successful, int* stop, int* ipm) {
-    if (h) { int rcw = gusto_finish(h); if (rcw) return rcw; }
-    if (!h || !h->have_problems) return GUSTO_ERR_STATE;
-    HIPCHK(h, hipSetDevice(h->device));
-    std::vector<int> st((size_t)h->B * ST_NI);
-    HIPCHK(h, hipMemcpy(st.data(), h->d_sti, sizeof(int) * st.size(), hipMemcpyDeviceToHost));
+    if (int rc = getter_enter(h, true)) return rc;
+    std::vector<int> st;
+    if (int rc = fetch_status(h, st)) return rc;
     for (int b = 0; b < h->B; b++) {
         if (iterations) iterations[b] = st[(size_t)b * ST_NI + ST_ITER];
         if (converged) converged[b] = st[(size_t)b * ST_NI + ST_CONV];
@@ -557,9 +511,8 @@ int gusto_get_status(gusto_handle h, int* iterations, int* converged, int* succe
 }
 
 int gusto_get_dual(gusto_handle h, double* dual) {
-    if (h) { int rcw = gusto_finish(h); if (rcw) return rcw; }
-    if (!h || !dual || !h->have_problems) return GUSTO_ERR_STATE;
-    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = getter_enter(h, true)) return rc;
+    if (!dual) return GUSTO_ERR_STATE;
     std::vector<double> sd((size_t)h->B * SD_ND);
     HIPCHK(h, hipMemcpy(sd.data(), h->d_std, sizeof(double) * sd.size(), hipMemcpyDeviceToHost));
     for (int b = 0; b < h->B; b++)
@@ -575,29 +528,27 @@ int gusto_get_hist_cap(gusto_handle h, int* hist_cap) {
 
 int gusto_get_history(gusto_handle h, gusto_history* o) {
     if (h && h->trajopt) { h->err = "gusto_get_history: TrajOpt handle, use gusto_get_trajopt_history"; return GUSTO_ERR_STATE; }
-    if (h) { int rcw = gusto_finish(h); if (rcw) return rcw; }
-    if (!h || !o || !h->have_problems) return GUSTO_ERR_STATE;
+    if (int rc = getter_enter(h, true)) return rc;
+    if (!o) return GUSTO_ERR_STATE;
     // o->hist_cap is the row capacity of the CALLER's arrays; rows are written with that pitch
     if (o->hist_cap < h->hist_cap) {
         h->err = "gusto_get_history: hist_cap of the output arrays is smaller than the handle's (gusto_get_hist_cap)";
         return GUSTO_ERR_ARG;
     }
-    HIPCHK(h, hipSetDevice(h->device));
-    std::vector<int> st((size_t)h->B * ST_NI);
-    HIPCHK(h, hipMemcpy(st.data(), h->d_sti, sizeof(int) * st.size(), hipMemcpyDeviceToHost));
+    std::vector<int> st;
+    if (int rc = fetch_status(h, st)) return rc;
     for (int b = 0; b < h->B; b++) {
         if (o->n_hist) o->n_hist[b] = st[(size_t)b * ST_NI + ST_NHIST];
         if (o->nJ) o->nJ[b] = st[(size_t)b * ST_NI + ST_NJ];
         if (o->n_rho) o->n_rho[b] = st[(size_t)b * ST_NI + ST_NRHO];
     }
-    const size_t H = h->hist_cap, Ho = o->hist_cap;
-#define CPD(dst, src) if (dst) HIPCHK(h, hipMemcpy2D(dst, sizeof(*(dst)) * Ho, src, sizeof(*(dst)) * H, sizeof(*(dst)) * H, h->B, hipMemcpyDeviceToHost))
-    CPD(o->J_true, h->d_Jt); CPD(o->J_full, h->d_Jf); CPD(o->convergence_measure, h->d_conv); CPD(o->Delta, h->d_Delta);
-    CPD(o->omega, h->d_omega); CPD(o->rho, h->d_rho); CPD(o->accept_solution, h->d_acc); CPD(o->scp_status, h->d_scp);
-    CPD(o->solver_status, h->d_sol); CPD(o->trust_region_satisfied, h->d_tr); CPD(o->convex_ineq_satisfied, h->d_cvx);
-    CPD(o->ipm_iters, h->d_ipm);
-#undef CPD
-    return GUSTO_OK;
+    int rc = GUSTO_OK;   // (of the first copy that fails; the ones behind it are skipped)
+    const auto cp = [&](auto* dst, const auto& src) { if (!rc) rc = copy_hist(h, dst, src.get(), o->hist_cap); };
+    cp(o->J_true, h->d_Jt); cp(o->J_full, h->d_Jf); cp(o->convergence_measure, h->d_conv); cp(o->Delta, h->d_Delta);
+    cp(o->omega, h->d_omega); cp(o->rho, h->d_rho); cp(o->accept_solution, h->d_acc); cp(o->scp_status, h->d_scp);
+    cp(o->solver_status, h->d_sol); cp(o->trust_region_satisfied, h->d_tr); cp(o->convex_ineq_satisfied, h->d_cvx);
+    cp(o->ipm_iters, h->d_ipm);
+    return rc;
 }
 
 // SCPParam_GuSTO supplied by the caller (scp_gusto.jl:60 keeps a param.alg that is already defined): overwrite the
@@ -607,8 +558,8 @@ int gusto_set_trust_state(gusto_handle h, const double* Delta, const double* ome
     if (h->trajopt) { h->err = "gusto_set_trust_state: TrajOpt handle (its trust region s and penalty mu follow SCPParam_TrajOpt)"; return GUSTO_ERR_STATE; }
     if (!h->have_problems) { h->err = "gusto_set_trust_state: call gusto_set_problems first"; return GUSTO_ERR_STATE; }
     { int rc = setter_enter(h); if (rc) return rc; }
-    std::vector<int> st((size_t)h->B * ST_NI);
-    HIPCHK(h, hipMemcpy(st.data(), h->d_sti, sizeof(int) * st.size(), hipMemcpyDeviceToHost));
+    std::vector<int> st;
+    if (int rc = fetch_status(h, st)) return rc;
     for (int b = 0; b < h->B; b++) {
         const size_t at = (size_t)b * h->hist_cap + st[(size_t)b * ST_NI + ST_NHIST] - 1;
         if (Delta) HIPCHK(h, hipMemcpy(h->d_Delta + at, Delta + b, sizeof(double), hipMemcpyHostToDevice));
@@ -672,12 +623,11 @@ int gusto_solve_trajopt(gusto_handle h, int max_iter) { return solve_trajopt_imp
 int gusto_solve_trajopt_async(gusto_handle h, int max_iter) { return solve_trajopt_impl(h, max_iter, false, "gusto_solve_trajopt_async"); }
 
 int gusto_get_trajopt_history(gusto_handle h, gusto_trajopt_history* o) {
-    if (h) { int rcw = gusto_finish(h); if (rcw) return rcw; }
-    if (!h || !o || !h->trajopt || !h->have_problems) return GUSTO_ERR_STATE;
+    if (int rc = getter_enter(h, true)) return rc;
+    if (!o || !h->trajopt) return GUSTO_ERR_STATE;
     if (o->hist_cap < h->hist_cap) { h->err = "gusto_get_trajopt_history: hist_cap of the output arrays is smaller than the handle's"; return GUSTO_ERR_ARG; }
-    HIPCHK(h, hipSetDevice(h->device));
-    std::vector<int> st((size_t)h->B * ST_NI);
-    HIPCHK(h, hipMemcpy(st.data(), h->d_sti, sizeof(int) * st.size(), hipMemcpyDeviceToHost));
+    std::vector<int> st;
+    if (int rc = fetch_status(h, st)) return rc;
     for (int b = 0; b < h->B; b++) {
         const int* q = st.data() + (size_t)b * ST_NI;
         if (o->n_solves) o->n_solves[b] = q[ST_ITER];
@@ -686,13 +636,12 @@ int gusto_get_trajopt_history(gusto_handle h, gusto_trajopt_history* o) {
         if (o->n_ftol) o->n_ftol[b] = q[ST_NFTOL];
         if (o->n_ctol) o->n_ctol[b] = q[ST_NCTOL];
     }
-    const size_t H = h->hist_cap, Ho = o->hist_cap;
-#define CPD(dst, src) if (dst) HIPCHK(h, hipMemcpy2D(dst, sizeof(*(dst)) * Ho, src, sizeof(*(dst)) * H, sizeof(*(dst)) * H, h->B, hipMemcpyDeviceToHost))
-    CPD(o->rho_vec, h->d_rho); CPD(o->s_vec, h->d_Delta); CPD(o->mu_vec, h->d_to_mu); CPD(o->xtol_vec, h->d_to_xtol);
-    CPD(o->ftol_vec, h->d_to_ftol); CPD(o->ctol_vec, h->d_to_ctol); CPD(o->J_true, h->d_Jt); CPD(o->J_full, h->d_Jf);
-    CPD(o->convergence_measure, h->d_conv); CPD(o->solver_status, h->d_sol); CPD(o->ipm_iters, h->d_ipm);
-#undef CPD
-    return GUSTO_OK;
+    int rc = GUSTO_OK;
+    const auto cp = [&](auto* dst, const auto& src) { if (!rc) rc = copy_hist(h, dst, src.get(), o->hist_cap); };
+    cp(o->rho_vec, h->d_rho); cp(o->s_vec, h->d_Delta); cp(o->mu_vec, h->d_to_mu); cp(o->xtol_vec, h->d_to_xtol);
+    cp(o->ftol_vec, h->d_to_ftol); cp(o->ctol_vec, h->d_to_ctol); cp(o->J_true, h->d_Jt); cp(o->J_full, h->d_Jf);
+    cp(o->convergence_measure, h->d_conv); cp(o->solver_status, h->d_sol); cp(o->ipm_iters, h->d_ipm);
+    return rc;
 }
 
 int gusto_subproblem_trajopt(gusto_handle h, int B, const double* Xp, const double* Up, const double* mu, const double* s,

@@ -1,10 +1,76 @@
-// handle.hpp -- the opaque gusto_handle and the per-model launch entry points (one translation unit per model).
+// handle.hpp -- the opaque gusto_handle: its owned device memory, the model table and the per-model launch operations
+// (one translation unit per model).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <utility>
 
 #include "common.hpp"
+
+// Device memory owned by the handle: freed when the handle goes, whatever entry point allocated it.  count() is the number
+// of elements asked for (0 while empty); a count of 0 still allocates one element, so get() is never null after a success.
+// A failed allocation hands the hipError_t back (HIPCHK) and leaves the buffer empty.
+template <class T> class __attribute__((visibility("hidden"))) DevBuf {
+    T* p_ = nullptr;
+    size_t n_ = 0;
+
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)), n_(std::exchange(o.n_, 0)) {}   // (move-only: no copies)
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { reset(); p_ = std::exchange(o.p_, nullptr); n_ = std::exchange(o.n_, 0); }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; n_ = 0; }
+    // allocates once: a buffer that holds memory already is left as it is
+    hipError_t alloc(size_t count) {
+        if (p_) return hipSuccess;
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, (count ? count : 1) * sizeof(T));
+        if (e == hipSuccess) { p_ = static_cast<T*>(q); n_ = count; }
+        return e;
+    }
+    // grow-only: a buffer too small is freed and allocated anew (its contents are not kept)
+    hipError_t ensure(size_t count) {
+        if (p_ && count <= n_) return hipSuccess;
+        reset();
+        return alloc(count);
+    }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    size_t count() const { return n_; }
+};
+
+// an event owned by the handle; create() is lazy and idempotent
+struct DevEvent {
+    hipEvent_t e = nullptr;
+    DevEvent() = default;
+    DevEvent(const DevEvent&) = delete;
+    ~DevEvent() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+    operator hipEvent_t() const { return e; }
+};
+
+// What the host side knows about a model, indexed by the public gusto_model_id: state and control dimensions, the internal id
+// of its TrajOpt variant (common.hpp: GUSTO_TO_*; -1 = none), whether it has keep-out sets and a shooting ODE.
+struct ModelInfo { int n, m, trajopt_variant; bool has_obs, has_shoot; };
+template <int MODEL> constexpr ModelInfo model_row(int trajopt_variant, bool has_shoot) {
+    return {gusto::MT<MODEL>::n, gusto::MT<MODEL>::m, trajopt_variant, gusto::MT<MODEL>::HAS_OBS, has_shoot};
+}
+constexpr ModelInfo MODEL_TABLE[] = {
+    model_row<GUSTO_FREEFLYER_SE2>(gusto::GUSTO_TO_FREEFLYER_SE2, false),
+    model_row<GUSTO_DUBINS_CAR>(-1, true),
+    model_row<GUSTO_ASTROBEE_SE3>(gusto::GUSTO_TO_ASTROBEE_SE3, false),
+    model_row<GUSTO_ASTROBEE_SE3_MANIFOLD>(gusto::GUSTO_TO_ASTROBEE_SE3_MANIFOLD, true),
+};
+static_assert(GUSTO_FREEFLYER_SE2 == 0 && GUSTO_DUBINS_CAR == 1 && GUSTO_ASTROBEE_SE3 == 2 && GUSTO_ASTROBEE_SE3_MANIFOLD == 3,
+              "MODEL_TABLE is indexed by gusto_model_id");
+// null: no such model
+static inline const ModelInfo* model_info(int model) {
+    return model >= 0 && model < (int)(sizeof(MODEL_TABLE) / sizeof(MODEL_TABLE[0])) ? &MODEL_TABLE[model] : nullptr;
+}
 
 struct gusto_handle_s {
     int model = 0, n = 0, m = 0, N = 0, batch_cap = 0, hist_cap = 0, device = 0, B = 0;
@@ -13,38 +79,35 @@ struct gusto_handle_s {
     bool trajopt = false;
     int m_pub = 0, model_pub = 0;
     gusto_trajopt_params tp{};
-    double *d_to_mu = nullptr, *d_to_xtol = nullptr, *d_to_ftol = nullptr, *d_to_ctol = nullptr;
+    DevBuf<double> d_to_mu, d_to_xtol, d_to_ftol, d_to_ctol;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     gusto_scp_params sp{};
     gusto_model_params mp{};
     gusto_ipm_opts io{};
     int n_box = 0, n_sph = 0;
-    double *d_box = nullptr, *d_sph = nullptr;
+    DevBuf<double> d_box, d_sph;
     // gusto_set_env_batch: one keep-out set per problem -- d_box / d_sph hold the concatenated tables, d_env the
     // (box offset, n_box, sphere offset, n_sph) record of every problem, env_B their number, n_obs_max the largest count
-    int* d_env = nullptr;
+    DevBuf<int> d_env;
     int env_B = 0, n_obs_max = 0;
-    double *d_X = nullptr, *d_U = nullptr, *d_xinit = nullptr, *d_glo = nullptr, *d_ghi = nullptr, *d_tf = nullptr;
-    int* d_sti = nullptr;
-    double* d_std = nullptr;
-    double *d_Jt = nullptr, *d_Jf = nullptr, *d_conv = nullptr, *d_Delta = nullptr, *d_omega = nullptr, *d_rho = nullptr;
-    int *d_acc = nullptr, *d_scp = nullptr, *d_sol = nullptr, *d_tr = nullptr, *d_cvx = nullptr, *d_ipm = nullptr;
-    double* d_ws = nullptr;
-    long long* d_prof = nullptr;
-    size_t ws_doubles = 0;
-    double *d_subD = nullptr, *d_subW = nullptr, *d_subT = nullptr, *d_subX = nullptr, *d_subU = nullptr, *d_subObj = nullptr;
-    int *d_subSt = nullptr, *d_subIt = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t ev_gather = nullptr;   // gusto_gather_peer: this shard's copy to the gathering GPU has been enqueued up to here
+    DevBuf<double> d_X, d_U, d_xinit, d_glo, d_ghi, d_tf;
+    DevBuf<int> d_sti;
+    DevBuf<double> d_std, d_Jt, d_Jf, d_conv, d_Delta, d_omega, d_rho;
+    DevBuf<int> d_acc, d_scp, d_sol, d_tr, d_cvx, d_ipm;
+    DevBuf<double> d_ws;       // interior point workspaces, one per resident workgroup (grown by the launches)
+    DevBuf<long long> d_prof;
+    DevBuf<double> d_subD, d_subW, d_subT, d_subX, d_subU, d_subObj;
+    DevBuf<int> d_subSt, d_subIt;
+    DevEvent ev0, ev1;
+    DevEvent ev_gather;   // gusto_gather_peer: this shard's copy to the gathering GPU has been enqueued up to here
     double last_ms = 0.0;
     bool pending = false;  // a gusto_solve_async launch has not been waited for yet
     int probe_iters = 2, probe_min_batch = 2048;  // longest-first schedule (gusto_set_schedule)
     bool sched_forced = false;                    // gusto_set_schedule was called: the caller's choice overrides the model default
-    int* d_order = nullptr;   // waiting lists of the scheduler, [SCHED_LEVELS][probe_iters * batch_cap]
-    size_t order_ints = 0;
-    int* d_queue = nullptr;   // work-queue heads, one per launch of a gusto_solve call
-    int* d_sched_ord = nullptr;   // [2][batch_cap]: difficulty bucket and hand-out order of the fresh problems (hardest first)
+    DevBuf<int> d_order;      // waiting lists of the scheduler, [SCHED_LEVELS][probe_iters * batch_cap]
+    DevBuf<int> d_queue;      // work-queue heads, one per launch of a gusto_solve call
+    DevBuf<int> d_sched_ord;  // [2][batch_cap]: difficulty bucket and hand-out order of the fresh problems (hardest first)
     int slots = 0;            // resident workgroups the last launch used (persistent kernel)
     int lds_bytes = 0, per_cu = 0;   // ... its dynamic LDS per workgroup and workgroups per CU (gusto_dev_launch_info)
     int sched_init[gusto::SQ_WORDS] = {0};   // initial scheduler words of a launch (host side of an async copy)
@@ -53,27 +116,32 @@ struct gusto_handle_s {
     int waves = 0;                 // waves per problem of the GuSTO kernel (0 = one per 64 knots; development builds: GUSTO_DEV_WAVES)
     // gusto_set_active: the problems the next gusto_solve calls iterate (n_active < 0: all of them); d_active = the mask [B]
     // (gusto_shoot reads it), d_active + batch_cap = the list of active problems (the hand-out order of the launch)
-    int* d_active = nullptr;
+    DevBuf<int> d_active;
     int n_active = -1;
     int sched_err = 0;             // latched scheduler error of the last solve (gusto_finish): getters and solves fail until the next set_problems
     int* h_sched_err = nullptr;    // pinned host word the error flag is copied to on the handle's stream, before the stream is waited for
-    double *d_gX = nullptr, *d_gU = nullptr;   // gusto_gather_peer: the shards of several handles, one after the other, on this handle's GPU
-    size_t gather_cap = 0;                     // ... capacity in problems
-    double* d_Upub = nullptr;      // TrajOpt handles: U compacted to the public [B][N][u_dim] layout for gusto_get_traj_dev
+    DevBuf<double> d_gX, d_gU;     // gusto_gather_peer: the shards of several handles, one after the other, on this handle's GPU
+    DevBuf<double> d_Upub;         // TrajOpt handles: U compacted to the public [B][N][u_dim] layout for gusto_get_traj_dev
     // indirect shooting (shoot.hip): trajectories, converged costates, seeds, residuals, status, Newton iterations
-    double *d_shX = nullptr, *d_shU = nullptr, *d_shP = nullptr, *d_shP0 = nullptr, *d_shRes = nullptr;
-    double *d_shXt = nullptr, *d_shUt = nullptr;   // knot-major staging of the shooting trajectories ([N][n][B])
-    int *d_shSt = nullptr, *d_shIt = nullptr, *d_shList = nullptr;
+    DevBuf<double> d_shX, d_shU, d_shP, d_shP0, d_shRes;
+    DevBuf<double> d_shXt, d_shUt;   // knot-major staging of the shooting trajectories ([N][n][B])
+    DevBuf<int> d_shSt, d_shIt, d_shList;
     // post-solve verification (verify.hip): the report ([4][batch_cap] ints: collision_free, first_knot, min_dense_sample, nfull;
     // [5][batch_cap] doubles: first_dist, min_dist_knots, dyn_defect_l1, min_dist_dense, max_gap), copies of a caller's X / U,
     // the dense trajectories of gusto_interpolate ([batch_cap][dense_rows][n], [batch_cap][dense_rows - 1][m]), its own events
-    int* d_vI = nullptr;
-    double *d_vD = nullptr, *d_vX = nullptr, *d_vU = nullptr, *d_vXf = nullptr, *d_vUf = nullptr;
+    DevBuf<int> d_vI;
+    DevBuf<double> d_vD, d_vX, d_vU, d_vXf, d_vUf;
     int dense_rows = 0;
     bool have_verify = false, have_dense = false;
-    hipEvent_t ev_v0 = nullptr, ev_v1 = nullptr;
+    DevEvent ev_v0, ev_v1;
     double last_verify_ms = 0.0;
     std::string err;
+
+    // (the buffers and events free themselves; the caller has made `device` current: gusto_destroy)
+    __attribute__((visibility("hidden"))) ~gusto_handle_s() {
+        if (h_sched_err) (void)hipHostFree(h_sched_err);
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
 };
 
 extern thread_local std::string g_err;
@@ -88,11 +156,6 @@ extern thread_local std::string g_err;
             return GUSTO_ERR_HIP;                                                              \
         }                                                                                      \
     } while (0)
-
-template <class Tp> static hipError_t dalloc(Tp** p, size_t count) {
-    return hipMalloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(Tp));
-}
-
 
 // completes an enqueued solve: blocks on the handle's stream and takes the kernel time from its events
 static inline int gusto_sched_err_rc(gusto_handle h) {
@@ -133,18 +196,40 @@ static inline hipError_t gusto_fetch_sched_err(gusto_handle h) {
     return hipMemcpyAsync(h->h_sched_err, h->d_queue + gusto::SQ_ERR, sizeof(int), hipMemcpyDeviceToHost, h->stream);
 }
 
-// defined in model_<id>.hip (the scp launch only enqueues; gusto_finish completes it)
-int gusto_launch_init_m0(gusto_handle h, bool straight);
-int gusto_launch_init_m1(gusto_handle h, bool straight);
-int gusto_launch_init_m2(gusto_handle h, bool straight);
-int gusto_launch_init_m3(gusto_handle h, bool straight);
-int gusto_launch_scp_m0(gusto_handle h, int mode, int max_iter, int force);
-int gusto_launch_scp_m1(gusto_handle h, int mode, int max_iter, int force);
-int gusto_launch_scp_m2(gusto_handle h, int mode, int max_iter, int force);
-int gusto_launch_scp_m3(gusto_handle h, int mode, int max_iter, int force);
-int gusto_launch_init_m4(gusto_handle h, bool straight);
-int gusto_launch_init_m5(gusto_handle h, bool straight);
-int gusto_launch_trajopt_m4(gusto_handle h, int mode, int max_iter);
-int gusto_launch_trajopt_m5(gusto_handle h, int mode, int max_iter);
-int gusto_launch_init_m6(gusto_handle h, bool straight);
-int gusto_launch_trajopt_m6(gusto_handle h, int mode, int max_iter);
+// every setter first completes an enqueued solve (gusto_solve_async) on the handle's own device; a latched scheduler error
+// is not the setter's business (it is surfaced by the getters and the solves until gusto_set_problems)
+static inline int setter_enter(gusto_handle h) {
+    HIPCHK(h, hipSetDevice(h->device));
+    return gusto_complete(h);
+}
+// every getter first completes an enqueued solve and fails with a latched scheduler error, then refuses a handle without
+// problems (need_problems) and makes the handle's device current.  A null handle is GUSTO_ERR_STATE here: the entry points
+// that answer GUSTO_ERR_ARG to one check it themselves.
+static inline int getter_enter(gusto_handle h, bool need_problems) {
+    if (!h) return GUSTO_ERR_STATE;
+    { int rc = gusto_finish(h); if (rc) return rc; }
+    if (need_problems && !h->have_problems) return GUSTO_ERR_STATE;
+    HIPCHK(h, hipSetDevice(h->device));
+    return GUSTO_OK;
+}
+
+// The keep-out part of KParams (P.B is set): one set for the whole batch (gusto_set_env), or one per problem
+// (gusto_set_env_batch: n_obs sizes the slots, the records say the rest).  false: the records describe another number of
+// problems than P.B (checked with check_B; the caller words the refusal).
+static inline bool fill_env(gusto_handle h, gusto::KParams& P, bool has_obs, bool check_B) {
+    P.n_box = h->n_box; P.n_sph = h->n_sph; P.box = h->d_box; P.sph = h->d_sph;
+    P.n_obs = has_obs ? h->n_box + h->n_sph : 0;
+    if (!has_obs || !h->d_env) return true;
+    if (check_B && h->env_B != P.B) return false;
+    P.n_obs = h->n_obs_max; P.n_box = 0; P.n_sph = 0; P.env = h->d_env;
+    return true;
+}
+
+// The launches of one model (launch.hpp), defined once in model_<id>.hip for the internal ids 0 .. 6; a null member: the
+// model has no such kernel.  (The solve launches only enqueue; gusto_finish completes them.)
+struct ModelOps {
+    int (*init)(gusto_handle, bool straight);
+    int (*scp)(gusto_handle, int mode, int max_iter, int force);
+    int (*trajopt)(gusto_handle, int mode, int max_iter);
+};
+template <int MODEL> __attribute__((visibility("hidden"))) const ModelOps& model_ops();

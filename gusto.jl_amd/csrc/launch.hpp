@@ -31,19 +31,15 @@ static inline int launch_waves(gusto_handle h) {
 template <int MODEL> static int fill_params(gusto_handle h, KParams& P, int B, bool need_env = true) {
     using T = MT<MODEL>;
     memset(&P, 0, sizeof(P));
-    P.N = h->N; P.B = B; P.n_fresh = B; P.n_box = h->n_box; P.n_sph = h->n_sph;
-    P.n_obs = T::HAS_OBS ? h->n_box + h->n_sph : 0;
-    if (T::HAS_OBS && h->d_env) {   // one keep-out set per problem (gusto_set_env_batch): n_obs sizes the slots, the records say the rest
-        if (need_env && h->env_B != B) {
-            h->err = "gusto_set_env_batch described a different number of problems than gusto_set_problems";
-            return GUSTO_ERR_STATE;
-        }
-        P.n_obs = h->n_obs_max; P.n_box = 0; P.n_sph = 0; P.env = h->d_env;
+    P.N = h->N; P.B = B; P.n_fresh = B;
+    if (!fill_env(h, P, T::HAS_OBS, need_env)) {
+        h->err = "gusto_set_env_batch described a different number of problems than gusto_set_problems";
+        return GUSTO_ERR_STATE;
     }
     P.hist_cap = h->hist_cap;
     P.sp = h->sp; P.mp = h->mp; P.io = h->io;
     warm_defaults(MODEL, P.io);
-    P.box = h->d_box; P.sph = h->d_sph; P.X = h->d_X; P.U = h->d_U;
+    P.X = h->d_X; P.U = h->d_U;
     P.x_init = h->d_xinit; P.goal_lo = h->d_glo; P.goal_hi = h->d_ghi; P.tf = h->d_tf;
     P.sub_Delta = h->d_subD; P.sub_omega = h->d_subW; P.sub_toggle = h->d_subT; P.sub_X = h->d_subX; P.sub_U = h->d_subU;
     P.sub_obj = h->d_subObj; P.sub_status = h->d_subSt; P.sub_iters = h->d_subIt;
@@ -54,11 +50,28 @@ template <int MODEL> static int fill_params(gusto_handle h, KParams& P, int B, b
     P.tp = h->tp; P.to_mu = h->d_to_mu; P.to_xtol = h->d_to_xtol; P.to_ftol = h->d_to_ftol; P.to_ctol = h->d_to_ctol;
     P.wl = make_ws_layout<MODEL>(h->N, P.n_obs);
     P.ll = make_lds_layout<MODEL>(h->N, launch_waves(h) > (h->N + 63) / 64);
-    if (!h->d_queue) HIPCHK(h, dalloc(&h->d_queue, (size_t)SQ_WORDS));
+    HIPCHK(h, h->d_queue.alloc(SQ_WORDS));
 #ifdef GUSTO_PROFILE
-    if (!h->d_prof) HIPCHK(h, dalloc(&h->d_prof, (size_t)h->batch_cap * PROF_N));
+    HIPCHK(h, h->d_prof.alloc((size_t)h->batch_cap * PROF_N));
 #endif
     P.prof = h->d_prof;
+    return GUSTO_OK;
+}
+
+// The tail of a solve launch: one workspace per workgroup of `grid`, the kernel between the handle's two events, the
+// scheduler's error word behind it.  `pre` enqueues what runs before the kernel and is timed with it.  Completed by gusto_finish.
+template <class Kern, class Pre>
+static int enqueue_solve(gusto_handle h, KParams& P, Kern kern, dim3 grid, dim3 block, size_t lds, Pre pre) {
+    HIPCHK(h, h->d_ws.ensure(P.wl.total * (size_t)grid.x));
+    P.ws = h->d_ws;
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    { int rc = pre(); if (rc) return rc; }
+    hipLaunchKernelGGL(kern, grid, block, lds, h->stream, P);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    h->sched_err = 0;
+    HIPCHK(h, gusto_fetch_sched_err(h));
+    h->pending = true;
     return GUSTO_OK;
 }
 
@@ -115,16 +128,6 @@ template <int MODEL> static int launch_scp(gusto_handle h, int mode, int max_ite
     if (const char* e = dev_env("GUSTO_DEV_SLOTS")) slots = std::max(1, atoi(e));   // occupancy experiments
     slots = std::min(slots, std::max(1, P.n_fresh));
     h->slots = slots; h->lds_bytes = (int)lds; h->per_cu = per_cu;
-    {
-        const size_t need = P.wl.total * (size_t)slots;
-        if (need > h->ws_doubles) {
-            if (h->d_ws) hipFree(h->d_ws);
-            h->d_ws = nullptr; h->ws_doubles = 0;
-            HIPCHK(h, dalloc(&h->d_ws, need));
-            h->ws_doubles = need;
-        }
-        P.ws = h->d_ws;
-    }
     // scheduler state of this launch (scp.hpp): counters to 0, waiting lists to -1
     // number of probing slices: the caller's (gusto_set_schedule) or the model's default (2; dubins_car 1)
     const int probe = h->sched_forced ? h->probe_iters : MT<MODEL>::SCHED_PROBE;
@@ -147,41 +150,30 @@ template <int MODEL> static int launch_scp(gusto_handle h, int mode, int max_ite
     // after its probing slices (slicing only moves time)
     if (pushes >= 127) { slice_q = 0; pushes = probe; }
     if (dyn) {
-        const size_t need = (size_t)SCHED_LEVELS * pushes * h->batch_cap;
-        if (need > h->order_ints) {
-            if (h->d_order) hipFree(h->d_order);
-            h->d_order = nullptr; h->order_ints = 0;
-            HIPCHK(h, dalloc(&h->d_order, need));
-            h->order_ints = need;
-        }
+        HIPCHK(h, h->d_order.ensure((size_t)SCHED_LEVELS * pushes * h->batch_cap));
         P.list_cap = pushes * h->B;
         HIPCHK(h, hipMemsetAsync(h->d_order, 0xFF, (size_t)SCHED_LEVELS * P.list_cap * sizeof(int), h->stream));
     }
     P.queue = h->d_queue; P.lists = h->d_order; P.probe_visits = dyn ? probe : 0; P.slice_q = slice_q;
     P.order = masked ? h->d_active + h->batch_cap : nullptr;
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));   // (the solve's time includes the ordering kernels below)
-    if (!masked && dyn && T::HAS_OBS && P.n_obs > 0 && !dev_env("GUSTO_DEV_NO_ORDER")) {   // hardest first (scp.hpp: sched_key_kernel)
-        if (!h->d_sched_ord) HIPCHK(h, dalloc(&h->d_sched_ord, (size_t)2 * h->batch_cap));
-        int* bucket = h->d_sched_ord;
-        int* order = h->d_sched_ord + h->batch_cap;
-        HIPCHK(h, hipMemsetAsync(bucket, 0, (size_t)h->B * sizeof(int), h->stream));
-        const int tot = h->B * h->N;
-        hipLaunchKernelGGL(sched_key_kernel<MODEL>, dim3((tot + 255) / 256), dim3(256), 0, h->stream, P, bucket);
-        hipLaunchKernelGGL(sched_order_kernel, dim3(1), dim3(1024), 0, h->stream, h->B, bucket, order);
-        HIPCHK(h, hipGetLastError());
-        P.order = order;
-    }
-    if (dev_env("GUSTO_DEV_DEBUG"))
-        fprintf(stderr, "launch: B %d slots %d dyn %d probe %d list_cap %d queue %p lists %p..%p ws %p..%p X %p st_i %p..%p hist Delta %p\n", h->B, slots,
-                (int)dyn, P.probe_visits, P.list_cap, (void*)P.queue, (void*)P.lists, (void*)(P.lists + h->order_ints), (void*)P.ws,
-                (void*)(P.ws + h->ws_doubles), (void*)P.X, (void*)P.st_i, (void*)(P.st_i + (size_t)h->batch_cap * ST_NI), (void*)P.Delta);
-    hipLaunchKernelGGL(kern, dim3(slots), dim3(NTL), lds, h->stream, P);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    h->sched_err = 0;
-    HIPCHK(h, gusto_fetch_sched_err(h));
-    h->pending = true;   // completed by gusto_finish (handle.hpp)
-    return GUSTO_OK;
+    return enqueue_solve(h, P, kern, dim3(slots), dim3(NTL), lds, [&]() -> int {   // (the solve's time includes the ordering kernels)
+        if (!masked && dyn && T::HAS_OBS && P.n_obs > 0 && !dev_env("GUSTO_DEV_NO_ORDER")) {   // hardest first (scp.hpp: sched_key_kernel)
+            HIPCHK(h, h->d_sched_ord.alloc((size_t)2 * h->batch_cap));
+            int* bucket = h->d_sched_ord;
+            int* order = h->d_sched_ord + h->batch_cap;
+            HIPCHK(h, hipMemsetAsync(bucket, 0, (size_t)h->B * sizeof(int), h->stream));
+            const int tot = h->B * h->N;
+            hipLaunchKernelGGL(sched_key_kernel<MODEL>, dim3((tot + 255) / 256), dim3(256), 0, h->stream, P, bucket);
+            hipLaunchKernelGGL(sched_order_kernel, dim3(1), dim3(1024), 0, h->stream, h->B, bucket, order);
+            HIPCHK(h, hipGetLastError());
+            P.order = order;
+        }
+        if (dev_env("GUSTO_DEV_DEBUG"))
+            fprintf(stderr, "launch: B %d slots %d dyn %d probe %d list_cap %d queue %p lists %p..%p ws %p..%p X %p st_i %p..%p hist Delta %p\n", h->B, slots,
+                    (int)dyn, P.probe_visits, P.list_cap, (void*)P.queue, (void*)P.lists, (void*)(P.lists + h->d_order.count()), (void*)P.ws,
+                    (void*)(P.ws + h->d_ws.count()), (void*)P.X, (void*)P.st_i, (void*)(P.st_i + (size_t)h->batch_cap * ST_NI), (void*)P.Delta);
+        return GUSTO_OK;
+    });
 }
 
 // TrajOpt: every problem of the batch through trajopt_kernel (scp.hpp); mode 1 = one subproblem per problem (parity hook)
@@ -200,23 +192,8 @@ template <int MODEL> static int launch_trajopt(gusto_handle h, int mode, int max
     HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
     const int slots = std::min(std::max(1, per_cu) * std::max(1, cus), h->B);
     h->slots = slots; h->lds_bytes = (int)lds; h->per_cu = per_cu;
-    const size_t need = P.wl.total * (size_t)slots;
-    if (need > h->ws_doubles) {
-        if (h->d_ws) hipFree(h->d_ws);
-        h->d_ws = nullptr; h->ws_doubles = 0;
-        HIPCHK(h, dalloc(&h->d_ws, need));
-        h->ws_doubles = need;
-    }
-    P.ws = h->d_ws;
     if (h->d_queue) HIPCHK(h, hipMemsetAsync(h->d_queue, 0, SQ_WORDS * sizeof(int), h->stream));
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(kern, dim3(slots), dim3(NT), lds, h->stream, P);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    h->sched_err = 0;
-    HIPCHK(h, gusto_fetch_sched_err(h));
-    h->pending = true;
-    return GUSTO_OK;
+    return enqueue_solve(h, P, kern, dim3(slots), dim3(NT), lds, [] { return (int)GUSTO_OK; });
 }
 
 template <int MODEL> static int launch_init(gusto_handle h, bool straight) {
@@ -234,3 +211,6 @@ template <int MODEL> static int launch_init(gusto_handle h, bool straight) {
     return GUSTO_OK;
 }
 
+// the one ModelOps object of a translation unit (handle.hpp): model_<id>.hip names the solve launch its model has, null for the other
+#define GUSTO_MODEL_OPS(MODEL, SCP, TRAJOPT) \
+    template <> const ModelOps& model_ops<MODEL>() { static const ModelOps ops{&launch_init<MODEL>, SCP, TRAJOPT}; return ops; }

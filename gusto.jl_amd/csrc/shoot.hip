@@ -359,7 +359,7 @@ int gusto_default_shoot_opts(gusto_shoot_opts* o) {
 
 int gusto_shoot(gusto_handle h, const double* p0, const gusto_shoot_opts* opts) {
     if (!h) return GUSTO_ERR_ARG;
-    if (h->model != GUSTO_DUBINS_CAR && h->model != GUSTO_ASTROBEE_SE3_MANIFOLD) {
+    if (h->trajopt || !model_info(h->model)->has_shoot) {
         h->err = "gusto_shoot: only DubinsCar and AstrobeeSE3Manifold have a shooting ODE (as in the reference)";
         return GUSTO_ERR_ARG;
     }
@@ -372,12 +372,10 @@ int gusto_shoot(gusto_handle h, const double* p0, const gusto_shoot_opts* opts) 
     if (opts) o = *opts;
     if (o.substeps < 1 || o.max_newton < 0 || !(o.ftol > 0) || (o.no_group_pass != 0 && o.no_group_pass != 1)) { h->err = "gusto_shoot: bad options"; return GUSTO_ERR_ARG; }
     const size_t B = h->batch_cap, N = h->N;
-    if (!h->d_shX) {
-        HIPCHK(h, dalloc(&h->d_shX, B * N * n)); HIPCHK(h, dalloc(&h->d_shU, B * N * m)); HIPCHK(h, dalloc(&h->d_shP, B * n));
-        HIPCHK(h, dalloc(&h->d_shXt, B * N * n)); HIPCHK(h, dalloc(&h->d_shUt, B * N * m));
-        HIPCHK(h, dalloc(&h->d_shP0, B * n)); HIPCHK(h, dalloc(&h->d_shRes, B)); HIPCHK(h, dalloc(&h->d_shSt, B)); HIPCHK(h, dalloc(&h->d_shIt, B));
-        HIPCHK(h, dalloc(&h->d_shList, B + 1));   // [B] problems for the group pass, [1] their number
-    }
+    HIPCHK(h, h->d_shX.alloc(B * N * n)); HIPCHK(h, h->d_shU.alloc(B * N * m)); HIPCHK(h, h->d_shP.alloc(B * n));
+    HIPCHK(h, h->d_shXt.alloc(B * N * n)); HIPCHK(h, h->d_shUt.alloc(B * N * m));
+    HIPCHK(h, h->d_shP0.alloc(B * n)); HIPCHK(h, h->d_shRes.alloc(B)); HIPCHK(h, h->d_shSt.alloc(B)); HIPCHK(h, h->d_shIt.alloc(B));
+    HIPCHK(h, h->d_shList.alloc(B + 1));   // [B] problems for the group pass, [1] their number
     if (p0) {
         HIPCHK(h, hipMemcpyAsync(h->d_shP0, p0, sizeof(double) * h->B * n, hipMemcpyHostToDevice, h->stream));
     } else {   // SCPS.dual of every problem (st_d rows: [toggle, spare, dual[n]])

@@ -211,8 +211,10 @@ int verify_impl(gusto_handle h, const double* X, const double* U, const gusto_ve
         return GUSTO_ERR_ARG;
     }
     const size_t B = h->B, Bc = h->batch_cap, N = h->N, n = h->n, m = h->m;
-    const bool has_obs = h->model != GUSTO_DUBINS_CAR;
-    if (has_obs && h->d_env && h->env_B != h->B) {
+    KParams P;
+    memset(&P, 0, sizeof(P));
+    P.N = h->N; P.B = h->B; P.mp = h->mp; P.tf = h->d_tf;
+    if (!fill_env(h, P, model_info(h->model)->has_obs, true)) {
         h->err = w + ": gusto_set_env_batch was called with a different number of problems than gusto_set_problems";
         return GUSTO_ERR_STATE;
     }
@@ -234,16 +236,16 @@ int verify_impl(gusto_handle h, const double* X, const double* U, const gusto_ve
         h->err = w + ": nstep above nstep_cap";
         return GUSTO_ERR_ARG;
     }
-    if (!h->d_vI) {
-        HIPCHK(h, dalloc(&h->d_vI, 4 * Bc)); HIPCHK(h, dalloc(&h->d_vD, 5 * Bc));
+    if (!h->d_vI) {   // (the report is zeroed once)
+        HIPCHK(h, h->d_vI.alloc(4 * Bc)); HIPCHK(h, h->d_vD.alloc(5 * Bc));
         HIPCHK(h, hipMemsetAsync(h->d_vI, 0, sizeof(int) * 4 * Bc, h->stream));
         HIPCHK(h, hipMemsetAsync(h->d_vD, 0, sizeof(double) * 5 * Bc, h->stream));
-        HIPCHK(h, hipEventCreate(&h->ev_v0)); HIPCHK(h, hipEventCreate(&h->ev_v1));
     }
+    HIPCHK(h, h->ev_v0.create()); HIPCHK(h, h->ev_v1.create());
     VerifyArgs V{};
     V.X = h->d_X; V.U = h->d_U;
     if (X) {   // the caller's trajectories: copies of their own, the handle's stay as they are
-        if (!h->d_vX) { HIPCHK(h, dalloc(&h->d_vX, Bc * N * n)); HIPCHK(h, dalloc(&h->d_vU, Bc * N * m)); }
+        HIPCHK(h, h->d_vX.alloc(Bc * N * n)); HIPCHK(h, h->d_vU.alloc(Bc * N * m));
         HIPCHK(h, hipMemcpyAsync(h->d_vX, X, sizeof(double) * B * N * n, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->d_vU, U, sizeof(double) * B * N * m, hipMemcpyHostToDevice, h->stream));
         V.X = h->d_vX; V.U = h->d_vU;
@@ -256,24 +258,15 @@ int verify_impl(gusto_handle h, const double* X, const double* U, const gusto_ve
     if (dense) {
         const int nf = nstep_max * (int)(N - 1) + 1;
         if (nf != h->dense_rows) {   // another layout: a new buffer, zeros everywhere
-            if (h->d_vXf) hipFree(h->d_vXf);
-            if (h->d_vUf) hipFree(h->d_vUf);
-            h->d_vXf = h->d_vUf = nullptr; h->dense_rows = 0; h->have_dense = false;
-            HIPCHK(h, dalloc(&h->d_vXf, Bc * nf * n)); HIPCHK(h, dalloc(&h->d_vUf, Bc * (nf - 1) * m));
+            h->d_vXf.reset(); h->d_vUf.reset();
+            h->dense_rows = 0; h->have_dense = false;
+            HIPCHK(h, h->d_vXf.alloc(Bc * nf * n)); HIPCHK(h, h->d_vUf.alloc(Bc * (nf - 1) * m));
             HIPCHK(h, hipMemsetAsync(h->d_vXf, 0, sizeof(double) * Bc * nf * n, h->stream));
             HIPCHK(h, hipMemsetAsync(h->d_vUf, 0, sizeof(double) * Bc * (nf - 1) * m, h->stream));
             HIPCHK(h, hipMemsetAsync(V.nfull, 0, sizeof(int) * Bc, h->stream));
             h->dense_rows = nf;
         }
         V.nfull_max = nf; V.Xfull = h->d_vXf; V.Ufull = h->d_vUf;
-    }
-    KParams P;
-    memset(&P, 0, sizeof(P));
-    P.N = h->N; P.B = h->B; P.mp = h->mp; P.tf = h->d_tf;
-    if (has_obs) {
-        P.box = h->d_box; P.sph = h->d_sph;
-        if (h->d_env) { P.n_obs = h->n_obs_max; P.env = h->d_env; }
-        else { P.n_box = h->n_box; P.n_sph = h->n_sph; P.n_obs = h->n_box + h->n_sph; }
     }
     HIPCHK(h, hipEventRecord(h->ev_v0, h->stream));
     int rc = GUSTO_ERR_ARG;
@@ -314,10 +307,10 @@ int gusto_interpolate(gusto_handle h, const double* X, const double* U, const gu
 }
 
 int gusto_get_verify(gusto_handle h, gusto_verify_report* out) {
-    if (h) { int rcw = gusto_finish(h); if (rcw) return rcw; }
-    if (!h || !out) return GUSTO_ERR_ARG;
+    if (!h) return GUSTO_ERR_ARG;
+    if (int rc = getter_enter(h, false)) return rc;
+    if (!out) return GUSTO_ERR_ARG;
     if (!h->have_verify) { h->err = "gusto_get_verify: call gusto_verify first"; return GUSTO_ERR_STATE; }
-    HIPCHK(h, hipSetDevice(h->device));
     const size_t B = h->B, Bc = h->batch_cap;
 #define CPV(dst, src) if (dst) HIPCHK(h, hipMemcpy(dst, src, sizeof(*(dst)) * B, hipMemcpyDeviceToHost))
     CPV(out->collision_free, h->d_vI); CPV(out->first_knot, h->d_vI + Bc); CPV(out->min_dense_sample, h->d_vI + 2 * Bc);
@@ -328,10 +321,9 @@ int gusto_get_verify(gusto_handle h, gusto_verify_report* out) {
 }
 
 int gusto_get_dense(gusto_handle h, int* nfull, double* Xfull, double* Ufull) {
-    if (h) { int rcw = gusto_finish(h); if (rcw) return rcw; }
     if (!h) return GUSTO_ERR_ARG;
+    if (int rc = getter_enter(h, false)) return rc;
     if (!h->have_dense) { h->err = "gusto_get_dense: call gusto_interpolate first"; return GUSTO_ERR_STATE; }
-    HIPCHK(h, hipSetDevice(h->device));
     const size_t B = h->B, Bc = h->batch_cap, nf = h->dense_rows;
     if (nfull) HIPCHK(h, hipMemcpy(nfull, h->d_vI + 3 * Bc, sizeof(int) * B, hipMemcpyDeviceToHost));
     if (Xfull) HIPCHK(h, hipMemcpy(Xfull, h->d_vXf, sizeof(double) * B * nf * h->n, hipMemcpyDeviceToHost));

@@ -252,3 +252,19 @@ def test_horizon_limits_of_the_lds_layouts(tmp_path):
         doc = hdr[hdr.rindex("/*", 0, hdr.index(fn)):hdr.index(fn)]
         for m, lim in table.items():
             assert re.search(r"\b%s (N <= )?%d\b" % (names[m], lim), doc), (fn, names[m], lim)
+
+
+def test_device_buffers_free_what_they_allocate(tmp_path):
+    """DevBuf<T> of csrc/handle.hpp, the owner of every device buffer of a handle, against a counting fake of hipMalloc / hipFree
+    (tests/c/devbuf_lifetime.cpp, host code only): each allocation is freed exactly once across alloc, ensure (growing and not),
+    reset, moves and destruction, and a failed allocation leaves the buffer empty."""
+    import json, subprocess
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path / "devbuf_lifetime")
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
+                           "-I" + os.path.join(ROOT, "gusto.jl_amd", "csrc"), "-x", "hip",
+                           os.path.join(ROOT, "tests", "c", "devbuf_lifetime.cpp"), "-o", exe], stderr=subprocess.DEVNULL)
+    d = json.loads(subprocess.check_output([exe]).decode())
+    assert d["mallocs"] == d["frees"] > 0 and d["bad_frees"] == 0 and d["live"] == 0, d

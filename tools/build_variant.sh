@@ -9,13 +9,9 @@ mkdir -p $V $W
 F="--offload-arch=gfx950 -O3 -std=c++17 -Iinclude -I$D/csrc -fPIC -Wno-unused-value -Wno-pass-failed $@"
 cat > $W/stub.hip <<EOS
 #include "handle.hpp"
-#define STUB(i) int gusto_launch_init_m##i(gusto_handle h, bool) { h->err = "model not in this dev build"; return GUSTO_ERR_ARG; } \
-                int gusto_launch_scp_m##i(gusto_handle h, int, int, int) { h->err = "model not in this dev build"; return GUSTO_ERR_ARG; }
-#define STUBT(i) int gusto_launch_init_m##i(gusto_handle h, bool) { h->err = "model not in this dev build"; return GUSTO_ERR_ARG; } \
-                 int gusto_launch_trajopt_m##i(gusto_handle h, int, int) { h->err = "model not in this dev build"; return GUSTO_ERR_ARG; }
+#define STUB(i) template <> const ModelOps& model_ops<i>() { static const ModelOps none{}; return none; }   // (no kernels: the launches are refused)
 EOS
-for i in 0 1 2 3; do [ $i != $M ] && echo "STUB($i)" >> $W/stub.hip; done
-for i in 4 5 6; do [ $i != $M ] && echo "STUBT($i)" >> $W/stub.hip; done
+for i in 0 1 2 3 4 5 6; do [ $i != $M ] && echo "STUB($i)" >> $W/stub.hip; done
 /opt/rocm/bin/hipcc $F -c $D/csrc/gusto_hip.hip -o $W/gusto_hip.o &
 /opt/rocm/bin/hipcc $F -c $W/stub.hip -o $W/stub.o &
 /opt/rocm/bin/hipcc $F -c $D/csrc/shoot.hip -o $W/shoot.o &
