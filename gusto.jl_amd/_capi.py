@@ -29,7 +29,8 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_get_trajopt_history", "gusto_subproblem_trajopt",
            "gusto_default_verify_opts", "gusto_verify", "gusto_get_verify", "gusto_interpolate", "gusto_get_dense",
            "gusto_last_verify_ms",
-           "gusto_dev_get_prof", "gusto_dev_launch_info"]
+           "gusto_default_tvlqr_opts", "gusto_tvlqr", "gusto_get_tvlqr", "gusto_last_tvlqr_ms",
+           "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr"]
 
 
 class ScpParams(C.Structure):
@@ -57,6 +58,20 @@ class ShootOpts(C.Structure):
 
 class VerifyOpts(C.Structure):
     _fields_ = [("dt_min", C.c_double), ("nstep", C.c_int), ("nstep_cap", C.c_int), ("dense_collision", C.c_int)]
+
+
+class TvlqrOpts(C.Structure):
+    """gusto_tvlqr_opts: diagonal weights, the roll-out of gusto_verify_opts, store_P"""
+    _fields_ = [("Q", C.c_double * MAXN), ("R", C.c_double * MAXM), ("Qf", C.c_double * MAXN), ("dt_min", C.c_double),
+                ("nstep", C.c_int), ("nstep_cap", C.c_int), ("store_P", C.c_int)]
+
+
+class TvlqrResult:
+    """What gusto_get_tvlqr returns: K [B, N-1, m, n], AB [B, N-1, n, n+m] (rows of [Ad | Bd]), status / fail_knot [B], and P --
+    [B, N, n, n] after a call with store_P, else [B, n, n], the P of knot 1."""
+
+    def __init__(self, K, P, AB, status, fail_knot):
+        self.K, self.P, self.AB, self.status, self.fail_knot = K, P, AB, status, fail_knot
 
 
 VERIFY_FIELDS = (("collision_free", np.int32), ("first_knot", np.int32), ("first_dist", np.float64),
@@ -100,7 +115,7 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(_ROOT, "include"), "-fPIC",
              "-Wno-unused-value", "-Wno-pass-failed"]
-    units = ["gusto_hip", "shoot", "verify", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
+    units = ["gusto_hip", "shoot", "verify", "tvlqr", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
     bdir = os.path.join(_HERE, "build")
     os.makedirs(bdir, exist_ok=True)
 
@@ -174,6 +189,11 @@ def lib():
         L.gusto_interpolate.argtypes = [vp, vp, vp, C.POINTER(VerifyOpts), C.POINTER(ci)]
         L.gusto_get_dense.argtypes = [vp, vp, vp, vp]
         L.gusto_last_verify_ms.argtypes = [vp, C.POINTER(C.c_double)]
+        L.gusto_default_tvlqr_opts.argtypes = [ci, C.POINTER(TvlqrOpts)]
+        L.gusto_tvlqr.argtypes = [vp, vp, vp, C.POINTER(TvlqrOpts)]
+        L.gusto_get_tvlqr.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.gusto_last_tvlqr_ms.argtypes = [vp, C.POINTER(C.c_double)]
+        L.gusto_dev_tvlqr.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.gusto_default_trajopt_params.argtypes = [ci, C.POINTER(TrajOptParams)]
         L.gusto_create_trajopt.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci]
         L.gusto_set_trajopt_params.argtypes = [vp, C.POINTER(TrajOptParams)]
@@ -214,6 +234,14 @@ def default_ipm_opts():
 def default_verify_opts():
     o = VerifyOpts()
     lib().gusto_default_verify_opts(C.byref(o))
+    return o
+
+
+def default_tvlqr_opts(model):
+    o = TvlqrOpts()
+    rc = lib().gusto_default_tvlqr_opts(model, C.byref(o))
+    if rc:
+        raise ValueError(f"gusto_default_tvlqr_opts({model}) -> {rc}")
     return o
 
 
@@ -488,6 +516,66 @@ class BatchSolver:
         self._chk(self.L.gusto_last_verify_ms(self.h, C.byref(ms)), "last_verify_ms")
         return ms.value
 
+    def tvlqr_opts(self, opts=None):
+        """a gusto_tvlqr_opts from None (the defaults), a TvlqrOpts, or a dict of its fields -- Q, R, Qf as scalars or vectors of
+        the model's x_dim / u_dim entries"""
+        if isinstance(opts, TvlqrOpts):
+            return opts
+        o = default_tvlqr_opts(self.model)
+        for k, v in (opts or {}).items():
+            if k in ("Q", "R", "Qf"):
+                dim = self.m if k == "R" else self.n
+                w = np.broadcast_to(np.asarray(v, dtype=np.float64), (dim,))
+                for i in range(dim):
+                    getattr(o, k)[i] = float(w[i])
+            elif k in ("nstep", "nstep_cap", "store_P"):
+                setattr(o, k, int(v))
+            elif k == "dt_min":
+                o.dt_min = float(v)
+            else:
+                raise TypeError(f"unknown tvlqr option {k!r}")
+        return o
+
+    def tvlqr(self, opts=None, X=None, U=None):
+        """gusto_tvlqr + gusto_get_tvlqr: the time-varying LQR gains K_k of u = U_k - K_k (x - X_k) around X, U (default: the
+        handle's trajectories, left as they are), on the exact derivative of the RK4 roll-out interpolate() performs."""
+        if (X is None) != (U is None):
+            raise ValueError("tvlqr: X and U are given together or not at all")
+        o = self.tvlqr_opts(opts)
+        Xa = None if X is None else _arr(X).reshape(self.B, self.N, self.n)
+        Ua = None if U is None else _arr(U).reshape(self.B, self.N, self.m)
+        self._chk(self.L.gusto_tvlqr(self.h, None if Xa is None else Xa.ctypes.data, None if Ua is None else Ua.ctypes.data,
+                                     C.byref(o)), "tvlqr")
+        self._tvlqr_store_P = bool(o.store_P)
+        return self.get_tvlqr()
+
+    def get_tvlqr(self, full_P=None):
+        """gusto_get_tvlqr as a TvlqrResult.  full_P: None = whatever the last call kept; True = the P of every knot, refused
+        (-3, as the C ABI's state errors) after a call without store_P; False = the P of knot 1 only."""
+        B, N, n, m = self.B, self.N, self.n, self.m
+        kept = getattr(self, "_tvlqr_store_P", None)
+        if full_P and kept is False:
+            raise GustoError("gusto_get_tvlqr -> -3: the last gusto_tvlqr ran without store_P: only the P of knot 1 exists")
+        st, fk = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        K, AB = np.zeros((B, N - 1, m, n)), np.zeros((B, N - 1, n, n + m))
+        P = np.zeros((B, N, n, n) if kept else (B, n, n))
+        self._chk(self.L.gusto_get_tvlqr(self.h, st.ctypes.data, fk.ctypes.data, K.ctypes.data, P.ctypes.data, AB.ctypes.data),
+                  "get_tvlqr")
+        if kept and full_P is False:
+            P = P[:, 0].copy()
+        return TvlqrResult(K, P, AB, st, fk)
+
+    def tvlqr_phase_ms(self):
+        """gusto_dev_tvlqr: (linearise ms, riccati ms) of the last tvlqr call"""
+        a, b = C.c_double(), C.c_double()
+        self._chk(self.L.gusto_dev_tvlqr(self.h, C.byref(a), C.byref(b)), "dev_tvlqr")
+        return a.value, b.value
+
+    def last_tvlqr_ms(self):
+        ms = C.c_double()
+        self._chk(self.L.gusto_last_tvlqr_ms(self.h, C.byref(ms)), "last_tvlqr_ms")
+        return ms.value
+
     def subproblem(self, Xp, Up, Delta, omega, toggle):
         B = self.B
         Xp, Up = _arr(Xp).reshape(B, self.N, self.n), _arr(Up).reshape(B, self.N, self.m)
@@ -554,3 +642,6 @@ class TrajOptSolver(BatchSolver):
         raise GustoError("TrajOptSolver: verify / interpolate are not supported on TrajOpt handles (gusto_verify answers GUSTO_ERR_ARG)")
 
     interpolate = verify
+
+    def tvlqr(self, *a, **k):
+        raise GustoError("TrajOptSolver: tvlqr is not supported on TrajOpt handles (gusto_tvlqr answers GUSTO_ERR_ARG)")

@@ -135,6 +135,15 @@ struct gusto_handle_s {
     bool have_verify = false, have_dense = false;
     DevEvent ev_v0, ev_v1;
     double last_verify_ms = 0.0;
+    // time-varying LQR gains (tvlqr.hip, the only file that touches them): [lq_B][N - 1][n][n + m] rows of [Ad | Bd], [lq_B][N - 1][m][n]
+    // gains, [lq_B][n][n] P of knot 1, [lq_B][N][n][n] P of every knot (first call with store_P only), [2][lq_B] status and
+    // fail_knot, copies of a caller's X / U.  Sized by the batch of the call that allocates them, grown (contents discarded) by a
+    // later call with a larger batch.  ev_qm sits between the two launches (gusto_dev_tvlqr: the split of the time)
+    DevBuf<double> d_lqAB, d_lqK, d_lqP1, d_lqPall, d_lqX, d_lqU;
+    DevBuf<int> d_lqSt;
+    bool have_tvlqr = false, lq_store_P = false, lq_have_Pall = false;
+    DevEvent ev_q0, ev_qm, ev_q1;
+    double last_tvlqr_ms = 0.0, lq_lin_ms = 0.0, lq_ric_ms = 0.0;
     std::string err;
 
     // (the buffers and events free themselves; the caller has made `device` current: gusto_destroy)

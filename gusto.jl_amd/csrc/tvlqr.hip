@@ -1,0 +1,448 @@
+// tvlqr.hip -- batched time-varying LQR tracking gains around the trajectories of a batch: u = U_k - K_k (x(t_k) - X_k).
+// No counterpart in the reference; include/gusto_hip.h states the definitions (roll-out map, discrete Jacobians, recursion).
+// Two launches on the handle's stream:
+//   tvlqr_linearise  grid (problem, tile of IPB intervals), 256 lanes.  Work item (k, j) = lane: interval k, column j of
+//     [dF_k/dx | dF_k/du].  A lane carries the nominal state (every lane of an interval recomputes the cheap nominal roll-out)
+//     and ONE tangent column, 2 n doubles, through the four RK4 stages of every substep: kd = A(stage point) d + B e_j, with
+//     Dyn<MODEL>::A written into a local array that full unrolling dissolves -- only its structural nonzeros (MT<MODEL>::Anz) are
+//     multiplied, nothing indexes it at run time.  A lane owns column j of the n rows of its interval, n + m doubles apart: the tile is staged in LDS
+//     ([interval][row][column], the layout of AB) and copied out by the whole workgroup, consecutive lanes to consecutive
+//     addresses (as verify.hip stages its dense samples).
+//   tvlqr_riccati    one wave per problem, for every N.  P, [Ad | Bd], T = P [Ad Bd], H and W live in LDS (9.4 KB for n = 13); the
+//     64 lanes split the entries of every product (entry e = lane + 64 r), each entry one dot product in a fixed order.  H and
+//     P' are computed on the upper triangle and mirrored, so P is symmetric to the bit.  The m x m Cholesky (m <= 6) is done by
+//     every lane on the same LDS values -- the pivot test is wave-uniform without a broadcast -- and lane j < n then solves
+//     column j of W = L^-1 H_ux and K = L^-T W.  [Ad | Bd] of the next stage is loaded into registers before the current stage
+//     computes.  K (and P with store_P) go out from LDS, lane e to double e.
+//     (The same stage with every product on v_mfma_f64_16x16x4_f64 and P resident in accumulators, modelled on
+//     factor_sweep_mfma, was built and measured for the 12/13-state models: 0.856 ms against 0.803 ms for this one at 8192
+//     astrobeeSE3 problems, N = 50 -- profiles/tvlqr.txt.  It lost and is not in the library.)
+// No atomics, nothing crosses a problem: a problem's output is the same bit for bit whatever batch it sits in.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "handle.hpp"
+#include "models.hpp"
+
+using namespace gusto;
+
+namespace {
+
+struct TvArgs {
+    const double *X, *U;     // [B][N][n], [B][N][m]: the handle's trajectories or the caller's copies
+    const int* active;       // gusto_set_active: null = every problem, else the mask [B]
+    double dt_min;
+    int nstep, store_P;
+    double Q[GUSTO_MAXN], R[GUSTO_MAXM], Qf[GUSTO_MAXN];
+    double *AB, *K, *P1, *Pall;
+    int *status, *fail_knot;
+};
+
+// kd = A d + bu over the structural nonzeros of A (MT<MODEL>::Anz: the loops are unrolled, so the pattern is a compile-time
+// choice per product -- a product with a constant 0.0 is not something the compiler may drop on its own in IEEE arithmetic)
+template <int MODEL> GD void tangent(const double* A, const double* d, const double* bu, double* kd) {
+    constexpr int n = MT<MODEL>::n;
+#pragma unroll
+    for (int i = 0; i < n; i++) {
+        double s = bu[i];
+#pragma unroll
+        for (int j = 0; j < n; j++)
+            if (MT<MODEL>::Anz(i, j)) s += A[i * n + j] * d[j];
+        kd[i] = s;
+    }
+}
+
+template <int MODEL> struct LinTile {
+    static constexpr int n = MT<MODEL>::n, m = MT<MODEL>::m, nz = n + m;
+    static constexpr int IPB = 256 / nz;   // whole intervals per workgroup: its slice of AB is one contiguous range
+};
+
+template <int MODEL> __global__ void __launch_bounds__(256) tvlqr_linearise(const KParams P, const TvArgs V) {
+    using D = Dyn<MODEL>;
+    using LT = LinTile<MODEL>;
+    constexpr int n = LT::n, m = LT::m, nz = LT::nz, IPB = LT::IPB;
+    __shared__ double stage[IPB * n * nz];
+    const int b = blockIdx.x, k0 = blockIdx.y * IPB, t = threadIdx.x, N = P.N;
+    if (V.active && !V.active[b]) return;   // (the whole workgroup)
+    const double dt = P.tf[b] / (N - 1);
+    const int nstep = V.nstep > 0 ? V.nstep : (int)ceil(dt / V.dt_min);   // (the host has checked 1 <= nstep <= nstep_cap)
+    const double h = dt / nstep;
+    const int kl = t / nz, j = t % nz;
+    const bool valid = kl < IPB && k0 + kl < N - 1;
+    const int k = valid ? k0 + kl : 0;   // (idle lanes roll interval 0 out and store nothing)
+    const double* Xk = V.X + ((size_t)b * N + k) * n;
+    const double* Uk = V.U + ((size_t)b * N + k) * m;
+    double x[n], u[m], d[n], bu[n];
+#pragma unroll
+    for (int i = 0; i < n; i++) { x[i] = Xk[i]; d[i] = i == j ? 1.0 : 0.0; }
+#pragma unroll
+    for (int i = 0; i < m; i++) u[i] = Uk[i];
+    {   // B e_j: B does not depend on the state in any model
+        double Bm[n * m];
+        D::B(P.mp, Bm);
+#pragma unroll
+        for (int i = 0; i < n; i++) {
+            double s = 0.0;
+#pragma unroll
+            for (int c = 0; c < m; c++)
+                if (MT<MODEL>::Bnz(i, c)) s += n + c == j ? Bm[i * m + c] : 0.0;
+            bu[i] = s;
+        }
+    }
+    for (int s = 0; s < nstep; s++) {
+        double A[n * n], w[n], dw[n], k1[n], kk[n], kd1[n], kdk[n], xs[n], ds[n];
+        D::f(P.mp, x, u, k1);
+        D::A(P.mp, x, u, A);
+        tangent<MODEL>(A, d, bu, kd1);
+#pragma unroll
+        for (int i = 0; i < n; i++) { xs[i] = k1[i]; ds[i] = kd1[i]; w[i] = x[i] + 0.5 * h * k1[i]; dw[i] = d[i] + 0.5 * h * kd1[i]; }
+        D::f(P.mp, w, u, kk);
+        D::A(P.mp, w, u, A);
+        tangent<MODEL>(A, dw, bu, kdk);
+#pragma unroll
+        for (int i = 0; i < n; i++) { xs[i] += 2 * kk[i]; ds[i] += 2 * kdk[i]; w[i] = x[i] + 0.5 * h * kk[i]; dw[i] = d[i] + 0.5 * h * kdk[i]; }
+        D::f(P.mp, w, u, kk);
+        D::A(P.mp, w, u, A);
+        tangent<MODEL>(A, dw, bu, kdk);
+#pragma unroll
+        for (int i = 0; i < n; i++) { xs[i] += 2 * kk[i]; ds[i] += 2 * kdk[i]; w[i] = x[i] + h * kk[i]; dw[i] = d[i] + h * kdk[i]; }
+        D::f(P.mp, w, u, kk);
+        D::A(P.mp, w, u, A);
+        tangent<MODEL>(A, dw, bu, kdk);
+#pragma unroll
+        for (int i = 0; i < n; i++) {
+            x[i] = x[i] + 1.0 / 6.0 * h * (xs[i] + kk[i]);
+            d[i] = d[i] + 1.0 / 6.0 * h * (ds[i] + kdk[i]);
+        }
+    }
+    if (valid)
+#pragma unroll
+        for (int i = 0; i < n; i++) stage[(kl * n + i) * nz + j] = d[i];
+    __syncthreads();
+    const int cnt = min(IPB, N - 1 - k0) * n * nz;
+    double* out = V.AB + ((size_t)b * (N - 1) + k0) * n * nz;
+    for (int e = t; e < cnt; e += 256) out[e] = stage[e];
+}
+
+template <int MODEL> __global__ void __launch_bounds__(64) tvlqr_riccati(const KParams P, const TvArgs V) {
+    constexpr int n = MT<MODEL>::n, m = MT<MODEL>::m, nz = n + m;
+    constexpr int NG = n * nz, RG = (NG + 63) / 64;                 // entries of [Ad | Bd] and of T, per lane
+    constexpr int NH = nz * (nz + 1) / 2, RH = (NH + 63) / 64;      // upper triangle of H
+    constexpr int NP = n * (n + 1) / 2, RP = (NP + 63) / 64;        // upper triangle of P
+    constexpr int NK = m * n, RK = (NK + 63) / 64, NPF = n * n, RPF = (NPF + 63) / 64;
+    __shared__ double sP[n * n], sG[NG], sT[NG], sH[nz * nz], sW[NK], sK[NK];
+    const int b = blockIdx.x, lane = threadIdx.x, N = P.N;
+    if (V.active && !V.active[b]) return;
+    const double* AB = V.AB + (size_t)b * (N - 1) * NG;
+    double* Kout = V.K + (size_t)b * (N - 1) * NK;
+    double* Pall = V.store_P ? V.Pall + (size_t)b * N * NPF : nullptr;
+
+    // the entries this lane owns: (row, column) of the upper triangles, found once
+    int ha[RH], hb[RH], pa[RP], pb[RP];
+#pragma unroll
+    for (int r = 0; r < RH; r++) {
+        int rem = lane + 64 * r, a = 0;
+        if (rem >= NH) rem = 0;
+        while (rem >= nz - a) { rem -= nz - a; a++; }
+        ha[r] = a; hb[r] = a + rem;
+    }
+#pragma unroll
+    for (int r = 0; r < RP; r++) {
+        int rem = lane + 64 * r, a = 0;
+        if (rem >= NP) rem = 0;
+        while (rem >= n - a) { rem -= n - a; a++; }
+        pa[r] = a; pb[r] = a + rem;
+    }
+    // P_N = diag(Qf)
+#pragma unroll
+    for (int r = 0; r < RPF; r++) {
+        const int e = lane + 64 * r;
+        if (e < NPF) {
+            const double v = e / n == e % n ? V.Qf[e / n] : 0.0;
+            sP[e] = v;
+            if (Pall) Pall[(size_t)(N - 1) * NPF + e] = v;
+        }
+    }
+    double g[RG];
+#pragma unroll
+    for (int r = 0; r < RG; r++) { const int e = lane + 64 * r; g[r] = e < NG ? AB[(size_t)(N - 2) * NG + e] : 0.0; }
+#pragma unroll
+    for (int r = 0; r < RG; r++) { const int e = lane + 64 * r; if (e < NG) sG[e] = g[r]; }
+    __syncthreads();
+
+    int fail = 0;
+    for (int k = N - 1; k >= 1; k--) {   // knot k (1-based): interval k - 1 of the arrays
+        if (k > 1)                       // [Ad | Bd] of the next stage, in flight while this one computes
+#pragma unroll
+            for (int r = 0; r < RG; r++) { const int e = lane + 64 * r; g[r] = e < NG ? AB[(size_t)(k - 2) * NG + e] : 0.0; }
+        // T = P [Ad Bd]
+#pragma unroll
+        for (int r = 0; r < RG; r++) {
+            const int e = lane + 64 * r;
+            if (e < NG) {
+                const int i = e / nz, c = e % nz;
+                double s = 0.0;
+#pragma unroll
+                for (int p = 0; p < n; p++) s += sP[i * n + p] * sG[p * nz + c];
+                sT[e] = s;
+            }
+        }
+        __syncthreads();
+        // H = diag(Q, R) + [Ad Bd]' T, upper triangle, mirrored
+#pragma unroll
+        for (int r = 0; r < RH; r++) {
+            if (lane + 64 * r < NH) {
+                const int a = ha[r], c = hb[r];
+                double s = a == c ? (a < n ? V.Q[a] : V.R[a - n]) : 0.0;
+#pragma unroll
+                for (int p = 0; p < n; p++) s += sG[p * nz + a] * sT[p * nz + c];
+                sH[a * nz + c] = s;
+                sH[c * nz + a] = s;
+            }
+        }
+        __syncthreads();
+        if (k > 1)
+#pragma unroll
+            for (int r = 0; r < RG; r++) { const int e = lane + 64 * r; if (e < NG) sG[e] = g[r]; }
+        // L = chol(H_uu): every lane, the same values
+        double L[m][m];
+        bool bad = false;
+#pragma unroll
+        for (int c = 0; c < m; c++) {
+            double dg = sH[(n + c) * nz + n + c];
+#pragma unroll
+            for (int p = 0; p < c; p++) dg -= L[c][p] * L[c][p];
+            if (!(dg > 0.0) || !(dg < INFINITY)) bad = true;
+            const double l = sqrt(dg);
+            L[c][c] = l;
+#pragma unroll
+            for (int q = c + 1; q < m; q++) {
+                double s = sH[(n + q) * nz + n + c];
+#pragma unroll
+                for (int p = 0; p < c; p++) s -= L[q][p] * L[c][p];
+                L[q][c] = s / l;
+            }
+        }
+        if (bad) { fail = k; break; }   // (wave-uniform)
+        // W = L^-1 H_ux, K = L^-T W: lane j solves column j
+        if (lane < n) {
+            double w[m];
+#pragma unroll
+            for (int c = 0; c < m; c++) {
+                double s = sH[(n + c) * nz + lane];
+#pragma unroll
+                for (int p = 0; p < c; p++) s -= L[c][p] * w[p];
+                w[c] = s / L[c][c];
+                sW[c * n + lane] = w[c];
+            }
+#pragma unroll
+            for (int c = m - 1; c >= 0; c--) {
+                double s = w[c];
+#pragma unroll
+                for (int p = c + 1; p < m; p++) s -= L[p][c] * w[p];
+                w[c] = s / L[c][c];
+                sK[c * n + lane] = w[c];
+            }
+        }
+        __syncthreads();
+        // P_k = H_xx - W' W, upper triangle, mirrored
+#pragma unroll
+        for (int r = 0; r < RP; r++) {
+            if (lane + 64 * r < NP) {
+                const int a = pa[r], c = pb[r];
+                double s = sH[a * nz + c];
+#pragma unroll
+                for (int p = 0; p < m; p++) s -= sW[p * n + a] * sW[p * n + c];
+                sP[a * n + c] = s;
+                sP[c * n + a] = s;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < RK; r++) { const int e = lane + 64 * r; if (e < NK) Kout[(size_t)(k - 1) * NK + e] = sK[e]; }
+        __syncthreads();
+        if (Pall)
+#pragma unroll
+            for (int r = 0; r < RPF; r++) { const int e = lane + 64 * r; if (e < NPF) Pall[(size_t)(k - 1) * NPF + e] = sP[e]; }
+    }
+    // a failed pivot at knot `fail`: zeros from there down to knot 1
+    for (int k = fail; k >= 1; k--) {
+#pragma unroll
+        for (int r = 0; r < RK; r++) { const int e = lane + 64 * r; if (e < NK) Kout[(size_t)(k - 1) * NK + e] = 0.0; }
+        if (Pall)
+#pragma unroll
+            for (int r = 0; r < RPF; r++) { const int e = lane + 64 * r; if (e < NPF) Pall[(size_t)(k - 1) * NPF + e] = 0.0; }
+    }
+#pragma unroll
+    for (int r = 0; r < RPF; r++) { const int e = lane + 64 * r; if (e < NPF) V.P1[(size_t)b * NPF + e] = fail ? 0.0 : sP[e]; }
+    if (lane == 0) { V.status[b] = fail ? 0 : 1; V.fail_knot[b] = fail; }
+}
+
+template <int MODEL> int launch_tvlqr(gusto_handle h, const KParams& P, const TvArgs& V) {
+    const int tiles = (h->N - 1 + LinTile<MODEL>::IPB - 1) / LinTile<MODEL>::IPB;
+    hipLaunchKernelGGL((tvlqr_linearise<MODEL>), dim3(h->B, tiles), dim3(256), 0, h->stream, P, V);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev_qm, h->stream));
+    hipLaunchKernelGGL((tvlqr_riccati<MODEL>), dim3(h->B), dim3(64), 0, h->stream, P, V);
+    HIPCHK(h, hipGetLastError());
+    return GUSTO_OK;
+}
+
+// grow-only, zeroed when (re)allocated.  Growing discards the contents: it happens only after a gusto_set_problems with a larger
+// batch, which has invalidated them (have_tvlqr) anyway
+template <class T> int ensure_zeroed(gusto_handle h, DevBuf<T>& buf, size_t count) {
+    if (buf && count <= buf.count()) return GUSTO_OK;
+    HIPCHK(h, buf.ensure(count));
+    HIPCHK(h, hipMemsetAsync(buf.get(), 0, sizeof(T) * count, h->stream));
+    return GUSTO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gusto_default_tvlqr_opts(int model_id, gusto_tvlqr_opts* o) {
+    const ModelInfo* mi = model_info(model_id);
+    if (!o || !mi) return GUSTO_ERR_ARG;
+    memset(o, 0, sizeof(*o));
+    for (int i = 0; i < mi->n; i++) o->Q[i] = o->Qf[i] = 1.0;
+    for (int i = 0; i < mi->m; i++) o->R[i] = 1.0;
+    o->dt_min = 0.1; o->nstep = 0; o->nstep_cap = 64; o->store_P = 0;
+    return GUSTO_OK;
+}
+
+int gusto_tvlqr(gusto_handle h, const double* X, const double* U, const gusto_tvlqr_opts* opts) {
+    if (!h) return GUSTO_ERR_ARG;
+    if (h->trajopt) { h->err = "gusto_tvlqr: TrajOpt handle (its controls carry the defect variables; not supported)"; return GUSTO_ERR_ARG; }
+    if (!h->have_problems) { h->err = "gusto_tvlqr: call gusto_set_problems first"; return GUSTO_ERR_STATE; }
+    if ((X == nullptr) != (U == nullptr)) { h->err = "gusto_tvlqr: X and U are given together or not at all"; return GUSTO_ERR_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    { int rc = gusto_finish(h); if (rc) return rc; }
+    gusto_tvlqr_opts o;
+    gusto_default_tvlqr_opts(h->model, &o);
+    if (opts) o = *opts;
+    if (o.nstep < 0 || o.nstep_cap < 1 || (o.nstep == 0 && !(o.dt_min > 0)) || (o.store_P != 0 && o.store_P != 1)) {
+        h->err = "gusto_tvlqr: bad options";
+        return GUSTO_ERR_ARG;
+    }
+    for (int i = 0; i < h->n; i++)
+        if (!(o.Q[i] >= 0 && o.Q[i] < INFINITY && o.Qf[i] >= 0 && o.Qf[i] < INFINITY)) {
+            h->err = "gusto_tvlqr: Q and Qf must be finite and >= 0 (entry " + std::to_string(i) + ")";
+            return GUSTO_ERR_ARG;
+        }
+    for (int i = 0; i < h->m; i++)
+        if (!(o.R[i] > 0 && o.R[i] < INFINITY)) {
+            h->err = "gusto_tvlqr: R must be finite and > 0 (entry " + std::to_string(i) + ")";
+            return GUSTO_ERR_ARG;
+        }
+    const size_t B = h->B, N = h->N, n = h->n, m = h->m;
+    if (o.nstep == 0) {   // Nstep of every problem: never clamped (as gusto_verify)
+        std::vector<double> tf(B);
+        HIPCHK(h, hipMemcpyAsync(tf.data(), h->d_tf, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (size_t b = 0; b < B; b++) {
+            const double q = ceil(tf[b] / (double)(N - 1) / o.dt_min);
+            if (!(q >= 1 && q <= (double)o.nstep_cap)) {
+                h->err = "gusto_tvlqr: problem " + std::to_string(b) + " needs ceil(dt / dt_min) = " + std::to_string(q) + " substeps, outside 1 .. nstep_cap";
+                return GUSTO_ERR_ARG;
+            }
+        }
+    } else if (o.nstep > o.nstep_cap) {
+        h->err = "gusto_tvlqr: nstep above nstep_cap";
+        return GUSTO_ERR_ARG;
+    }
+    KParams P;
+    memset(&P, 0, sizeof(P));
+    P.N = h->N; P.B = h->B; P.mp = h->mp; P.tf = h->d_tf;
+    { int rc;
+      if ((rc = ensure_zeroed(h, h->d_lqAB, B * (N - 1) * n * (n + m)))) return rc;
+      if ((rc = ensure_zeroed(h, h->d_lqK, B * (N - 1) * m * n))) return rc;
+      if ((rc = ensure_zeroed(h, h->d_lqP1, B * n * n))) return rc;
+      if ((rc = ensure_zeroed(h, h->d_lqSt, 2 * B))) return rc;
+      if (o.store_P && (rc = ensure_zeroed(h, h->d_lqPall, B * N * n * n))) return rc; }
+    if (!h->have_tvlqr) h->lq_have_Pall = false;   // (new problems: whatever P the buffer holds belongs to the old ones)
+    // a masked first call since gusto_set_problems: the inactive problems read as zeros, not as the last problem set's gains
+    // (an unmasked call writes every problem)
+    if (h->n_active >= 0) {
+        if (!h->have_tvlqr) {
+            HIPCHK(h, hipMemsetAsync(h->d_lqAB, 0, sizeof(double) * h->d_lqAB.count(), h->stream));
+            HIPCHK(h, hipMemsetAsync(h->d_lqK, 0, sizeof(double) * h->d_lqK.count(), h->stream));
+            HIPCHK(h, hipMemsetAsync(h->d_lqP1, 0, sizeof(double) * h->d_lqP1.count(), h->stream));
+            HIPCHK(h, hipMemsetAsync(h->d_lqSt, 0, sizeof(int) * h->d_lqSt.count(), h->stream));
+        }
+        if (o.store_P && !h->lq_have_Pall) HIPCHK(h, hipMemsetAsync(h->d_lqPall, 0, sizeof(double) * h->d_lqPall.count(), h->stream));
+    }
+    HIPCHK(h, h->ev_q0.create()); HIPCHK(h, h->ev_qm.create()); HIPCHK(h, h->ev_q1.create());
+    TvArgs V{};
+    V.X = h->d_X; V.U = h->d_U;
+    if (X) {   // the caller's trajectories: copies of their own, the handle's stay as they are
+        HIPCHK(h, h->d_lqX.ensure(B * N * n)); HIPCHK(h, h->d_lqU.ensure(B * N * m));
+        HIPCHK(h, hipMemcpyAsync(h->d_lqX, X, sizeof(double) * B * N * n, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_lqU, U, sizeof(double) * B * N * m, hipMemcpyHostToDevice, h->stream));
+        V.X = h->d_lqX; V.U = h->d_lqU;
+    }
+    V.active = h->n_active >= 0 ? h->d_active : nullptr;
+    V.dt_min = o.dt_min; V.nstep = o.nstep; V.store_P = o.store_P;
+    memcpy(V.Q, o.Q, sizeof(V.Q)); memcpy(V.R, o.R, sizeof(V.R)); memcpy(V.Qf, o.Qf, sizeof(V.Qf));
+    V.AB = h->d_lqAB; V.K = h->d_lqK; V.P1 = h->d_lqP1; V.Pall = h->d_lqPall;
+    V.status = h->d_lqSt; V.fail_knot = h->d_lqSt + h->d_lqSt.count() / 2;
+    HIPCHK(h, hipEventRecord(h->ev_q0, h->stream));
+    int rc = GUSTO_ERR_ARG;
+    switch (h->model) {
+    case GUSTO_FREEFLYER_SE2: rc = launch_tvlqr<GUSTO_FREEFLYER_SE2>(h, P, V); break;
+    case GUSTO_DUBINS_CAR: rc = launch_tvlqr<GUSTO_DUBINS_CAR>(h, P, V); break;
+    case GUSTO_ASTROBEE_SE3: rc = launch_tvlqr<GUSTO_ASTROBEE_SE3>(h, P, V); break;
+    case GUSTO_ASTROBEE_SE3_MANIFOLD: rc = launch_tvlqr<GUSTO_ASTROBEE_SE3_MANIFOLD>(h, P, V); break;
+    }
+    if (rc) return rc;
+    HIPCHK(h, hipEventRecord(h->ev_q1, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev_q0, h->ev_q1));
+    h->last_tvlqr_ms = ms;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev_q0, h->ev_qm));
+    h->lq_lin_ms = ms;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev_qm, h->ev_q1));
+    h->lq_ric_ms = ms;
+    if (o.store_P) h->lq_have_Pall = true;
+    h->have_tvlqr = true;
+    h->lq_store_P = o.store_P != 0;
+    return GUSTO_OK;
+}
+
+int gusto_get_tvlqr(gusto_handle h, int* status, int* fail_knot, double* K, double* Pm, double* AB) {
+    if (!h) return GUSTO_ERR_ARG;
+    if (int rc = getter_enter(h, false)) return rc;
+    if (!h->have_tvlqr) { h->err = "gusto_get_tvlqr: call gusto_tvlqr first"; return GUSTO_ERR_STATE; }
+    const size_t B = h->B, N = h->N, n = h->n, m = h->m;
+    if (status) HIPCHK(h, hipMemcpy(status, h->d_lqSt, sizeof(int) * B, hipMemcpyDeviceToHost));
+    if (fail_knot) HIPCHK(h, hipMemcpy(fail_knot, h->d_lqSt + h->d_lqSt.count() / 2, sizeof(int) * B, hipMemcpyDeviceToHost));
+    if (K) HIPCHK(h, hipMemcpy(K, h->d_lqK, sizeof(double) * B * (N - 1) * m * n, hipMemcpyDeviceToHost));
+    if (AB) HIPCHK(h, hipMemcpy(AB, h->d_lqAB, sizeof(double) * B * (N - 1) * n * (n + m), hipMemcpyDeviceToHost));
+    if (Pm) {
+        if (h->lq_store_P) HIPCHK(h, hipMemcpy(Pm, h->d_lqPall, sizeof(double) * B * N * n * n, hipMemcpyDeviceToHost));
+        else HIPCHK(h, hipMemcpy(Pm, h->d_lqP1, sizeof(double) * B * n * n, hipMemcpyDeviceToHost));
+    }
+    return GUSTO_OK;
+}
+
+int gusto_dev_tvlqr(gusto_handle h, double* linearise_ms, double* riccati_ms) {
+    if (!h) return GUSTO_ERR_ARG;
+    if (!h->have_tvlqr) { h->err = "gusto_dev_tvlqr: call gusto_tvlqr first"; return GUSTO_ERR_STATE; }
+    if (linearise_ms) *linearise_ms = h->lq_lin_ms;
+    if (riccati_ms) *riccati_ms = h->lq_ric_ms;
+    return GUSTO_OK;
+}
+
+int gusto_last_tvlqr_ms(gusto_handle h, double* ms) {
+    if (!h || !ms) return GUSTO_ERR_ARG;
+    if (!h->have_tvlqr) { h->err = "gusto_last_tvlqr_ms: call gusto_tvlqr first"; return GUSTO_ERR_STATE; }
+    *ms = h->last_tvlqr_ms;
+    return GUSTO_OK;
+}
+
+}  // extern "C"

@@ -24,7 +24,7 @@ INDEX_MAPS = {
 }
 
 
-def _tree(model_id, X, U, tf, extra=None, column_major_reader=False):
+def _tree(model_id, X, U, tf, extra=None, column_major_reader=False, K=None):
     """X [.., N, n], U [.., N, m] in the C ABI layout -> the notebook's layout (state index first, knot second).
     column_major_reader: keep the C layout [.., N, n] -- HDF5 dimensions are row-major, so HDF5.jl / MATLAB present such
     a data set as n x N (x B), exactly the matrix the notebook wrote."""
@@ -37,6 +37,11 @@ def _tree(model_id, X, U, tf, extra=None, column_major_reader=False):
     out = {"traj": {"x_traj": sw(X), "u_traj": sw(U), "t_traj": t},
            "ind_x": {k: np.int64(i) for i, k in enumerate(names_x)},
            "ind_u": {k: np.int64(i) for i, k in enumerate(names_u)}}
+    if K is not None:       # gusto_tvlqr: [.., N - 1, u_dim, x_dim], the C layout in every format (K_k is a matrix, not a column)
+        K = np.asarray(K, float)
+        if K.shape[-3:] != (N - 1, U.shape[-1], X.shape[-1]) or K.shape[:-3] != X.shape[:-2]:
+            raise ValueError("export: K must be [.., N - 1, u_dim, x_dim] with the leading axes of X")
+        out["traj"]["k_traj"] = K
     if extra:
         out["status"] = {k: np.asarray(v) for k, v in extra.items()}
     return out
@@ -52,10 +57,11 @@ def _flatten(tree, prefix=""):
     return flat
 
 
-def write(path, model_id, X, U, tf, status=None):
+def write(path, model_id, X, U, tf, status=None, K=None):
     """path ending in .h5 -> HDF5 (the notebook's container); .mat -> MATLAB v5 with nested structs; .npz -> flat keys
-    'traj/x_traj', ...  Returns the tree that was written."""
-    tree = _tree(model_id, X, U, tf, status, column_major_reader=path.endswith((".h5", ".hdf5")))
+    'traj/x_traj', ...  K (optional): the tracking gains of BatchSolver.tvlqr, written as traj/k_traj [N-1][u_dim][x_dim] per
+    trajectory next to x_traj, u_traj and t_traj.  Returns the tree that was written."""
+    tree = _tree(model_id, X, U, tf, status, column_major_reader=path.endswith((".h5", ".hdf5")), K=K)
     if path.endswith((".h5", ".hdf5")):
         from . import h5lite
         h5lite.write_h5(path, tree)
@@ -69,20 +75,20 @@ def write(path, model_id, X, U, tf, status=None):
     return tree
 
 
-def write_solution(path, TOS):
+def write_solution(path, TOS, K=None):
     """One TrajectoryOptimizationSolution (host mirror): TOS.traj.X is already x_dim x N as in the reference."""
     model_id = TOS.SCPS.SCPP.PD.model.model_id
     return write(path, model_id, TOS.traj.X.T, TOS.traj.U.T, TOS.traj.Tf,
-                 dict(converged=TOS.SCPS.converged, successful=TOS.SCPS.successful, iterations=TOS.SCPS.iterations))
+                 dict(converged=TOS.SCPS.converged, successful=TOS.SCPS.successful, iterations=TOS.SCPS.iterations), K=K)
 
 
-def write_batch(path, solver, tf):
-    """Everything a BatchSolver holds after a solve: X [B][n][N], U [B][m][N], t [B][N] + per-problem status."""
+def write_batch(path, solver, tf, K=None):
+    """Everything a BatchSolver holds after a solve: X [B][n][N], U [B][m][N], t [B][N] + per-problem status (+ K [B][N-1][m][n])."""
     X, U = solver.traj()
     st = solver.status()
     return write(path, solver.model, X, U, np.asarray(tf, float),
                  dict(converged=st["converged"].astype(np.int8), successful=st["successful"].astype(np.int8),
-                      iterations=st["iterations"], stop_reason=st["stop_reason"]))
+                      iterations=st["iterations"], stop_reason=st["stop_reason"]), K=K)
 
 
 def read(path):

@@ -572,6 +572,19 @@ def dynamics_constraint_satisfaction(traj, SCPP):
     return float(r["dyn_defect_l1"][0])
 
 
+def tvlqr(traj, SCPP, Q=1.0, R=1.0, Qf=1.0, dt_min=0.1, store_P=False):
+    """Time-varying LQR gains around one trajectory (gusto_tvlqr; no counterpart in the reference): the feedback law
+    u = U[:, k] - K[k] (x(t_k) - X[:, k]) on the exact derivative of the zero-order-hold RK4 roll-out interpolate_traj performs.
+    Q, R, Qf: diagonal weights, scalars or vectors.  Returns the one-problem result: K [N-1, u_dim, x_dim], AB [N-1, x_dim,
+    x_dim + u_dim], P [x_dim, x_dim] of knot 1 ([N, x_dim, x_dim] with store_P), status, fail_knot."""
+    bs = _verify_handle(traj, SCPP)
+    try:
+        r = bs.tvlqr(dict(Q=Q, R=R, Qf=Qf, dt_min=dt_min, nstep_cap=max(64, int(np.ceil(traj.dt / dt_min))), store_P=int(store_P)))
+    finally:
+        bs.close()
+    return _capi.TvlqrResult(r.K[0], r.P[0], r.AB[0], int(r.status[0]), int(r.fail_knot[0]))
+
+
 def shard_bounds(B, world_size, rank):
     """Contiguous block of ceil(B/G) problems per rank; the tail rank may get fewer."""
     per = -(-B // world_size)
@@ -580,12 +593,16 @@ def shard_bounds(B, world_size, rank):
 
 
 def solve_SCP_batch(TOSs, TOPs, solve_method=None, init_method=init_traj_straightline, solver="hip", max_iter=30,
-                    force=False, device=0, devices=None, decomposition=0, verify=False):
+                    force=False, device=0, devices=None, decomposition=0, verify=False, tvlqr=None):
     """All TOPs must share model and N (each may bring its own environment); one gusto_solve covers the whole list.
 
     `verify` (GuSTO handles only): one gusto_verify per shard after its solve; every SCPS then carries `verify`, the dict of its
     problem's report (collision_free, first_knot, first_dist, min_dist_knots, dyn_defect_l1, min_dist_dense, min_dense_sample,
     max_gap).  A dict of gusto_verify_opts fields instead of True sets them.  Without it the solutions are what they were.
+
+    `tvlqr` (GuSTO handles only): a dict of gusto_tvlqr_opts fields (Q, R, Qf, dt_min, nstep, nstep_cap, store_P; {} = the
+    defaults) -- one gusto_tvlqr per shard after its solve; every SCPS then carries `tvlqr`, its problem's K, P, AB, status and
+    fail_knot.  Without it the solutions are what they were.
 
     `decomposition` (gusto_set_decomposition; GuSTO handles only): 0 = the library's choice by batch size -- for the 12/13-state
     models two or four wavefronts per problem while the batch leaves SIMDs idle --, 1 one wave per problem, 3 / 4 two / four.
@@ -598,6 +615,8 @@ def solve_SCP_batch(TOSs, TOPs, solve_method=None, init_method=init_traj_straigh
     trajopt = solve_method is solve_trajopt_hip
     if verify and trajopt:
         raise NotImplementedError("solve_SCP_batch!: verify is not available for TrajOpt handles")
+    if tvlqr is not None and trajopt:
+        raise NotImplementedError("solve_SCP_batch!: tvlqr is not available for TrajOpt handles")
     if len(TOSs) != len(TOPs) or not TOPs:
         raise ValueError("solve_SCP_batch!: need as many solutions as problems, at least one")
     TOP0 = TOPs[0]
@@ -656,12 +675,16 @@ def solve_SCP_batch(TOSs, TOPs, solve_method=None, init_method=init_traj_straigh
         snap = _fetch(bs, None if gathered is None else (gathered[0][b0:b1], gathered[1][b0:b1]))
         per = bs.last_solve_ms() * 1e-3 / (b1 - b0)
         rep = bs.verify(**(verify if isinstance(verify, dict) else {})) if verify else None
+        lq = bs.tvlqr(tvlqr) if tvlqr is not None else None
         for b in range(b0, b1):
             SCPP = SCPProblem(TOPs[b])
             SCPS = SCPSolution(SCPP, inits[b])
             (_fill_trajopt_solution if trajopt else _fill_solution)(SCPS, SCPP, snap, b - b0, per)
             if rep is not None:
                 SCPS.verify = {k: v[b - b0].item() for k, v in rep.items()}
+            if lq is not None:
+                SCPS.tvlqr = _capi.TvlqrResult(lq.K[b - b0], lq.P[b - b0], lq.AB[b - b0], int(lq.status[b - b0]),
+                                               int(lq.fail_knot[b - b0]))
             TOSs[b].traj, TOSs[b].SCPS = SCPS.traj, SCPS
             out[b] = SCPS
     return out

@@ -429,3 +429,33 @@ function verify_collision_free_hip(traj::Trajectory, SCPS::SCPSolution)
   r = verify_batch!(h, 1, Float64.(traj.X), Float64.(traj.U); nstep=1, dense_collision=false)
   r.collision_free[1], r.first_knot[1], r.first_dist[1]
 end
+
+# ---- time-varying LQR tracking gains on the GPU (gusto_tvlqr, csrc/tvlqr.hip) ------------------------------------------------
+# u = U[:,k] - K_k (x(t_k) - X[:,k]) around every trajectory of a handle, on the exact derivative of the zero-order-hold RK4
+# roll-out gusto_interpolate performs (include/gusto_hip.h states the definitions; the reference has no counterpart).
+# GuSTO handles only (TrajOpt handles answer GUSTO_ERR_ARG).
+struct GustoTvlqrOpts      # gusto_tvlqr_opts
+  Q::NTuple{13,Cdouble}; R::NTuple{6,Cdouble}; Qf::NTuple{13,Cdouble}
+  dt_min::Cdouble; nstep::Cint; nstep_cap::Cint
+  store_P::Cint
+end
+gusto_weights(w, dim, cap) = (v = w isa Number ? fill(Float64(w), dim) : Float64.(collect(w)); ntuple(i -> i <= dim ? v[i] : 0.0, cap))
+
+# The gains of B problems of handle h (x_dim n, u_dim m, N knots); X [n,N,B], U [m,N,B] or nothing = the handle's own trajectories.
+# Q, R, Qf: diagonal weights, numbers or vectors.  The C arrays are row-major, so the Julia arrays carry the transposes:
+# K [n,m,N-1,B] with K[:,:,k,b]' = K_k, AB [n+m,n,N-1,B] with AB[:,:,k,b]' = [Ad_k Bd_k], P [n,n,B] of knot 1 or [n,n,N,B] with store_P.
+function tvlqr_batch!(h::Ptr{Cvoid}, B::Integer, n::Integer, m::Integer, N::Integer, X=nothing, U=nothing; Q=1.0, R=1.0, Qf=1.0,
+                      dt_min=0.1, nstep=0, nstep_cap=64, store_P=false)
+  Xp = X === nothing ? Ptr{Cdouble}(C_NULL) : pointer(X); Up = U === nothing ? Ptr{Cdouble}(C_NULL) : pointer(U)
+  o = GustoTvlqrOpts(gusto_weights(Q, n, 13), gusto_weights(R, m, 6), gusto_weights(Qf, n, 13), dt_min, nstep, nstep_cap, store_P ? 1 : 0)
+  GC.@preserve X U gusto_check(ccall((:gusto_tvlqr, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{GustoTvlqrOpts}),
+                    h, Xp, Up, o), h, "tvlqr")
+  status, fail_knot = zeros(Cint, B), zeros(Cint, B)
+  K, AB = zeros(n, m, N - 1, B), zeros(n + m, n, N - 1, B)
+  P = store_P ? zeros(n, n, N, B) : zeros(n, n, B)
+  gusto_check(ccall((:gusto_get_tvlqr, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    h, status, fail_knot, K, P, AB), h, "get_tvlqr")
+  ms = Ref{Cdouble}(0.0)
+  gusto_check(ccall((:gusto_last_tvlqr_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, ms), h, "last_tvlqr_ms")
+  (K = K, P = P, AB = AB, status = Int.(status), fail_knot = Int.(fail_knot), ms = ms[])
+end

@@ -283,6 +283,50 @@ int gusto_interpolate(gusto_handle h, const double* X, const double* U, const gu
 int gusto_get_dense(gusto_handle h, int* nfull, double* Xfull, double* Ufull);
 int gusto_last_verify_ms(gusto_handle h, double* ms);
 
+/* Time-varying LQR tracking gains around every trajectory of the batch (csrc/tvlqr.hip): the feedback law
+ *     u = U[:,k] - K_k (x(t_k) - X[:,k])
+ * that goes with the open-loop X, U, t.  No counterpart in the reference (it hands its trajectories over open loop); the
+ * definitions are therefore stated here.
+ * Roll-out map: F_k(x, u) is Nstep_b classical RK4 steps of dt_b / Nstep_b from x under the held control u, Nstep_b exactly as
+ *   gusto_verify computes it (nstep, or ceil(dt_b / dt_min); outside 1 .. nstep_cap: GUSTO_ERR_ARG for the whole call, nothing
+ *   is launched).  It is the map whose value at (X[:,k], U[:,k]) gusto_interpolate rolls out.  States are not renormalised: the
+ *   quaternion of AstrobeeSE3Manifold is carried as 13 plain states.
+ * Discrete Jacobians: Ad_k = dF_k/dx, Bd_k = dF_k/du at (X[:,k], U[:,k]), k = 1 .. N-1 -- the exact derivative of that discrete
+ *   map, forward mode through the four RK4 stages of every substep with the models' own A = df/dx at each stage point and
+ *   B = df/du (not a matrix exponential, not a finite difference).
+ * Riccati recursion: P_N = diag(Qf); for k = N-1 .. 1
+ *     H = diag(Q, R) + [Ad_k Bd_k]' P_{k+1} [Ad_k Bd_k],   L = chol(H_uu),   W = L^-1 H_ux,   K_k = L^-T W,
+ *     P_k = H_xx - W' W   (stored symmetric; H_uu^-1 is never formed).
+ * Status: a Cholesky pivot <= 0 or not finite at knot k gives the problem status 0 and fail_knot k (1-based); its gains, and
+ *   its P, from that knot down to knot 1 are zeros.  Otherwise status 1, fail_knot 0.  Failures are data, not return codes.
+ * X [B][N][x_dim], U [B][N][u_dim]: host trajectories, or NULL, NULL = the handle's current ones; exactly one NULL is
+ *   GUSTO_ERR_ARG.  The call honours gusto_set_active (an inactive problem's outputs stay as the last call wrote them), runs on
+ *   the handle's stream after any pending gusto_solve_async, is timed with events of its own (gusto_last_solve_ms and
+ *   gusto_last_verify_ms keep their values) and never changes trajectories, status or histories.  TrajOpt handles answer
+ *   GUSTO_ERR_ARG, a handle without problems GUSTO_ERR_STATE, a weight out of range (Q, Qf >= 0 and R > 0 on the model's
+ *   x_dim / u_dim entries, all finite) GUSTO_ERR_ARG.  Every horizon gusto_create accepts, all four models.
+ * The device buffers (AB, K, P; several hundred MB at 8192 problems of AstrobeeSE3) exist only after the first call and are
+ *   sized by the batch of that call (a later call with a larger batch, after a new gusto_set_problems, grows them); the P of
+ *   every knot only after the first call with store_P.  A masked first call after gusto_set_problems leaves zeros for the
+ *   inactive problems.  "As the last call wrote them" holds per buffer: the P of every knot is written by calls with store_P
+ *   only, so after calls that mix store_P an inactive problem's full P can be older than its K and its P of knot 1. */
+typedef struct {
+    double Q[GUSTO_MAXN], R[GUSTO_MAXM], Qf[GUSTO_MAXN]; /* diagonal weights */
+    double dt_min; int nstep, nstep_cap;                 /* the roll-out of gusto_verify_opts, same meaning, same refusal */
+    int store_P;                                         /* 1: keep P of every knot; 0 (default): only P of knot 1 */
+} gusto_tvlqr_opts;
+/* Q = Qf = R = 1 on the model's entries (0 behind them), dt_min 0.1, nstep 0, nstep_cap 64, store_P 0 */
+int gusto_default_tvlqr_opts(int model_id, gusto_tvlqr_opts* o);
+int gusto_tvlqr(gusto_handle h, const double* X, const double* U, const gusto_tvlqr_opts* o);
+/* Caller-owned arrays; any pointer may be NULL.  status, fail_knot [B]; K [B][N-1][u_dim][x_dim]; AB [B][N-1][x_dim][x_dim + u_dim],
+ * the rows of [Ad | Bd]; P [B][N][x_dim][x_dim] when the LAST call ran with store_P (P_N = diag(Qf) included), else
+ * [B][x_dim][x_dim], the P of knot 1.  The signature carries no size: a caller that wants every knot's P passes store_P = 1
+ * to the call before (gusto.jl_amd/_capi.py refuses the full P after a call without store_P with GUSTO_ERR_STATE's code).
+ * Before the first gusto_tvlqr since gusto_set_problems: GUSTO_ERR_STATE. */
+int gusto_get_tvlqr(gusto_handle h, int* status, int* fail_knot, double* K, double* P, double* AB);
+/* GPU time of both phases of the last gusto_tvlqr (linearise + Riccati), from HIP events on the handle's stream */
+int gusto_last_tvlqr_ms(gusto_handle h, double* ms);
+
 /* One convex subproblem per problem (what scp_gusto.jl:82-104 builds and solves in one trip), linearised at
  * (Xp,Up)[b] with the given Delta/omega/obstacle_toggle_distance[b].  Used by the parity tests.
  * Outputs: Xn,Un [B][N][.], obj [B] (JuMP.objective_value), status [B] (GUSTO_SOLVER_*), iters [B]. */
@@ -336,6 +380,9 @@ int gusto_subproblem_trajopt(gusto_handle h, int B, const double* Xp, const doub
 /* Development hook (libraries built with -DGUSTO_PROFILE only, otherwise GUSTO_ERR_STATE): per-problem cycle counters of
  * the kernel's phases, [B][48] (tools/gpu_prof.py).  Stands in for SCPS.iter_elapsed_times at a finer grain. */
 int gusto_dev_get_prof(gusto_handle h, long long* out);
+/* Development hook: the GPU time of the two launches of the last gusto_tvlqr -- linearise, Riccati -- split by a third event
+ * between them (tools/tvlqr_time.py).  Either pointer may be NULL; GUSTO_ERR_STATE before the first gusto_tvlqr. */
+int gusto_dev_tvlqr(gusto_handle h, double* linearise_ms, double* riccati_ms);
 /* Development hook: shape of the last gusto_solve / gusto_subproblem launch -- resident (persistent) workgroups, dynamic
  * LDS bytes per workgroup, workgroups per CU.  GUSTO_ERR_STATE before the first launch.  (The freeflyerSE2 N = 50 kernel
  * is tuned to 4 problems per CU: 40 664 B of the 160 KiB; tests/test_gpu_parity.py guards it.) */
