@@ -383,9 +383,7 @@ class BatchSolver:
         self.B = int(B)
 
     def last_solve_ms(self):
-        ms = C.c_double()
-        self._chk(self.L.gusto_last_solve_ms(self.h, C.byref(ms)), "last_solve_ms")
-        return ms.value
+        return self._last_ms("last_solve_ms")
 
     def traj(self):
         X, U = np.zeros((self.B, self.N, self.n)), np.zeros((self.B, self.N, self.m))
@@ -470,17 +468,28 @@ class BatchSolver:
                                          X.ctypes.data, U.ctypes.data), "get_shoot")
         return dict(status=st, newton_iters=it, resid=res, p0=pp, X=X, U=U)
 
-    def _verify_args(self, X, U, opts):
+    def _traj_ptrs(self, X, U, who):
+        """the optional X, U of verify / interpolate / tvlqr -- given together or not at all -- as [B, N, n] and [B, N, m] arrays:
+        (their addresses or None, None; the arrays, for the caller to hold during the call)"""
         if (X is None) != (U is None):
-            raise ValueError("verify / interpolate: X and U are given together or not at all")
+            raise ValueError(f"{who}: X and U are given together or not at all")
+        if X is None:
+            return None, None, ()
+        keep = _arr(X).reshape(self.B, self.N, self.n), _arr(U).reshape(self.B, self.N, self.m)
+        return keep[0].ctypes.data, keep[1].ctypes.data, keep
+
+    def _last_ms(self, what):
+        ms = C.c_double()
+        self._chk(getattr(self.L, "gusto_" + what)(self.h, C.byref(ms)), what)
+        return ms.value
+
+    def _verify_args(self, opts):
         o = default_verify_opts()
         for k, v in opts.items():
             if k not in ("dt_min", "nstep", "nstep_cap", "dense_collision"):
                 raise TypeError(f"unknown verify option {k!r}")
             setattr(o, k, float(v) if k == "dt_min" else int(v))
-        Xa = None if X is None else _arr(X).reshape(self.B, self.N, self.n)
-        Ua = None if U is None else _arr(U).reshape(self.B, self.N, self.m)
-        return Xa, Ua, o
+        return o
 
     def get_verify(self):
         """gusto_get_verify: the report of the last verify() / interpolate() as a dict of [B] arrays."""
@@ -494,27 +503,23 @@ class BatchSolver:
         """gusto_verify + gusto_get_verify: collision check at the knots, forward-Euler defect, RK4 roll-out between the knots
         (dense minimum distance, gap at the knots) of X, U (default: the handle's trajectories, left as they are).
         opts: dt_min, nstep, nstep_cap, dense_collision (gusto_verify_opts)."""
-        Xa, Ua, o = self._verify_args(X, U, opts)
-        self._chk(self.L.gusto_verify(self.h, None if Xa is None else Xa.ctypes.data, None if Ua is None else Ua.ctypes.data,
-                                      C.byref(o)), "verify")
+        px, pu, _keep = self._traj_ptrs(X, U, "verify")
+        self._chk(self.L.gusto_verify(self.h, px, pu, C.byref(self._verify_args(opts))), "verify")
         return self.get_verify()
 
     def interpolate(self, X=None, U=None, **opts):
         """gusto_interpolate + gusto_get_dense: (nfull [B], Xfull [B, nfull_max, n], Ufull [B, nfull_max - 1, m]); rows behind
         nfull[b] are zeros.  get_verify() then holds the report of the same pass."""
-        Xa, Ua, o = self._verify_args(X, U, opts)
+        px, pu, _keep = self._traj_ptrs(X, U, "interpolate")
         nf = C.c_int()
-        self._chk(self.L.gusto_interpolate(self.h, None if Xa is None else Xa.ctypes.data,
-                                           None if Ua is None else Ua.ctypes.data, C.byref(o), C.byref(nf)), "interpolate")
+        self._chk(self.L.gusto_interpolate(self.h, px, pu, C.byref(self._verify_args(opts)), C.byref(nf)), "interpolate")
         nfull = np.zeros(self.B, dtype=np.int32)
         Xf, Uf = np.zeros((self.B, nf.value, self.n)), np.zeros((self.B, nf.value - 1, self.m))
         self._chk(self.L.gusto_get_dense(self.h, nfull.ctypes.data, Xf.ctypes.data, Uf.ctypes.data), "get_dense")
         return nfull, Xf, Uf
 
     def last_verify_ms(self):
-        ms = C.c_double()
-        self._chk(self.L.gusto_last_verify_ms(self.h, C.byref(ms)), "last_verify_ms")
-        return ms.value
+        return self._last_ms("last_verify_ms")
 
     def tvlqr_opts(self, opts=None):
         """a gusto_tvlqr_opts from None (the defaults), a TvlqrOpts, or a dict of its fields -- Q, R, Qf as scalars or vectors of
@@ -539,13 +544,9 @@ class BatchSolver:
     def tvlqr(self, opts=None, X=None, U=None):
         """gusto_tvlqr + gusto_get_tvlqr: the time-varying LQR gains K_k of u = U_k - K_k (x - X_k) around X, U (default: the
         handle's trajectories, left as they are), on the exact derivative of the RK4 roll-out interpolate() performs."""
-        if (X is None) != (U is None):
-            raise ValueError("tvlqr: X and U are given together or not at all")
+        px, pu, _keep = self._traj_ptrs(X, U, "tvlqr")
         o = self.tvlqr_opts(opts)
-        Xa = None if X is None else _arr(X).reshape(self.B, self.N, self.n)
-        Ua = None if U is None else _arr(U).reshape(self.B, self.N, self.m)
-        self._chk(self.L.gusto_tvlqr(self.h, None if Xa is None else Xa.ctypes.data, None if Ua is None else Ua.ctypes.data,
-                                     C.byref(o)), "tvlqr")
+        self._chk(self.L.gusto_tvlqr(self.h, px, pu, C.byref(o)), "tvlqr")
         self._tvlqr_store_P = bool(o.store_P)
         return self.get_tvlqr()
 
@@ -572,9 +573,7 @@ class BatchSolver:
         return a.value, b.value
 
     def last_tvlqr_ms(self):
-        ms = C.c_double()
-        self._chk(self.L.gusto_last_tvlqr_ms(self.h, C.byref(ms)), "last_tvlqr_ms")
-        return ms.value
+        return self._last_ms("last_tvlqr_ms")
 
     def subproblem(self, Xp, Up, Delta, omega, toggle):
         B = self.B

@@ -38,20 +38,34 @@ public:
         reset();
         return alloc(count);
     }
+    // ensure(), and zeros (enqueued on `s`) whenever that (re)allocated: a buffer large enough keeps its contents
+    hipError_t ensure_zeroed(size_t count, hipStream_t s) {
+        if (p_ && count <= n_) return hipSuccess;
+        const hipError_t e = ensure(count);
+        return e != hipSuccess ? e : hipMemsetAsync(p_, 0, sizeof(T) * count, s);
+    }
     T* get() const { return p_; }
     operator T*() const { return p_; }
     size_t count() const { return n_; }
 };
 
 // an event owned by the handle; create() is lazy and idempotent
-struct DevEvent {
+struct __attribute__((visibility("hidden"))) DevEvent {
     hipEvent_t e = nullptr;
     DevEvent() = default;
     DevEvent(const DevEvent&) = delete;
     ~DevEvent() { if (e) (void)hipEventDestroy(e); }
     hipError_t create(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
     operator hipEvent_t() const { return e; }
+    hipError_t record(hipStream_t s) { const hipError_t c = create(); return c != hipSuccess ? c : hipEventRecord(e, s); }
 };
+// a timer on a stream: from.record() (which creates it the first time), the launches, to.record(), hipStreamSynchronize, this
+static inline hipError_t event_ms(const DevEvent& from, const DevEvent& to, double* ms) {
+    float f = 0;
+    const hipError_t e = hipEventElapsedTime(&f, from, to);
+    if (e == hipSuccess) *ms = f;
+    return e;
+}
 
 // What the host side knows about a model, indexed by the public gusto_model_id: state and control dimensions, the internal id
 // of its TrajOpt variant (common.hpp: GUSTO_TO_*; -1 = none), whether it has keep-out sets and a shooting ODE.
@@ -71,6 +85,40 @@ static_assert(GUSTO_FREEFLYER_SE2 == 0 && GUSTO_DUBINS_CAR == 1 && GUSTO_ASTROBE
 static inline const ModelInfo* model_info(int model) {
     return model >= 0 && model < (int)(sizeof(MODEL_TABLE) / sizeof(MODEL_TABLE[0])) ? &MODEL_TABLE[model] : nullptr;
 }
+
+// What the post-solve stages (post.hpp) keep on the handle; invalidate() is gusto_set_problems: the buffers stay.
+// Indirect shooting (shoot.hip): trajectories, converged costates, seeds, residuals, status, Newton iterations
+struct __attribute__((visibility("hidden"))) ShootState {
+    DevBuf<double> X, U, P, P0, Res;
+    DevBuf<double> Xt, Ut;   // knot-major staging of the shooting trajectories ([N][n][B])
+    DevBuf<int> St, It, List;
+    bool have = false;
+    void invalidate() { have = false; }
+};
+// Verification (verify.hip): the report ([4][batch_cap] ints: collision_free, first_knot, min_dense_sample, nfull; [5][batch_cap]
+// doubles: first_dist, min_dist_knots, dyn_defect_l1, min_dist_dense, max_gap), copies of a caller's X / U, the dense
+// trajectories of gusto_interpolate ([batch_cap][dense_rows][n], [batch_cap][dense_rows - 1][m])
+struct __attribute__((visibility("hidden"))) VerifyState {
+    DevBuf<int> I;
+    DevBuf<double> D, X, U, Xf, Uf;
+    int dense_rows = 0;
+    bool have = false, have_dense = false;
+    DevEvent t0, t1;
+    double last_ms = 0.0;
+    void invalidate() { have = false; have_dense = false; }
+};
+// Time-varying LQR gains (tvlqr.hip), B the batch of the call that allocated them: [B][N - 1][n][n + m] rows of [Ad | Bd],
+// [B][N - 1][m][n] gains, [B][n][n] P of knot 1, [B][N][n][n] P of every knot (first call with store_P only), [2][B] status and
+// fail_knot, copies of a caller's X / U.  A later call with a larger batch grows them, contents discarded.  `mid` is recorded
+// between the two launches (gusto_dev_tvlqr).  have_Pall outlives invalidate(): the next gusto_tvlqr resets it
+struct __attribute__((visibility("hidden"))) TvlqrState {
+    DevBuf<double> AB, K, P1, Pall, X, U;
+    DevBuf<int> St;
+    bool have = false, store_P = false, have_Pall = false;
+    DevEvent t0, mid, t1;
+    double last_ms = 0.0, lin_ms = 0.0, ric_ms = 0.0;
+    void invalidate() { have = false; }
+};
 
 struct gusto_handle_s {
     int model = 0, n = 0, m = 0, N = 0, batch_cap = 0, hist_cap = 0, device = 0, B = 0;
@@ -111,7 +159,7 @@ struct gusto_handle_s {
     int slots = 0;            // resident workgroups the last launch used (persistent kernel)
     int lds_bytes = 0, per_cu = 0;   // ... its dynamic LDS per workgroup and workgroups per CU (gusto_dev_launch_info)
     int sched_init[gusto::SQ_WORDS] = {0};   // initial scheduler words of a launch (host side of an async copy)
-    bool have_problems = false, have_shoot = false;
+    bool have_problems = false;
     int decomposition = 0;         // gusto_set_decomposition: 0 auto, 1 a wave per problem, 3 / 4 two / four waves per problem (2: reserved, refused)
     int waves = 0;                 // waves per problem of the GuSTO kernel (0 = one per 64 knots; development builds: GUSTO_DEV_WAVES)
     // gusto_set_active: the problems the next gusto_solve calls iterate (n_active < 0: all of them); d_active = the mask [B]
@@ -122,28 +170,7 @@ struct gusto_handle_s {
     int* h_sched_err = nullptr;    // pinned host word the error flag is copied to on the handle's stream, before the stream is waited for
     DevBuf<double> d_gX, d_gU;     // gusto_gather_peer: the shards of several handles, one after the other, on this handle's GPU
     DevBuf<double> d_Upub;         // TrajOpt handles: U compacted to the public [B][N][u_dim] layout for gusto_get_traj_dev
-    // indirect shooting (shoot.hip): trajectories, converged costates, seeds, residuals, status, Newton iterations
-    DevBuf<double> d_shX, d_shU, d_shP, d_shP0, d_shRes;
-    DevBuf<double> d_shXt, d_shUt;   // knot-major staging of the shooting trajectories ([N][n][B])
-    DevBuf<int> d_shSt, d_shIt, d_shList;
-    // post-solve verification (verify.hip): the report ([4][batch_cap] ints: collision_free, first_knot, min_dense_sample, nfull;
-    // [5][batch_cap] doubles: first_dist, min_dist_knots, dyn_defect_l1, min_dist_dense, max_gap), copies of a caller's X / U,
-    // the dense trajectories of gusto_interpolate ([batch_cap][dense_rows][n], [batch_cap][dense_rows - 1][m]), its own events
-    DevBuf<int> d_vI;
-    DevBuf<double> d_vD, d_vX, d_vU, d_vXf, d_vUf;
-    int dense_rows = 0;
-    bool have_verify = false, have_dense = false;
-    DevEvent ev_v0, ev_v1;
-    double last_verify_ms = 0.0;
-    // time-varying LQR gains (tvlqr.hip, the only file that touches them): [lq_B][N - 1][n][n + m] rows of [Ad | Bd], [lq_B][N - 1][m][n]
-    // gains, [lq_B][n][n] P of knot 1, [lq_B][N][n][n] P of every knot (first call with store_P only), [2][lq_B] status and
-    // fail_knot, copies of a caller's X / U.  Sized by the batch of the call that allocates them, grown (contents discarded) by a
-    // later call with a larger batch.  ev_qm sits between the two launches (gusto_dev_tvlqr: the split of the time)
-    DevBuf<double> d_lqAB, d_lqK, d_lqP1, d_lqPall, d_lqX, d_lqU;
-    DevBuf<int> d_lqSt;
-    bool have_tvlqr = false, lq_store_P = false, lq_have_Pall = false;
-    DevEvent ev_q0, ev_qm, ev_q1;
-    double last_tvlqr_ms = 0.0, lq_lin_ms = 0.0, lq_ric_ms = 0.0;
+    ShootState shoot; VerifyState verify; TvlqrState tvlqr;   // the post-solve stages
     std::string err;
 
     // (the buffers and events free themselves; the caller has made `device` current: gusto_destroy)
@@ -182,9 +209,7 @@ static inline int gusto_sched_err_rc(gusto_handle h) {
 static inline int gusto_complete(gusto_handle h) {
     if (!h->pending) return GUSTO_OK;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->last_ms = ms;
+    HIPCHK(h, event_ms(h->ev0, h->ev1, &h->last_ms));
     h->pending = false;
     if (h->h_sched_err && *h->h_sched_err) h->sched_err = *h->h_sched_err;
     return GUSTO_OK;

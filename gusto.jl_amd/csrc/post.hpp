@@ -1,0 +1,91 @@
+// post.hpp -- the host path of the post-solve stages (shoot.hip, verify.hip, tvlqr.hip; nothing else includes it).  Plain
+// functions that answer a GUSTO_* code and leave the text in h->err: `if (int rc = ...) return rc;` at the call site.  A new
+// stage starts from these and from a struct of its own next to ShootState / VerifyState / TvlqrState (handle.hpp).
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <type_traits>
+#include <vector>
+
+#include "handle.hpp"
+
+// the refusals every stage begins with (a stage without X, U passes nulls), then the handle's device and its enqueued solve
+static inline int post_enter(gusto_handle h, const char* who, const double* X, const double* U) {
+    if (!h) return GUSTO_ERR_ARG;
+    const std::string w(who);
+    if (h->trajopt) { h->err = w + ": TrajOpt handle (its controls carry the defect variables; not supported)"; return GUSTO_ERR_ARG; }
+    if (!h->have_problems) { h->err = w + ": call gusto_set_problems first"; return GUSTO_ERR_STATE; }
+    if ((X == nullptr) != (U == nullptr)) { h->err = w + ": X and U are given together or not at all"; return GUSTO_ERR_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    return gusto_finish(h);
+}
+
+// the roll-out options of gusto_verify_opts / gusto_tvlqr_opts (false: the caller's "bad options")
+static inline bool nstep_opts_ok(double dt_min, int nstep, int nstep_cap) {
+    return nstep >= 0 && nstep_cap >= 1 && (nstep > 0 || dt_min > 0);
+}
+// Nstep of every problem, never clamped: nstep, or ceil(dt / dt_min) and the largest of them in *nstep_max; outside
+// 1 .. nstep_cap: GUSTO_ERR_ARG and the text, which names the first such problem, in *err.  No device, no handle.
+static inline int resolve_nstep_host(const double* tf, size_t B, int N, double dt_min, int nstep, int nstep_cap, const char* who,
+                                     int* nstep_max, std::string* err) {
+    *nstep_max = nstep;
+    if (nstep > nstep_cap) { *err = std::string(who) + ": nstep above nstep_cap"; return GUSTO_ERR_ARG; }
+    for (size_t b = 0; nstep == 0 && b < B; b++) {
+        const double q = ceil(tf[b] / (double)(N - 1) / dt_min);
+        if (!(q >= 1 && q <= (double)nstep_cap)) {
+            *err = std::string(who) + ": problem " + std::to_string(b) + " needs ceil(dt / dt_min) = " + std::to_string(q) + " substeps, outside 1 .. nstep_cap";
+            return GUSTO_ERR_ARG;
+        }
+        *nstep_max = std::max(*nstep_max, (int)q);
+    }
+    return GUSTO_OK;
+}
+// ... of the handle's problems: tf comes back from the device when the count depends on it
+static inline int resolve_nstep(gusto_handle h, const char* who, double dt_min, int nstep, int nstep_cap, int* nstep_max) {
+    std::vector<double> tf(nstep == 0 ? h->B : 0);
+    if (!tf.empty()) {
+        HIPCHK(h, hipMemcpyAsync(tf.data(), h->d_tf, sizeof(double) * tf.size(), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return resolve_nstep_host(tf.data(), tf.size(), h->N, dt_min, nstep, nstep_cap, who, nstep_max, &h->err);
+}
+
+// KParams of a kernel that reads trajectories: zeros but for the sizes, the model parameters and tf
+static inline gusto::KParams post_params(gusto_handle h) {
+    gusto::KParams P;
+    memset(&P, 0, sizeof(P));
+    P.N = h->N; P.B = h->B; P.mp = h->mp; P.tf = h->d_tf;
+    return P;
+}
+// The trajectories a stage reads: the handle's, or copies of the caller's X, U in the stage's dX, dU (room for `slots`
+// problems, grow-only: a constant `slots` allocates once); the handle's own stay as they are
+static inline int stage_traj(gusto_handle h, const double* X, const double* U, size_t slots, DevBuf<double>& dX, DevBuf<double>& dU,
+                             const double** Xd, const double** Ud) {
+    *Xd = h->d_X; *Ud = h->d_U;
+    if (!X) return GUSTO_OK;
+    const size_t B = h->B, N = h->N, n = h->n, m = h->m;
+    HIPCHK(h, dX.ensure(slots * N * n)); HIPCHK(h, dU.ensure(slots * N * m));
+    HIPCHK(h, hipMemcpyAsync(dX, X, sizeof(double) * B * N * n, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dU, U, sizeof(double) * B * N * m, hipMemcpyHostToDevice, h->stream));
+    *Xd = dX; *Ud = dU;
+    return GUSTO_OK;
+}
+// gusto_set_active: null = every problem, else the mask [B]
+static inline const int* active_mask(gusto_handle h) { return h->n_active >= 0 ? h->d_active.get() : nullptr; }
+
+// f(std::integral_constant<int, MODEL>{}), which answers a GUSTO_* code, for the public model id `model`
+template <class F> static int for_model(int model, F&& f) {
+    switch (model) {
+    case GUSTO_FREEFLYER_SE2: return f(std::integral_constant<int, GUSTO_FREEFLYER_SE2>{});
+    case GUSTO_DUBINS_CAR: return f(std::integral_constant<int, GUSTO_DUBINS_CAR>{});
+    case GUSTO_ASTROBEE_SE3: return f(std::integral_constant<int, GUSTO_ASTROBEE_SE3>{});
+    case GUSTO_ASTROBEE_SE3_MANIFOLD: return f(std::integral_constant<int, GUSTO_ASTROBEE_SE3_MANIFOLD>{});
+    }
+    return GUSTO_ERR_ARG;
+}
+// a getter's array: `count` elements to the caller's dst (null: not asked for)
+template <class T> static int copy_out(gusto_handle h, T* dst, const std::common_type_t<T>* src, size_t count) {
+    if (dst) HIPCHK(h, hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost));
+    return GUSTO_OK;
+}

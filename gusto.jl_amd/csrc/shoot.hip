@@ -19,7 +19,7 @@
 // consecutive addresses -- and a tiled transpose (shoot_transpose_kernel) produces the [b][k][i] layout of the C ABI.
 #include <hip/hip_runtime.h>
 
-#include "handle.hpp"
+#include "post.hpp"
 
 using namespace gusto;
 
@@ -346,6 +346,26 @@ __global__ void __launch_bounds__(256) shoot_transpose_kernel(const double* in, 
     }
 }
 
+// the launches of the two passes; a model without a ShootModel has no kernels (gusto_shoot has refused it)
+template <int MODEL> int launch_lane_pass(gusto_handle h, const ShootParams& S) {
+    if constexpr (MODEL_TABLE[MODEL].has_shoot) {
+        hipLaunchKernelGGL(shoot_kernel<MODEL>, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, S);
+        HIPCHK(h, hipGetLastError());
+        return GUSTO_OK;
+    }
+    return GUSTO_ERR_ARG;
+}
+// (16 lanes per problem: the 14 candidates of a line search in one round; measured 83 ms against 104 with 8 lanes and 112 with 4
+// for dubins_car B = 65 536, 368 ms with the lane-per-problem pass alone)
+template <int MODEL> int launch_group_pass(gusto_handle h, const ShootParams& S, int count) {
+    if constexpr (MODEL_TABLE[MODEL].has_shoot) {
+        hipLaunchKernelGGL((shoot_group_kernel<MODEL, 16>), dim3((count + 3) / 4), dim3(64), 0, h->stream, S, count);
+        HIPCHK(h, hipGetLastError());
+        return GUSTO_OK;
+    }
+    return GUSTO_ERR_ARG;
+}
+
 }  // namespace
 
 extern "C" {
@@ -358,79 +378,69 @@ int gusto_default_shoot_opts(gusto_shoot_opts* o) {
 }
 
 int gusto_shoot(gusto_handle h, const double* p0, const gusto_shoot_opts* opts) {
-    if (!h) return GUSTO_ERR_ARG;
-    if (h->trajopt || !model_info(h->model)->has_shoot) {
+    if (h && (h->trajopt || !model_info(h->model)->has_shoot)) {
         h->err = "gusto_shoot: only DubinsCar and AstrobeeSE3Manifold have a shooting ODE (as in the reference)";
         return GUSTO_ERR_ARG;
     }
-    const size_t n = h->n, m = h->m;
-    if (!h->have_problems) { h->err = "gusto_shoot: call gusto_set_problems first"; return GUSTO_ERR_STATE; }
-    HIPCHK(h, hipSetDevice(h->device));
-    { int rc = gusto_finish(h); if (rc) return rc; }
+    if (int rc = post_enter(h, "gusto_shoot", nullptr, nullptr)) return rc;
     gusto_shoot_opts o;
     gusto_default_shoot_opts(&o);
     if (opts) o = *opts;
     if (o.substeps < 1 || o.max_newton < 0 || !(o.ftol > 0) || (o.no_group_pass != 0 && o.no_group_pass != 1)) { h->err = "gusto_shoot: bad options"; return GUSTO_ERR_ARG; }
-    const size_t B = h->batch_cap, N = h->N;
-    HIPCHK(h, h->d_shX.alloc(B * N * n)); HIPCHK(h, h->d_shU.alloc(B * N * m)); HIPCHK(h, h->d_shP.alloc(B * n));
-    HIPCHK(h, h->d_shXt.alloc(B * N * n)); HIPCHK(h, h->d_shUt.alloc(B * N * m));
-    HIPCHK(h, h->d_shP0.alloc(B * n)); HIPCHK(h, h->d_shRes.alloc(B)); HIPCHK(h, h->d_shSt.alloc(B)); HIPCHK(h, h->d_shIt.alloc(B));
-    HIPCHK(h, h->d_shList.alloc(B + 1));   // [B] problems for the group pass, [1] their number
+    ShootState& T = h->shoot;
+    const size_t B = h->batch_cap, N = h->N, n = h->n, m = h->m;
+    HIPCHK(h, T.X.alloc(B * N * n)); HIPCHK(h, T.U.alloc(B * N * m)); HIPCHK(h, T.P.alloc(B * n));
+    HIPCHK(h, T.Xt.alloc(B * N * n)); HIPCHK(h, T.Ut.alloc(B * N * m));
+    HIPCHK(h, T.P0.alloc(B * n)); HIPCHK(h, T.Res.alloc(B)); HIPCHK(h, T.St.alloc(B)); HIPCHK(h, T.It.alloc(B));
+    HIPCHK(h, T.List.alloc(B + 1));   // [B] problems for the group pass, [1] their number
     if (p0) {
-        HIPCHK(h, hipMemcpyAsync(h->d_shP0, p0, sizeof(double) * h->B * n, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(T.P0, p0, sizeof(double) * h->B * n, hipMemcpyHostToDevice, h->stream));
     } else {   // SCPS.dual of every problem (st_d rows: [toggle, spare, dual[n]])
-        HIPCHK(h, hipMemcpy2DAsync(h->d_shP0, sizeof(double) * n, h->d_std + SD_DUAL, sizeof(double) * SD_ND, sizeof(double) * n, h->B,
+        HIPCHK(h, hipMemcpy2DAsync(T.P0, sizeof(double) * n, h->d_std + SD_DUAL, sizeof(double) * SD_ND, sizeof(double) * n, h->B,
                                    hipMemcpyDeviceToDevice, h->stream));
     }
     ShootParams S{};
     S.B = h->B; S.N = h->N; S.substeps = o.substeps; S.max_newton = o.max_newton; S.ftol = o.ftol;
     S.v = h->mp.dubins_v; S.k = h->mp.dubins_k; S.mass = h->mp.mass;
     for (int i = 0; i < 3; i++) S.J[i] = h->mp.Jdiag[i];
-    S.x_init = h->d_xinit; S.goal_lo = h->d_glo; S.goal_hi = h->d_ghi; S.tf = h->d_tf; S.p0 = h->d_shP0;
-    S.X = h->d_shXt; S.U = h->d_shUt; S.p_out = h->d_shP; S.resid = h->d_shRes; S.status = h->d_shSt; S.iters = h->d_shIt;
+    S.x_init = h->d_xinit; S.goal_lo = h->d_glo; S.goal_hi = h->d_ghi; S.tf = h->d_tf; S.p0 = T.P0;
+    S.X = T.Xt; S.U = T.Ut; S.p_out = T.P; S.resid = T.Res; S.status = T.St; S.iters = T.It;
     // two passes: a lane per problem for the first SHOOT_CAP Newton iterations (the problems that converge need 0-4), then
     // the stragglers with a group of lanes each (shoot_group_kernel)
     constexpr int SHOOT_CAP = 8;
     S.cap = (o.no_group_pass || o.max_newton <= SHOOT_CAP) ? o.max_newton : SHOOT_CAP;
-    S.list = h->d_shList; S.count = h->d_shList + h->batch_cap;
-    S.active = h->n_active >= 0 ? h->d_active : nullptr;
+    S.list = T.List; S.count = T.List + h->batch_cap;
+    S.active = active_mask(h);
     HIPCHK(h, hipMemsetAsync(S.count, 0, sizeof(int), h->stream));
-    if (h->model == GUSTO_DUBINS_CAR) hipLaunchKernelGGL(shoot_kernel<GUSTO_DUBINS_CAR>, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, S);
-    else hipLaunchKernelGGL(shoot_kernel<GUSTO_ASTROBEE_SE3_MANIFOLD>, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, S);
-    HIPCHK(h, hipGetLastError());
+    if (int rc = for_model(h->model, [&](auto M) { return launch_lane_pass<M()>(h, S); })) return rc;
     int n_later = 0;
     HIPCHK(h, hipMemcpyAsync(&n_later, S.count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (n_later > 0) {
-        // (16 lanes per problem: the 14 candidates of a line search in one round; measured 83 ms against 104 with 8 lanes and
-        // 112 with 4 for dubins_car B = 65 536, 368 ms with the lane-per-problem pass alone)
-        if (h->model == GUSTO_DUBINS_CAR) hipLaunchKernelGGL((shoot_group_kernel<GUSTO_DUBINS_CAR, 16>), dim3((n_later + 3) / 4), dim3(64), 0, h->stream, S, n_later);
-        else hipLaunchKernelGGL((shoot_group_kernel<GUSTO_ASTROBEE_SE3_MANIFOLD, 16>), dim3((n_later + 3) / 4), dim3(64), 0, h->stream, S, n_later);
-        HIPCHK(h, hipGetLastError());
-    }
+    if (n_later > 0)   // (the stragglers)
+        if (int rc = for_model(h->model, [&](auto M) { return launch_group_pass<M()>(h, S, n_later); })) return rc;
     {   // knot-major staging -> X[b][k][i], U[b][k][i]
         const int RX = (int)(N * n), RU = (int)(N * m);
-        hipLaunchKernelGGL(shoot_transpose_kernel, dim3((h->B + 31) / 32, (RX + 31) / 32), dim3(256), 0, h->stream, h->d_shXt, h->d_shX, h->d_shSt, RX, h->B);
-        hipLaunchKernelGGL(shoot_transpose_kernel, dim3((h->B + 31) / 32, (RU + 31) / 32), dim3(256), 0, h->stream, h->d_shUt, h->d_shU, h->d_shSt, RU, h->B);
+        hipLaunchKernelGGL(shoot_transpose_kernel, dim3((h->B + 31) / 32, (RX + 31) / 32), dim3(256), 0, h->stream, T.Xt, T.X, T.St, RX, h->B);
+        hipLaunchKernelGGL(shoot_transpose_kernel, dim3((h->B + 31) / 32, (RU + 31) / 32), dim3(256), 0, h->stream, T.Ut, T.U, T.St, RU, h->B);
         HIPCHK(h, hipGetLastError());
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->have_shoot = true;
+    T.have = true;
     return GUSTO_OK;
 }
 
 int gusto_get_shoot(gusto_handle h, int* status, int* newton_iters, double* resid, double* p0, double* X, double* U) {
     if (!h) return GUSTO_ERR_ARG;
-    if (!h->have_shoot) { h->err = "gusto_get_shoot: call gusto_shoot first"; return GUSTO_ERR_STATE; }
-    HIPCHK(h, hipSetDevice(h->device));
+    const ShootState& T = h->shoot;
+    if (!T.have) { h->err = "gusto_get_shoot: call gusto_shoot first"; return GUSTO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));   // (no gusto_finish, unlike the other getters)
     const size_t B = h->B, N = h->N, n = h->n, m = h->m;
-    if (status) HIPCHK(h, hipMemcpy(status, h->d_shSt, sizeof(int) * B, hipMemcpyDeviceToHost));
-    if (newton_iters) HIPCHK(h, hipMemcpy(newton_iters, h->d_shIt, sizeof(int) * B, hipMemcpyDeviceToHost));
-    if (resid) HIPCHK(h, hipMemcpy(resid, h->d_shRes, sizeof(double) * B, hipMemcpyDeviceToHost));
-    if (p0) HIPCHK(h, hipMemcpy(p0, h->d_shP, sizeof(double) * B * n, hipMemcpyDeviceToHost));
-    if (X) HIPCHK(h, hipMemcpy(X, h->d_shX, sizeof(double) * B * N * n, hipMemcpyDeviceToHost));
-    if (U) HIPCHK(h, hipMemcpy(U, h->d_shU, sizeof(double) * B * N * m, hipMemcpyDeviceToHost));
-    return GUSTO_OK;
+    if (int rc = copy_out(h, status, T.St, B)) return rc;
+    if (int rc = copy_out(h, newton_iters, T.It, B)) return rc;
+    if (int rc = copy_out(h, resid, T.Res, B)) return rc;
+    if (int rc = copy_out(h, p0, T.P, B * n)) return rc;
+    if (int rc = copy_out(h, X, T.X, B * N * n)) return rc;
+    return copy_out(h, U, T.U, B * N * m);
 }
 
 }  // extern "C"

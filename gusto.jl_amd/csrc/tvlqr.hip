@@ -20,14 +20,8 @@
 // No atomics, nothing crosses a problem: a problem's output is the same bit for bit whatever batch it sits in.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "handle.hpp"
 #include "models.hpp"
+#include "post.hpp"
 
 using namespace gusto;
 
@@ -286,18 +280,9 @@ template <int MODEL> int launch_tvlqr(gusto_handle h, const KParams& P, const Tv
     const int tiles = (h->N - 1 + LinTile<MODEL>::IPB - 1) / LinTile<MODEL>::IPB;
     hipLaunchKernelGGL((tvlqr_linearise<MODEL>), dim3(h->B, tiles), dim3(256), 0, h->stream, P, V);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev_qm, h->stream));
+    HIPCHK(h, h->tvlqr.mid.record(h->stream));
     hipLaunchKernelGGL((tvlqr_riccati<MODEL>), dim3(h->B), dim3(64), 0, h->stream, P, V);
     HIPCHK(h, hipGetLastError());
-    return GUSTO_OK;
-}
-
-// grow-only, zeroed when (re)allocated.  Growing discards the contents: it happens only after a gusto_set_problems with a larger
-// batch, which has invalidated them (have_tvlqr) anyway
-template <class T> int ensure_zeroed(gusto_handle h, DevBuf<T>& buf, size_t count) {
-    if (buf && count <= buf.count()) return GUSTO_OK;
-    HIPCHK(h, buf.ensure(count));
-    HIPCHK(h, hipMemsetAsync(buf.get(), 0, sizeof(T) * count, h->stream));
     return GUSTO_OK;
 }
 
@@ -316,16 +301,11 @@ int gusto_default_tvlqr_opts(int model_id, gusto_tvlqr_opts* o) {
 }
 
 int gusto_tvlqr(gusto_handle h, const double* X, const double* U, const gusto_tvlqr_opts* opts) {
-    if (!h) return GUSTO_ERR_ARG;
-    if (h->trajopt) { h->err = "gusto_tvlqr: TrajOpt handle (its controls carry the defect variables; not supported)"; return GUSTO_ERR_ARG; }
-    if (!h->have_problems) { h->err = "gusto_tvlqr: call gusto_set_problems first"; return GUSTO_ERR_STATE; }
-    if ((X == nullptr) != (U == nullptr)) { h->err = "gusto_tvlqr: X and U are given together or not at all"; return GUSTO_ERR_ARG; }
-    HIPCHK(h, hipSetDevice(h->device));
-    { int rc = gusto_finish(h); if (rc) return rc; }
+    if (int rc = post_enter(h, "gusto_tvlqr", X, U)) return rc;
     gusto_tvlqr_opts o;
     gusto_default_tvlqr_opts(h->model, &o);
     if (opts) o = *opts;
-    if (o.nstep < 0 || o.nstep_cap < 1 || (o.nstep == 0 && !(o.dt_min > 0)) || (o.store_P != 0 && o.store_P != 1)) {
+    if (!nstep_opts_ok(o.dt_min, o.nstep, o.nstep_cap) || (o.store_P != 0 && o.store_P != 1)) {
         h->err = "gusto_tvlqr: bad options";
         return GUSTO_ERR_ARG;
     }
@@ -339,109 +319,75 @@ int gusto_tvlqr(gusto_handle h, const double* X, const double* U, const gusto_tv
             h->err = "gusto_tvlqr: R must be finite and > 0 (entry " + std::to_string(i) + ")";
             return GUSTO_ERR_ARG;
         }
+    TvlqrState& S = h->tvlqr;
     const size_t B = h->B, N = h->N, n = h->n, m = h->m;
-    if (o.nstep == 0) {   // Nstep of every problem: never clamped (as gusto_verify)
-        std::vector<double> tf(B);
-        HIPCHK(h, hipMemcpyAsync(tf.data(), h->d_tf, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (size_t b = 0; b < B; b++) {
-            const double q = ceil(tf[b] / (double)(N - 1) / o.dt_min);
-            if (!(q >= 1 && q <= (double)o.nstep_cap)) {
-                h->err = "gusto_tvlqr: problem " + std::to_string(b) + " needs ceil(dt / dt_min) = " + std::to_string(q) + " substeps, outside 1 .. nstep_cap";
-                return GUSTO_ERR_ARG;
-            }
-        }
-    } else if (o.nstep > o.nstep_cap) {
-        h->err = "gusto_tvlqr: nstep above nstep_cap";
-        return GUSTO_ERR_ARG;
-    }
-    KParams P;
-    memset(&P, 0, sizeof(P));
-    P.N = h->N; P.B = h->B; P.mp = h->mp; P.tf = h->d_tf;
-    { int rc;
-      if ((rc = ensure_zeroed(h, h->d_lqAB, B * (N - 1) * n * (n + m)))) return rc;
-      if ((rc = ensure_zeroed(h, h->d_lqK, B * (N - 1) * m * n))) return rc;
-      if ((rc = ensure_zeroed(h, h->d_lqP1, B * n * n))) return rc;
-      if ((rc = ensure_zeroed(h, h->d_lqSt, 2 * B))) return rc;
-      if (o.store_P && (rc = ensure_zeroed(h, h->d_lqPall, B * N * n * n))) return rc; }
-    if (!h->have_tvlqr) h->lq_have_Pall = false;   // (new problems: whatever P the buffer holds belongs to the old ones)
+    int nstep_max = 0;   // (as gusto_verify; the largest count is of no use here)
+    if (int rc = resolve_nstep(h, "gusto_tvlqr", o.dt_min, o.nstep, o.nstep_cap, &nstep_max)) return rc;
+    const KParams P = post_params(h);
+    // grow-only, zeroed when (re)allocated.  Growing discards the contents: it happens only after a gusto_set_problems with a
+    // larger batch, which has invalidated them (S.have) anyway
+    HIPCHK(h, S.AB.ensure_zeroed(B * (N - 1) * n * (n + m), h->stream));
+    HIPCHK(h, S.K.ensure_zeroed(B * (N - 1) * m * n, h->stream));
+    HIPCHK(h, S.P1.ensure_zeroed(B * n * n, h->stream));
+    HIPCHK(h, S.St.ensure_zeroed(2 * B, h->stream));
+    if (o.store_P) HIPCHK(h, S.Pall.ensure_zeroed(B * N * n * n, h->stream));
+    if (!S.have) S.have_Pall = false;   // (new problems: whatever P the buffer holds belongs to the old ones)
     // a masked first call since gusto_set_problems: the inactive problems read as zeros, not as the last problem set's gains
     // (an unmasked call writes every problem)
     if (h->n_active >= 0) {
-        if (!h->have_tvlqr) {
-            HIPCHK(h, hipMemsetAsync(h->d_lqAB, 0, sizeof(double) * h->d_lqAB.count(), h->stream));
-            HIPCHK(h, hipMemsetAsync(h->d_lqK, 0, sizeof(double) * h->d_lqK.count(), h->stream));
-            HIPCHK(h, hipMemsetAsync(h->d_lqP1, 0, sizeof(double) * h->d_lqP1.count(), h->stream));
-            HIPCHK(h, hipMemsetAsync(h->d_lqSt, 0, sizeof(int) * h->d_lqSt.count(), h->stream));
+        if (!S.have) {
+            HIPCHK(h, hipMemsetAsync(S.AB, 0, sizeof(double) * S.AB.count(), h->stream));
+            HIPCHK(h, hipMemsetAsync(S.K, 0, sizeof(double) * S.K.count(), h->stream));
+            HIPCHK(h, hipMemsetAsync(S.P1, 0, sizeof(double) * S.P1.count(), h->stream));
+            HIPCHK(h, hipMemsetAsync(S.St, 0, sizeof(int) * S.St.count(), h->stream));
         }
-        if (o.store_P && !h->lq_have_Pall) HIPCHK(h, hipMemsetAsync(h->d_lqPall, 0, sizeof(double) * h->d_lqPall.count(), h->stream));
+        if (o.store_P && !S.have_Pall) HIPCHK(h, hipMemsetAsync(S.Pall, 0, sizeof(double) * S.Pall.count(), h->stream));
     }
-    HIPCHK(h, h->ev_q0.create()); HIPCHK(h, h->ev_qm.create()); HIPCHK(h, h->ev_q1.create());
     TvArgs V{};
-    V.X = h->d_X; V.U = h->d_U;
-    if (X) {   // the caller's trajectories: copies of their own, the handle's stay as they are
-        HIPCHK(h, h->d_lqX.ensure(B * N * n)); HIPCHK(h, h->d_lqU.ensure(B * N * m));
-        HIPCHK(h, hipMemcpyAsync(h->d_lqX, X, sizeof(double) * B * N * n, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->d_lqU, U, sizeof(double) * B * N * m, hipMemcpyHostToDevice, h->stream));
-        V.X = h->d_lqX; V.U = h->d_lqU;
-    }
-    V.active = h->n_active >= 0 ? h->d_active : nullptr;
+    if (int rc = stage_traj(h, X, U, B, S.X, S.U, &V.X, &V.U)) return rc;
+    V.active = active_mask(h);
     V.dt_min = o.dt_min; V.nstep = o.nstep; V.store_P = o.store_P;
     memcpy(V.Q, o.Q, sizeof(V.Q)); memcpy(V.R, o.R, sizeof(V.R)); memcpy(V.Qf, o.Qf, sizeof(V.Qf));
-    V.AB = h->d_lqAB; V.K = h->d_lqK; V.P1 = h->d_lqP1; V.Pall = h->d_lqPall;
-    V.status = h->d_lqSt; V.fail_knot = h->d_lqSt + h->d_lqSt.count() / 2;
-    HIPCHK(h, hipEventRecord(h->ev_q0, h->stream));
-    int rc = GUSTO_ERR_ARG;
-    switch (h->model) {
-    case GUSTO_FREEFLYER_SE2: rc = launch_tvlqr<GUSTO_FREEFLYER_SE2>(h, P, V); break;
-    case GUSTO_DUBINS_CAR: rc = launch_tvlqr<GUSTO_DUBINS_CAR>(h, P, V); break;
-    case GUSTO_ASTROBEE_SE3: rc = launch_tvlqr<GUSTO_ASTROBEE_SE3>(h, P, V); break;
-    case GUSTO_ASTROBEE_SE3_MANIFOLD: rc = launch_tvlqr<GUSTO_ASTROBEE_SE3_MANIFOLD>(h, P, V); break;
-    }
-    if (rc) return rc;
-    HIPCHK(h, hipEventRecord(h->ev_q1, h->stream));
+    V.AB = S.AB; V.K = S.K; V.P1 = S.P1; V.Pall = S.Pall;
+    V.status = S.St; V.fail_knot = S.St + S.St.count() / 2;
+    HIPCHK(h, S.t0.record(h->stream));
+    if (int rc = for_model(h->model, [&](auto M) { return launch_tvlqr<M()>(h, P, V); })) return rc;
+    HIPCHK(h, S.t1.record(h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev_q0, h->ev_q1));
-    h->last_tvlqr_ms = ms;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev_q0, h->ev_qm));
-    h->lq_lin_ms = ms;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev_qm, h->ev_q1));
-    h->lq_ric_ms = ms;
-    if (o.store_P) h->lq_have_Pall = true;
-    h->have_tvlqr = true;
-    h->lq_store_P = o.store_P != 0;
+    HIPCHK(h, event_ms(S.t0, S.t1, &S.last_ms));
+    HIPCHK(h, event_ms(S.t0, S.mid, &S.lin_ms));
+    HIPCHK(h, event_ms(S.mid, S.t1, &S.ric_ms));
+    if (o.store_P) S.have_Pall = true;
+    S.have = true;
+    S.store_P = o.store_P != 0;
     return GUSTO_OK;
 }
 
 int gusto_get_tvlqr(gusto_handle h, int* status, int* fail_knot, double* K, double* Pm, double* AB) {
     if (!h) return GUSTO_ERR_ARG;
     if (int rc = getter_enter(h, false)) return rc;
-    if (!h->have_tvlqr) { h->err = "gusto_get_tvlqr: call gusto_tvlqr first"; return GUSTO_ERR_STATE; }
+    const TvlqrState& S = h->tvlqr;
+    if (!S.have) { h->err = "gusto_get_tvlqr: call gusto_tvlqr first"; return GUSTO_ERR_STATE; }
     const size_t B = h->B, N = h->N, n = h->n, m = h->m;
-    if (status) HIPCHK(h, hipMemcpy(status, h->d_lqSt, sizeof(int) * B, hipMemcpyDeviceToHost));
-    if (fail_knot) HIPCHK(h, hipMemcpy(fail_knot, h->d_lqSt + h->d_lqSt.count() / 2, sizeof(int) * B, hipMemcpyDeviceToHost));
-    if (K) HIPCHK(h, hipMemcpy(K, h->d_lqK, sizeof(double) * B * (N - 1) * m * n, hipMemcpyDeviceToHost));
-    if (AB) HIPCHK(h, hipMemcpy(AB, h->d_lqAB, sizeof(double) * B * (N - 1) * n * (n + m), hipMemcpyDeviceToHost));
-    if (Pm) {
-        if (h->lq_store_P) HIPCHK(h, hipMemcpy(Pm, h->d_lqPall, sizeof(double) * B * N * n * n, hipMemcpyDeviceToHost));
-        else HIPCHK(h, hipMemcpy(Pm, h->d_lqP1, sizeof(double) * B * n * n, hipMemcpyDeviceToHost));
-    }
-    return GUSTO_OK;
+    if (int rc = copy_out(h, status, S.St, B)) return rc;
+    if (int rc = copy_out(h, fail_knot, S.St + S.St.count() / 2, B)) return rc;
+    if (int rc = copy_out(h, K, S.K, B * (N - 1) * m * n)) return rc;
+    if (int rc = copy_out(h, AB, S.AB, B * (N - 1) * n * (n + m))) return rc;
+    return S.store_P ? copy_out(h, Pm, S.Pall, B * N * n * n) : copy_out(h, Pm, S.P1, B * n * n);
 }
 
 int gusto_dev_tvlqr(gusto_handle h, double* linearise_ms, double* riccati_ms) {
     if (!h) return GUSTO_ERR_ARG;
-    if (!h->have_tvlqr) { h->err = "gusto_dev_tvlqr: call gusto_tvlqr first"; return GUSTO_ERR_STATE; }
-    if (linearise_ms) *linearise_ms = h->lq_lin_ms;
-    if (riccati_ms) *riccati_ms = h->lq_ric_ms;
+    if (!h->tvlqr.have) { h->err = "gusto_dev_tvlqr: call gusto_tvlqr first"; return GUSTO_ERR_STATE; }
+    if (linearise_ms) *linearise_ms = h->tvlqr.lin_ms;
+    if (riccati_ms) *riccati_ms = h->tvlqr.ric_ms;
     return GUSTO_OK;
 }
 
 int gusto_last_tvlqr_ms(gusto_handle h, double* ms) {
     if (!h || !ms) return GUSTO_ERR_ARG;
-    if (!h->have_tvlqr) { h->err = "gusto_last_tvlqr_ms: call gusto_tvlqr first"; return GUSTO_ERR_STATE; }
-    *ms = h->last_tvlqr_ms;
+    if (!h->tvlqr.have) { h->err = "gusto_last_tvlqr_ms: call gusto_tvlqr first"; return GUSTO_ERR_STATE; }
+    *ms = h->tvlqr.last_ms;
     return GUSTO_OK;
 }
 

@@ -24,14 +24,8 @@
 // lane's DENSE_TILE n doubles; the held controls are copied straight from U (thread e writes double e of the problem).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "handle.hpp"
 #include "models.hpp"
+#include "post.hpp"
 
 using namespace gusto;
 
@@ -196,94 +190,50 @@ template <int MODEL> int launch_verify(gusto_handle h, const KParams& P, const V
 }
 
 int verify_impl(gusto_handle h, const double* X, const double* U, const gusto_verify_opts* opts, bool dense, int* nfull_max, const char* who) {
-    if (!h) return GUSTO_ERR_ARG;
-    const std::string w(who);
-    if (h->trajopt) { h->err = w + ": TrajOpt handle (its controls carry the defect variables; not supported)"; return GUSTO_ERR_ARG; }
-    if (!h->have_problems) { h->err = w + ": call gusto_set_problems first"; return GUSTO_ERR_STATE; }
-    if ((X == nullptr) != (U == nullptr)) { h->err = w + ": X and U are given together or not at all"; return GUSTO_ERR_ARG; }
-    HIPCHK(h, hipSetDevice(h->device));
-    { int rc = gusto_finish(h); if (rc) return rc; }
+    if (int rc = post_enter(h, who, X, U)) return rc;
     gusto_verify_opts o;
     gusto_default_verify_opts(&o);
     if (opts) o = *opts;
-    if (o.nstep < 0 || o.nstep_cap < 1 || (o.nstep == 0 && !(o.dt_min > 0)) || (o.dense_collision != 0 && o.dense_collision != 1)) {
-        h->err = w + ": bad options";
+    if (!nstep_opts_ok(o.dt_min, o.nstep, o.nstep_cap) || (o.dense_collision != 0 && o.dense_collision != 1)) {
+        h->err = std::string(who) + ": bad options";
         return GUSTO_ERR_ARG;
     }
-    const size_t B = h->B, Bc = h->batch_cap, N = h->N, n = h->n, m = h->m;
-    KParams P;
-    memset(&P, 0, sizeof(P));
-    P.N = h->N; P.B = h->B; P.mp = h->mp; P.tf = h->d_tf;
+    VerifyState& S = h->verify;
+    const size_t Bc = h->batch_cap, N = h->N, n = h->n, m = h->m;
+    KParams P = post_params(h);
     if (!fill_env(h, P, model_info(h->model)->has_obs, true)) {
-        h->err = w + ": gusto_set_env_batch was called with a different number of problems than gusto_set_problems";
+        h->err = std::string(who) + ": gusto_set_env_batch was called with a different number of problems than gusto_set_problems";
         return GUSTO_ERR_STATE;
     }
-    // Nstep of every problem: never clamped
-    int nstep_max = o.nstep;
-    if (o.nstep == 0) {
-        std::vector<double> tf(B);
-        HIPCHK(h, hipMemcpyAsync(tf.data(), h->d_tf, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (size_t b = 0; b < B; b++) {
-            const double q = ceil(tf[b] / (double)(N - 1) / o.dt_min);
-            if (!(q >= 1 && q <= (double)o.nstep_cap)) {
-                h->err = w + ": problem " + std::to_string(b) + " needs ceil(dt / dt_min) = " + std::to_string(q) + " substeps, outside 1 .. nstep_cap";
-                return GUSTO_ERR_ARG;
-            }
-            nstep_max = std::max(nstep_max, (int)q);
-        }
-    } else if (o.nstep > o.nstep_cap) {
-        h->err = w + ": nstep above nstep_cap";
-        return GUSTO_ERR_ARG;
-    }
-    if (!h->d_vI) {   // (the report is zeroed once)
-        HIPCHK(h, h->d_vI.alloc(4 * Bc)); HIPCHK(h, h->d_vD.alloc(5 * Bc));
-        HIPCHK(h, hipMemsetAsync(h->d_vI, 0, sizeof(int) * 4 * Bc, h->stream));
-        HIPCHK(h, hipMemsetAsync(h->d_vD, 0, sizeof(double) * 5 * Bc, h->stream));
-    }
-    HIPCHK(h, h->ev_v0.create()); HIPCHK(h, h->ev_v1.create());
+    int nstep_max = 0;
+    if (int rc = resolve_nstep(h, who, o.dt_min, o.nstep, o.nstep_cap, &nstep_max)) return rc;
+    // (the report is zeroed once)
+    HIPCHK(h, S.I.ensure_zeroed(4 * Bc, h->stream)); HIPCHK(h, S.D.ensure_zeroed(5 * Bc, h->stream));
     VerifyArgs V{};
-    V.X = h->d_X; V.U = h->d_U;
-    if (X) {   // the caller's trajectories: copies of their own, the handle's stay as they are
-        HIPCHK(h, h->d_vX.alloc(Bc * N * n)); HIPCHK(h, h->d_vU.alloc(Bc * N * m));
-        HIPCHK(h, hipMemcpyAsync(h->d_vX, X, sizeof(double) * B * N * n, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->d_vU, U, sizeof(double) * B * N * m, hipMemcpyHostToDevice, h->stream));
-        V.X = h->d_vX; V.U = h->d_vU;
-    }
-    V.active = h->n_active >= 0 ? h->d_active : nullptr;
+    if (int rc = stage_traj(h, X, U, Bc, S.X, S.U, &V.X, &V.U)) return rc;
+    V.active = active_mask(h);
     V.dt_min = o.dt_min; V.nstep = o.nstep; V.dense_collision = o.dense_collision;
-    V.collision_free = h->d_vI; V.first_knot = h->d_vI + Bc; V.min_dense_sample = h->d_vI + 2 * Bc; V.nfull = h->d_vI + 3 * Bc;
-    V.first_dist = h->d_vD; V.min_dist_knots = h->d_vD + Bc; V.dyn_defect_l1 = h->d_vD + 2 * Bc; V.min_dist_dense = h->d_vD + 3 * Bc;
-    V.max_gap = h->d_vD + 4 * Bc;
+    V.collision_free = S.I; V.first_knot = S.I + Bc; V.min_dense_sample = S.I + 2 * Bc; V.nfull = S.I + 3 * Bc;
+    V.first_dist = S.D; V.min_dist_knots = S.D + Bc; V.dyn_defect_l1 = S.D + 2 * Bc; V.min_dist_dense = S.D + 3 * Bc;
+    V.max_gap = S.D + 4 * Bc;
     if (dense) {
         const int nf = nstep_max * (int)(N - 1) + 1;
-        if (nf != h->dense_rows) {   // another layout: a new buffer, zeros everywhere
-            h->d_vXf.reset(); h->d_vUf.reset();
-            h->dense_rows = 0; h->have_dense = false;
-            HIPCHK(h, h->d_vXf.alloc(Bc * nf * n)); HIPCHK(h, h->d_vUf.alloc(Bc * (nf - 1) * m));
-            HIPCHK(h, hipMemsetAsync(h->d_vXf, 0, sizeof(double) * Bc * nf * n, h->stream));
-            HIPCHK(h, hipMemsetAsync(h->d_vUf, 0, sizeof(double) * Bc * (nf - 1) * m, h->stream));
+        if (nf != S.dense_rows) {   // another layout: a new buffer, zeros everywhere
+            S.Xf.reset(); S.Uf.reset();
+            S.dense_rows = 0; S.have_dense = false;
+            HIPCHK(h, S.Xf.ensure_zeroed(Bc * nf * n, h->stream)); HIPCHK(h, S.Uf.ensure_zeroed(Bc * (nf - 1) * m, h->stream));
             HIPCHK(h, hipMemsetAsync(V.nfull, 0, sizeof(int) * Bc, h->stream));
-            h->dense_rows = nf;
+            S.dense_rows = nf;
         }
-        V.nfull_max = nf; V.Xfull = h->d_vXf; V.Ufull = h->d_vUf;
+        V.nfull_max = nf; V.Xfull = S.Xf; V.Ufull = S.Uf;
     }
-    HIPCHK(h, hipEventRecord(h->ev_v0, h->stream));
-    int rc = GUSTO_ERR_ARG;
-    switch (h->model) {
-    case GUSTO_FREEFLYER_SE2: rc = launch_verify<GUSTO_FREEFLYER_SE2>(h, P, V, dense); break;
-    case GUSTO_DUBINS_CAR: rc = launch_verify<GUSTO_DUBINS_CAR>(h, P, V, dense); break;
-    case GUSTO_ASTROBEE_SE3: rc = launch_verify<GUSTO_ASTROBEE_SE3>(h, P, V, dense); break;
-    case GUSTO_ASTROBEE_SE3_MANIFOLD: rc = launch_verify<GUSTO_ASTROBEE_SE3_MANIFOLD>(h, P, V, dense); break;
-    }
-    if (rc) return rc;
-    HIPCHK(h, hipEventRecord(h->ev_v1, h->stream));
+    HIPCHK(h, S.t0.record(h->stream));
+    if (int rc = for_model(h->model, [&](auto M) { return launch_verify<M()>(h, P, V, dense); })) return rc;
+    HIPCHK(h, S.t1.record(h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev_v0, h->ev_v1));
-    h->last_verify_ms = ms;
-    h->have_verify = true;
-    if (dense) { h->have_dense = true; if (nfull_max) *nfull_max = V.nfull_max; }
+    HIPCHK(h, event_ms(S.t0, S.t1, &S.last_ms));
+    S.have = true;
+    if (dense) { S.have_dense = true; if (nfull_max) *nfull_max = V.nfull_max; }
     return GUSTO_OK;
 }
 
@@ -310,31 +260,34 @@ int gusto_get_verify(gusto_handle h, gusto_verify_report* out) {
     if (!h) return GUSTO_ERR_ARG;
     if (int rc = getter_enter(h, false)) return rc;
     if (!out) return GUSTO_ERR_ARG;
-    if (!h->have_verify) { h->err = "gusto_get_verify: call gusto_verify first"; return GUSTO_ERR_STATE; }
+    const VerifyState& S = h->verify;
+    if (!S.have) { h->err = "gusto_get_verify: call gusto_verify first"; return GUSTO_ERR_STATE; }
     const size_t B = h->B, Bc = h->batch_cap;
-#define CPV(dst, src) if (dst) HIPCHK(h, hipMemcpy(dst, src, sizeof(*(dst)) * B, hipMemcpyDeviceToHost))
-    CPV(out->collision_free, h->d_vI); CPV(out->first_knot, h->d_vI + Bc); CPV(out->min_dense_sample, h->d_vI + 2 * Bc);
-    CPV(out->first_dist, h->d_vD); CPV(out->min_dist_knots, h->d_vD + Bc); CPV(out->dyn_defect_l1, h->d_vD + 2 * Bc);
-    CPV(out->min_dist_dense, h->d_vD + 3 * Bc); CPV(out->max_gap, h->d_vD + 4 * Bc);
-#undef CPV
-    return GUSTO_OK;
+    if (int rc = copy_out(h, out->collision_free, S.I, B)) return rc;
+    if (int rc = copy_out(h, out->first_knot, S.I + Bc, B)) return rc;
+    if (int rc = copy_out(h, out->min_dense_sample, S.I + 2 * Bc, B)) return rc;
+    if (int rc = copy_out(h, out->first_dist, S.D, B)) return rc;
+    if (int rc = copy_out(h, out->min_dist_knots, S.D + Bc, B)) return rc;
+    if (int rc = copy_out(h, out->dyn_defect_l1, S.D + 2 * Bc, B)) return rc;
+    if (int rc = copy_out(h, out->min_dist_dense, S.D + 3 * Bc, B)) return rc;
+    return copy_out(h, out->max_gap, S.D + 4 * Bc, B);
 }
 
 int gusto_get_dense(gusto_handle h, int* nfull, double* Xfull, double* Ufull) {
     if (!h) return GUSTO_ERR_ARG;
     if (int rc = getter_enter(h, false)) return rc;
-    if (!h->have_dense) { h->err = "gusto_get_dense: call gusto_interpolate first"; return GUSTO_ERR_STATE; }
-    const size_t B = h->B, Bc = h->batch_cap, nf = h->dense_rows;
-    if (nfull) HIPCHK(h, hipMemcpy(nfull, h->d_vI + 3 * Bc, sizeof(int) * B, hipMemcpyDeviceToHost));
-    if (Xfull) HIPCHK(h, hipMemcpy(Xfull, h->d_vXf, sizeof(double) * B * nf * h->n, hipMemcpyDeviceToHost));
-    if (Ufull) HIPCHK(h, hipMemcpy(Ufull, h->d_vUf, sizeof(double) * B * (nf - 1) * h->m, hipMemcpyDeviceToHost));
-    return GUSTO_OK;
+    const VerifyState& S = h->verify;
+    if (!S.have_dense) { h->err = "gusto_get_dense: call gusto_interpolate first"; return GUSTO_ERR_STATE; }
+    const size_t B = h->B, nf = S.dense_rows;
+    if (int rc = copy_out(h, nfull, S.I + 3 * h->batch_cap, B)) return rc;
+    if (int rc = copy_out(h, Xfull, S.Xf, B * nf * h->n)) return rc;
+    return copy_out(h, Ufull, S.Uf, B * (nf - 1) * h->m);
 }
 
 int gusto_last_verify_ms(gusto_handle h, double* ms) {
     if (!h || !ms) return GUSTO_ERR_ARG;
-    if (!h->have_verify) { h->err = "gusto_last_verify_ms: call gusto_verify first"; return GUSTO_ERR_STATE; }
-    *ms = h->last_verify_ms;
+    if (!h->verify.have) { h->err = "gusto_last_verify_ms: call gusto_verify first"; return GUSTO_ERR_STATE; }
+    *ms = h->verify.last_ms;
     return GUSTO_OK;
 }
 
