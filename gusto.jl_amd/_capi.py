@@ -30,6 +30,7 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_default_verify_opts", "gusto_verify", "gusto_get_verify", "gusto_interpolate", "gusto_get_dense",
            "gusto_last_verify_ms",
            "gusto_default_tvlqr_opts", "gusto_tvlqr", "gusto_get_tvlqr", "gusto_last_tvlqr_ms",
+           "gusto_default_simulate_opts", "gusto_simulate", "gusto_get_simulate", "gusto_get_simulate_knots", "gusto_last_simulate_ms",
            "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr"]
 
 
@@ -74,6 +75,27 @@ class TvlqrResult:
         self.K, self.P, self.AB, self.status, self.fail_knot = K, P, AB, status, fail_knot
 
 
+class SimulateOpts(C.Structure):
+    """gusto_simulate_opts: samples, the generated perturbations, actuator limits, the roll-out of gusto_verify_opts"""
+    _fields_ = [("n_samples", C.c_int), ("seed", C.c_ulonglong), ("first_problem", C.c_ulonglong), ("dx0", C.c_double * MAXN),
+                ("du0", C.c_double * MAXM), ("u_lo", C.c_double * MAXM), ("u_hi", C.c_double * MAXM), ("dt_min", C.c_double),
+                ("nstep", C.c_int), ("nstep_cap", C.c_int), ("dense_collision", C.c_int), ("store_knots", C.c_int)]
+
+
+# gusto_simulate_report in the header's order: (field, dtype, shape as a function of (B, S, n))
+SIMULATE_FIELDS = (("n_free", np.int32, lambda B, S, n: (B,)), ("n_finite", np.int32, lambda B, S, n: (B,)),
+                   ("n_clipped", np.int32, lambda B, S, n: (B,)), ("worst_sample", np.int32, lambda B, S, n: (B,)),
+                   ("worst_dense_sample", np.int32, lambda B, S, n: (B,)), ("min_dist", np.float64, lambda B, S, n: (B,)),
+                   ("max_dev", np.float64, lambda B, S, n: (B, n)), ("max_final_dev", np.float64, lambda B, S, n: (B, n)),
+                   ("sample_min_dist", np.float64, lambda B, S, n: (B, S)), ("sample_dense_index", np.int32, lambda B, S, n: (B, S)),
+                   ("sample_flags", np.int32, lambda B, S, n: (B, S)), ("x_final", np.float64, lambda B, S, n: (B, S, n)))
+
+
+class SimulateReport(C.Structure):
+    """gusto_simulate_report: caller-owned arrays"""
+    _fields_ = [(k, C.c_void_p) for k, _, _ in SIMULATE_FIELDS]
+
+
 VERIFY_FIELDS = (("collision_free", np.int32), ("first_knot", np.int32), ("first_dist", np.float64),
                  ("min_dist_knots", np.float64), ("dyn_defect_l1", np.float64), ("min_dist_dense", np.float64),
                  ("min_dense_sample", np.int32), ("max_gap", np.float64))
@@ -115,7 +137,7 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(_ROOT, "include"), "-fPIC",
              "-Wno-unused-value", "-Wno-pass-failed"]
-    units = ["gusto_hip", "shoot", "verify", "tvlqr", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
+    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
     bdir = os.path.join(_HERE, "build")
     os.makedirs(bdir, exist_ok=True)
 
@@ -194,6 +216,11 @@ def lib():
         L.gusto_get_tvlqr.argtypes = [vp, vp, vp, vp, vp, vp]
         L.gusto_last_tvlqr_ms.argtypes = [vp, C.POINTER(C.c_double)]
         L.gusto_dev_tvlqr.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.gusto_default_simulate_opts.argtypes = [ci, C.POINTER(SimulateOpts)]
+        L.gusto_simulate.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SimulateOpts)]
+        L.gusto_get_simulate.argtypes = [vp, C.POINTER(SimulateReport)]
+        L.gusto_get_simulate_knots.argtypes = [vp, vp]
+        L.gusto_last_simulate_ms.argtypes = [vp, C.POINTER(C.c_double)]
         L.gusto_default_trajopt_params.argtypes = [ci, C.POINTER(TrajOptParams)]
         L.gusto_create_trajopt.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci]
         L.gusto_set_trajopt_params.argtypes = [vp, C.POINTER(TrajOptParams)]
@@ -242,6 +269,14 @@ def default_tvlqr_opts(model):
     rc = lib().gusto_default_tvlqr_opts(model, C.byref(o))
     if rc:
         raise ValueError(f"gusto_default_tvlqr_opts({model}) -> {rc}")
+    return o
+
+
+def default_simulate_opts(model):
+    o = SimulateOpts()
+    rc = lib().gusto_default_simulate_opts(model, C.byref(o))
+    if rc:
+        raise ValueError(f"gusto_default_simulate_opts({model}) -> {rc}")
     return o
 
 
@@ -575,6 +610,57 @@ class BatchSolver:
     def last_tvlqr_ms(self):
         return self._last_ms("last_tvlqr_ms")
 
+    def simulate_opts(self, opts=None):
+        """a gusto_simulate_opts from None (the defaults), a SimulateOpts, or a dict of its fields -- dx0, du0, u_lo, u_hi as
+        scalars or vectors of the model's x_dim / u_dim entries"""
+        if isinstance(opts, SimulateOpts):
+            return opts
+        o = default_simulate_opts(self.model)
+        for k, v in (opts or {}).items():
+            if k in ("dx0", "du0", "u_lo", "u_hi"):
+                dim = self.n if k == "dx0" else self.m
+                w = np.broadcast_to(np.asarray(v, dtype=np.float64), (dim,))
+                for i in range(dim):
+                    getattr(o, k)[i] = float(w[i])
+            elif k in ("n_samples", "seed", "first_problem", "nstep", "nstep_cap", "dense_collision", "store_knots"):
+                setattr(o, k, int(v))
+            elif k == "dt_min":
+                o.dt_min = float(v)
+            else:
+                raise TypeError(f"unknown simulate option {k!r}")
+        return o
+
+    def simulate(self, opts=None, X=None, U=None, K=None, pert=None):
+        """gusto_simulate + gusto_get_simulate: closed-loop roll-outs of u = U_k - K_k (x - X_k), clipped to u_lo .. u_hi, from
+        n_samples perturbed starts per problem, around X, U (default: the handle's trajectories) with the gains K [B, N-1, m, n]
+        (default: those of the last tvlqr()) and the perturbations pert [B, S, n + m] (default: generated on the device).
+        Returns the report as a dict (gusto_simulate_report's fields)."""
+        px, pu, _keep = self._traj_ptrs(X, U, "simulate")
+        o = self.simulate_opts(opts)
+        Kk = None if K is None else _arr(K).reshape(self.B, self.N - 1, self.m, self.n)
+        pp = None if pert is None else _arr(pert).reshape(self.B, o.n_samples, self.n + self.m)
+        self._chk(self.L.gusto_simulate(self.h, px, pu, None if Kk is None else Kk.ctypes.data,
+                                        None if pp is None else pp.ctypes.data, C.byref(o)), "simulate")
+        self._simulate_S = int(o.n_samples)
+        return self.get_simulate()
+
+    def get_simulate(self):
+        """gusto_get_simulate: the report of the last simulate() as a dict of arrays"""
+        S = getattr(self, "_simulate_S", 1)
+        out = {k: np.zeros(shape(self.B, S, self.n), dtype=t) for k, t, shape in SIMULATE_FIELDS}
+        rep = SimulateReport(**{k: v.ctypes.data for k, v in out.items()})
+        self._chk(self.L.gusto_get_simulate(self.h, C.byref(rep)), "get_simulate")
+        return out
+
+    def get_simulate_knots(self):
+        """gusto_get_simulate_knots: Xcl [B, N, S, n] of the last simulate() with store_knots = 1"""
+        Xcl = np.zeros((self.B, self.N, getattr(self, "_simulate_S", 1), self.n))
+        self._chk(self.L.gusto_get_simulate_knots(self.h, Xcl.ctypes.data), "get_simulate_knots")
+        return Xcl
+
+    def last_simulate_ms(self):
+        return self._last_ms("last_simulate_ms")
+
     def subproblem(self, Xp, Up, Delta, omega, toggle):
         B = self.B
         Xp, Up = _arr(Xp).reshape(B, self.N, self.n), _arr(Up).reshape(B, self.N, self.m)
@@ -644,3 +730,6 @@ class TrajOptSolver(BatchSolver):
 
     def tvlqr(self, *a, **k):
         raise GustoError("TrajOptSolver: tvlqr is not supported on TrajOpt handles (gusto_tvlqr answers GUSTO_ERR_ARG)")
+
+    def simulate(self, *a, **k):
+        raise GustoError("TrajOptSolver: simulate is not supported on TrajOpt handles (gusto_simulate answers GUSTO_ERR_ARG)")

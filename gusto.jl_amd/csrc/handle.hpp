@@ -120,6 +120,21 @@ struct __attribute__((visibility("hidden"))) TvlqrState {
     void invalidate() { have = false; }
 };
 
+// Closed-loop roll-outs (simulate.hip), S the n_samples of the last call: per sample [batch_cap][S] the smallest distance (D),
+// its dense index and the flags (I: [2][batch_cap][S]), [batch_cap][S][n] the final state and the largest deviation per state
+// (Xfin, Dev); the per-problem report (RI: [5][batch_cap] n_free, n_finite, n_clipped, worst_sample, worst_dense_sample; RD:
+// [batch_cap] min_dist, then [batch_cap][n] max_dev, [batch_cap][n] max_final_dev); the knots [batch_cap][N][S][n] (first call
+// with store_knots only); copies of a caller's X / U / K / pert
+struct __attribute__((visibility("hidden"))) SimulateState {
+    DevBuf<double> D, Xfin, Dev, RD, Knots, X, U, K, Pert;
+    DevBuf<int> I, RI;
+    int S = 0;
+    bool have = false, have_knots = false;
+    DevEvent t0, t1;
+    double last_ms = 0.0;
+    void invalidate() { have = false; have_knots = false; }
+};
+
 struct gusto_handle_s {
     int model = 0, n = 0, m = 0, N = 0, batch_cap = 0, hist_cap = 0, device = 0, B = 0;
     // TrajOpt handles (gusto_create_trajopt): `model` is the internal variant (common.hpp: GUSTO_TO_*), `m` its control
@@ -170,7 +185,7 @@ struct gusto_handle_s {
     int* h_sched_err = nullptr;    // pinned host word the error flag is copied to on the handle's stream, before the stream is waited for
     DevBuf<double> d_gX, d_gU;     // gusto_gather_peer: the shards of several handles, one after the other, on this handle's GPU
     DevBuf<double> d_Upub;         // TrajOpt handles: U compacted to the public [B][N][u_dim] layout for gusto_get_traj_dev
-    ShootState shoot; VerifyState verify; TvlqrState tvlqr;   // the post-solve stages
+    ShootState shoot; VerifyState verify; TvlqrState tvlqr; SimulateState simulate;   // the post-solve stages
     std::string err;
 
     // (the buffers and events free themselves; the caller has made `device` current: gusto_destroy)

@@ -1,6 +1,6 @@
-// post.hpp -- the host path of the post-solve stages (shoot.hip, verify.hip, tvlqr.hip; nothing else includes it).  Plain
+// post.hpp -- the host path of the post-solve stages (shoot.hip, verify.hip, tvlqr.hip, simulate.hip; nothing else includes it).  Plain
 // functions that answer a GUSTO_* code and leave the text in h->err: `if (int rc = ...) return rc;` at the call site.  A new
-// stage starts from these and from a struct of its own next to ShootState / VerifyState / TvlqrState (handle.hpp).
+// stage starts from these and from a struct of its own next to ShootState / VerifyState / TvlqrState / SimulateState (handle.hpp).
 #pragma once
 #include <algorithm>
 #include <cmath>

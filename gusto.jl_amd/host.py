@@ -585,6 +585,23 @@ def tvlqr(traj, SCPP, Q=1.0, R=1.0, Qf=1.0, dt_min=0.1, store_P=False):
     return _capi.TvlqrResult(r.K[0], r.P[0], r.AB[0], int(r.status[0]), int(r.fail_knot[0]))
 
 
+def simulate(traj, SCPP, K=None, pert=None, Q=1.0, R=1.0, Qf=1.0, **opts):
+    """Closed-loop Monte Carlo roll-outs of the tracking law around one trajectory (gusto_simulate; no counterpart in the
+    reference): u = clip(U[:, k] - K[k] (x(t_k) - X[:, k]), u_lo, u_hi) from n_samples perturbed starts.  K [N-1, u_dim, x_dim]:
+    the gains, default those of tvlqr(traj, SCPP, Q, R, Qf); pert [S, x_dim + u_dim]: the perturbations, default generated on
+    the device; opts: gusto_simulate_opts fields.  Returns the one-problem report as a dict."""
+    bs = _verify_handle(traj, SCPP)
+    try:
+        cap = max(64, int(np.ceil(traj.dt / opts.get("dt_min", 0.1))))
+        if K is None:
+            bs.tvlqr(dict(Q=Q, R=R, Qf=Qf, dt_min=opts.get("dt_min", 0.1), nstep=opts.get("nstep", 0), nstep_cap=opts.get("nstep_cap", cap)))
+        r = bs.simulate(dict(dict(nstep_cap=cap), **opts), K=None if K is None else np.asarray(K, float)[None],
+                        pert=None if pert is None else np.asarray(pert, float)[None])
+    finally:
+        bs.close()
+    return {k: v[0] for k, v in r.items()}
+
+
 def shard_bounds(B, world_size, rank):
     """Contiguous block of ceil(B/G) problems per rank; the tail rank may get fewer."""
     per = -(-B // world_size)
@@ -593,7 +610,7 @@ def shard_bounds(B, world_size, rank):
 
 
 def solve_SCP_batch(TOSs, TOPs, solve_method=None, init_method=init_traj_straightline, solver="hip", max_iter=30,
-                    force=False, device=0, devices=None, decomposition=0, verify=False, tvlqr=None):
+                    force=False, device=0, devices=None, decomposition=0, verify=False, tvlqr=None, simulate=None):
     """All TOPs must share model and N (each may bring its own environment); one gusto_solve covers the whole list.
 
     `verify` (GuSTO handles only): one gusto_verify per shard after its solve; every SCPS then carries `verify`, the dict of its
@@ -603,6 +620,10 @@ def solve_SCP_batch(TOSs, TOPs, solve_method=None, init_method=init_traj_straigh
     `tvlqr` (GuSTO handles only): a dict of gusto_tvlqr_opts fields (Q, R, Qf, dt_min, nstep, nstep_cap, store_P; {} = the
     defaults) -- one gusto_tvlqr per shard after its solve; every SCPS then carries `tvlqr`, its problem's K, P, AB, status and
     fail_knot.  Without it the solutions are what they were.
+
+    `simulate` (requires `tvlqr`): a dict of gusto_simulate_opts fields ({} = the defaults) -- one gusto_simulate per shard after
+    its gusto_tvlqr, with that shard's gains and first_problem = the shard's offset, so the generated perturbations are those of
+    the unsharded batch; every SCPS then carries `simulate`, the dict of its problem's report.
 
     `decomposition` (gusto_set_decomposition; GuSTO handles only): 0 = the library's choice by batch size -- for the 12/13-state
     models two or four wavefronts per problem while the batch leaves SIMDs idle --, 1 one wave per problem, 3 / 4 two / four.
@@ -617,6 +638,8 @@ def solve_SCP_batch(TOSs, TOPs, solve_method=None, init_method=init_traj_straigh
         raise NotImplementedError("solve_SCP_batch!: verify is not available for TrajOpt handles")
     if tvlqr is not None and trajopt:
         raise NotImplementedError("solve_SCP_batch!: tvlqr is not available for TrajOpt handles")
+    if simulate is not None and tvlqr is None:
+        raise ValueError("solve_SCP_batch!: simulate needs the gains: pass tvlqr= as well")
     if len(TOSs) != len(TOPs) or not TOPs:
         raise ValueError("solve_SCP_batch!: need as many solutions as problems, at least one")
     TOP0 = TOPs[0]
@@ -676,6 +699,7 @@ def solve_SCP_batch(TOSs, TOPs, solve_method=None, init_method=init_traj_straigh
         per = bs.last_solve_ms() * 1e-3 / (b1 - b0)
         rep = bs.verify(**(verify if isinstance(verify, dict) else {})) if verify else None
         lq = bs.tvlqr(tvlqr) if tvlqr is not None else None
+        sim = bs.simulate(dict(simulate, first_problem=simulate.get("first_problem", 0) + b0)) if simulate is not None else None
         for b in range(b0, b1):
             SCPP = SCPProblem(TOPs[b])
             SCPS = SCPSolution(SCPP, inits[b])
@@ -685,6 +709,8 @@ def solve_SCP_batch(TOSs, TOPs, solve_method=None, init_method=init_traj_straigh
             if lq is not None:
                 SCPS.tvlqr = _capi.TvlqrResult(lq.K[b - b0], lq.P[b - b0], lq.AB[b - b0], int(lq.status[b - b0]),
                                                int(lq.fail_knot[b - b0]))
+            if sim is not None:
+                SCPS.simulate = {k: v[b - b0] for k, v in sim.items()}
             TOSs[b].traj, TOSs[b].SCPS = SCPS.traj, SCPS
             out[b] = SCPS
     return out

@@ -459,3 +459,55 @@ function tvlqr_batch!(h::Ptr{Cvoid}, B::Integer, n::Integer, m::Integer, N::Inte
   gusto_check(ccall((:gusto_last_tvlqr_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, ms), h, "last_tvlqr_ms")
   (K = K, P = P, AB = AB, status = Int.(status), fail_knot = Int.(fail_knot), ms = ms[])
 end
+
+# ---- closed-loop Monte Carlo roll-outs of the tracking law on the GPU (gusto_simulate, csrc/simulate.hip) ---------------------
+# Every trajectory of a handle flown n_samples times with its gains, from perturbed starts and with clipped controls
+# (include/gusto_hip.h states the definitions; the reference has no counterpart).  GuSTO handles only.
+struct GustoSimulateOpts      # gusto_simulate_opts
+  n_samples::Cint
+  seed::Culonglong; first_problem::Culonglong
+  dx0::NTuple{13,Cdouble}; du0::NTuple{6,Cdouble}
+  u_lo::NTuple{6,Cdouble}; u_hi::NTuple{6,Cdouble}
+  dt_min::Cdouble; nstep::Cint; nstep_cap::Cint
+  dense_collision::Cint
+  store_knots::Cint
+end
+mutable struct GustoSimulateReport      # gusto_simulate_report
+  n_free::Ptr{Cint}; n_finite::Ptr{Cint}; n_clipped::Ptr{Cint}; worst_sample::Ptr{Cint}; worst_dense_sample::Ptr{Cint}
+  min_dist::Ptr{Cdouble}; max_dev::Ptr{Cdouble}; max_final_dev::Ptr{Cdouble}
+  sample_min_dist::Ptr{Cdouble}
+  sample_dense_index::Ptr{Cint}; sample_flags::Ptr{Cint}
+  x_final::Ptr{Cdouble}
+end
+gusto_bounds(w, dim, cap, off) = (v = w isa Number ? fill(Float64(w), dim) : Float64.(collect(w)); ntuple(i -> i <= dim ? v[i] : off, cap))
+
+# The roll-outs of B problems of handle h (x_dim n, u_dim m, N knots).  X [n,N,B], U [m,N,B] or nothing = the handle's own
+# trajectories; K [n,m,N-1,B] (K[:,:,k,b]' = K_k, as tvlqr_batch! returns it) or nothing = the gains of the last tvlqr_batch!;
+# pert [n+m,S,B] or nothing = generated on the device.  The per-sample arrays come back as [S,B], x_final as [n,S,B], max_dev as
+# [n,B]; with store_knots Xcl is [n,S,N,B].
+function simulate_batch!(h::Ptr{Cvoid}, B::Integer, n::Integer, m::Integer, N::Integer, X=nothing, U=nothing, K=nothing, pert=nothing;
+                         n_samples=64, seed=0, first_problem=0, dx0=0.01, du0=0.0, u_lo=-Inf, u_hi=Inf, dt_min=0.1, nstep=0,
+                         nstep_cap=64, dense_collision=true, store_knots=false)
+  ptr(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+  S = Int(n_samples)
+  o = GustoSimulateOpts(S, seed, first_problem, gusto_weights(dx0, n, 13), gusto_weights(du0, m, 6), gusto_bounds(u_lo, m, 6, -Inf),
+                        gusto_bounds(u_hi, m, 6, Inf), dt_min, nstep, nstep_cap, dense_collision ? 1 : 0, store_knots ? 1 : 0)
+  GC.@preserve X U K pert gusto_check(ccall((:gusto_simulate, libgusto_hip), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{GustoSimulateOpts}),
+                    h, ptr(X), ptr(U), ptr(K), ptr(pert), o), h, "simulate")
+  nfree, nfin, nclip, worst, wdense = zeros(Cint, B), zeros(Cint, B), zeros(Cint, B), zeros(Cint, B), zeros(Cint, B)
+  dmin, dev, fdev = zeros(B), zeros(n, B), zeros(n, B)
+  sdist, sidx, sflags, xfin = zeros(S, B), zeros(Cint, S, B), zeros(Cint, S, B), zeros(n, S, B)
+  GC.@preserve nfree nfin nclip worst wdense dmin dev fdev sdist sidx sflags xfin begin
+    rep = GustoSimulateReport(pointer(nfree), pointer(nfin), pointer(nclip), pointer(worst), pointer(wdense), pointer(dmin),
+                              pointer(dev), pointer(fdev), pointer(sdist), pointer(sidx), pointer(sflags), pointer(xfin))
+    gusto_check(ccall((:gusto_get_simulate, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoSimulateReport}), h, rep), h, "get_simulate")
+  end
+  Xcl = store_knots ? zeros(n, S, N, B) : nothing
+  store_knots && gusto_check(ccall((:gusto_get_simulate_knots, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, Xcl), h, "get_simulate_knots")
+  ms = Ref{Cdouble}(0.0)
+  gusto_check(ccall((:gusto_last_simulate_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, ms), h, "last_simulate_ms")
+  (n_free = Int.(nfree), n_finite = Int.(nfin), n_clipped = Int.(nclip), worst_sample = Int.(worst), worst_dense_sample = Int.(wdense),
+   min_dist = dmin, max_dev = dev, max_final_dev = fdev, sample_min_dist = sdist, sample_dense_index = Int.(sidx),
+   sample_flags = Int.(sflags), x_final = xfin, Xcl = Xcl, ms = ms[])
+end

@@ -327,6 +327,77 @@ int gusto_get_tvlqr(gusto_handle h, int* status, int* fail_knot, double* K, doub
 /* GPU time of both phases of the last gusto_tvlqr (linearise + Riccati), from HIP events on the handle's stream */
 int gusto_last_tvlqr_ms(gusto_handle h, double* ms);
 
+/* Closed-loop Monte Carlo roll-outs of the tracking law (csrc/simulate.hip): every trajectory of the batch is flown S times
+ * with its gains, from perturbed starts and with limited actuators.  No counterpart in the reference; the definitions:
+ * Roll-out of sample s of problem b, p = pert[b][s] a vector of x_dim + u_dim numbers:
+ *     x <- X[:,1] + p[0:x_dim];
+ *     at every knot k = 1 .. N-1:  v = (U[:,k] - K_k (x - X[:,k])) + p[x_dim:],  u = clip(v, u_lo, u_hi) entry-wise
+ *     (u_i = u_lo_i if v_i < u_lo_i, u_hi_i if v_i > u_hi_i, else v_i; +-infinity = no bound); u is held for Nstep_b classical
+ *     RK4 steps of dt_b / Nstep_b -- the map gusto_interpolate rolls out and gusto_tvlqr linearised, Nstep_b by the same rule
+ *     (nstep, or ceil(dt_b / dt_min); outside 1 .. nstep_cap: GUSTO_ERR_ARG for the whole call).  The state is NOT restarted at
+ *     the knots and not renormalised: the quaternion of AstrobeeSE3Manifold is 13 plain states.
+ * Dense samples: j = (k - 1) Nstep_b + i (0-based) is the state before substep i of interval k; j = (N - 1) Nstep_b is knot N.
+ * Signed distance: the smallest over the robot's components and the keep-out components of gusto_set_env / _batch, at every
+ *   dense sample (dense_collision = 1) or at the knots only (0; the index stays the dense one).  sample_min_dist is the
+ *   smallest over the samples evaluated, sample_dense_index the first j it occurs at.  A sample COLLIDES when that distance
+ *   is < 0, the raw test of verify_collision_free.  DubinsCar, or an empty keep-out set: +inf, index -1, never a collision.
+ * Non-finite: a sample whose state has an entry that is not finite -- at the start or after any RK4 step -- is flagged and
+ *   advanced no further: its state stays what it was then (x_final and the knots from there on hold it), its distance is
+ *   the smallest up to there.  It counts as not free and is left out of every minimum and maximum of the per-problem report.
+ * Perturbations: the caller's pert [B][S][x_dim + u_dim] as given, or (pert = NULL) generated on the device from integers only
+ *   (csrc/simrng.hpp, which host and device code both compile): sample 0 is always the unperturbed one (zeros); for entry i
+ *   of sample s >= 1 of problem b
+ *     idx = ((first_problem + b) S + s) (x_dim + u_dim) + i,   z = seed + 0x9E3779B97F4A7C15 (idx + 1),
+ *     z = (z ^ z >> 30) 0xBF58476D1CE4E5B9,   z = (z ^ z >> 27) 0x94D049BB133111EB,   z ^= z >> 31     (mod 2^64: splitmix64)
+ *     r = (z >> 11) 2^-53,   p[i] = (2 r - 1) w[i],   w = (dx0, du0)
+ *   so a shard created with first_problem = its offset draws what the whole batch would draw.
+ * K [B][N-1][u_dim][x_dim]: host gains, or NULL = the gains of the handle's last gusto_tvlqr (before any: GUSTO_ERR_STATE).
+ * X, U: host trajectories or NULL, NULL = the handle's current ones (exactly one NULL: GUSTO_ERR_ARG).  The call honours
+ *   gusto_set_active: an inactive problem's report, per-sample arrays and knots stay as the last call with the same n_samples
+ *   wrote them (zeros after new problems or another n_samples).  It runs on the handle's stream after any pending
+ *   gusto_solve_async, is timed with events of its own and changes neither trajectories, status, histories nor gains.
+ *   TrajOpt handles answer GUSTO_ERR_ARG, a handle without problems GUSTO_ERR_STATE; n_samples outside 1 .. 4096, a
+ *   half-width that is negative or not finite, u_lo > u_hi (or a NaN bound), dense_collision / store_knots other than 0 / 1 and
+ *   bad roll-out options answer GUSTO_ERR_ARG.  The device buffers exist only after the first call and only grow.
+ * A problem's report and per-sample arrays are the same bit for bit whatever batch it sits in and whatever else is active. */
+typedef struct {
+    int n_samples;                            /* S, 1 .. 4096; default 64 */
+    unsigned long long seed, first_problem;   /* generated perturbations only; default 0, 0 */
+    double dx0[GUSTO_MAXN], du0[GUSTO_MAXM];  /* half-widths of the generated perturbations.  The default dx0 = 0.01 on every
+                                               * state is a PLACEHOLDER: the states have different units, the caller sets it */
+    double u_lo[GUSTO_MAXM], u_hi[GUSTO_MAXM];/* actuator limits; default -inf, +inf: no clipping */
+    double dt_min; int nstep, nstep_cap;      /* the roll-out of gusto_verify_opts, same meaning, same refusal */
+    int dense_collision;                      /* default 1 */
+    int store_knots;                          /* 1: keep the closed-loop states at the knots; default 0 */
+} gusto_simulate_opts;
+/* 64 samples, seed 0, first_problem 0, dx0 = 0.01 on the model's x_dim entries (0 behind them), du0 = 0, no clipping,
+ * dt_min 0.1, nstep 0, nstep_cap 64, dense_collision 1, store_knots 0 */
+int gusto_default_simulate_opts(int model_id, gusto_simulate_opts* o);
+int gusto_simulate(gusto_handle h, const double* X, const double* U, const double* K, const double* pert,
+                   const gusto_simulate_opts* o);
+/* Caller-owned arrays; any pointer may be NULL.  Per problem ([B] unless stated), reduced over the samples in a fixed order:
+ * n_free: samples that stayed finite and did not collide; n_finite: samples that stayed finite; n_clipped: samples with a
+ *   clipped control entry at some knot.
+ * min_dist: the smallest sample_min_dist over the finite samples (+inf without obstacles or finite samples); worst_sample: the
+ *   lowest sample it occurs at, worst_dense_sample: that sample's sample_dense_index (both -1 when min_dist is +inf).
+ * max_dev [B][x_dim]: the largest |x_i(t_k) - X[i,k]| over the finite samples and the knots k = 1 .. N; max_final_dev
+ *   [B][x_dim]: the same at knot N (zeros without finite samples).
+ * Per sample: sample_min_dist, sample_dense_index, sample_flags [B][S] (bit 0 collided, bit 1 some control entry was clipped,
+ *   bit 2 non-finite), x_final [B][S][x_dim]. */
+typedef struct {
+    int *n_free, *n_finite, *n_clipped, *worst_sample, *worst_dense_sample;
+    double *min_dist, *max_dev, *max_final_dev;
+    double *sample_min_dist;
+    int *sample_dense_index, *sample_flags;
+    double *x_final;
+} gusto_simulate_report;
+int gusto_get_simulate(gusto_handle h, gusto_simulate_report* out);
+/* Xcl [B][N][S][x_dim], the closed-loop state of every sample at every knot: one knot of the 64 samples of a wavefront is one
+ * contiguous range.  Only after a gusto_simulate with store_knots = 1, otherwise GUSTO_ERR_STATE. */
+int gusto_get_simulate_knots(gusto_handle h, double* Xcl);
+/* GPU time of the last gusto_simulate (roll-out and, for more than 256 samples, the reduction launch), from HIP events */
+int gusto_last_simulate_ms(gusto_handle h, double* ms);
+
 /* One convex subproblem per problem (what scp_gusto.jl:82-104 builds and solves in one trip), linearised at
  * (Xp,Up)[b] with the given Delta/omega/obstacle_toggle_distance[b].  Used by the parity tests.
  * Outputs: Xn,Un [B][N][.], obj [B] (JuMP.objective_value), status [B] (GUSTO_SOLVER_*), iters [B]. */
