@@ -31,6 +31,7 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_last_verify_ms",
            "gusto_default_tvlqr_opts", "gusto_tvlqr", "gusto_get_tvlqr", "gusto_last_tvlqr_ms",
            "gusto_default_simulate_opts", "gusto_simulate", "gusto_get_simulate", "gusto_get_simulate_knots", "gusto_last_simulate_ms",
+           "gusto_default_lincov_opts", "gusto_lincov", "gusto_get_lincov", "gusto_last_lincov_ms",
            "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr"]
 
 
@@ -96,6 +97,24 @@ class SimulateReport(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in SIMULATE_FIELDS]
 
 
+class LincovOpts(C.Structure):
+    """gusto_lincov_opts: the half-widths of the default start covariance, the actuator noise and limits, store_S"""
+    _fields_ = [("dx0", C.c_double * MAXN), ("du0", C.c_double * MAXM), ("du_white", C.c_double * MAXM), ("u_lo", C.c_double * MAXM),
+                ("u_hi", C.c_double * MAXM), ("store_S", C.c_int)]
+
+
+# gusto_lincov_report in the header's order: (field, dtype, shape as a function of (B, N, n, m))
+LINCOV_FIELDS = tuple((k, np.int32, lambda B, N, n, m: (B,)) for k in ("status", "fail_knot", "obs_knot", "obs_pair", "ctl_knot", "ctl_entry")) + \
+                tuple((k, np.float64, lambda B, N, n, m: (B,)) for k in ("min_z_obs", "p_collision_bound", "min_z_ctl")) + \
+                (("sigma_x", np.float64, lambda B, N, n, m: (B, N, n)), ("sigma_u", np.float64, lambda B, N, n, m: (B, N - 1, m)),
+                 ("z_obs", np.float64, lambda B, N, n, m: (B, N)), ("Sxx", np.float64, lambda B, N, n, m: (B, N, n, n)))
+
+
+class LincovReport(C.Structure):
+    """gusto_lincov_report: caller-owned arrays"""
+    _fields_ = [(k, C.c_void_p) for k, _, _ in LINCOV_FIELDS]
+
+
 VERIFY_FIELDS = (("collision_free", np.int32), ("first_knot", np.int32), ("first_dist", np.float64),
                  ("min_dist_knots", np.float64), ("dyn_defect_l1", np.float64), ("min_dist_dense", np.float64),
                  ("min_dense_sample", np.int32), ("max_gap", np.float64))
@@ -137,7 +156,7 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(_ROOT, "include"), "-fPIC",
              "-Wno-unused-value", "-Wno-pass-failed"]
-    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
+    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
     bdir = os.path.join(_HERE, "build")
     os.makedirs(bdir, exist_ok=True)
 
@@ -221,6 +240,10 @@ def lib():
         L.gusto_get_simulate.argtypes = [vp, C.POINTER(SimulateReport)]
         L.gusto_get_simulate_knots.argtypes = [vp, vp]
         L.gusto_last_simulate_ms.argtypes = [vp, C.POINTER(C.c_double)]
+        L.gusto_default_lincov_opts.argtypes = [ci, C.POINTER(LincovOpts)]
+        L.gusto_lincov.argtypes = [vp, vp, vp, vp, vp, C.POINTER(LincovOpts)]
+        L.gusto_get_lincov.argtypes = [vp, C.POINTER(LincovReport)]
+        L.gusto_last_lincov_ms.argtypes = [vp, C.POINTER(C.c_double)]
         L.gusto_default_trajopt_params.argtypes = [ci, C.POINTER(TrajOptParams)]
         L.gusto_create_trajopt.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci]
         L.gusto_set_trajopt_params.argtypes = [vp, C.POINTER(TrajOptParams)]
@@ -277,6 +300,14 @@ def default_simulate_opts(model):
     rc = lib().gusto_default_simulate_opts(model, C.byref(o))
     if rc:
         raise ValueError(f"gusto_default_simulate_opts({model}) -> {rc}")
+    return o
+
+
+def default_lincov_opts(model):
+    o = LincovOpts()
+    rc = lib().gusto_default_lincov_opts(model, C.byref(o))
+    if rc:
+        raise ValueError(f"gusto_default_lincov_opts({model}) -> {rc}")
     return o
 
 
@@ -661,6 +692,51 @@ class BatchSolver:
     def last_simulate_ms(self):
         return self._last_ms("last_simulate_ms")
 
+    def lincov_opts(self, opts=None):
+        """a gusto_lincov_opts from None (the defaults), a LincovOpts, or a dict of its fields -- dx0, du0, du_white, u_lo, u_hi as
+        scalars or vectors of the model's x_dim / u_dim entries"""
+        if isinstance(opts, LincovOpts):
+            return opts
+        o = default_lincov_opts(self.model)
+        for k, v in (opts or {}).items():
+            if k in ("dx0", "du0", "du_white", "u_lo", "u_hi"):
+                dim = self.n if k == "dx0" else self.m
+                w = np.broadcast_to(np.asarray(v, dtype=np.float64), (dim,))
+                for i in range(dim):
+                    getattr(o, k)[i] = float(w[i])
+            elif k == "store_S":
+                o.store_S = int(v)
+            else:
+                raise TypeError(f"unknown lincov option {k!r}")
+        return o
+
+    def lincov(self, opts=None, X=None, U=None, K=None, S0=None):
+        """gusto_lincov + gusto_get_lincov: the covariance of (state deviation, control offset) carried through the closed loop of
+        u = U_k - K_k (x - X_k) on the [Ad | Bd] of the last tvlqr(), from S0 [B, n + m, n + m] (default: the variances of
+        simulate()'s generated perturbations with the same dx0, du0), around X, U (default: the handle's trajectories; pass what
+        that tvlqr() saw) with the gains K [B, N-1, m, n] (default: those of the last tvlqr()).  Returns the report as a dict
+        (gusto_lincov_report's fields; Sxx only with store_S = 1)."""
+        px, pu, _keep = self._traj_ptrs(X, U, "lincov")
+        o = self.lincov_opts(opts)
+        Kk = None if K is None else _arr(K).reshape(self.B, self.N - 1, self.m, self.n)
+        Ss = None if S0 is None else _arr(S0).reshape(self.B, self.n + self.m, self.n + self.m)
+        self._chk(self.L.gusto_lincov(self.h, px, pu, None if Kk is None else Kk.ctypes.data,
+                                      None if Ss is None else Ss.ctypes.data, C.byref(o)), "lincov")
+        self._lincov_store_S = bool(o.store_S)
+        return self.get_lincov()
+
+    def get_lincov(self, Sxx=None):
+        """gusto_get_lincov: the report of the last lincov() as a dict of arrays.  Sxx: None = with Sxx [B, N, n, n] if the last
+        call kept it; True = ask for it (refused with -3 after a call without store_S); False = without."""
+        want = getattr(self, "_lincov_store_S", False) if Sxx is None else bool(Sxx)
+        out = {k: np.zeros(shape(self.B, self.N, self.n, self.m), dtype=t) for k, t, shape in LINCOV_FIELDS if k != "Sxx" or want}
+        rep = LincovReport(**{k: v.ctypes.data for k, v in out.items()})
+        self._chk(self.L.gusto_get_lincov(self.h, C.byref(rep)), "get_lincov")
+        return out
+
+    def last_lincov_ms(self):
+        return self._last_ms("last_lincov_ms")
+
     def subproblem(self, Xp, Up, Delta, omega, toggle):
         B = self.B
         Xp, Up = _arr(Xp).reshape(B, self.N, self.n), _arr(Up).reshape(B, self.N, self.m)
@@ -733,3 +809,6 @@ class TrajOptSolver(BatchSolver):
 
     def simulate(self, *a, **k):
         raise GustoError("TrajOptSolver: simulate is not supported on TrajOpt handles (gusto_simulate answers GUSTO_ERR_ARG)")
+
+    def lincov(self, *a, **k):
+        raise GustoError("TrajOptSolver: lincov is not supported on TrajOpt handles (gusto_lincov answers GUSTO_ERR_ARG)")

@@ -309,7 +309,7 @@ static int set_problems_impl(gusto_handle h, int B, const double* x_init, const 
     int rc = do_init(h, X0 == nullptr);
     if (rc) return rc;
     h->have_problems = true;
-    h->shoot.invalidate(); h->verify.invalidate(); h->tvlqr.invalidate(); h->simulate.invalidate();
+    h->shoot.invalidate(); h->verify.invalidate(); h->tvlqr.invalidate(); h->simulate.invalidate(); h->lincov.invalidate();
     h->n_active = -1;   // (gusto_set_active belongs to the problems it was set for)
     return GUSTO_OK;
 }

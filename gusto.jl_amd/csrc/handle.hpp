@@ -135,6 +135,19 @@ struct __attribute__((visibility("hidden"))) SimulateState {
     void invalidate() { have = false; have_knots = false; }
 };
 
+// Linear covariance analysis (lincov.hip): I [6][batch_cap] status, fail_knot, obs_knot, obs_pair, ctl_knot, ctl_entry; D
+// [3][batch_cap] min_z_obs, p_collision_bound, min_z_ctl; Sx [batch_cap][N][n], Su [batch_cap][N - 1][m], Z [batch_cap][N] the
+// per-knot rows; Sxx [batch_cap][N][n][n] (first call with store_S only); copies of a caller's X / U / K / S0.  have_Sxx
+// outlives invalidate(): the next gusto_lincov resets it
+struct __attribute__((visibility("hidden"))) LincovState {
+    DevBuf<double> D, Sx, Su, Z, Sxx, X, U, K, S0;
+    DevBuf<int> I;
+    bool have = false, store_S = false, have_Sxx = false;
+    DevEvent t0, t1;
+    double last_ms = 0.0;
+    void invalidate() { have = false; }
+};
+
 struct gusto_handle_s {
     int model = 0, n = 0, m = 0, N = 0, batch_cap = 0, hist_cap = 0, device = 0, B = 0;
     // TrajOpt handles (gusto_create_trajopt): `model` is the internal variant (common.hpp: GUSTO_TO_*), `m` its control
@@ -185,7 +198,7 @@ struct gusto_handle_s {
     int* h_sched_err = nullptr;    // pinned host word the error flag is copied to on the handle's stream, before the stream is waited for
     DevBuf<double> d_gX, d_gU;     // gusto_gather_peer: the shards of several handles, one after the other, on this handle's GPU
     DevBuf<double> d_Upub;         // TrajOpt handles: U compacted to the public [B][N][u_dim] layout for gusto_get_traj_dev
-    ShootState shoot; VerifyState verify; TvlqrState tvlqr; SimulateState simulate;   // the post-solve stages
+    ShootState shoot; VerifyState verify; TvlqrState tvlqr; SimulateState simulate; LincovState lincov;   // the post-solve stages
     std::string err;
 
     // (the buffers and events free themselves; the caller has made `device` current: gusto_destroy)

@@ -1,0 +1,419 @@
+// lincov.hip -- linear covariance analysis of the tracking law u = U_k - K_k (x(t_k) - X_k) + b + w_k around every trajectory of a
+// batch: the joint covariance S_k of the state deviation and the constant control offset is carried through the closed loop of
+// the discrete Jacobians [Ad_k | Bd_k] of the handle's last gusto_tvlqr, and turned into margins -- the signed distance of every
+// (robot component, keep-out component) pair and the room of every control entry under its bounds, each divided by its standard
+// deviation.  No counterpart in the reference; include/gusto_hip.h states the definitions (recursion, margins, summaries,
+// status).  The analytic counterpart of simulate.hip: one pass per problem instead of S roll-outs.
+// One launch, one wave per problem, the knots in sequence (as tvlqr_riccati).  S_k, G_k = [Ad - Bd K | Bd], T = G_k S_k, K_k
+// and V = [-K I] S_k live in LDS (8.4 KB for n = 13); the 64 lanes split the entries of every product (entry e = lane + 64 r),
+// each entry one dot product in a fixed order.  [Ad | Bd] arrives in the buffer of G: the product Bd K reads its Bd columns
+// and K, and overwrites the Ad columns only.  Sxx of the next knot is computed on the upper triangle and mirrored, so it is
+// symmetric to the bit.  [Ad | Bd] and K of the next knot are loaded into registers while the current knot computes.
+// Margins: lanes take the (component, obstacle) pairs, pair p = lane + 64 r (ordinal component n_obs + obstacle, as
+// verify.hip); the obstacle tables go through problem_env, shared or per problem.  The minimum of a knot is a wave_reduce of
+// the lanes' minima, its ordinal a second one over the lanes that hold that minimum: the lowest ordinal of equal minima.
+// Over the knots a strict < keeps the lowest knot.  The control margins (m <= 6) are walked by every lane on the same LDS values.
+// No atomics, nothing crosses a problem: a problem's outputs are the same bit for bit whatever batch it sits in.
+#include <hip/hip_runtime.h>
+
+#include "models.hpp"
+#include "post.hpp"
+
+using namespace gusto;
+
+namespace {
+
+constexpr int NO_ORD = 1 << 30;    // (ordinals stay below 2 * 64)
+
+struct LcArgs {
+    const double *X, *U, *K, *AB;  // [B][N][n], [B][N][m], [B][N-1][m][n], [B][N-1][n][n+m]
+    const double* S0;              // [B][n+m][n+m], or null: diag(dx0^2 / 3, du0^2 / 3)
+    const int* active;             // gusto_set_active: null = every problem, else the mask [B]
+    const int *tv_status, *tv_fail;   // K = NULL: status and fail_knot of the gains' gusto_tvlqr; a caller's K: null
+    double dx0[GUSTO_MAXN], du0[GUSTO_MAXM], du_white[GUSTO_MAXM], u_lo[GUSTO_MAXM], u_hi[GUSTO_MAXM];
+    int store_S;
+    int *status, *fail_knot, *obs_knot, *obs_pair, *ctl_knot, *ctl_entry;   // [B]
+    double *min_z_obs, *p_bound, *min_z_ctl;                                // [B]
+    double *sigma_x, *sigma_u, *z_obs, *Sxx;   // [B][N][n], [B][N-1][m], [B][N], [B][N][n][n] (store_S)
+};
+
+// the standard deviation of a variance: what rounding leaves below zero counts as zero (a NaN stays one)
+GD double sigma_of(double var) { return sqrt(var < 0.0 ? 0.0 : var); }
+
+// a margin in standard deviations; without any deviation the sign of the margin decides
+GD double margin_z(double d, double sigma) {
+    if (sigma == 0.0) return d >= 0.0 ? INFINITY : -INFINITY;
+    return d / sigma;
+}
+
+// z_obs of one knot and the ordinal of the pair it occurs at (NO_ORD: +inf), the same in every lane.  xk: the knot's state;
+// sS: S_k, whose leading WS x WS block is the covariance of the workspace location (the component offsets are translations)
+template <int MODEL> GD void obstacle_margin(const KParams& P, const Env& E, const double* xk, const double* sS, int lane, double* zk, int* pk) {
+    using T = MT<MODEL>;
+    constexpr int WS = T::WS, nz = T::n + T::m;
+    double zb = INFINITY;
+    int ob = NO_ORD;
+    if constexpr (T::HAS_OBS) {
+        const int npair = P.mp.n_robot_comp * E.n_obs;
+        double x[WS];
+#pragma unroll
+        for (int j = 0; j < WS; j++) x[j] = xk[j];
+        for (int p0 = 0; p0 < npair; p0 += 64) {   // (uniform bound)
+            const int p = p0 + lane;
+            if (p < npair) {
+                const int c = p / E.n_obs, i = p % E.n_obs;
+                double nh[WS];
+                const double d = signed_distance<WS>(P, E, c, x, i, nh);
+                double q = 0.0;
+#pragma unroll
+                for (int a = 0; a < WS; a++) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int j = 0; j < WS; j++) s += sS[a * nz + j] * nh[j];
+                    q += nh[a] * s;
+                }
+                const double z = margin_z(d, sigma_of(q));
+                if (z < zb) { zb = z; ob = p; }   // (ascending ordinals: the first of equal minima stays; a NaN never wins)
+            }
+        }
+    }
+    const double zmin = wave_reduce(zb, OpMin());
+    *pk = (int)wave_reduce((ob != NO_ORD && zb == zmin) ? (double)ob : (double)NO_ORD, OpMin());
+    *zk = zmin;
+}
+
+template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const KParams P, const LcArgs V) {
+    using T = MT<MODEL>;
+    constexpr int n = T::n, m = T::m, nz = n + m;
+    constexpr int NG = n * nz, RG = (NG + 63) / 64;                 // entries of [Ad | Bd], of G and of T, per lane
+    constexpr int NK = m * n, RK = (NK + 63) / 64;
+    constexpr int NV = m * nz, RV = (NV + 63) / 64;                 // V = [-K I] S
+    constexpr int NP = n * (n + 1) / 2, RP = (NP + 63) / 64;        // upper triangle of Sxx
+    constexpr int NS = nz * nz, RS = (NS + 63) / 64, NPF = n * n, RPF = (NPF + 63) / 64;
+    __shared__ double sS[NS], sG[NG], sT[NG], sK[NK], sV[NV], sSu[m];
+    const int b = blockIdx.x, lane = threadIdx.x, N = P.N;
+    if (V.active && !V.active[b]) return;   // (an inactive problem's outputs are left as they are)
+    const double* X = V.X + (size_t)b * N * n;
+    const double* U = V.U + (size_t)b * N * m;
+    const double* AB = V.AB + (size_t)b * (N - 1) * NG;
+    const double* K = V.K + (size_t)b * (N - 1) * NK;
+    double* sx = V.sigma_x + (size_t)b * N * n;
+    double* su = V.sigma_u + (size_t)b * (N - 1) * m;
+    double* zo = V.z_obs + (size_t)b * N;
+    double* Sall = V.store_S ? V.Sxx + (size_t)b * N * NPF : nullptr;
+    const Env E = problem_env(P, b);
+
+    // gains of a failed gusto_tvlqr: its fail_knot, every output zero
+    const bool dead = V.tv_status && !V.tv_status[b];   // (wave-uniform)
+    int fail = dead ? V.tv_fail[b] : 0;
+    int zero_from = dead ? 1 : N + 1;                   // the per-knot rows from this knot on are zeros
+
+    // the upper-triangle entries this lane owns, found once
+    int pa[RP], pb[RP];
+#pragma unroll
+    for (int r = 0; r < RP; r++) {
+        int rem = lane + 64 * r, a = 0;
+        if (rem >= NP) rem = 0;
+        while (rem >= n - a) { rem -= n - a; a++; }
+        pa[r] = a; pb[r] = a + rem;
+    }
+    double w2[m];
+#pragma unroll
+    for (int q = 0; q < m; q++) w2[q] = V.du_white[q] * V.du_white[q];
+
+    // S_1 = S0
+#pragma unroll
+    for (int r = 0; r < RS; r++) {
+        const int e = lane + 64 * r;
+        if (e < NS) {
+            const int i = e / nz, c = e % nz;
+            double v = 0.0;
+            if (V.S0) v = V.S0[(size_t)b * NS + e];
+            else if (i == c) { const double w = i < n ? V.dx0[i] : V.du0[i - n]; v = w * w / 3.0; }
+            sS[e] = v;
+        }
+    }
+    double g[RG], kr[RK];
+#pragma unroll
+    for (int r = 0; r < RG; r++) { const int e = lane + 64 * r; g[r] = (!dead && e < NG) ? AB[e] : 0.0; }
+#pragma unroll
+    for (int r = 0; r < RK; r++) { const int e = lane + 64 * r; kr[r] = (!dead && e < NK) ? K[e] : 0.0; }
+    __syncthreads();
+
+    double zo_min = INFINITY, zc_min = INFINITY, psum = 0.0;
+    int zo_knot = 0, zo_pair = -1, zc_knot = 0, zc_entry = -1;
+
+    // rows of knot k from S_k: sigma_x, z_obs, Sxx; sigma_u on the knots that have a control
+    auto emit = [&](int k, double zk, bool with_u) {
+        if (lane < n) sx[(size_t)(k - 1) * n + lane] = sigma_of(sS[lane * nz + lane]);
+        if (with_u && lane < m) su[(size_t)(k - 1) * m + lane] = sSu[lane];
+        if (lane == 0) zo[k - 1] = zk;
+        if (Sall)
+#pragma unroll
+            for (int r = 0; r < RPF; r++) { const int e = lane + 64 * r; if (e < NPF) Sall[(size_t)(k - 1) * NPF + e] = sS[(e / n) * nz + e % n]; }
+    };
+    auto note_obstacles = [&](int k, double zk, int pk) {
+        if (zk < zo_min) { zo_min = zk; zo_knot = k; zo_pair = pk; }   // (strict: the lowest knot of equal minima)
+        psum += 0.5 * erfc(zk / sqrt(2.0));
+    };
+
+    for (int k = 1; k <= N - 1 && !dead; k++) {   // knot k (1-based): interval k - 1 of the arrays
+#pragma unroll
+        for (int r = 0; r < RG; r++) { const int e = lane + 64 * r; if (e < NG) sG[e] = g[r]; }
+#pragma unroll
+        for (int r = 0; r < RK; r++) { const int e = lane + 64 * r; if (e < NK) sK[e] = kr[r]; }
+        __syncthreads();
+        // [Ad | Bd] and K of the next knot, in flight while this one computes
+        double gp[RG], kp[RK];
+#pragma unroll
+        for (int r = 0; r < RG; r++) { const int e = lane + 64 * r; gp[r] = (k < N - 1 && e < NG) ? AB[(size_t)k * NG + e] : 0.0; }
+#pragma unroll
+        for (int r = 0; r < RK; r++) { const int e = lane + 64 * r; kp[r] = (k < N - 1 && e < NK) ? K[(size_t)k * NK + e] : 0.0; }
+        // G = [Ad - Bd K | Bd]: reads the Bd columns and K, writes the Ad columns
+#pragma unroll
+        for (int r = 0; r < RG; r++) {
+            const int e = lane + 64 * r;
+            if (e < NG && e % nz < n) {
+                const int i = e / nz, c = e % nz;
+                double s = g[r];
+#pragma unroll
+                for (int q = 0; q < m; q++) s -= sG[i * nz + n + q] * sK[q * n + c];
+                sG[e] = s;
+            }
+        }
+        // V = [-K I] S
+#pragma unroll
+        for (int r = 0; r < RV; r++) {
+            const int e = lane + 64 * r;
+            if (e < NV) {
+                const int i = e / nz, c = e % nz;
+                double s = sS[(n + i) * nz + c];
+#pragma unroll
+                for (int j = 0; j < n; j++) s -= sK[i * n + j] * sS[j * nz + c];
+                sV[e] = s;
+            }
+        }
+        __syncthreads();
+        bool bad = false;
+        // T = G S; its last m columns are Sxb of the next knot
+#pragma unroll
+        for (int r = 0; r < RG; r++) {
+            const int e = lane + 64 * r;
+            if (e < NG) {
+                const int i = e / nz, c = e % nz;
+                double s = 0.0;
+#pragma unroll
+                for (int p = 0; p < nz; p++) s += sG[i * nz + p] * sS[p * nz + c];
+                sT[e] = s;
+                if (c >= n && !(fabs(s) < INFINITY)) bad = true;
+            }
+        }
+        // sigma_u = sqrt(diag(V [-K I]') + du_white^2)
+        if (lane < m) {
+            double s = sV[lane * nz + n + lane];
+#pragma unroll
+            for (int j = 0; j < n; j++) s -= sV[lane * nz + j] * sK[lane * n + j];
+            const double w = V.du_white[lane];
+            s += w * w;
+            const double sd = sigma_of(s);
+            sSu[lane] = sd;
+            if (!(fabs(sd) < INFINITY)) bad = true;
+        }
+        __syncthreads();
+        // Sxx of the next knot = T G' + Bd diag(du_white^2) Bd', upper triangle
+        double pn[RP];
+#pragma unroll
+        for (int r = 0; r < RP; r++) {
+            pn[r] = 0.0;
+            if (lane + 64 * r < NP) {
+                const int a = pa[r], c = pb[r];
+                double s = 0.0;
+#pragma unroll
+                for (int p = 0; p < nz; p++) s += sT[a * nz + p] * sG[c * nz + p];
+#pragma unroll
+                for (int q = 0; q < m; q++) s += sG[a * nz + n + q] * w2[q] * sG[c * nz + n + q];
+                pn[r] = s;
+                if (!(fabs(s) < INFINITY)) bad = true;
+            }
+        }
+        if (wave_reduce(bad ? 1.0 : 0.0, OpMax()) != 0.0) { fail = k; zero_from = k; break; }   // (wave-uniform)
+        // the margins of knot k on S_k
+        double zk;
+        int pk;
+        obstacle_margin<MODEL>(P, E, X + (size_t)(k - 1) * n, sS, lane, &zk, &pk);
+        note_obstacles(k, zk, pk);
+        {
+            double zc = INFINITY;
+            int ec = -1;
+#pragma unroll
+            for (int i = 0; i < m; i++) {
+                const double u = U[(size_t)(k - 1) * m + i];
+                const double z = margin_z(fmin(V.u_hi[i] - u, u - V.u_lo[i]), sSu[i]);
+                if (z < zc) { zc = z; ec = i; }
+            }
+            if (zc < zc_min) { zc_min = zc; zc_knot = k; zc_entry = ec; }
+        }
+        emit(k, zk, true);
+        __syncthreads();   // (the readers of S_k are done)
+        // S_{k+1}: Sxx mirrored, Sxb and its transpose; Sbb stays
+#pragma unroll
+        for (int r = 0; r < RP; r++) {
+            if (lane + 64 * r < NP) { sS[pa[r] * nz + pb[r]] = pn[r]; sS[pb[r] * nz + pa[r]] = pn[r]; }
+        }
+#pragma unroll
+        for (int r = 0; r < RG; r++) {
+            const int e = lane + 64 * r;
+            if (e < NG && e % nz >= n) { const int i = e / nz, c = e % nz; const double v = sT[e]; sS[i * nz + c] = v; sS[c * nz + i] = v; }
+        }
+#pragma unroll
+        for (int r = 0; r < RG; r++) g[r] = gp[r];
+#pragma unroll
+        for (int r = 0; r < RK; r++) kr[r] = kp[r];
+        __syncthreads();
+    }
+    if (!dead && !fail) {   // knot N: no control
+        double zk;
+        int pk;
+        obstacle_margin<MODEL>(P, E, X + (size_t)(N - 1) * n, sS, lane, &zk, &pk);
+        note_obstacles(N, zk, pk);
+        emit(N, zk, false);
+    }
+    for (int k = zero_from; k <= N; k++) {
+        if (lane < n) sx[(size_t)(k - 1) * n + lane] = 0.0;
+        if (k <= N - 1 && lane < m) su[(size_t)(k - 1) * m + lane] = 0.0;
+        if (lane == 0) zo[k - 1] = 0.0;
+        if (Sall)
+#pragma unroll
+            for (int r = 0; r < RPF; r++) { const int e = lane + 64 * r; if (e < NPF) Sall[(size_t)(k - 1) * NPF + e] = 0.0; }
+    }
+    if (lane == 0) {
+        V.status[b] = (dead || fail) ? 0 : 1;
+        V.fail_knot[b] = fail;
+        V.obs_knot[b] = dead ? 0 : zo_knot;
+        V.obs_pair[b] = dead ? 0 : (zo_knot ? zo_pair : -1);
+        V.ctl_knot[b] = dead ? 0 : zc_knot;
+        V.ctl_entry[b] = dead ? 0 : (zc_knot ? zc_entry : -1);
+        V.min_z_obs[b] = dead ? 0.0 : zo_min;
+        V.p_bound[b] = dead ? 0.0 : fmin(1.0, psum);
+        V.min_z_ctl[b] = dead ? 0.0 : zc_min;
+    }
+}
+
+template <int MODEL> int launch_lincov(gusto_handle h, const KParams& P, const LcArgs& V) {
+    hipLaunchKernelGGL((lincov_kernel<MODEL>), dim3(h->B), dim3(64), 0, h->stream, P, V);
+    HIPCHK(h, hipGetLastError());
+    return GUSTO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gusto_default_lincov_opts(int model_id, gusto_lincov_opts* o) {
+    const ModelInfo* mi = model_info(model_id);
+    if (!o || !mi) return GUSTO_ERR_ARG;
+    memset(o, 0, sizeof(*o));
+    for (int i = 0; i < mi->n; i++) o->dx0[i] = 0.01;   // (a placeholder: the caller knows the units of its states)
+    for (int i = 0; i < GUSTO_MAXM; i++) { o->u_lo[i] = -INFINITY; o->u_hi[i] = INFINITY; }
+    return GUSTO_OK;
+}
+
+int gusto_lincov(gusto_handle h, const double* X, const double* U, const double* K, const double* S0, const gusto_lincov_opts* opts) {
+    if (int rc = post_enter(h, "gusto_lincov", X, U)) return rc;
+    gusto_lincov_opts o;
+    gusto_default_lincov_opts(h->model, &o);
+    if (opts) o = *opts;
+    if (int rc = lincov_args_host(h->n, h->m, h->B, &o, S0, &h->err)) return rc;
+    if (!h->tvlqr.have) {
+        h->err = "gusto_lincov: no discrete Jacobians: call gusto_tvlqr first";
+        return GUSTO_ERR_STATE;
+    }
+    LincovState& S = h->lincov;
+    const size_t Bc = h->batch_cap, B = h->B, N = h->N, n = h->n, m = h->m, nz = n + m;
+    KParams P = post_params(h);
+    if (!fill_env(h, P, model_info(h->model)->has_obs, true)) {
+        h->err = "gusto_lincov: gusto_set_env_batch was called with a different number of problems than gusto_set_problems";
+        return GUSTO_ERR_STATE;
+    }
+    // grow-only, zeroed when (re)allocated
+    HIPCHK(h, S.I.ensure_zeroed(6 * Bc, h->stream)); HIPCHK(h, S.D.ensure_zeroed(3 * Bc, h->stream));
+    HIPCHK(h, S.Sx.ensure_zeroed(Bc * N * n, h->stream)); HIPCHK(h, S.Su.ensure_zeroed(Bc * (N - 1) * m, h->stream));
+    HIPCHK(h, S.Z.ensure_zeroed(Bc * N, h->stream));
+    if (o.store_S) HIPCHK(h, S.Sxx.ensure_zeroed(Bc * N * n * n, h->stream));
+    if (!S.have) S.have_Sxx = false;   // (new problems: whatever Sxx the buffer holds belongs to the old ones)
+    // a masked first call since gusto_set_problems: the inactive problems read as zeros (an unmasked call writes every problem)
+    if (h->n_active >= 0) {
+        if (!S.have) {
+            HIPCHK(h, hipMemsetAsync(S.I, 0, sizeof(int) * S.I.count(), h->stream));
+            HIPCHK(h, hipMemsetAsync(S.D, 0, sizeof(double) * S.D.count(), h->stream));
+            HIPCHK(h, hipMemsetAsync(S.Sx, 0, sizeof(double) * S.Sx.count(), h->stream));
+            HIPCHK(h, hipMemsetAsync(S.Su, 0, sizeof(double) * S.Su.count(), h->stream));
+            HIPCHK(h, hipMemsetAsync(S.Z, 0, sizeof(double) * S.Z.count(), h->stream));
+        }
+        if (o.store_S && !S.have_Sxx) HIPCHK(h, hipMemsetAsync(S.Sxx, 0, sizeof(double) * S.Sxx.count(), h->stream));
+    }
+    LcArgs V{};
+    if (int rc = stage_traj(h, X, U, Bc, S.X, S.U, &V.X, &V.U)) return rc;
+    V.AB = h->tvlqr.AB;
+    V.K = h->tvlqr.K;
+    V.tv_status = h->tvlqr.St; V.tv_fail = h->tvlqr.St + h->tvlqr.St.count() / 2;
+    if (K) {
+        HIPCHK(h, S.K.ensure(Bc * (N - 1) * m * n));
+        HIPCHK(h, hipMemcpyAsync(S.K, K, sizeof(double) * B * (N - 1) * m * n, hipMemcpyHostToDevice, h->stream));
+        V.K = S.K; V.tv_status = nullptr; V.tv_fail = nullptr;
+    }
+    if (S0) {
+        HIPCHK(h, S.S0.ensure(Bc * nz * nz));
+        HIPCHK(h, hipMemcpyAsync(S.S0, S0, sizeof(double) * B * nz * nz, hipMemcpyHostToDevice, h->stream));
+        V.S0 = S.S0;
+    }
+    V.active = active_mask(h);
+    memcpy(V.dx0, o.dx0, sizeof(V.dx0)); memcpy(V.du0, o.du0, sizeof(V.du0)); memcpy(V.du_white, o.du_white, sizeof(V.du_white));
+    memcpy(V.u_lo, o.u_lo, sizeof(V.u_lo)); memcpy(V.u_hi, o.u_hi, sizeof(V.u_hi));
+    V.store_S = o.store_S;
+    V.status = S.I; V.fail_knot = S.I + Bc; V.obs_knot = S.I + 2 * Bc; V.obs_pair = S.I + 3 * Bc; V.ctl_knot = S.I + 4 * Bc;
+    V.ctl_entry = S.I + 5 * Bc;
+    V.min_z_obs = S.D; V.p_bound = S.D + Bc; V.min_z_ctl = S.D + 2 * Bc;
+    V.sigma_x = S.Sx; V.sigma_u = S.Su; V.z_obs = S.Z; V.Sxx = S.Sxx;
+    HIPCHK(h, S.t0.record(h->stream));
+    if (int rc = for_model(h->model, [&](auto M) { return launch_lincov<M()>(h, P, V); })) return rc;
+    HIPCHK(h, S.t1.record(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, event_ms(S.t0, S.t1, &S.last_ms));
+    if (o.store_S) S.have_Sxx = true;
+    S.have = true;
+    S.store_S = o.store_S != 0;
+    return GUSTO_OK;
+}
+
+int gusto_get_lincov(gusto_handle h, gusto_lincov_report* out) {
+    if (!h) return GUSTO_ERR_ARG;
+    if (int rc = getter_enter(h, false)) return rc;
+    if (!out) return GUSTO_ERR_ARG;
+    const LincovState& S = h->lincov;
+    if (!S.have) { h->err = "gusto_get_lincov: call gusto_lincov first"; return GUSTO_ERR_STATE; }
+    if (out->Sxx && !S.store_S) { h->err = "gusto_get_lincov: the last gusto_lincov did not run with store_S = 1"; return GUSTO_ERR_STATE; }
+    const size_t B = h->B, Bc = h->batch_cap, N = h->N, n = h->n, m = h->m;
+    if (int rc = copy_out(h, out->status, S.I, B)) return rc;
+    if (int rc = copy_out(h, out->fail_knot, S.I + Bc, B)) return rc;
+    if (int rc = copy_out(h, out->obs_knot, S.I + 2 * Bc, B)) return rc;
+    if (int rc = copy_out(h, out->obs_pair, S.I + 3 * Bc, B)) return rc;
+    if (int rc = copy_out(h, out->ctl_knot, S.I + 4 * Bc, B)) return rc;
+    if (int rc = copy_out(h, out->ctl_entry, S.I + 5 * Bc, B)) return rc;
+    if (int rc = copy_out(h, out->min_z_obs, S.D, B)) return rc;
+    if (int rc = copy_out(h, out->p_collision_bound, S.D + Bc, B)) return rc;
+    if (int rc = copy_out(h, out->min_z_ctl, S.D + 2 * Bc, B)) return rc;
+    if (int rc = copy_out(h, out->sigma_x, S.Sx, B * N * n)) return rc;
+    if (int rc = copy_out(h, out->sigma_u, S.Su, B * (N - 1) * m)) return rc;
+    if (int rc = copy_out(h, out->z_obs, S.Z, B * N)) return rc;
+    return copy_out(h, out->Sxx, S.Sxx, B * N * n * n);
+}
+
+int gusto_last_lincov_ms(gusto_handle h, double* ms) {
+    if (!h || !ms) return GUSTO_ERR_ARG;
+    if (!h->lincov.have) { h->err = "gusto_last_lincov_ms: call gusto_lincov first"; return GUSTO_ERR_STATE; }
+    *ms = h->lincov.last_ms;
+    return GUSTO_OK;
+}
+
+}  // extern "C"

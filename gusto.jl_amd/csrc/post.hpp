@@ -1,10 +1,12 @@
-// post.hpp -- the host path of the post-solve stages (shoot.hip, verify.hip, tvlqr.hip, simulate.hip; nothing else includes it).  Plain
+// post.hpp -- the host path of the post-solve stages (shoot.hip, verify.hip, tvlqr.hip, simulate.hip, lincov.hip; nothing else includes it).  Plain
 // functions that answer a GUSTO_* code and leave the text in h->err: `if (int rc = ...) return rc;` at the call site.  A new
-// stage starts from these and from a struct of its own next to ShootState / VerifyState / TvlqrState / SimulateState (handle.hpp).
+// stage starts from these and from a struct of its own next to ShootState / VerifyState / TvlqrState / SimulateState / LincovState
+// (handle.hpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -49,6 +51,40 @@ static inline int resolve_nstep(gusto_handle h, const char* who, double dt_min, 
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     return resolve_nstep_host(tf.data(), tf.size(), h->N, dt_min, nstep, nstep_cap, who, nstep_max, &h->err);
+}
+
+// The arguments of gusto_lincov for a model of n states and m controls: the options, and the caller's S0 [B][n + m][n + m]
+// (null: the default start).  GUSTO_ERR_ARG and the text, which names the offending entry (and problem), in *err.  Whether S0
+// is positive semi-definite is the caller's business.  No device, no handle.
+static inline int lincov_args_host(int n, int m, size_t B, const gusto_lincov_opts* o, const double* S0, std::string* err) {
+    const std::string w("gusto_lincov: ");
+    const auto width_ok = [](double v) { return v >= 0 && v < INFINITY; };
+    if (o->store_S != 0 && o->store_S != 1) { *err = w + "store_S must be 0 or 1"; return GUSTO_ERR_ARG; }
+    for (int i = 0; i < n; i++)
+        if (!width_ok(o->dx0[i])) { *err = w + "dx0 must be finite and >= 0 (entry " + std::to_string(i) + ")"; return GUSTO_ERR_ARG; }
+    for (int i = 0; i < m; i++) {
+        if (!width_ok(o->du0[i])) { *err = w + "du0 must be finite and >= 0 (entry " + std::to_string(i) + ")"; return GUSTO_ERR_ARG; }
+        if (!width_ok(o->du_white[i])) { *err = w + "du_white must be finite and >= 0 (entry " + std::to_string(i) + ")"; return GUSTO_ERR_ARG; }
+        if (!(o->u_lo[i] <= o->u_hi[i])) { *err = w + "u_lo must not exceed u_hi (entry " + std::to_string(i) + ")"; return GUSTO_ERR_ARG; }
+    }
+    const size_t nz = (size_t)(n + m);
+    for (size_t b = 0; S0 && b < B; b++) {
+        const double* S = S0 + b * nz * nz;
+        const auto where = [&](size_t i, size_t j) {
+            return " (problem " + std::to_string(b) + ", entry " + std::to_string(i) + ", " + std::to_string(j) + ")";
+        };
+        for (size_t i = 0; i < nz; i++)
+            for (size_t j = 0; j < nz; j++) {
+                const double v = S[i * nz + j];
+                if (!(fabs(v) < INFINITY)) { *err = w + "S0 must be finite" + where(i, j); return GUSTO_ERR_ARG; }
+                if (i == j && v < 0) { *err = w + "S0 has a negative diagonal entry" + where(i, j); return GUSTO_ERR_ARG; }
+                if (j > i && memcmp(&S[i * nz + j], &S[j * nz + i], sizeof(double)) != 0) {
+                    *err = w + "S0 must be symmetric to the bit" + where(i, j);
+                    return GUSTO_ERR_ARG;
+                }
+            }
+    }
+    return GUSTO_OK;
 }
 
 // KParams of a kernel that reads trajectories: zeros but for the sizes, the model parameters and tf

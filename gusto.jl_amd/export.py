@@ -24,7 +24,7 @@ INDEX_MAPS = {
 }
 
 
-def _tree(model_id, X, U, tf, extra=None, column_major_reader=False, K=None):
+def _tree(model_id, X, U, tf, extra=None, column_major_reader=False, K=None, sigma=None):
     """X [.., N, n], U [.., N, m] in the C ABI layout -> the notebook's layout (state index first, knot second).
     column_major_reader: keep the C layout [.., N, n] -- HDF5 dimensions are row-major, so HDF5.jl / MATLAB present such
     a data set as n x N (x B), exactly the matrix the notebook wrote."""
@@ -42,6 +42,11 @@ def _tree(model_id, X, U, tf, extra=None, column_major_reader=False, K=None):
         if K.shape[-3:] != (N - 1, U.shape[-1], X.shape[-1]) or K.shape[:-3] != X.shape[:-2]:
             raise ValueError("export: K must be [.., N - 1, u_dim, x_dim] with the leading axes of X")
         out["traj"]["k_traj"] = K
+    if sigma is not None:   # gusto_lincov: sigma_x [.., N, x_dim], the C layout in every format (a row per knot, as k_traj)
+        sigma = np.asarray(sigma, float)
+        if sigma.shape != X.shape:
+            raise ValueError("export: sigma must be [.., N, x_dim], the shape of X")
+        out["traj"]["sigma_traj"] = sigma
     if extra:
         out["status"] = {k: np.asarray(v) for k, v in extra.items()}
     return out
@@ -57,11 +62,12 @@ def _flatten(tree, prefix=""):
     return flat
 
 
-def write(path, model_id, X, U, tf, status=None, K=None):
+def write(path, model_id, X, U, tf, status=None, K=None, sigma=None):
     """path ending in .h5 -> HDF5 (the notebook's container); .mat -> MATLAB v5 with nested structs; .npz -> flat keys
     'traj/x_traj', ...  K (optional): the tracking gains of BatchSolver.tvlqr, written as traj/k_traj [N-1][u_dim][x_dim] per
-    trajectory next to x_traj, u_traj and t_traj.  Returns the tree that was written."""
-    tree = _tree(model_id, X, U, tf, status, column_major_reader=path.endswith((".h5", ".hdf5")), K=K)
+    trajectory next to x_traj, u_traj and t_traj.  sigma (optional): the standard deviations sigma_x of BatchSolver.lincov,
+    written as traj/sigma_traj [N][x_dim] next to k_traj.  Returns the tree that was written."""
+    tree = _tree(model_id, X, U, tf, status, column_major_reader=path.endswith((".h5", ".hdf5")), K=K, sigma=sigma)
     if path.endswith((".h5", ".hdf5")):
         from . import h5lite
         h5lite.write_h5(path, tree)
@@ -75,20 +81,20 @@ def write(path, model_id, X, U, tf, status=None, K=None):
     return tree
 
 
-def write_solution(path, TOS, K=None):
+def write_solution(path, TOS, K=None, sigma=None):
     """One TrajectoryOptimizationSolution (host mirror): TOS.traj.X is already x_dim x N as in the reference."""
     model_id = TOS.SCPS.SCPP.PD.model.model_id
     return write(path, model_id, TOS.traj.X.T, TOS.traj.U.T, TOS.traj.Tf,
-                 dict(converged=TOS.SCPS.converged, successful=TOS.SCPS.successful, iterations=TOS.SCPS.iterations), K=K)
+                 dict(converged=TOS.SCPS.converged, successful=TOS.SCPS.successful, iterations=TOS.SCPS.iterations), K=K, sigma=sigma)
 
 
-def write_batch(path, solver, tf, K=None):
+def write_batch(path, solver, tf, K=None, sigma=None):
     """Everything a BatchSolver holds after a solve: X [B][n][N], U [B][m][N], t [B][N] + per-problem status (+ K [B][N-1][m][n])."""
     X, U = solver.traj()
     st = solver.status()
     return write(path, solver.model, X, U, np.asarray(tf, float),
                  dict(converged=st["converged"].astype(np.int8), successful=st["successful"].astype(np.int8),
-                      iterations=st["iterations"], stop_reason=st["stop_reason"]), K=K)
+                      iterations=st["iterations"], stop_reason=st["stop_reason"]), K=K, sigma=sigma)
 
 
 def read(path):

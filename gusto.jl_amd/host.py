@@ -602,6 +602,22 @@ def simulate(traj, SCPP, K=None, pert=None, Q=1.0, R=1.0, Qf=1.0, **opts):
     return {k: v[0] for k, v in r.items()}
 
 
+def lincov(traj, SCPP, K=None, S0=None, Q=1.0, R=1.0, Qf=1.0, dt_min=0.1, **opts):
+    """Linear covariance analysis of the tracking law around one trajectory (gusto_lincov; no counterpart in the reference): the
+    covariance of the state deviation and of a constant control offset carried through the closed loop of
+    u = U[:, k] - K[k] (x(t_k) - X[:, k]) on the discrete Jacobians of tvlqr(traj, SCPP, Q, R, Qf, dt_min), and the margins it leaves
+    to the keep-out set and the control bounds.  K [N-1, u_dim, x_dim]: the gains, default those of that tvlqr; S0
+    [x_dim + u_dim, x_dim + u_dim]: the start covariance, default diag(dx0^2 / 3, du0^2 / 3); opts: gusto_lincov_opts fields.
+    Returns the one-problem report as a dict."""
+    bs = _verify_handle(traj, SCPP)
+    try:
+        bs.tvlqr(dict(Q=Q, R=R, Qf=Qf, dt_min=dt_min, nstep_cap=max(64, int(np.ceil(traj.dt / dt_min)))))
+        r = bs.lincov(opts, K=None if K is None else np.asarray(K, float)[None], S0=None if S0 is None else np.asarray(S0, float)[None])
+    finally:
+        bs.close()
+    return {k: v[0] for k, v in r.items()}
+
+
 def shard_bounds(B, world_size, rank):
     """Contiguous block of ceil(B/G) problems per rank; the tail rank may get fewer."""
     per = -(-B // world_size)

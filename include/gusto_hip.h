@@ -398,6 +398,73 @@ int gusto_get_simulate_knots(gusto_handle h, double* Xcl);
 /* GPU time of the last gusto_simulate (roll-out and, for more than 256 samples, the reduction launch), from HIP events */
 int gusto_last_simulate_ms(gusto_handle h, double* ms);
 
+/* Linear covariance analysis of the tracking law (csrc/lincov.hip): the analytic counterpart of gusto_simulate -- one forward
+ * pass per problem carries a covariance through the closed loop and turns it into margins.  No counterpart in the reference;
+ * the definitions, for one problem with n = x_dim, m = u_dim:
+ * Augmented deviation z = [dx; b]: dx the deviation of the closed-loop state from X[:,k], b the constant control offset (the
+ *   p[x_dim:] of gusto_simulate).  S_k = [[Sxx, Sxb], [Sbx, Sbb]], (n + m) x (n + m), is its covariance at knot k.
+ * Start: S_1 = S0, the caller's [B][n + m][n + m] array, or (S0 = NULL) diag(dx0_i^2 / 3, du0_j^2 / 3): the variances of the
+ *   uniform draws of gusto_simulate's generator with the same half-widths.
+ * Recursion, k = 1 .. N-1, with [Ad_k | Bd_k] of the handle's LAST gusto_tvlqr and G_k = [Ad_k - Bd_k K_k | Bd_k] (n x (n + m)):
+ *     Sxx_{k+1} = G_k S_k G_k' + Bd_k diag(du_white^2) Bd_k',   Sxb_{k+1} = G_k S_k[:, n:],   Sbb stays.
+ *   Sxx is computed on the upper triangle and mirrored: symmetric to the bit.  du_white is the standard deviation of an
+ *   independent actuator noise w_k per hold interval (gusto_simulate has no such term).
+ * Commanded control at knot k: its deviation is dv = [-K_k | I] z + w_k,
+ *     sigma_u[k][i] = sqrt(([-K_k I] S_k [-K_k I]' + diag(du_white^2))_ii);   sigma_x[k][i] = sqrt(Sxx_k[i][i]).
+ *   Under every square root here and below, a variance that rounding leaves below zero counts as zero: the feedback cancels a
+ *   constant offset, so the variance of the commanded control decays to rounding noise along a long horizon.
+ * Obstacle margin at knot k: for every robot component c and keep-out component i (gusto_set_env / gusto_set_env_batch) the
+ *   signed distance d at X[:,k] and its outward normal nh -- the component offsets are translations, so nh is the exact
+ *   gradient with respect to the first WS states (2 in the plane, 3 in space);
+ *     sigma_d = sqrt(nh' Sxx[0:WS, 0:WS] nh),   z = d / sigma_d;   sigma_d == 0: z = +inf for d >= 0, -inf for d < 0.
+ *   z_obs[k] is the smallest z over the pairs in loop order, components outermost: pair ordinal c n_obs + i.  DubinsCar, or an
+ *   empty keep-out set: +inf.  (A z that is NaN never wins a minimum.)
+ * Control margin at knot k <= N-1, entry i: min(u_hi_i - U[i,k], U[i,k] - u_lo_i) / sigma_u[k][i]; an infinite bound gives +inf,
+ *   sigma_u == 0 is decided by the sign of the room as for sigma_d.
+ * Per problem: min_z_obs, the smallest z_obs[k], with obs_knot (1-based; 0 when it is +inf) and obs_pair (the ordinal; -1 when
+ *   it is +inf); min_z_ctl with ctl_knot and ctl_entry likewise; ties go to the lowest knot, then the lowest ordinal / entry;
+ *     p_collision_bound = min(1, sum_k erfc(z_obs[k] / sqrt(2)) / 2)
+ *   -- Boole's inequality over the knots if the deviations are read as Gaussian.  It is a BOUND UNDER THAT READING, not a
+ *   probability: nothing here says the deviations are Gaussian, and between the knots nothing is looked at.
+ * Status: 1 and fail_knot 0 normally.  K = NULL and a problem whose gusto_tvlqr status is 0: status 0, fail_knot that of
+ *   gusto_tvlqr, every output zero.  A non-finite entry in Sxx_{k+1}, Sxb_{k+1} or sigma_u at knot k: status 0, fail_knot k, the
+ *   per-knot rows from that knot on are zeros and the summaries cover the knots before it.  Failures are data, not return codes.
+ * K [B][N-1][u_dim][x_dim]: host gains, or NULL = the gains of the handle's last gusto_tvlqr.  [Ad | Bd] ALWAYS come from the
+ *   handle's last gusto_tvlqr (before any since gusto_set_problems: GUSTO_ERR_STATE): the caller passes the X, U that call saw,
+ *   as for gusto_simulate.  X, U: host trajectories or NULL, NULL = the handle's current ones (exactly one NULL: GUSTO_ERR_ARG).
+ * The call honours gusto_set_active (an inactive problem keeps what the last call wrote; zeros after a masked first call since
+ *   gusto_set_problems), runs on the handle's stream after any pending gusto_solve_async, is timed with events of its own and
+ *   changes neither trajectories, status, histories nor gains.  TrajOpt handles answer GUSTO_ERR_ARG, a handle without problems
+ *   GUSTO_ERR_STATE.  GUSTO_ERR_ARG, with the offending problem and entry in gusto_last_error: a half-width or du_white that is
+ *   negative or not finite, u_lo > u_hi or a NaN bound, store_S other than 0 / 1, an S0 that is not finite, has a negative
+ *   diagonal entry or is not symmetric to the bit.  Whether S0 is positive semi-definite is the caller's business.
+ * The device buffers exist only after the first call and only grow; Sxx of every knot only after a call with store_S.  All
+ *   reductions run in a fixed order without atomics: a problem's outputs are the same bit for bit in any batch and under any
+ *   gusto_set_active mask. */
+typedef struct {
+    double dx0[GUSTO_MAXN], du0[GUSTO_MAXM];   /* default S0: half-widths as in gusto_simulate_opts; the default dx0 = 0.01 is the
+                                                * same PLACEHOLDER, du0 = 0 */
+    double du_white[GUSTO_MAXM];               /* default 0 */
+    double u_lo[GUSTO_MAXM], u_hi[GUSTO_MAXM]; /* default -inf, +inf */
+    int store_S;                               /* 1: keep Sxx of every knot; default 0 */
+} gusto_lincov_opts;
+int gusto_default_lincov_opts(int model_id, gusto_lincov_opts* o);
+int gusto_lincov(gusto_handle h, const double* X, const double* U, const double* K, const double* S0, const gusto_lincov_opts* o);
+/* Caller-owned arrays; any pointer may be NULL.  Per problem [B]: status, fail_knot, obs_knot, obs_pair, ctl_knot, ctl_entry,
+ * min_z_obs, p_collision_bound, min_z_ctl.  Per knot: sigma_x, sigma_u, z_obs, and Sxx after a call with store_S = 1 (asked for
+ * after a call without: GUSTO_ERR_STATE). */
+typedef struct {
+    int *status, *fail_knot, *obs_knot, *obs_pair, *ctl_knot, *ctl_entry;
+    double *min_z_obs, *p_collision_bound, *min_z_ctl;
+    double *sigma_x;   /* [B][N][x_dim]   */
+    double *sigma_u;   /* [B][N-1][u_dim] */
+    double *z_obs;     /* [B][N]          */
+    double *Sxx;       /* [B][N][x_dim][x_dim] */
+} gusto_lincov_report;
+int gusto_get_lincov(gusto_handle h, gusto_lincov_report* out);
+/* GPU time of the last gusto_lincov (one launch), from HIP events on the handle's stream */
+int gusto_last_lincov_ms(gusto_handle h, double* ms);
+
 /* One convex subproblem per problem (what scp_gusto.jl:82-104 builds and solves in one trip), linearised at
  * (Xp,Up)[b] with the given Delta/omega/obstacle_toggle_distance[b].  Used by the parity tests.
  * Outputs: Xn,Un [B][N][.], obj [B] (JuMP.objective_value), status [B] (GUSTO_SOLVER_*), iters [B]. */
