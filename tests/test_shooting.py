@@ -111,11 +111,11 @@ def test_oracle_manifold_shooting_against_scipy(b):
     assert np.abs(s["p0"] - r["dual"]).max() < 1.0 * np.abs(r["dual"]).max()
 
 
-@pytest.mark.gpu
-def test_gpu_shooting_matches_the_oracle():
-    B = 256
+def check_dubins_shooting_against_the_oracle(B, batch_cap):
+    """gusto_shoot of B DubinsCar problems on a handle of batch_cap against the oracle (tests/test_gpu_post_handle_reuse.py runs
+    it with batch_cap > B)"""
     x0, glo, ghi, tf = P.dubins_batch(B)
-    s = g.BatchSolver(g.DUBINS_CAR, 30, B, hist_cap=40)
+    s = g.BatchSolver(g.DUBINS_CAR, 30, batch_cap, hist_cap=40)
     s.set_problems(x0, glo, ghi, tf)
     s.solve(30)
     duals = s.dual()
@@ -135,6 +135,11 @@ def test_gpu_shooting_matches_the_oracle():
             assert np.abs(r["X"][b] - ro["X"]).max() < 1e-4 and np.abs(r["U"][b] - ro["U"]).max() < 1e-4   # (both sides stop at ftol = 1e-3 from seeds that agree to 1e-9: measured 4.7e-5)
             assert np.abs(r["X"][b, -1] - glo[b]).max() <= 1e-3          # ftol of shooting.jl:14
     assert n_opt > B // 2
+
+
+@pytest.mark.gpu
+def test_gpu_shooting_matches_the_oracle():
+    check_dubins_shooting_against_the_oracle(256, 256)
     with pytest.raises(g.GustoError):                # models without a shooting ODE are refused, not approximated
         f = g.BatchSolver(g.FREEFLYER_SE2, 20, 1, boxes=P.freeflyer_env())
         f.set_problems(P.FREEFLYER_X_INIT[None], P.FREEFLYER_X_GOAL[None], P.FREEFLYER_X_GOAL[None], [200.0])
