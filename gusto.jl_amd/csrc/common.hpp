@@ -20,7 +20,7 @@ constexpr int ROW_HARD_EQ = 4;  // j=1 half of a penalised equality: 0 <= s1 <= 
 constexpr int ROW_EQ = 5;       // hard equality h = 0 (TrajOpt's convex_state_eq rows)                  scp_trajopt.jl:200-208
 GD bool row_is_hard(int kind) { return kind == ROW_HARD || kind == ROW_HARD_EQ; }
 
-// per-row interior point state, stored [var][slot][k] so that lane k's accesses coalesce
+// per-row interior point state, stored so that lane k's accesses coalesce (MT::RS_FORM below, rows.hpp: RowState)
 constexpr int RS_T = 0, RS_LAM = 1, RS_LAMB = 2, RS_S = 3, RS_DT = 4, RS_DL = 5, RS_DS = 6, RS_KA = 7, RS_KB = 8,
               RS_NVAR = 9;
 
@@ -50,11 +50,18 @@ constexpr int RS_T = 0, RS_LAM = 1, RS_LAMB = 2, RS_S = 3, RS_DT = 4, RS_DL = 5,
 constexpr int GUSTO_TO_FREEFLYER_SE2 = 4, GUSTO_TO_ASTROBEE_SE3 = 5, GUSTO_TO_ASTROBEE_SE3_MANIFOLD = 6;
 // vanishing quadratic cost on the defects next to their L1 penalty (the oracle's GO_TRAJOPT_DEFECT_REG)
 constexpr double TRAJOPT_DEFECT_REG = 1e-4;
+// Layout and addressing of the per-row interior point state (rows.hpp: RowState), per model (MT::RS_FORM):
+//   RS_EARLIER   [var][slot][N] with the control rows behind the obstacle rows, one scalar address per (variable, row)
+//   RS_ROW       [slot][var][KP], KP = N padded to whole waves, the rows every knot has at compile-time slots; one scalar base, a
+//                32-bit lane offset aimed at the row and the distance of the variable as immediate (one-wave kernels) or scalar
+//   RS_ROW_LANE  as RS_ROW, but kernels with a run-time stride form the whole offset in the lane
+constexpr int RS_EARLIER = 0, RS_ROW = 1, RS_ROW_LANE = 2;
 template <int MODEL> struct MT;
 template <> struct MT<GUSTO_FREEFLYER_SE2> {
     static constexpr int NDEF = 0;   // (no defect controls: the dynamics are hard rows)
     static constexpr int n = 6, m = 3, WS = 2, NFIX = 3, NHU = 2;
     static constexpr int WAVES_PER_EU = GUSTO_WAVES_PER_EU;   // register budget of the one-wave kernel: 512 / this
+    static constexpr int RS_FORM = RS_ROW;   // layout and addressing of the row state, see RS_EARLIER .. RS_ROW_LANE above
     static constexpr bool SWEEP_CALL = false;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool MFMA = false;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 2;   // default number of one-trip probing slices of the longest-first scheduler
@@ -79,6 +86,7 @@ template <> struct MT<GUSTO_DUBINS_CAR> {
     static constexpr int NDEF = 0;   // (no defect controls: the dynamics are hard rows)
     static constexpr int n = 3, m = 1, WS = 2, NFIX = 6, NHU = 2;
     static constexpr int WAVES_PER_EU = GUSTO_DUBINS_WAVES;   // register budget of the one-wave kernel: 512 / this
+    static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_CALL = false;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool MFMA = false;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (short problems: 2 slices cost more than they order -- 316 vs 211 ms at B = 65 536)
@@ -96,6 +104,7 @@ template <> struct MT<GUSTO_ASTROBEE_SE3> {
     static constexpr int NDEF = 0;   // (no defect controls: the dynamics are hard rows)
     static constexpr int n = 12, m = 6, WS = 3, NFIX = 3, NHU = 2;
     static constexpr int WAVES_PER_EU = 1;   // register budget of the one-wave kernel: 512 / this
+    static constexpr int RS_FORM = RS_ROW_LANE;   // (lane form: the only one that adds nothing to the scratch of its multi-wave kernel)
     static constexpr bool SWEEP_CALL = true;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool MFMA = GUSTO_USE_MFMA;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (measured with raised-penalty problems ahead of fresh ones: 123.0 / 127.1 / 132.7 ms for 1 / 2 / 3 slices)
@@ -118,6 +127,7 @@ template <> struct MT<GUSTO_ASTROBEE_SE3_MANIFOLD> {
     static constexpr int NDEF = 0;   // (no defect controls: the dynamics are hard rows)
     static constexpr int n = 13, m = 6, WS = 3, NFIX = 5, NHU = 2;
     static constexpr int WAVES_PER_EU = 1;   // register budget of the one-wave kernel: 512 / this
+    static constexpr int RS_FORM = RS_EARLIER;   // (config 5 measured 0.9 % slower with RS_ROW: profiles/r07_rowstate_layout.txt)
     static constexpr bool SWEEP_CALL = true ;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool MFMA = GUSTO_USE_MFMA;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (130.1 / 133.7 / 130.9 ms for 1 / 2 / 3 slices)
@@ -139,6 +149,7 @@ template <> struct MT<GUSTO_TO_FREEFLYER_SE2> {
     using G = MT<GUSTO_FREEFLYER_SE2>;
     static constexpr int NDEF = 6, n = 6, m = 3 + NDEF, WS = 2, NFIX = 3, NHU = 2 + 2 * NDEF;
     static constexpr int WAVES_PER_EU = 1, SCHED_PROBE = 0, SCHED_SLICE = 0;
+    static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_CALL = GUSTO_TO4_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }
@@ -152,6 +163,7 @@ template <> struct MT<GUSTO_TO_ASTROBEE_SE3> {
     using G = MT<GUSTO_ASTROBEE_SE3>;
     static constexpr int NDEF = 12, n = 12, m = 6 + NDEF, WS = 3, NFIX = 3, NHU = 2 + 2 * NDEF;
     static constexpr int WAVES_PER_EU = 1, SCHED_PROBE = 0, SCHED_SLICE = 0;
+    static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_CALL = GUSTO_TO_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }
@@ -167,6 +179,7 @@ template <> struct MT<GUSTO_TO_ASTROBEE_SE3_MANIFOLD> {
     // fixed state rows of a knot: the +- band of the (hard) quaternion norm row, orientation sign, speed, rate
     static constexpr int NDEF = 13, n = 13, m = 6 + NDEF, WS = 3, NFIX = 5, NHU = 2 + 2 * NDEF;
     static constexpr int WAVES_PER_EU = 1, SCHED_PROBE = 0, SCHED_SLICE = 0;
+    static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_CALL = GUSTO_TO_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }
@@ -275,6 +288,16 @@ template <int MODEL> struct SpPG {
     static constexpr bool USE = T::MFMA && T::NDEF == 0;
 };
 
+// knot stride of the row state: the knot count, for RS_ROW padded to whole waves.  The one-wave kernels then know it at compile
+// time (N <= 64), which makes every (variable, row) distance of a compile-time row an instruction immediate.
+template <int MODEL> constexpr int rs_stride_rt(int N) { return MT<MODEL>::RS_FORM == RS_EARLIER ? N : (N + 63) & ~63; }
+template <int MODEL, bool ONE> GD int rs_stride(int N) {
+    if constexpr (ONE && MT<MODEL>::RS_FORM != RS_EARLIER) return 64;
+    else return rs_stride_rt<MODEL>(N);
+}
+// the form of a kernel's accesses: RS_ROW_LANE is for run-time strides only
+template <int MODEL, bool ONE> constexpr int rs_form() { return (ONE && MT<MODEL>::RS_FORM == RS_ROW_LANE) ? RS_ROW : MT<MODEL>::RS_FORM; }
+
 // per-problem global workspace, offsets in doubles
 struct WsLayout {
     int nslot;
@@ -287,7 +310,9 @@ template <int MODEL> inline WsLayout make_ws_layout(int N, int n_obs) {
     L.nslot = T::NFIX + n_obs + 2 * n + T::NHU;
     size_t o = 0;
     auto take = [&](size_t c) { size_t r = o; o += (c + 1) & ~size_t(1); return r; };
-    L.rowstate = take((size_t)RS_NVAR * L.nslot * N);
+    // (RS_ROW: first in the block and a multiple of 64 doubles per slab -- with the block itself a whole number of 128-byte lines,
+    //  below, every [slot][var] slab of every workspace slot starts on a cache line)
+    L.rowstate = take((size_t)RS_NVAR * L.nslot * rs_stride_rt<MODEL>(N));
     L.obs_nh = take((size_t)n_obs * T::WS * N);
     L.obs_c0 = take((size_t)n_obs * N);
     L.obs_mask = take((size_t)N);
@@ -301,7 +326,7 @@ template <int MODEL> inline WsLayout make_ws_layout(int N, int n_obs) {
     L.Phicl = take((size_t)N * R::SNN);
     L.pvt = take((size_t)N * (5 * n + 5 * m));   // rd qrd dXs | dUs qu dv | gAx gBx gAu gBu (corrector row sums)
     L.to_traj = take(T::NDEF > 0 ? (size_t)2 * N * (n + m) : 0);   // TrajOpt: old_penalty_traj and old_convex_traj (X | U each)
-    L.total = o;
+    L.total = T::RS_FORM == RS_EARLIER ? o : (o + 15) & ~size_t(15);
     return L;
 }
 

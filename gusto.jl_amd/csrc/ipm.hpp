@@ -2145,8 +2145,8 @@ template <int MODEL, class BLK> GD void costate_close_x1(BLK& K, double hdt, con
         K.nun[i] = -s;
     }
 }
-template <int MODEL, class BLK, bool CLOSE = true, int NCH = 0>
-GD StepOut step_phase(BLK& K, const RowCtx<MODEL>& ctx, const RowState& rs, int k, bool act, int pass, int ncomp, double hdt,
+template <int MODEL, class BLK, bool CLOSE = true, int NCH = 0, class RS>
+GD StepOut step_phase(BLK& K, const RowCtx<MODEL>& ctx, const RS& rs, int k, bool act, int pass, int ncomp, double hdt,
                       double tau, double mu_t, const double* mugn, const double* gxs) {
     using T = MT<MODEL>;
     using R = Rec<MODEL>;
@@ -2220,7 +2220,7 @@ GD StepOut step_phase(BLK& K, const RowCtx<MODEL>& ctx, const RowState& rs, int 
         constexpr int NP = (n <= 8 && T::NDEF == 0) ? T::NFIX + T::NHU : 0;
         RowPre<NP> pre;
         if constexpr (NP > 0) {
-            const int slot_u = T::NFIX + K.P.n_obs + 2 * n;
+            const int slot_u = RowSlots<MODEL>::ctl(K.P.n_obs);
             pre.load(rs, T::NFIX, slot_u, [&](int var) {
                 return var == RS_T || var == RS_LAM || var == RS_S || var == RS_LAMB || (pass && (var == RS_KA || var == RS_KB));
             });
@@ -2228,7 +2228,7 @@ GD StepOut step_phase(BLK& K, const RowCtx<MODEL>& ctx, const RowState& rs, int 
         double hdx[ADJ ? n : 1];
 #pragma unroll
         for (int i = 0; i < (ADJ ? n : 1); i++) hdx[i] = 0;
-        OpStep<NP, ADJ> op{rs, dxs, dus, pass, mu_t, tau, gAx, gAu, gBx, gBu, &pre, hdx};
+        OpStep<NP, ADJ, RS> op{rs, dxs, dus, pass, mu_t, tau, gAx, gAu, gBx, gBu, &pre, hdx};
         ctx.tick(0);
 #if GUSTO_SEG_W2
         if constexpr (NCH > 0) {
@@ -2285,12 +2285,13 @@ GD StepOut step_phase(BLK& K, const RowCtx<MODEL>& ctx, const RowState& rs, int 
 }
 // the row context of knot k, as ipm_solve builds it (the called phases rebuild theirs from three numbers)
 template <int MODEL, class BLK>
-GD void make_row_ctx(const BLK& K, int k, bool act, double kappa, double omega, double Delta, RowCtx<MODEL>& ctx, RowState& rs) {
+GD void make_row_ctx(const BLK& K, int k, bool act, double kappa, double omega, double Delta, RowCtx<MODEL>& ctx,
+                     RowState<rs_form<MODEL, BLK::ONE>()>& rs) {
     constexpr int n = BLK::n;
     ctx.P = &K.P; ctx.N = K.N; ctx.k = k; ctx.nslot = K.P.wl.nslot; ctx.kappa = kappa; ctx.omega = omega; ctx.Delta = Delta;
     ctx.xp = K.Xp + (act ? k : 0) * n; ctx.mask = act ? K.obs_mask[k] : 0; ctx.obs_nh = K.obs_nh; ctx.obs_c0 = K.obs_c0;
     ctx.goal_lo = K.goal_lo; ctx.goal_hi = K.goal_hi; ctx.boxmask = K.boxmask;
-    rs = RowState{K.rowstate, K.P.wl.nslot, K.N, act ? k : 0};
+    rs = RowState<rs_form<MODEL, BLK::ONE>()>{K.rowstate, K.P.wl.nslot, rs_stride<MODEL, BLK::ONE>(K.N), act ? k : 0};
 }
 struct RowScal { double kappa, omega, Delta; };
 template <int MODEL, class BLK, bool CLOSE = true, int NCH = 0>
@@ -2299,7 +2300,7 @@ __device__ __noinline__ StepOut step_phase_call(typename BLK::Args a, RowScal sc
     BLK K(a, gusto_dyn_lds);
     using C = typename BLK::C;
     RowCtx<MODEL> ctx;
-    RowState rs;
+    RowState<rs_form<MODEL, BLK::ONE>()> rs;
     make_row_ctx<MODEL>(K, k, act, sc.kappa, sc.omega, sc.Delta, ctx, rs);
 #ifdef GUSTO_PROFILE
     ctx.pf = pf; ctx.pfb = PF_S0;
@@ -2312,8 +2313,8 @@ __device__ __noinline__ StepOut step_phase_call(typename BLK::Args a, RowScal sc
 // row sums and the LQR stage cost QQ_k of this knot (before the workgroup reductions).  A function of its own for
 // MT::SWEEP_CALL models.
 struct ResidOut { double resp, resd, comp, numax; };
-template <int MODEL, class BLK, int NCH = 0>
-GD ResidOut resid_phase(BLK& K, const RowCtx<MODEL>& ctx, const RowState& rs, int k, bool act, double hdt, double wk,
+template <int MODEL, class BLK, int NCH = 0, class RS>
+GD ResidOut resid_phase(BLK& K, const RowCtx<MODEL>& ctx, const RS& rs, int k, bool act, double hdt, double wk,
                         double alpha_prev, const double* mug) {
     using T = MT<MODEL>;
     using R = Rec<MODEL>;
@@ -2366,7 +2367,7 @@ GD ResidOut resid_phase(BLK& K, const RowCtx<MODEL>& ctx, const RowState& rs, in
         constexpr int NP = (n <= 8 && T::NDEF == 0) ? T::NFIX + T::NHU : 0;
         RowPre<NP> pre;
         if constexpr (NP > 0) {
-            const int slot_u = T::NFIX + K.P.n_obs + 2 * n;
+            const int slot_u = RowSlots<MODEL>::ctl(K.P.n_obs);
             const bool upd = alpha_prev != 0.0;
             pre.load(rs, T::NFIX, slot_u, [&](int var) {
                 return var == RS_T || var == RS_LAM || var == RS_S || var == RS_LAMB ||
@@ -2374,7 +2375,7 @@ GD ResidOut resid_phase(BLK& K, const RowCtx<MODEL>& ctx, const RowState& rs, in
             });
         }
         constexpr bool LRTR = MODEL == GUSTO_ASTROBEE_SE3;   // (the manifold model has no trust region row)
-        OpResidHess<n, m, NP, LRTR> op{rs, Hx, Hu, rdx, rdu, gx0, gu0, alpha_prev, &pre};
+        OpResidHess<n, m, NP, LRTR, RS> op{rs, Hx, Hu, rdx, rdu, gx0, gu0, alpha_prev, &pre};
         ctx.tick(0);   // (profile builds: PF_R0.. = prologue | fixed rows | obstacle rows | control rows | stage cost)
 #if GUSTO_SEG_W2
         if constexpr (NCH > 0) {   // the knot's obstacle rows shared with the helper waves (segw.hpp)
@@ -2530,7 +2531,7 @@ __device__ __noinline__ ResidOut resid_phase_call(typename BLK::Args a, RowScal 
     BLK K(a, gusto_dyn_lds);
     using C = typename BLK::C;
     RowCtx<MODEL> ctx;
-    RowState rs;
+    RowState<rs_form<MODEL, BLK::ONE>()> rs;
     make_row_ctx<MODEL>(K, k, act, sc.kappa, sc.omega, sc.Delta, ctx, rs);
 #ifdef GUSTO_PROFILE
     ctx.pf = pf; ctx.pfb = PF_R0;
@@ -2576,7 +2577,8 @@ template <int MODEL, class BLK, int NCH = 0> GD void ipm_solve(BLK& K, double De
     ctx.P = &K.P; ctx.N = N; ctx.k = k; ctx.nslot = K.P.wl.nslot; ctx.kappa = kappa; ctx.omega = omega; ctx.Delta = Delta;
     ctx.xp = K.Xp + (act ? k : 0) * n; ctx.mask = act ? K.obs_mask[k] : 0; ctx.obs_nh = K.obs_nh; ctx.obs_c0 = K.obs_c0;
     ctx.goal_lo = K.goal_lo; ctx.goal_hi = K.goal_hi; ctx.boxmask = K.boxmask;
-    RowState rs{K.rowstate, K.P.wl.nslot, N, act ? k : 0};
+    using RS = RowState<rs_form<MODEL, BLK::ONE>()>;
+    RS rs{K.rowstate, K.P.wl.nslot, rs_stride<MODEL, BLK::ONE>(N), act ? k : 0};
     // The knot index is made opaque at every phase boundary: otherwise the compiler hoists each phase's address
     // arithmetic out of the interior point loop and its registers (hundreds) stay live across the sweeps.
 #define GUSTO_REFRESH_K()                                     \
@@ -2601,7 +2603,7 @@ template <int MODEL, class BLK, int NCH = 0> GD void ipm_solve(BLK& K, double De
         for (int i = 0; i < n; i++) { xs[i] = (k == 0) ? K.x_init[i] : K.Xp[k * n + i]; K.Xw[k * n + i] = xs[i]; K.nu[k * n + i] = 0; }
 #pragma unroll
         for (int i = 0; i < m; i++) { us[i] = K.Up[k * m + i]; K.Uw[k * m + i] = us[i]; }
-        OpInit op{rs, muw};
+        OpInit<RS> op{rs, muw};
         visit_rows<MODEL>(ctx, xs, us, op);
         ncomp_l = op.ncomp;
     }
@@ -2904,7 +2906,7 @@ template <int MODEL, class BLK, int NCH = 0> GD void ipm_solve(BLK& K, double De
         load_iter(xs, us);
 #pragma unroll
         for (int i = 0; i < m; i++) l_obj += ((i < m - T::NDEF) ? wk : TRAJOPT_DEFECT_REG * wk) * us[i] * us[i];
-        OpSlackSum op{rs};
+        OpSlackSum<RS> op{rs};
         visit_rows<MODEL>(ctx, xs, us, op);
         l_obj += op.sum;
     }

@@ -83,6 +83,18 @@ GD void lin_row(Op& op, int slot, int kind, const double* v, const double* b, do
     op.template row<ISU, I0, CNT, FX>(slot, kind, ev);
 }
 
+// Slot numbers of the rows of a knot: they name addresses of the row state (RowState) and nothing else -- the order in which
+// visit_rows walks and sums the rows does not depend on them.  RS_ROW: the rows every knot has come first, at compile-time slots
+// (the NFIX state rows, the NHU control rows, the 2n goal rows), the obstacle rows last at a constant + the obstacle index.  RS_EARLIER:
+// the obstacle rows sit behind the state rows and the goal and control rows follow at n_obs-dependent slots.
+template <int MODEL> struct RowSlots {
+    using T = MT<MODEL>;
+    static constexpr bool CT = T::RS_FORM != RS_EARLIER;
+    GD static int ctl(int n_obs) { return CT ? T::NFIX : T::NFIX + n_obs + 2 * T::n; }
+    GD static int goal(int n_obs) { return CT ? T::NFIX + T::NHU : T::NFIX + n_obs; }
+    GD static int obs(int n_obs) { return CT ? T::NFIX + T::NHU + 2 * T::n : T::NFIX; }
+};
+
 // ncsi_*_obstacle_avoidance_*_convexified (freeflyer_se2.jl:265-288): clearance - (d + nhat.(r - r0)), the rows of the obstacles in
 // `mk` (the knot's active set, or one wave's share of it: segw.hpp).
 // The rows of one knot are walked in batches of OBS_BATCH: every load of a batch (normal, offset AND the row state
@@ -93,7 +105,7 @@ GD void lin_row(Op& op, int slot, int kind, const double* v, const double* b, do
 template <int MODEL, class Op> GD void visit_obs_rows(const RowCtx<MODEL>& c, const double* xs, Op& op, uint64_t mk) {
     using T = MT<MODEL>;
     const double kw = c.kappa * c.omega;
-    const int slot_obs = T::NFIX;
+    const int slot_obs = RowSlots<MODEL>::obs(c.P->n_obs);
     while (mk) {
         int oi[OBS_BATCH], oslot[OBS_BATCH];
         bool ov[OBS_BATCH];
@@ -126,7 +138,7 @@ template <int MODEL, class Op> GD void visit_ctl_rows(const RowCtx<MODEL>& c, co
     constexpr int n = T::n;
     constexpr bool is2 = MODEL == GUSTO_FREEFLYER_SE2, FB = Op::FIX_BATCH;
     const gusto_model_params& mp = c.P->mp;
-    const int slot_u = T::NFIX + c.P->n_obs + 2 * n;
+    const int slot_u = RowSlots<MODEL>::ctl(c.P->n_obs);
     if (c.k < c.N - 1) {
         constexpr int nf = is2 ? 2 : 3, im = is2 ? 2 : 3, nm = is2 ? 1 : 3;
         double af[nf], am[nm];
@@ -153,7 +165,7 @@ template <int MODEL, class Op> GD void visit_rows(const RowCtx<MODEL>& c, const 
     constexpr int n = T::n;
     const gusto_model_params& mp = c.P->mp;
     const double kw = c.kappa * c.omega;
-    const int slot_obs = T::NFIX, slot_goal = T::NFIX + c.P->n_obs, slot_u = slot_goal + 2 * n;
+    const int slot_obs = RowSlots<MODEL>::obs(c.P->n_obs), slot_goal = RowSlots<MODEL>::goal(c.P->n_obs), slot_u = RowSlots<MODEL>::ctl(c.P->n_obs);
     double one[n];
 #pragma unroll
     for (int j = 0; j < n; j++) one[j] = 1.0;
@@ -346,12 +358,30 @@ template <int MODEL, class Op> GD void visit_rows(const RowCtx<MODEL>& c, const 
 }
 
 // ---- per-row state access --------------------------------------------------------------------------
-struct RowState {
+// RS_ROW: element (row slot, variable, knot) sits at base + (slot * RS_NVAR + var) * kp + k, kp = the padded knot stride (rs_stride).
+// An access is ONE uniform (scalar) base for the whole block + a per-lane 32-bit byte offset that points at the row's middle
+// variable + the distance of the variable from it: the SGPR-base + VGPR-offset + immediate form of global_load/store.
+//   compile-time stride (one-wave kernels; the slot of a row every knot has is a compile-time number too): the lane offset is
+//     k * 8 + a literal and the distance, (var - 4) * 512 bytes, within +-2 KB, is the instruction's immediate -- no scalar address
+//     per (variable, row) to compute, keep live across the pass and spill.
+//   run-time stride (the multi-wave kernels, TrajOpt): the RS_NVAR distances are scalars of the whole kernel; RS_ROW_LANE forms
+//     the whole offset in the lane instead.
+//   (32 bits: the block of the largest problem, 9 variables x ~110 slots x 256 knots, is 2 MB)
+// RS_EARLIER: base + (var * nslot + slot) * N + k, a scalar address per (variable, row) and the knot as lane index.
+// The form is a template parameter (common.hpp: rs_form): each kernel holds the code of its own form and nothing of the others.
+template <int FORM> struct RowState {
     GPtr<double> base;
-    int nslot, N, k;
-    // uniform (scalar) row base + per-lane knot index: lets the compiler use the SGPR-base + VGPR-offset form of
-    // global_load/store instead of materialising (and hoisting, and spilling) one 64-bit VGPR address per row
-    GD auto& at(int var, int slot) const { return (base + (size_t)(var * nslot + slot) * (size_t)N)[k]; }
+    int nslot, kp, k;
+    GD auto& at(int var, int slot) const {
+        if constexpr (FORM == RS_EARLIER) return (base + (size_t)(var * nslot + slot) * (size_t)kp)[k];
+        else {
+            typedef __attribute__((address_space(1))) char GC;
+            typedef __attribute__((address_space(1))) double GV;
+            const int mid = FORM == RS_ROW_LANE ? var : RS_NVAR / 2;
+            GC* r = (GC*)base.p + (size_t)(((unsigned)(slot * RS_NVAR + mid) * (unsigned)kp + (unsigned)k) * 8u);
+            return *(GV*)(r + (ptrdiff_t)((var - mid) * kp) * 8);
+        }
+    }
 };
 
 // State of the rows every knot has at compile-time positions (the NFIX state rows, then the NHU control rows; template
@@ -359,7 +389,7 @@ struct RowState {
 // the pass reaches it, behind the stores of the row before, and the pass pays one memory round trip per row.
 template <int NP> struct RowPre {
     double v[RS_NVAR][NP > 0 ? NP : 1];
-    template <class F> GD void load(const RowState& rs, int nfix, int slot_u, F&& want) {
+    template <class RS, class F> GD void load(const RS& rs, int nfix, int slot_u, F&& want) {
 #pragma unroll
         for (int var = 0; var < RS_NVAR; var++)
 #pragma unroll
@@ -372,7 +402,7 @@ template <int NP> struct RowPre {
 // id FX_OBS + q of a row = position q of the current batch.
 struct ObsPre {
     double v[RS_NVAR][OBS_BATCH];
-    template <class F> GD void load(const RowState& rs, const int* slot, F&& want) {
+    template <class RS, class F> GD void load(const RS& rs, const int* slot, F&& want) {
 #pragma unroll
         for (int var = 0; var < RS_NVAR; var++)
             if (want(var)) {
@@ -388,9 +418,9 @@ struct ObsPre {
 // Warm (the iterate starts at the optimum of the previous subproblem): every penalised row is put ON the central
 // path at muw for its value g at the start point:  s - t = g, t lam_a = s lam_b = muw, lam_a + lam_b = 1
 //   <=>  {s, t} = muw + (sqrt(g^2 + 4 muw^2) +- g) / 2;   hard rows get lam = muw / t.
-struct OpInit {
+template <class RS> struct OpInit {
     static constexpr bool FIX_BATCH = false;
-    RowState rs;
+    RS rs;
     double muw;
     int ncomp = 0;
     GD void obs_load(const int*) {}
@@ -422,9 +452,9 @@ struct OpInit {
 // saves the predictor its own pass over the rows.
 // LRTR: a row over ALL states (the trust region) is not added to H_x; its dyad sigma * grad grad^T and diagonal come back
 // as (trs, trg, trh) and resid_phase applies them to the stage cost in factored form.
-template <int n, int m, int NP, bool LRTR = false> struct OpResidHess {
+template <int n, int m, int NP, bool LRTR, class RS> struct OpResidHess {
     static constexpr bool FIX_BATCH = NP == 0;   // (visit_rows: the fixed rows through the obstacle batch buffer)
-    RowState rs;
+    RS rs;
     double *Hx, *Hu, *rdx, *rdu, *gx0, *gu0;
     double alpha_prev;  // 0 on the first trip
     const RowPre<NP>* pre;
@@ -521,9 +551,9 @@ struct StepFrac {
 // HDX: the pass also leaves hdx = H_x dx of this knot, H_x = sum over the state rows of sigma grad grad^T + lam hess -- the
 // condensed Hessian the residual pass put into the stage cost, applied to the step instead of stored (the adjoint costate
 // recursion of the 12/13-state kernels, ipm.hpp: adjoint_sweep_1w, needs H_x dx_k and nothing else of H_x).
-template <int NP, bool HDX = false> struct OpStep {
+template <int NP, bool HDX, class RS> struct OpStep {
     static constexpr bool FIX_BATCH = NP == 0;
-    RowState rs;
+    RS rs;
     const double *dxs, *dus;
     int pass;
     double mu_t, tau;
@@ -620,9 +650,9 @@ template <int NP, bool HDX = false> struct OpStep {
     }
 };
 
-struct OpSlackSum {
+template <class RS> struct OpSlackSum {
     static constexpr bool FIX_BATCH = false;
-    RowState rs;
+    RS rs;
     double sum = 0;
     GD void obs_load(const int*) {}
     template <bool ISU, int I0, int CNT, int FX> GD void row(int slot, int kind, const RowEv<CNT>&) {

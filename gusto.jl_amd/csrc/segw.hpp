@@ -398,7 +398,8 @@ template <int MODEL, int NCH> GD void segw_rows_resid_helper(Blk<MODEL, true>& B
     const bool act = k < B.N;
     const double alpha_prev = L[mb + 8], kappa = L[mb + 9], omega = L[mb + 10], Delta = L[mb + 11];
     RowCtx<MODEL> ctx;
-    RowState rs;
+    using RS = RowState<rs_form<MODEL, true>()>;
+    RS rs;
     make_row_ctx<MODEL>(B, k, act, kappa, omega, Delta, ctx, rs);
     double xs[n], Hx[NHX], Hu[1] = {0}, rdx[n], rdu[1] = {0}, gx0[n], gu0[1] = {0};
 #pragma unroll
@@ -406,7 +407,7 @@ template <int MODEL, int NCH> GD void segw_rows_resid_helper(Blk<MODEL, true>& B
 #pragma unroll
     for (int i = 0; i < NHX; i++) Hx[i] = 0;
     RowPre<0> pre;
-    OpResidHess<n, m, 0, false> op{rs, Hx, Hu, rdx, rdu, gx0, gu0, alpha_prev, &pre};
+    OpResidHess<n, m, 0, false, RS> op{rs, Hx, Hu, rdx, rdu, gx0, gu0, alpha_prev, &pre};
     visit_obs_rows<MODEL>(ctx, xs, op, ctx.mask & seg_obs_share(rank, nshare));
     const int o = sb + SB::sPG2(hi) + k;
     L[o] = op.comp; L[o + 64] = op.maxrp;
@@ -450,7 +451,8 @@ template <int MODEL, int NCH> GD void segw_rows_step_helper(Blk<MODEL, true>& B,
     const int pass = (int)L[mb + 8];
     const double kappa = L[mb + 9], omega = L[mb + 10], Delta = L[mb + 11], mu_t = L[mb + 12], tau = L[mb + 13];
     RowCtx<MODEL> ctx;
-    RowState rs;
+    using RS = RowState<rs_form<MODEL, true>()>;
+    RS rs;
     make_row_ctx<MODEL>(B, k, act, kappa, omega, Delta, ctx, rs);
     double xs[n], dxs[n], dus[1] = {0}, gAx[n], gBx[n], gAu[1] = {0}, gBu[1] = {0};
 #pragma unroll
@@ -458,7 +460,7 @@ template <int MODEL, int NCH> GD void segw_rows_step_helper(Blk<MODEL, true>& B,
 #pragma unroll
     for (int i = 0; i < WS; i++) dxs[i] = act ? B.dXs[k * n + i] : 0.0;   // (the main wave's step phase has stored the primal step)
     RowPre<0> pre;
-    OpStep<0, false> op{rs, dxs, dus, pass, mu_t, tau, gAx, gAu, gBx, gBu, &pre, nullptr};
+    OpStep<0, false, RS> op{rs, dxs, dus, pass, mu_t, tau, gAx, gAu, gBx, gBu, &pre, nullptr};
     visit_obs_rows<MODEL>(ctx, xs, op, ctx.mask & seg_obs_share(rank, nshare));
     const int o = sb + SB::sPG2(hi) + k;
     L[o] = op.amax.an; L[o + 64] = op.amax.ad; L[o + 128] = op.c0; L[o + 192] = op.c1; L[o + 256] = op.c2;

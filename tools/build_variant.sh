@@ -14,9 +14,9 @@ EOS
 for i in 0 1 2 3 4 5 6; do [ $i != $M ] && echo "STUB($i)" >> $W/stub.hip; done
 /opt/rocm/bin/hipcc $F -c $D/csrc/gusto_hip.hip -o $W/gusto_hip.o &
 /opt/rocm/bin/hipcc $F -c $W/stub.hip -o $W/stub.o &
-/opt/rocm/bin/hipcc $F -c $D/csrc/shoot.hip -o $W/shoot.o &
+for u in shoot verify tvlqr simulate lincov; do /opt/rocm/bin/hipcc $F -c $D/csrc/$u.hip -o $W/$u.o & done   # (the C ABI loads as a whole)
 /opt/rocm/bin/hipcc $F -c $D/csrc/model_$M.hip -o $W/model_$M.o -Rpass-analysis=kernel-resource-usage > $W/model.log 2>&1 || { grep -B2 -A6 "error" $W/model.log | head -40; echo "FAILED"; wait; exit 1; }
 grep -A9 "Function Name: .*scp_kernel" $W/model.log | grep -E "Name|VGPRs:|AGPRs|Scratch|Occupancy" | head -12 || true
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $W/gusto_hip.o $W/shoot.o $W/stub.o $W/model_$M.o -o $V/$NAME.so
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $W/gusto_hip.o $W/shoot.o $W/verify.o $W/tvlqr.o $W/simulate.o $W/lincov.o $W/stub.o $W/model_$M.o -o $V/$NAME.so
 echo "built $V/$NAME.so (model $M, flags: $@)"
