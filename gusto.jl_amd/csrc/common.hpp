@@ -40,6 +40,11 @@ constexpr int RS_T = 0, RS_LAM = 1, RS_LAMB = 2, RS_S = 3, RS_DT = 4, RS_DL = 5,
 #ifndef GUSTO_TO4_SWEEP_CALL
 #define GUSTO_TO4_SWEEP_CALL true   // ... of the freeflyer TrajOpt kernel (B = 1024: 58.3 -> 53.4 ms; the same schedule, results within 1e-9: contraction differs across the call)
 #endif
+#ifndef GUSTO_SWEEP_DPP
+// the one-wave vector sweeps of freeflyerSE2 on v_fmac_f64_dpp row_newbcast with row swaps between the rows of 16 lanes
+// (ipm.hpp: backward_sweep_dpp); -DGUSTO_SWEEP_DPP=0: the v_readlane sweeps (A/B measurements).  Bit-identical either way.
+#define GUSTO_SWEEP_DPP 1
+#endif
 #ifndef GUSTO_USE_MFMA
 #define GUSTO_USE_MFMA true   // -DGUSTO_USE_MFMA=false: the VALU two-step contraction instead (A/B measurements)
 #endif
@@ -63,6 +68,7 @@ template <> struct MT<GUSTO_FREEFLYER_SE2> {
     static constexpr int WAVES_PER_EU = GUSTO_WAVES_PER_EU;   // register budget of the one-wave kernel: 512 / this
     static constexpr int RS_FORM = RS_ROW;   // layout and addressing of the row state, see RS_EARLIER .. RS_ROW_LANE above
     static constexpr bool SWEEP_CALL = false;   // factor sweep as a function call (ipm.hpp:factor_sweep)
+    static constexpr bool SWEEP_DPP = GUSTO_SWEEP_DPP;   // one-wave vector sweeps on the fp64 DPP broadcast (ipm.hpp:backward_sweep_dpp; needs n = 6, PG2)
     static constexpr bool MFMA = false;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 2;   // default number of one-trip probing slices of the longest-first scheduler
     static constexpr int SCHED_SLICE = 4;   // then slices of 4 trips for problems of penalty level 0 (34.1 vs 34.65 ms; the 12/13-state models lose with any)
@@ -88,6 +94,7 @@ template <> struct MT<GUSTO_DUBINS_CAR> {
     static constexpr int WAVES_PER_EU = GUSTO_DUBINS_WAVES;   // register budget of the one-wave kernel: 512 / this
     static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_CALL = false;   // factor sweep as a function call (ipm.hpp:factor_sweep)
+    static constexpr bool SWEEP_DPP = false;
     static constexpr bool MFMA = false;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (short problems: 2 slices cost more than they order -- 316 vs 211 ms at B = 65 536)
     static constexpr bool LTI = false, HAS_OBS = false;
@@ -106,6 +113,7 @@ template <> struct MT<GUSTO_ASTROBEE_SE3> {
     static constexpr int WAVES_PER_EU = 1;   // register budget of the one-wave kernel: 512 / this
     static constexpr int RS_FORM = RS_ROW_LANE;   // (lane form: the only one that adds nothing to the scratch of its multi-wave kernel)
     static constexpr bool SWEEP_CALL = true;   // factor sweep as a function call (ipm.hpp:factor_sweep)
+    static constexpr bool SWEEP_DPP = false;
     static constexpr bool MFMA = GUSTO_USE_MFMA;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (measured with raised-penalty problems ahead of fresh ones: 123.0 / 127.1 / 132.7 ms for 1 / 2 / 3 slices)
     static constexpr bool LTI = false, HAS_OBS = true;
@@ -129,6 +137,7 @@ template <> struct MT<GUSTO_ASTROBEE_SE3_MANIFOLD> {
     static constexpr int WAVES_PER_EU = 1;   // register budget of the one-wave kernel: 512 / this
     static constexpr int RS_FORM = RS_EARLIER;   // (config 5 measured 0.9 % slower with RS_ROW: profiles/r07_rowstate_layout.txt)
     static constexpr bool SWEEP_CALL = true ;   // factor sweep as a function call (ipm.hpp:factor_sweep)
+    static constexpr bool SWEEP_DPP = false;
     static constexpr bool MFMA = GUSTO_USE_MFMA;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (130.1 / 133.7 / 130.9 ms for 1 / 2 / 3 slices)
     static constexpr bool LTI = false, HAS_OBS = true;
@@ -150,6 +159,7 @@ template <> struct MT<GUSTO_TO_FREEFLYER_SE2> {
     static constexpr int NDEF = 6, n = 6, m = 3 + NDEF, WS = 2, NFIX = 3, NHU = 2 + 2 * NDEF;
     static constexpr int WAVES_PER_EU = 1, SCHED_PROBE = 0, SCHED_SLICE = 0;
     static constexpr int RS_FORM = RS_ROW;
+    static constexpr bool SWEEP_DPP = false;
     static constexpr bool SWEEP_CALL = GUSTO_TO4_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }
@@ -164,6 +174,7 @@ template <> struct MT<GUSTO_TO_ASTROBEE_SE3> {
     static constexpr int NDEF = 12, n = 12, m = 6 + NDEF, WS = 3, NFIX = 3, NHU = 2 + 2 * NDEF;
     static constexpr int WAVES_PER_EU = 1, SCHED_PROBE = 0, SCHED_SLICE = 0;
     static constexpr int RS_FORM = RS_ROW;
+    static constexpr bool SWEEP_DPP = false;
     static constexpr bool SWEEP_CALL = GUSTO_TO_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }
@@ -180,6 +191,7 @@ template <> struct MT<GUSTO_TO_ASTROBEE_SE3_MANIFOLD> {
     static constexpr int NDEF = 13, n = 13, m = 6 + NDEF, WS = 3, NFIX = 5, NHU = 2 + 2 * NDEF;
     static constexpr int WAVES_PER_EU = 1, SCHED_PROBE = 0, SCHED_SLICE = 0;
     static constexpr int RS_FORM = RS_ROW;
+    static constexpr bool SWEEP_DPP = false;
     static constexpr bool SWEEP_CALL = GUSTO_TO_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }

@@ -1422,12 +1422,177 @@ template <class BLKA> GD void forward_sweep_1w(BLKA K) {
     K.sync();
 }
 
-// (Round 4 tried the vector sweeps on the fp64 DPP broadcast gfx950 has -- `v_fmac_f64_dpp ... row_newbcast:L`, the n-vector
-// replicated in every row of 16 lanes -- instead of 2 n v_readlane per step.  In isolation a step of n = 6 is 67 cycles against
-// 136 (tools/ub/dpp.hip), but the sweep then forms its column of Phicl per knot and lane instead of once per ten knots by groups
-// of lanes: bit-identical and 35.9 ms against 34.1 ms per config-2 batch.  The variant without per-knot operands,
-// Phi^T p - K^T (Gam^T p), is as fast as the readlane sweep and numerically worse -- it subtracts two large terms that
-// Phi - Gam K cancels entry by entry first: 1.5 % more interior point iterations, lock-step tolerances missed.  Neither kept.)
+// The vector sweeps of the double integrator (n = 6, operands rebuilt from K: LdsC::PHI_FROM_K) on the fp64 DPP broadcast gfx950
+// has, `v_fmac_f64_dpp ... row_newbcast:L` (every lane of a row of 16 multiplies by lane L of ITS row), instead of 2 n v_readlane
+// per step: in isolation a step is 6 dependent fmac_dpp, 64 cycles against 128 (tools/ub/dpp.hip).  A row holds TWO knot groups,
+// A = lanes 0..5 and B = lanes 8..13 (lanes 6, 7, 14, 15 idle on clamped operands): group B takes the vector of the knot before from
+// group A's lanes (L = 0..5) and group A from group B's (L = 8..13), no transfer instruction at all.  After B's step the vector hops
+// to the B lanes of the next row by one row swap per dword (v_permlane16_swap / v_permlane32_swap, row_hop); the rows take their
+// turns in the order 0, 1, 3, 2 -- each of the four hops, the wrap 2 -> 0 at the end of the chunk included, is one of the two
+// halves of one swap.  Four rows are 8 groups: a chunk is 8 knots, and as in the readlane sweep lane i of a group forms ITS column
+// (row) of Phicl = Phi - Gam K for the group's knot ONCE PER CHUNK, the next chunk's K read from LDS while this one runs.  Every lane
+// executes every step; only the group whose turn it is computes on the right vector, the others on stale ones whose results
+// nobody reads: the chain register takes the sum unconditionally and the value a group stores is selected OFF the chain.
+// Same sums in the same order as backward_sweep_1w / forward_sweep_1w (acc = q, acc = fma(p_l, col_l, acc), l = 0..5): bit-identical.
+// (Round 4 built the sweep with the vector REPLICATED in every row, which needs no hops but has every lane form its column per
+// knot -- 3 LDS reads, 6 FMAs and the right-hand side, ~29 cycles per knot on top of a 67-cycle step: bit-identical and 35.9 ms
+// against 34.1 ms.  The variant without per-knot operands, Phi^T p - K^T (Gam^T p), subtracts two large terms that Phi - Gam K
+// cancels entry by entry first: 1.5 % more interior point iterations, lock-step tolerances missed.  Numbers of this version:
+// profiles/r08_dpp_sweeps.txt.)
+// HOP 0: row 0 -> 1, 1: row 1 -> 3, 2: row 3 -> 2, 3: row 2 -> 0.  x is the vector, g any value that is dead (the vector of the
+// step before): the rows that are not a target keep what g held, so no copy of x is made.
+template <int HOP> GD double row_hop(double x, double g) {
+    const unsigned long long ux = __builtin_bit_cast(unsigned long long, x), ug = __builtin_bit_cast(unsigned long long, g);
+    const unsigned xl = (unsigned)ux, xh = (unsigned)(ux >> 32), gl = (unsigned)ug, gh = (unsigned)(ug >> 32);
+    unsigned lo, hi;
+    if constexpr (HOP == 0) { lo = __builtin_amdgcn_permlane16_swap(gl, xl, false, false)[0]; hi = __builtin_amdgcn_permlane16_swap(gh, xh, false, false)[0]; }
+    if constexpr (HOP == 1) { lo = __builtin_amdgcn_permlane32_swap(gl, xl, false, false)[0]; hi = __builtin_amdgcn_permlane32_swap(gh, xh, false, false)[0]; }
+    if constexpr (HOP == 2) { lo = __builtin_amdgcn_permlane16_swap(xl, gl, false, false)[1]; hi = __builtin_amdgcn_permlane16_swap(xh, gh, false, false)[1]; }
+    if constexpr (HOP == 3) { lo = __builtin_amdgcn_permlane32_swap(xl, gl, false, false)[1]; hi = __builtin_amdgcn_permlane32_swap(xh, gh, false, false)[1]; }
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+// q + sum_l p[lane 8 HALF + l of the row] c[l], l = 0..5 in this order.  (One asm block: the fp64 DPP form has no builtin, and the
+// 2 wait states between the VALU write of p -- the step before, or the hop -- and its first DPP read are the s_nop in the string.)
+template <int HALF> GD double dpp_step6(double p, double q, const double* c) {
+    double acc = q;
+    if constexpr (HALF == 0)
+        asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\tv_fmac_f64_dpp %0, %1, %3 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f64_dpp %0, %1, %4 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\tv_fmac_f64_dpp %0, %1, %5 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f64_dpp %0, %1, %6 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\tv_fmac_f64_dpp %0, %1, %7 row_newbcast:5 row_mask:0xf bank_mask:0xf"
+            : "+v"(acc) : "v"(p), "v"(c[0]), "v"(c[1]), "v"(c[2]), "v"(c[3]), "v"(c[4]), "v"(c[5]));
+    else
+        asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\tv_fmac_f64_dpp %0, %1, %3 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f64_dpp %0, %1, %4 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\tv_fmac_f64_dpp %0, %1, %5 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f64_dpp %0, %1, %6 row_newbcast:12 row_mask:0xf bank_mask:0xf\n\tv_fmac_f64_dpp %0, %1, %7 row_newbcast:13 row_mask:0xf bank_mask:0xf"
+            : "+v"(acc) : "v"(p), "v"(c[0]), "v"(c[1]), "v"(c[2]), "v"(c[3]), "v"(c[4]), "v"(c[5]));
+    return acc;
+}
+// one chunk of up to 8 steps: step gs is group gs's (2 turn + half), from the vector group gs - 1 left -- group 7 of the chunk before
+// at gs = 0.  `live(gs)` is wave-uniform: the steps past the end of the sweep are not executed.
+template <class LIVE> GD void dpp_chunk(double& p, double& keep, double q, const double* c, int g, LIVE live) {
+    static_for<0, 8>([&](auto GS) {
+        constexpr int gs = decltype(GS)::value;
+        if (live(gs)) {
+            const double acc = dpp_step6<(gs & 1) ? 0 : 1>(p, q, c);
+            keep = (g == gs) ? acc : keep;
+            if constexpr (gs & 1) p = row_hop<gs / 2>(acc, p); else p = acc;
+        }
+    });
+}
+// pt_{k-1} = Phicl_k^T pt_k + q_k, k = N-1..1 (see backward_sweep_1w, whose operand formation and order of loads and stores this keeps)
+template <class BLKA> GD void backward_sweep_dpp(BLKA K) {
+    using BLK = std::remove_cv_t<std::remove_reference_t<BLKA>>;
+    constexpr int n = BLK::n, m = BLK::m, C = 8;
+    static_assert(n == 6 && BLK::C::PHI_FROM_K, "two groups of 6 lanes per row, operands from K");
+    const int tid = K.tid, N = K.N;
+    const int row = tid >> 4, j = tid & 15;
+    const bool act = (j & 7) < n;
+    const int g = 2 * (row ^ (row >> 1)) + (j >> 3), i = act ? (j & 7) : 0;   // (turn of the rows 0, 1, 3, 2: 0, 1, 2, 3)
+    double gl[n];
+    auto phi_e = [&](int r_, int c_) { return (r_ == c_) ? 1.0 : ((c_ == r_ + n / 2) ? K.dt : 0.0); };
+    {
+        double Bd[n * m];
+        Dyn<BLK::MODEL_ID>::B(*K.mpp, Bd);
+        const double h = 0.5 * K.dt;
+#pragma unroll
+        for (int l = 0; l < n; l++) {
+            const int c_ = l % m;
+            const double hb = h * Bd[(c_ + n / 2) * m + c_];
+            gl[l] = (l < n / 2) ? 2.0 * (h * hb) : 2.0 * hb;
+        }
+    }
+    double phc[n];   // column i of Phi
+#pragma unroll
+    for (int l = 0; l < n; l++) phc[l] = phi_e(l, i);
+    double col[n], kc[m], qv, qvn, p, keep = 0.0;
+    // the operands of a chunk in two halves: the LDS reads (clamped, unconditional: always loadable) are issued a whole chunk
+    // ahead, the FMAs that form the column from them come behind the chunk's steps -- in front of them they waited out the LDS
+    // round trip once per chunk
+    auto load = [&](int k0, double& q) {
+        const int kk = (k0 - g >= 1) ? k0 - g : 1;
+#pragma unroll
+        for (int a = 0; a < m; a++) kc[a] = K.kdl[kk * BLK::C::KDS + a * n + i];
+        q = K.pv[kk * n + i];
+    };
+    auto form = [&]() {
+#pragma unroll
+        for (int l = 0; l < n; l++) col[l] = phc[l] - gl[l] * kc[l % m];
+    };
+    load(N - 1, qv);
+    form();
+    p = K.rv[(N - 1) * n + i];          // every group starts from pt_{N-1}; step 0 reads the B lanes of row 0
+    K.sync();
+    if (tid < n) K.pv[(N - 1) * n + tid] = p;
+    for (int k0 = N - 1; k0 >= 1; k0 -= C) {
+        load(k0 - C, qvn);
+        if (k0 - (C - 1) >= 1) dpp_chunk(p, keep, qv, col, g, [](int) { return true; });   // (a whole chunk: no branch per step)
+        else dpp_chunk(p, keep, qv, col, g, [&](int gs) { return k0 - gs >= 1; });
+        {   // group g produced pt_{kk-1}, kk = k0 - g
+            const int kk = k0 - g;
+            if (act && kk >= 1) K.pv[(kk - 1) * n + i] = keep;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        form();
+        qv = qvn;
+    }
+    K.sync();
+}
+// dy_k = Phicl_k dy_{k-1} + ct_k, k = 0..N-1, dy_{-1} = 0 (see forward_sweep_1w)
+template <class BLKA> GD void forward_sweep_dpp(BLKA K) {
+    using BLK = std::remove_cv_t<std::remove_reference_t<BLKA>>;
+    constexpr int n = BLK::n, m = BLK::m, C = 8;
+    static_assert(n == 6 && BLK::C::PHI_FROM_K, "two groups of 6 lanes per row, operands from K");
+    const int tid = K.tid, N = K.N;
+    const int row = tid >> 4, j = tid & 15;
+    const bool act = (j & 7) < n;
+    const int g = 2 * (row ^ (row >> 1)) + (j >> 3), i = act ? (j & 7) : 0;   // (see backward_sweep_dpp)
+    double gi = 0.0;
+    auto phi_e = [&](int r_, int c_) { return (r_ == c_) ? 1.0 : ((c_ == r_ + n / 2) ? K.dt : 0.0); };
+    {
+        double Bd[n * m];
+        Dyn<BLK::MODEL_ID>::B(*K.mpp, Bd);
+        const double h = 0.5 * K.dt;
+#pragma unroll
+        for (int l = 0; l < n; l++) {   // Gam[i][i mod m] of this lane's row
+            const int c_ = l % m;
+            const double hb = h * Bd[(c_ + n / 2) * m + c_];
+            const double gv = (l < n / 2) ? 2.0 * (h * hb) : 2.0 * hb;
+            gi = (i == l) ? gv : gi;
+        }
+    }
+    double phr[n];   // row i of Phi
+#pragma unroll
+    for (int l = 0; l < n; l++) phr[l] = phi_e(i, l);
+    double rw[n], kr[n], cv, cvn, p = 0.0, keep = 0.0;
+    auto load = [&](int k0, double& c) {   // (see backward_sweep_dpp)
+        const int kk = (k0 + g < N) ? k0 + g : N - 1;
+        const int ic = (i < m) ? i : i - m;
+#pragma unroll
+        for (int l = 0; l < n; l++) kr[l] = K.kdl[kk * BLK::C::KDS + ic * n + l];
+        c = K.dY[kk * n + i];
+    };
+    auto form = [&]() {
+#pragma unroll
+        for (int l = 0; l < n; l++) rw[l] = phr[l] - gi * kr[l];
+    };
+    load(0, cv);
+    form();
+    K.sync();
+    for (int k0 = 0; k0 < N; k0 += C) {
+        load(k0 + C, cvn);
+        if (k0 + C - 1 < N) dpp_chunk(p, keep, cv, rw, g, [](int) { return true; });
+        else dpp_chunk(p, keep, cv, rw, g, [&](int gs) { return k0 + gs < N; });
+        {
+            const int kk = k0 + g;
+            if (act && kk < N) K.dY[kk * n + i] = keep;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        form();
+        cv = cvn;
+    }
+    K.sync();
+}
+
 // nu_{k+1} = P_k dy_k + p_k + Pi_k mu_g of every knot (the new costates of the corrector), for the 12/13-state models by
 // groups of n lanes: lane i of group g forms row i for knot k0 + g from ITS rows of the P_k and Pi_k records (stored transposed:
 // the lanes of a group read consecutive doubles), the next chunk's rows in flight while this one is summed.  A load
@@ -1637,12 +1802,14 @@ template <int MODEL, class BLK> GD void backward_sweep(BLK& K) {
     if constexpr (!BLK::ONE && MT<MODEL>::SWEEP_CALL && MT<MODEL>::NDEF > 0) backward_sweep_mw_call<BLK>(K.args());
     else if constexpr (!BLK::ONE) backward_sweep_mw(K);
     else if constexpr (MT<MODEL>::SWEEP_CALL) backward_sweep_1w_call<MODEL>(K.args());
+    else if constexpr (MT<MODEL>::SWEEP_DPP) backward_sweep_dpp(SweepView<MODEL>::make(K));
     else backward_sweep_1w(SweepView<MODEL>::make(K));
 }
 template <int MODEL, class BLK> GD void forward_sweep(BLK& K) {
     if constexpr (!BLK::ONE && MT<MODEL>::SWEEP_CALL && MT<MODEL>::NDEF > 0) forward_sweep_mw_call<BLK>(K.args());
     else if constexpr (!BLK::ONE) forward_sweep_mw(K);
     else if constexpr (MT<MODEL>::SWEEP_CALL) forward_sweep_1w_call<MODEL>(K.args());
+    else if constexpr (MT<MODEL>::SWEEP_DPP) forward_sweep_dpp(SweepView<MODEL>::make(K));
     else forward_sweep_1w(SweepView<MODEL>::make(K));
 }
 

@@ -35,3 +35,7 @@ print("phase: share, cycles per IPM iteration")
 for i, nm in enumerate(names):
     print(f"  {nm:7s} {100*tot[i]/tot.sum():5.1f}%  {tot[i]/ipm:9.0f}")
 print("total cycles/ipm-iter", tot.sum()/ipm, " mean cycles per problem", tot.sum()/B)
+# the problem with the most KKT solves (the chain that bounds a balanced batch): its phases per KKT solve and its total
+j = int(np.argmax(st["ipm_iters"])); nj = int(st["ipm_iters"][j])
+print(f"longest problem {j}: {nj} KKT solves, {prof[j].sum()} cycles, {prof[j].sum() / nj:.0f} per KKT solve; " +
+      " ".join(f"{names[i]} {prof[j, i] / nj:.0f}" for i in (0, 2, 4, 5, 7, 8)))
