@@ -45,6 +45,22 @@ constexpr int RS_T = 0, RS_LAM = 1, RS_LAMB = 2, RS_S = 3, RS_DT = 4, RS_DL = 5,
 // (ipm.hpp: backward_sweep_dpp); -DGUSTO_SWEEP_DPP=0: the v_readlane sweeps (A/B measurements).  Bit-identical either way.
 #define GUSTO_SWEEP_DPP 1
 #endif
+#ifndef GUSTO_FACTOR_LDS
+// the factor stage of freeflyerSE2 (factor1w.hpp: factor_sweep_pg2) with fewer LDS instructions: one stream for r_k = P_k c_k and
+// Pi_k^T c_k (_MV) and operand rows laid out for 128-bit reads (_ROWS); H_uu to the Cholesky by broadcast reads instead of
+// v_readlane (_HUU) is built but off, it measured no gain of its own.  -DGUSTO_FACTOR_LDS=0: the stage as it was (A/B
+// measurements); the sub-switches take one item out or put _HUU in.  Bit-identical either way.
+#define GUSTO_FACTOR_LDS 1
+#endif
+#ifndef GUSTO_FACTOR_LDS_MV
+#define GUSTO_FACTOR_LDS_MV 1
+#endif
+#ifndef GUSTO_FACTOR_LDS_HUU
+#define GUSTO_FACTOR_LDS_HUU 0   // (built and bit-identical, but no measured gain on top of the other two: profiles/r09_factor_stage_lds.txt, section 2)
+#endif
+#ifndef GUSTO_FACTOR_LDS_ROWS
+#define GUSTO_FACTOR_LDS_ROWS 1
+#endif
 #ifndef GUSTO_USE_MFMA
 #define GUSTO_USE_MFMA true   // -DGUSTO_USE_MFMA=false: the VALU two-step contraction instead (A/B measurements)
 #endif
@@ -69,6 +85,7 @@ template <> struct MT<GUSTO_FREEFLYER_SE2> {
     static constexpr int RS_FORM = RS_ROW;   // layout and addressing of the row state, see RS_EARLIER .. RS_ROW_LANE above
     static constexpr bool SWEEP_CALL = false;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool SWEEP_DPP = GUSTO_SWEEP_DPP;   // one-wave vector sweeps on the fp64 DPP broadcast (ipm.hpp:backward_sweep_dpp; needs n = 6, PG2)
+    static constexpr bool FACTOR_LDS = GUSTO_FACTOR_LDS;   // factor stage laid out for one-address LDS reads (factor1w.hpp:factor_sweep_pg2; needs n = 6, m = 3, PG2)
     static constexpr bool MFMA = false;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 2;   // default number of one-trip probing slices of the longest-first scheduler
     static constexpr int SCHED_SLICE = 4;   // then slices of 4 trips for problems of penalty level 0 (34.1 vs 34.65 ms; the 12/13-state models lose with any)
@@ -95,6 +112,7 @@ template <> struct MT<GUSTO_DUBINS_CAR> {
     static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_CALL = false;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool SWEEP_DPP = false;
+    static constexpr bool FACTOR_LDS = false;
     static constexpr bool MFMA = false;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (short problems: 2 slices cost more than they order -- 316 vs 211 ms at B = 65 536)
     static constexpr bool LTI = false, HAS_OBS = false;
@@ -114,6 +132,7 @@ template <> struct MT<GUSTO_ASTROBEE_SE3> {
     static constexpr int RS_FORM = RS_ROW_LANE;   // (lane form: the only one that adds nothing to the scratch of its multi-wave kernel)
     static constexpr bool SWEEP_CALL = true;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool SWEEP_DPP = false;
+    static constexpr bool FACTOR_LDS = false;
     static constexpr bool MFMA = GUSTO_USE_MFMA;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (measured with raised-penalty problems ahead of fresh ones: 123.0 / 127.1 / 132.7 ms for 1 / 2 / 3 slices)
     static constexpr bool LTI = false, HAS_OBS = true;
@@ -138,6 +157,7 @@ template <> struct MT<GUSTO_ASTROBEE_SE3_MANIFOLD> {
     static constexpr int RS_FORM = RS_EARLIER;   // (config 5 measured 0.9 % slower with RS_ROW: profiles/r07_rowstate_layout.txt)
     static constexpr bool SWEEP_CALL = true ;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool SWEEP_DPP = false;
+    static constexpr bool FACTOR_LDS = false;
     static constexpr bool MFMA = GUSTO_USE_MFMA;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (130.1 / 133.7 / 130.9 ms for 1 / 2 / 3 slices)
     static constexpr bool LTI = false, HAS_OBS = true;
@@ -160,6 +180,7 @@ template <> struct MT<GUSTO_TO_FREEFLYER_SE2> {
     static constexpr int WAVES_PER_EU = 1, SCHED_PROBE = 0, SCHED_SLICE = 0;
     static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_DPP = false;
+    static constexpr bool FACTOR_LDS = false;
     static constexpr bool SWEEP_CALL = GUSTO_TO4_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }
@@ -175,6 +196,7 @@ template <> struct MT<GUSTO_TO_ASTROBEE_SE3> {
     static constexpr int WAVES_PER_EU = 1, SCHED_PROBE = 0, SCHED_SLICE = 0;
     static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_DPP = false;
+    static constexpr bool FACTOR_LDS = false;
     static constexpr bool SWEEP_CALL = GUSTO_TO_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }
@@ -192,6 +214,7 @@ template <> struct MT<GUSTO_TO_ASTROBEE_SE3_MANIFOLD> {
     static constexpr int WAVES_PER_EU = 1, SCHED_PROBE = 0, SCHED_SLICE = 0;
     static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_DPP = false;
+    static constexpr bool FACTOR_LDS = false;
     static constexpr bool SWEEP_CALL = GUSTO_TO_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }

@@ -497,6 +497,21 @@ template <int MODEL> GD void factor_sweep_1w(SweepView<MODEL> K, double* fail, P
 // ds_read_b128) and read by ROWS for r_k = P c (P is exactly symmetric), Pi is kept transposed (the column for Pi^T c is a
 // row), only the upper triangle of H is written, and what a lane reads back from itself (its entry of Gd, its entry of Z)
 // stays in a register.
+// MT::FACTOR_LDS (freeflyerSE2; -DGUSTO_FACTOR_LDS=0 and its sub-switches, common.hpp: the stage without it, A/B measurements)
+// takes the two-address reads and a duplicated stream out of the stage -- same sums in the same order:
+//   _MV    the rows of the transposed Pi carry P's column interleave too, and r_k = P_k c_k (lanes 0 .. n-1) and Pi_k^T c_k (lanes
+//          8 .. 8+n-1) are ONE stream of 3 row reads, 3 reads of c_k, n FMAs and one store, issued where Pi_k (tail) and P_k
+//          (until L[wP]) are both in place; the pair of Pi a lane of Z needs is adjacent: one 128-bit read
+//   _ROWS  the rows of H sit at the even stride NZ + 1 (rows 0 .. n-1 only: H_uu is not read from there) and Z_u is stored
+//          transposed in rows of four doubles (Z_y nowhere: its only reader is the lane that formed it), so the m = 3 operands a
+//          lane needs from H_yu and from Z_u are one 128-bit and one 64-bit read each
+//   _HUU   (OFF by default) the six lanes of the upper triangle of H_uu store it packed (six doubles of the T buffer behind the
+//          dummy slots) and every lane fetches it for the Cholesky with three broadcast 128-bit reads instead of 12 v_readlane_b32.
+//          The store -> read round trip sits on the critical chain h -> chol and nothing arithmetic covers it: hipcc hoists the
+//          FMAs of the goal chain's tail in front of the store of h, so only the issue slots of the LDS instructions behind it
+//          (the tail's stores, the head's reads, about 150 cycles) run inside it.  Bit-identical, and measured as no gain on top
+//          of the other two (profiles/r09_factor_stage_lds.txt, section 2), so S = H_uu still comes by v_readlane.
+// All of it stays inside the LDS words this sweep alone uses (the H, Z and T buffers of LdsC): no offset of LdsC moves.
 template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, Prof& pf) {
     using T = MT<MODEL>;
     using R = Rec<MODEL>;
@@ -506,11 +521,20 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
     static_assert(T::PG2 && T::LTI && C::KD_LDS && NQ <= 64 && NZN <= 64 && NN <= 64 && n >= 2 * m, "shape");
     static_assert(T::pg_r1(0) == T::pg_r0(0) + h3 && T::pg_r1(n) == T::pg_r0(n) + h3 && T::pg_r1(n - 1) == T::pg_r0(n - 1) + h3, "PG2 row pairs");
     static_assert(NH + NN < R::SNN && !C::BIG, "P | Pi record, dummy slot");
+    // MT::FACTOR_LDS, item by item (common.hpp: GUSTO_FACTOR_LDS*; all off: the stage as it was, instruction for instruction)
+    constexpr bool F_MV = T::FACTOR_LDS && GUSTO_FACTOR_LDS_MV, F_HUU = T::FACTOR_LDS && GUSTO_FACTOR_LDS_HUU,
+                   F_ROWS = T::FACTOR_LDS && GUSTO_FACTOR_LDS_ROWS;
+    static_assert(!(F_MV || F_HUU || F_ROWS) || (n == 6 && m == 3), "FACTOR_LDS: rows of three 128-bit reads, m = 2 + 1");
+    // F_MV reads the pair (z0, z0 + n/2) of a row of Pi^T at the interleaved positions 2 z0, 2 z0 + 1: every column's first
+    // structural row must lie in the upper half, its second n/2 below it
+    constexpr bool PG_UPPER = [] { for (int c = 0; c < NZ; c++) if (!(T::pg_r0(c) < h3 && T::pg_r1(c) == T::pg_r0(c) + h3)) return false; return true; }();
+    static_assert(!F_MV || PG_UPPER, "F_MV: pg_r0(c) < n/2 and pg_r1(c) = pg_r0(c) + n/2 for every column of [Phi Gam]");
     const int tid = K.tid, N = K.N;
     // ---- lane roles ----
     const int ijh = K.lut[tid < NQ ? tid : 0], hc = ijh >> 8, hj = ijh & 255, i0 = T::pg_r0(hc), j0 = T::pg_r0(hj);   // H[hc][hj]
     const int zc = tid < NZN ? tid / n : 0, zg = tid < NZN ? tid % n : 0, z0 = T::pg_r0(zc);                       // Z[zc][zg]
     const int ri = tid < n ? tid : 0;                                                                             // r[ri], Pi^T c [ri]
+    const bool isnu = tid >= 8 && tid < 8 + n;                                                                    // (F_MV: Pi^T c [tid - 8])
     const bool on = tid < NN;
     const int i = on ? tid / n : 0, j = on ? tid % n : 0;                                                         // P[i][j], Pi[i][j]
     // ---- LDS operands (offsets in doubles from the base of the dynamic LDS) ----
@@ -519,16 +543,27 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
     auto ld2 = [&](int off) { return *(const __attribute__((address_space(3))) v2d*)(L.p + off); };   // ds_read_b128 (off even)
     const int dmy = C::sT0 + (tid & 15);             // dummy slot of this lane (+ immediates < 36 stay inside the T buffer)
     static_assert(n * NZ >= 16 + 36, "dummy slot");
+    // F_HUU: the upper triangle of H_uu, six doubles packed row-major behind the dummy slots (its lanes write, every lane reads)
+    constexpr int oHuu = C::sT0 + 46, NHU = m * (m + 1) / 2;
+    static_assert(oHuu % 2 == 0 && 15 + (2 * m - 1) * n < 46 && 15 + NHU < 46 && 46 + NHU <= n * NZ, "H_uu behind the dummy slots, in the T buffer");
+    // F_ROWS: rows of H at an even stride (H_uu is not among them: rows 0 .. n-1 only), Z_u transposed in rows of four doubles
+    // on the first even offset of the Z buffer (Z_y is only ever read back by the lane that formed it: zR)
+    constexpr int NZH = F_ROWS ? NZ + 1 : NZ, oZu = (C::sZ + 1) & ~1;
+    static_assert(!F_ROWS || (C::sHh % 2 == 0 && NZH % 2 == 0 && n * NZH <= NZ * NZ && oZu + 4 * n <= C::sZ + NZN), "128-bit rows of H_yu and Z_u");
     auto pcol = [](int j_) { return 2 * (j_ % h3) + j_ / h3; };       // column j of P sits at position pcol(j) of its row
     static_assert(C::sP % 2 == 0 && C::sPi % 2 == 0 && n % 2 == 0 && C::vecs % 2 == 0, "16-byte aligned rows");
-    const int oPP = C::sP + i0 * n + 2 * j0, oPZ = C::sPi + zg * n + z0, oPr = C::sP + ri * n, oPir = C::sPi + ri * n;
-    const int wH1 = tid < NQ ? C::sHh + hc * NZ + hj : dmy;           // (upper triangle only: hc <= hj)
-    const int wZ = tid < NZN ? C::sZ + tid : dmy;
-    const int oHi = C::sHh + i * NZ + n, oHj = C::sHh + j * NZ + n, oPn = C::sHh + (i < j ? i : j) * NZ + (i < j ? j : i);
-    const int oZi = C::sZ + n * n + i, oZj = C::sZ + n * n + j;
-    const int wP = on ? C::sP + i * n + pcol(j) : dmy, wPi = on ? C::sPi + j * n + i : dmy, wGd = on ? C::sGd + tid : dmy;
+    // (F_MV: the rows of the transposed Pi carry P's column interleave, so the pair a lane of Z needs is adjacent and even)
+    const int oPP = C::sP + i0 * n + 2 * j0, oPZ = C::sPi + zg * n + (F_MV ? 2 * z0 : z0), oPr = C::sP + ri * n, oPir = C::sPi + ri * n;
+    const int oRow = tid < n ? C::sP + tid * n : (isnu ? C::sPi + (tid - 8) * n : C::sP);   // (F_MV: row of P | of Pi^T of this lane)
+    const int wH1 = tid < NQ ? ((hc >= n && F_HUU) ? oHuu + sidx(hc - n, hj - n, m) : ((hc >= n && F_ROWS) ? dmy : C::sHh + hc * NZH + hj))
+                             : dmy;                                   // (upper triangle only: hc <= hj)
+    const int wZ = tid < NZN ? (F_ROWS ? (zc >= n ? oZu + zg * 4 + (zc - n) : dmy) : C::sZ + tid) : dmy;
+    const int oHi = C::sHh + i * NZH + n, oHj = C::sHh + j * NZH + n, oPn = C::sHh + (i < j ? i : j) * NZH + (i < j ? j : i);
+    const int oZi = F_ROWS ? oZu + i * 4 : C::sZ + n * n + i, oZj = F_ROWS ? oZu + j * 4 : C::sZ + n * n + j;
+    const int wP = on ? C::sP + i * n + pcol(j) : dmy, wPi = on ? C::sPi + j * n + (F_MV ? pcol(i) : i) : dmy, wGd = on ? C::sGd + tid : dmy;
     const int vecs = C::vecs, oCv = vecs + 3 * N * n, oRv = vecs + 4 * N * n, oNun = vecs + 6 * N * n;   // (Blk::rebind_lds)
     const int wRv = tid < n ? oRv + tid : dmy, wNun = tid < n ? oNun + tid : dmy, sRv = tid < n ? n : 0;
+    const int wRN = tid < n ? oRv + tid : (isnu ? oNun + (tid - 8) : dmy), sRN = (tid < n || isnu) ? n : 0;   // (F_MV: both, one store)
     const int kdo = K.kd_off;
     const int wKD = tid < n ? kdo + tid : dmy, sKD = tid < n ? C::KDS : 0;             // K[a][tid] at + a n, D[a][tid] at + (m + a) n
     const int wSi = tid == 0 ? kdo + 2 * m * n : dmy, sSi = tid == 0 ? C::KDS : 0;     // S^-1, upper triangle
@@ -609,26 +644,37 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
 #define STAMP(v) do {} while (0)
 #define STAMPS_END() do {} while (0)
 #endif
+    // F_ROWS: the m operands of a lane's rows i and j -- H_yu[i][0..m-1] | H_yu[j][..] (at oHi | oHj) or Z_u[0..m-1][i] | Z_u[..][j]
+    // (at oZi | oZj) -- are rows at even offsets: one 128-bit read and one 64-bit read each
+    auto ld3 = [&](int oi, int oj, double* vi, double* vj) {
+        const v2d a2 = ld2(oi), b2 = ld2(oj);
+        vi[0] = a2.x; vi[1] = a2.y; vi[2] = L[oi + 2]; vj[0] = b2.x; vj[1] = b2.y; vj[2] = L[oj + 2];
+    };
     auto stage = [&](int k, const PGC& c, bool last) {
         STAMP(t0_);
         // ---- operands of this iteration, one batch ----
         const v2d pA = ld2(oPP), pB = ld2(oPP + h3 * n);
         const double p00 = pA.x, p01 = pA.y, p10 = pB.x, p11 = pB.y;
         double ra[n], rb[n];
+        if constexpr (!F_MV) {
 #pragma unroll
-        for (int l = 0; l < n; l += 2) {
-            const v2d a2 = ld2(oPr + l), b2 = ld2(oCv + k * n + l);
-            // row ri of P holds the columns in the order 0, n/2, 1, n/2 + 1, ...: ra[] back in natural order
-            ra[l / 2] = a2.x; ra[l / 2 + h3] = a2.y; rb[l] = b2.x; rb[l + 1] = b2.y;
+            for (int l = 0; l < n; l += 2) {
+                const v2d a2 = ld2(oPr + l), b2 = ld2(oCv + k * n + l);
+                // row ri of P holds the columns in the order 0, n/2, 1, n/2 + 1, ...: ra[] back in natural order
+                ra[l / 2] = a2.x; ra[l / 2 + h3] = a2.y; rb[l] = b2.x; rb[l + 1] = b2.y;
+            }
         }
         double zi[m], zj[m];
+        if constexpr (F_ROWS) ld3(oZi, oZj, zi, zj);
+        else {
 #pragma unroll
-        for (int l = 0; l < m; l++) { zi[l] = L[oZi + l * n]; zj[l] = L[oZj + l * n]; }
+            for (int l = 0; l < m; l++) { zi[l] = L[oZi + l * n]; zj[l] = L[oZj + l * n]; }
+        }
         const double qqn = K.kdl[((k > 0) ? k - 1 : 0) * C::KDS + (tid < NQ ? tid : 0)];   // (slot k-1 still holds QQ_{k-1})
         // ---- value function chain, first half: H, r_k = P_k c_k ----
         const double h = qq + c.a0 * (c.b0 * p00 + c.b1 * p01) + c.a1 * (c.b0 * p10 + c.b1 * p11);
         L[wH1] = h;
-        {
+        if constexpr (!F_MV) {
             double rr = 0;
 #pragma unroll
             for (int l = 0; l < n; l++) rr += ra[l] * rb[l];
@@ -637,26 +683,47 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
         STAMP(t1_);
         msync();
         double S[m * m], Li[m * m];
+        if constexpr (F_HUU) {   // three broadcast reads of the packed upper triangle its six lanes have just stored
+            const v2d s0 = ld2(oHuu), s1 = ld2(oHuu + 2), s2 = ld2(oHuu + 4);
+            const double su[NHU] = {s0.x, s0.y, s1.x, s1.y, s2.x, s2.y};
 #pragma unroll
-        for (int a = 0; a < m; a++)
+            for (int a = 0; a < m; a++)
 #pragma unroll
-            for (int b = 0; b < m; b++) {
-                const int e = sidx(n + (a < b ? a : b), n + (a < b ? b : a), NZ);
-                S[a * m + b] = readlane_f64(h, e);
-            }
+                for (int b = 0; b < m; b++) S[a * m + b] = su[sidx(a, b, m)];
+        } else {
+#pragma unroll
+            for (int a = 0; a < m; a++)
+#pragma unroll
+                for (int b = 0; b < m; b++) {
+                    const int e = sidx(n + (a < b ? a : b), n + (a < b ? b : a), NZ);
+                    S[a * m + b] = readlane_f64(h, e);
+                }
+        }
         double hi[m], hjv[m];
+        if constexpr (F_ROWS) ld3(oHi, oHj, hi, hjv);
+        else {
 #pragma unroll
-        for (int l = 0; l < m; l++) { hi[l] = L[oHi + l]; hjv[l] = L[oHj + l]; }
+            for (int l = 0; l < m; l++) { hi[l] = L[oHi + l]; hjv[l] = L[oHj + l]; }
+        }
         double pn = L[oPn];
         // ---- goal chain: tail of the stage before, head of this one (independent of the factorisation below) ----
         tail(k + 1 < N ? k + 1 : N - 1, zi, zj);
         STAMP(t2_);
         msync();
         // (operands of the head first, then the factorisation: its ~45 dependent flops run while they are in flight)
-        const double zb0 = L[oPZ], zb1 = L[oPZ + h3];
+        // F_MV: r_k = P_k c_k (lanes 0 .. n-1) and Pi_k^T c_k (lanes 8 .. 8+n-1) are ONE stream: Pi_k is in place since the tail above,
+        // P_k until L[wP] below, the rows of both hold the columns in the order 0, n/2, 1, n/2 + 1, ..., and the pair of Pi a lane of
+        // Z needs is one 128-bit read
+        const double zb0 = F_MV ? ld2(oPZ).x : L[oPZ], zb1 = F_MV ? ld2(oPZ).y : L[oPZ + h3];
         double pa[n];
 #pragma unroll
-        for (int l = 0; l < n; l += 2) { const v2d a2 = ld2(oPir + l); pa[l] = a2.x; pa[l + 1] = a2.y; }
+        for (int l = 0; l < n; l += 2) {
+            const v2d a2 = ld2((F_MV ? oRow : oPir) + l);
+            if constexpr (F_MV) {
+                const v2d b2 = ld2(oCv + k * n + l);
+                pa[l / 2] = a2.x; pa[l / 2 + h3] = a2.y; rb[l] = b2.x; rb[l + 1] = b2.y;
+            } else { pa[l] = a2.x; pa[l + 1] = a2.y; }
+        }
         // ---- value function chain, second half: L = chol(H_uu), W = L^-1 H_uy, K = L^-T W, P_{k-1} = H_yy - W^T W ----
         okall = chol_inv<m>(S, Li) && okall;
         STAMP(t3_);
@@ -669,7 +736,8 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
             double rr = 0;
 #pragma unroll
             for (int l = 0; l < n; l++) rr += pa[l] * rb[l];
-            L[wNun + k * sRv] = rr;
+            if constexpr (F_MV) L[wRN + k * sRN] = rr;
+            else L[wNun + k * sRv] = rr;
         }
         STAMP(t4_);
         double wi[m], wj[m], kj[m];
@@ -720,8 +788,11 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
     stage(0, c0, false);
     {   // the goal chain is one half stage behind: tail of stage 0 (Gd, D_0; its Pi lands in record -1)
         double zi[m], zj[m];
+        if constexpr (F_ROWS) ld3(oZi, oZj, zi, zj);
+        else {
 #pragma unroll
-        for (int l = 0; l < m; l++) { zi[l] = L[oZi + l * n]; zj[l] = L[oZj + l * n]; }
+            for (int l = 0; l < m; l++) { zi[l] = L[oZi + l * n]; zj[l] = L[oZj + l * n]; }
+        }
         tail(0, zi, zj);
     }
     L[wGd] = gdR;
