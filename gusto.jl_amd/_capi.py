@@ -350,8 +350,7 @@ class BatchSolver:
             raise GustoError(f"gusto_create -> {rc}: {msg.decode() if msg else ''}")
         self.B = 0
         if scp_params is not None or model_params is not None:
-            self._chk(self.L.gusto_set_params(self.h, C.byref(scp_params) if scp_params is not None else None,
-                                              C.byref(model_params) if model_params is not None else None), "set_params")
+            self.set_params(scp_params, model_params)
         if ipm_opts is not None:
             self._chk(self.L.gusto_set_ipm_opts(self.h, C.byref(ipm_opts)), "set_ipm_opts")
         if BatchSolver.default_decomposition and type(self) is BatchSolver and model in (ASTROBEE_SE3, ASTROBEE_SE3_MANIFOLD):
@@ -365,6 +364,11 @@ class BatchSolver:
         if rc:
             msg = self.L.gusto_last_error(self.h)
             raise GustoError(f"gusto_{what} -> {rc}: {msg.decode() if msg else ''}")
+
+    def set_params(self, scp_params=None, model_params=None):
+        """gusto_set_params: the SCP and / or the robot and model parameters of every later call on this handle (None: kept)"""
+        self._chk(self.L.gusto_set_params(self.h, C.byref(scp_params) if scp_params is not None else None,
+                                          C.byref(model_params) if model_params is not None else None), "set_params")
 
     def close(self):
         if getattr(self, "h", None) and self.h:

@@ -13,6 +13,8 @@ the reference's model files -- NOT through the oracle's row list:
 
 subproblem_rows states the rows; solve_subproblem hands them to scipy SLSQP in the full slack form (variables X, U and one
 slack per penalised row); np_kkt.certify checks a candidate point against them."""
+import contextlib
+
 import numpy as np
 import scipy.optimize as so
 
@@ -33,7 +35,7 @@ class Dubins:
 
 
 class Astrobee:
-    mass, J = 7.0, 0.1083
+    mass, J = 7.0, np.array([0.1083, 0.1083, 0.1083])       # J: the diagonal of the inertia
     r = np.sqrt(3.0) * 0.5 * 0.305
     v_max, a_max, w_max, al_max = 0.5, 0.1, 45 * PI / 180, 50 * PI / 180
     clearance = 0.03
@@ -41,6 +43,11 @@ class Astrobee:
 
 def _cross(a, b):
     return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]])
+
+
+def _per_axis(J, w):
+    """the diagonal J shaped to scale the rows of w ([3] or [3, K])"""
+    return np.reshape(J, (3,) + (1,) * (np.ndim(w) - 1))
 
 
 class AstrobeeSE3(Astrobee):
@@ -53,7 +60,8 @@ class AstrobeeSE3(Astrobee):
         v, p, w = x[3:6], x[6:9], x[9:12]
         F, M = u[0:3], u[3:6]
         pd = 0.25 * ((1 - np.sum(p * p)) * w - 2 * _cross(w, p) + 2 * np.sum(w * p) * p)      # mrp_derivative
-        wd = (M - _cross(w, Astrobee.J * w)) / Astrobee.J
+        J = _per_axis(Astrobee.J, w)
+        wd = (M - _cross(w, J * w)) / J
         return np.concatenate([v, F / Astrobee.mass, pd, wd])
 
 
@@ -71,7 +79,8 @@ class AstrobeeSE3Manifold(Astrobee):
         qd = 0.5 * np.array([-wx * qx - wy * qy - wz * qz, wx * qw - wz * qy + wy * qz, wy * qw + wz * qx - wx * qz,
                              wz * qw - wy * qx + wx * qy])
         w = x[10:13]
-        wd = (M - _cross(w, Astrobee.J * w)) / Astrobee.J
+        J = _per_axis(Astrobee.J, w)
+        wd = (M - _cross(w, J * w)) / J
         return np.concatenate([v, F / Astrobee.mass, qd, wd])
 
 
@@ -81,16 +90,17 @@ class FreeflyerSE2:
     against the keep-out components in the plane); the arm component (freeflyer.jl:55-57) enters trust_region_ratio_gusto only --
     ncsi_arm_obstacle_avoidance_constraints_convexified is written but not registered."""
     n, m = 6, 3
-    mass, J = 0.5 * (15.36 + 18.08), 0.184
+    mass, J = 0.5 * (15.36 + 18.08), np.array([0.184, 0.184, 0.184])    # the plane turns about z: J[2] (freeflyer.jl Jinv)
     r, clearance = 0.157, 0.05
     v_max, w_max = 0.2, 20 * PI / 180
     a_max, al_max = 2 * 0.185 / (0.5 * (15.36 + 18.08)), 0.593 / (0.184 / 6.43)
     Delta0, eps = 3.0, 1e-2
     has_tr = True
+    J_AXIS = 2
 
     @staticmethod
     def f(x, u):
-        return np.concatenate([x[3:6], u[0:2] / FreeflyerSE2.mass, u[2:3] / FreeflyerSE2.J])
+        return np.concatenate([x[3:6], u[0:2] / FreeflyerSE2.mass, u[2:3] / FreeflyerSE2.J[FreeflyerSE2.J_AXIS]])
 
 
 def jac(model, x, u):
@@ -104,6 +114,34 @@ def jac(model, x, u):
         uc = u.astype(complex); uc[j] += 1j * h
         B[:, j] = model.f(x.astype(complex), uc).imag / h
     return A, B
+
+
+# ---- non-default robot constants -----------------------------------------------------------------------------------------
+_ROBOT = {0: FreeflyerSE2, 1: Dubins, 2: Astrobee, 3: Astrobee}
+
+
+@contextlib.contextmanager
+def model_params(model_id, mp):
+    """Run a block with the robot constants of a ModelParams (the oracle's or the library's ctypes struct: the fields are read by
+    name) in place of the defaults above -- mass, J, radius, clearance and the four hard limits; the Dubins car's v, k, u_max and
+    clearance -- and put the defaults back afterwards.  mp = None leaves everything as it is."""
+    cls = _ROBOT[model_id]
+    if mp is None:
+        yield
+        return
+    if cls is Dubins:
+        new = dict(v=mp.dubins_v, k=mp.dubins_k, u_max=mp.u_max, clearance=mp.clearance)
+    else:
+        new = dict(mass=mp.mass, J=np.array([mp.Jdiag[0], mp.Jdiag[1], mp.Jdiag[2]]), r=mp.radius, clearance=mp.clearance,
+                   v_max=mp.hard_limit_vel, a_max=mp.hard_limit_accel, w_max=mp.hard_limit_omega, al_max=mp.hard_limit_alpha)
+    old = {k: getattr(cls, k) for k in new}
+    for k, v in new.items():
+        setattr(cls, k, v)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            setattr(cls, k, v)
 
 
 # ---- signed distance of a sphere (a disc in 2-D) of radius r centred at c ---------------------------------------------
@@ -233,7 +271,8 @@ def subproblem_rows(model, N, tf, x_init, goal_lo, goal_hi, Xp, Up, Delta, omega
             nf, im, nm = (2, 2, 1) if se2 else (3, 3, 3)
             hard.append((quad([iu(k, j) for j in range(nf)], [1 / model.mass ** 2] * nf, -model.a_max ** 2),
                          1 / model.a_max ** 2, "hard"))
-            hard.append((quad([iu(k, im + j) for j in range(nm)], [1 / model.J ** 2] * nm, -model.al_max ** 2),
+            Jm = [model.J[model.J_AXIS]] if se2 else model.J              # 1 / J_j^2 per axis
+            hard.append((quad([iu(k, im + j) for j in range(nm)], [1 / Jm[j] ** 2 for j in range(nm)], -model.al_max ** 2),
                          1 / model.al_max ** 2, "hard"))
     for i in range(n):              # csbci_goal_constraints (BoxGoal): hard
         if goal_lo[i] != goal_hi[i]:

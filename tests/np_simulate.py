@@ -56,7 +56,8 @@ def f_cols(model_id, x, u):
         return np.asarray(model.f(x, u))
     v, p, w = x[3:6], x[6:9], x[9:12]              # astrobee_se3.jl:180-190 with quat_functions.jl:253-257 (mrp_derivative)
     pd = 0.25 * ((1 - np.sum(p * p, axis=0)) * w - 2 * _cross0(w, p) + 2 * np.sum(w * p, axis=0) * p)
-    wd = (u[3:6] - _cross0(w, M.Astrobee.J * w)) / M.Astrobee.J
+    J = M._per_axis(M.Astrobee.J, w).astype(x.dtype)
+    wd = (u[3:6] - _cross0(w, J * w)) / J
     return np.concatenate([v, u[0:3] / M.Astrobee.mass, pd, wd])
 
 

@@ -27,14 +27,16 @@ def _mods():
 
 
 def _certify(model, N, boxes, spheres, prob, Xp, Up, Delta, omega, toggle, dec=None, sample=4, seed=0, ipm_opts=None,
-             slsqp=True, label=""):
+             slsqp=True, label="", model_params=None):
     """One batch through the device; certify a seeded sample.  prob = (x0, glo, ghi, tf) [B]; Delta, omega, toggle [B] or scalar.
+    model_params (default: the model's own) goes to the solver, to the rows of the certificate and to the oracle alike.
     Returns the worst residuals; asserts every gate."""
     g, _ = _mods()
     x0, glo, ghi, tf = prob
     B = len(x0)
     Delta, omega, toggle = (np.broadcast_to(np.asarray(v, float), (B,)).copy() for v in (Delta, omega, toggle))
-    s = g.BatchSolver(model, N, B, hist_cap=8, boxes=boxes, spheres=spheres, ipm_opts=ipm_opts)
+    s = g.BatchSolver(model, N, B, hist_cap=8, boxes=boxes, spheres=spheres, ipm_opts=ipm_opts,
+                      model_params=T.as_params(g.ModelParams, model_params))
     if dec is not None:
         s.set_decomposition(dec)
     s.set_problems(x0, glo, ghi, tf)
@@ -50,10 +52,11 @@ def _certify(model, N, boxes, spheres, prob, Xp, Up, Delta, omega, toggle, dec=N
         st = int(sub["status"][b])
         pb = (x0[b], glo[b], ghi[b], tf[b])
         if st == 3 and ipm_opts is None:        # FAILED: only where the oracle fails on the same subproblem (infeasible ones)
-            assert _oracle(model, N, boxes, spheres, pb, Xp[b], Up[b], Delta[b], omega[b], toggle[b])["status"] == 3, (label, b)
+            assert _oracle(model, N, boxes, spheres, pb, Xp[b], Up[b], Delta[b], omega[b], toggle[b],
+                           model_params)["status"] == 3, (label, b)
             continue
         assert st in (1, 2), (label, b, st)
-        R = T.rows(model, N, pb, Xp[b], Up[b], Delta[b], omega[b], toggle[b], boxes, spheres)
+        R = T.rows(model, N, pb, Xp[b], Up[b], Delta[b], omega[b], toggle[b], boxes, spheres, model_params)
         c = K.certify(R, sub["X"][b], sub["U"][b])
         certs.append((b, st, c))
         if ipm_opts is not None:
@@ -67,8 +70,9 @@ def _certify(model, N, boxes, spheres, prob, Xp, Up, Delta, omega, toggle, dec=N
             worst[k] = max(worst[k], c[k])
         worst["gap"] = max(worst["gap"], abs(gap))
         if slsqp and N <= 16 and b == min(pick):       # a second solver that shares nothing with the kernel
-            r = M.solve_subproblem(T.MODEL[model], N, tf[b], x0[b], glo[b], ghi[b], Xp[b], Up[b], Delta[b], omega[b],
-                                   () if boxes is None else boxes, () if spheres is None else spheres, toggle=toggle[b])
+            with M.model_params(model, model_params):
+                r = M.solve_subproblem(T.MODEL[model], N, tf[b], x0[b], glo[b], ghi[b], Xp[b], Up[b], Delta[b], omega[b],
+                                       () if boxes is None else boxes, () if spheres is None else spheres, toggle=toggle[b])
             assert abs(r["obj"] - sub["obj"][b]) <= 1e-6 * max(1.0, abs(sub["obj"][b])), (label, b, r["obj"], sub["obj"][b])
     if ipm_opts is None:
         print(f"kkt {label} N={N} dec={dec} B={B} slots={slots} certified={len(pick)}",
@@ -76,9 +80,9 @@ def _certify(model, N, boxes, spheres, prob, Xp, Up, Delta, omega, toggle, dec=N
     return worst, certs
 
 
-def _oracle(model, N, boxes, spheres, pb, Xp, Up, Delta, omega, toggle):
+def _oracle(model, N, boxes, spheres, pb, Xp, Up, Delta, omega, toggle, model_params=None):
     _, go = _mods()
-    o = go.Oracle(model, N, boxes=boxes, spheres=spheres)
+    o = go.Oracle(model, N, boxes=boxes, spheres=spheres, model_params=T.as_params(go.ModelParams, model_params))
     o.set_problem(*pb)
     return o.subproblem(Xp, Up, Delta, omega, toggle)
 
@@ -89,13 +93,13 @@ def _resident(s):
     return s.launch_info()[2] * torch.cuda.get_device_properties(s.device).multi_processor_count
 
 
-def _trip_batch(model, N, boxes, spheres, prob, idx, raise_omega=1.0, delta=None):
+def _trip_batch(model, N, boxes, spheres, prob, idx, raise_omega=1.0, delta=None, model_params=None):
     """oracle trips (first, second, middle, last) of the problems `idx`: (prob, Xp, Up, Delta, omega) batched"""
     x0, glo, ghi, tf = prob
     rows = []
     for b in idx:
         pb = (x0[b], glo[b], ghi[b], tf[b])
-        for Xp, Up, D, om in T.oracle_trips(model, N, boxes, spheres, pb):
+        for Xp, Up, D, om in T.oracle_trips(model, N, boxes, spheres, pb, model_params=model_params):
             rows.append((b, Xp, Up, D if delta is None else delta, raise_omega * om))
     bi = np.array([r[0] for r in rows])
     return ((x0[bi], glo[bi], ghi[bi], tf[bi]), np.stack([r[1] for r in rows]), np.stack([r[2] for r in rows]),

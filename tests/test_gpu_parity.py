@@ -14,6 +14,8 @@ subproblem is solved scaled by 1/omega, and the tolerances carry that factor exp
 import numpy as np
 import pytest
 
+from test_kkt_certificate import as_params
+
 pytestmark = pytest.mark.gpu
 
 SUB_ATOL = 1e-6
@@ -28,14 +30,15 @@ def _mods():
     return g, go
 
 
-def _sub_parity(model, N, env, spheres, x0, glo, ghi, tf, Delta, omega, toggle, X0=None, U0=None, atol=SUB_ATOL, u_atol=None):
+def _sub_parity(model, N, env, spheres, x0, glo, ghi, tf, Delta, omega, toggle, X0=None, U0=None, atol=SUB_ATOL, u_atol=None,
+                model_params=None):
     g, go = _mods()
     B = len(x0)
-    s = g.BatchSolver(model, N, B, hist_cap=8, boxes=env, spheres=spheres)
+    s = g.BatchSolver(model, N, B, hist_cap=8, boxes=env, spheres=spheres, model_params=as_params(g.ModelParams, model_params))
     s.set_problems(x0, glo, ghi, tf, X0, U0)
     Xp, Up = s.traj()
     r = s.subproblem(Xp, Up, Delta, omega, toggle)
-    o = go.Oracle(model, N, boxes=env, spheres=spheres)
+    o = go.Oracle(model, N, boxes=env, spheres=spheres, model_params=as_params(go.ModelParams, model_params))
     worst = 0.0
     for b in range(B):
         o.set_problem(x0[b], glo[b], ghi[b], tf[b])
@@ -96,13 +99,13 @@ def test_subproblem_parity_astrobee_manifold():
     _sub_parity(g.ASTROBEE_SE3_MANIFOLD, 50, boxes, sph, x0, glo, ghi, tf, 1e3, 1.0, 1e3 / 8 + 0.03, atol=1e-4, u_atol=1e-6)
 
 
-def _oracle_runs(model, N, env, spheres, x0, glo, ghi, tf, max_iter, cold=True):
+def _oracle_runs(model, N, env, spheres, x0, glo, ghi, tf, max_iter, cold=True, model_params=None):
     """Oracle solve of every problem with its per-trip trace (traj_prev, subproblem optimum).  The run itself warm-
     starts every interior point solve after the first; the device's lock-step trips start cold, so each traced trip
     is ALSO re-solved cold through the oracle's pieces (same start on both sides): keys Xc, Uc, conv_c, rho_c, J_c, obj_c."""
     g, go = _mods()
-    clr = g.default_params(model)[1].clearance
-    o = go.Oracle(model, N, boxes=env, spheres=spheres)
+    clr = (model_params or g.default_params(model)[1]).clearance
+    o = go.Oracle(model, N, boxes=env, spheres=spheres, model_params=as_params(go.ModelParams, model_params))
     runs = []
     for b in range(len(x0)):
         o.set_trace(max_iter + 2)
@@ -118,7 +121,7 @@ def _oracle_runs(model, N, env, spheres, x0, glo, ghi, tf, max_iter, cold=True):
 
 
 def _lockstep_parity(model, N, env, spheres, x0, glo, ghi, tf, max_iter=30, sub_atol=SUB_ATOL, max_flag_mismatch=0.005,
-                     u_atol=SUB_ATOL, q_tight=0.9, min_same_iters=0.9, max_cold_fail=1):
+                     u_atol=SUB_ATOL, q_tight=0.9, min_same_iters=0.9, max_cold_fail=1, model_params=None):
     """EVERY trip of EVERY problem (no omega cut-off): the oracle's (traj_prev, Delta, omega) of the trip is fed to
     the device, first through gusto_subproblem (the convex solve alone), then as ONE GuSTO trip of the real state
     machine (gusto_set_trust_state + gusto_solve(1)), whose post-solve quantities -- convergence_measure, rho, the
@@ -130,7 +133,7 @@ def _lockstep_parity(model, N, env, spheres, x0, glo, ghi, tf, max_iter=30, sub_
     residual test) is gated at 20 x sub_atol.  Verdicts and updates exact on all but `max_flag_mismatch` of the trips
     (a verdict whose margin is below the solver tolerance may flip)."""
     g, go = _mods()
-    runs = _oracle_runs(model, N, env, spheres, x0, glo, ghi, tf, max_iter)
+    runs = _oracle_runs(model, N, env, spheres, x0, glo, ghi, tf, max_iter, model_params=model_params)
     all_trips = [(b, t) for b, (r, tr) in enumerate(runs) for t in range(len(tr))]
     # a trip the oracle's warm-started run solved may fail from the cold start both sides use here (subproblems at the
     # edge of feasibility, dubins): such trips are compared by status only -- below -- and are rare
@@ -147,8 +150,8 @@ def _lockstep_parity(model, N, env, spheres, x0, glo, ghi, tf, max_iter=30, sub_
     C_ = lambda k: np.array([runs[b][1][t][k] for b, t in trips])      # cold oracle pieces of the trip
     Delta = np.array([runs[b][0]["Delta"][t] for b, t in trips])
     omega = np.array([runs[b][0]["omega"][t] for b, t in trips])
-    sp, mp = g.default_params(model)
-    s = g.BatchSolver(model, N, T, hist_cap=8, boxes=env, spheres=spheres)
+    mp = model_params or g.default_params(model)[1]
+    s = g.BatchSolver(model, N, T, hist_cap=8, boxes=env, spheres=spheres, model_params=as_params(g.ModelParams, model_params))
     s.set_schedule(0, 1)
     # (1) the convex subproblem of every trip
     s.set_problems(x0[bi], glo[bi], ghi[bi], tf[bi])

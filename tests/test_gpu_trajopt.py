@@ -12,6 +12,7 @@ import pytest
 import gusto_jl_amd as g
 import gusto_oracle as go
 import horizons as HZ
+from test_kkt_certificate import as_params
 
 pytestmark = pytest.mark.gpu
 P = g.problems
@@ -30,13 +31,20 @@ def _setup(model, B):
 @pytest.mark.parametrize("model", [g.FREEFLYER_SE2, g.ASTROBEE_SE3, g.ASTROBEE_SE3_MANIFOLD])
 @pytest.mark.parametrize("mu,s_tr", [(1.0, 1.0), (5.0, 0.25), (125.0, 0.03)])
 def test_subproblem_parity(model, mu, s_tr):
-    B = 24
-    (x0, glo, ghi, tf), boxes, spheres = _setup(model, B)
-    s = g.TrajOptSolver(model, 50, B, boxes=boxes, spheres=spheres)
+    (x0, glo, ghi, tf), boxes, spheres = _setup(model, 24)
+    _subproblem_parity(model, 50, boxes, spheres, (x0, glo, ghi, tf), mu, s_tr)
+
+
+def _subproblem_parity(model, N, boxes, spheres, prob, mu, s_tr, Xp=None, Up=None, model_params=None):
+    """one TrajOpt subproblem per problem of `prob` from (Xp, Up) (default: the straight line) against the oracle's; model_params
+    (default: the model's own) goes to both sides"""
+    x0, glo, ghi, tf = prob
+    B = len(x0)
+    s = g.TrajOptSolver(model, N, B, boxes=boxes, spheres=spheres, model_params=as_params(g.ModelParams, model_params))
     s.set_problems(x0, glo, ghi, tf)
-    X0, U0 = s.traj()
+    X0, U0 = s.traj() if Xp is None else (Xp, Up)
     r = s.subproblem(X0, U0, mu, s_tr)
-    o = go.OracleTrajOpt(model, 50, boxes=boxes, spheres=spheres)
+    o = go.OracleTrajOpt(model, N, boxes=boxes, spheres=spheres, model_params=as_params(go.ModelParams, model_params))
     for b in range(B):
         o.set_problem(x0[b], glo[b], ghi[b], tf[b])
         ro = o.subproblem(X0[b], U0[b], mu, s_tr)
@@ -56,6 +64,7 @@ def test_subproblem_parity(model, mu, s_tr):
             assert ed[:6].max() < wd and ed[10:].max() < wd and ed[6:10].max() < 1e-2 * max(1.0, mu)
         else:
             assert ed.max() < wd
+    return r
 
 
 @pytest.mark.parametrize("model", [g.FREEFLYER_SE2, g.ASTROBEE_SE3, g.ASTROBEE_SE3_MANIFOLD])

@@ -51,10 +51,16 @@ def batch(model, B, first=0):
     return P.astrobee_manifold_batch(B, first)
 
 
-def rows(model, N, prob, Xp, Up, Delta, omega, toggle, boxes, spheres):
+def as_params(cls, mp):
+    """a ModelParams of the oracle's or the library's binding as `cls` (the two structs have one layout); None stays None"""
+    return None if mp is None else cls.from_buffer_copy(bytes(mp))
+
+
+def rows(model, N, prob, Xp, Up, Delta, omega, toggle, boxes, spheres, model_params=None):
     x0, glo, ghi, tf = prob
-    return M.subproblem_rows(MODEL[model], N, tf, x0, glo, ghi, Xp, Up, Delta, omega, toggle,
-                             () if boxes is None else boxes, () if spheres is None else spheres)
+    with M.model_params(model, model_params):
+        return M.subproblem_rows(MODEL[model], N, tf, x0, glo, ghi, Xp, Up, Delta, omega, toggle,
+                                 () if boxes is None else boxes, () if spheres is None else spheres)
 
 
 def obj_gap(model, r_obj, c, kappa):
@@ -69,10 +75,10 @@ def obj_gate(model, c):
     return max(OBJ_GAP[model], c["n_pairs"] * K.STOP_MU)
 
 
-def oracle_trips(model, N, boxes, spheres, prob, max_iter=30):
+def oracle_trips(model, N, boxes, spheres, prob, max_iter=30, model_params=None):
     """(Xp, Up, Delta, omega) of the first, second, middle and last trip of an oracle SCP run; an empty list for a run that stops
     before its first trip (SubproblemFailed at the first subproblem: dubins_car at N = 3, where no control reaches the goal)"""
-    o = go.Oracle(model, N, boxes=boxes, spheres=spheres)
+    o = go.Oracle(model, N, boxes=boxes, spheres=spheres, model_params=as_params(go.ModelParams, model_params))
     o.set_trace(max_iter + 2)
     o.set_problem(*prob)
     r = o.solve(max_iter)

@@ -15,17 +15,25 @@ P = g.problems
 REG = 1e-4      # GO_TRAJOPT_DEFECT_REG
 
 
-def _ff(N, env, b=0):
+def _ff(N, env, b=0, model_params=None, x_init=None):
     x0, glo, ghi, tf = P.freeflyer_batch(b + 1)
-    o = go.OracleTrajOpt(go.FREEFLYER_SE2, N, boxes=env)
+    if x_init is not None:
+        x0[b] = x_init
+    o = go.OracleTrajOpt(go.FREEFLYER_SE2, N, boxes=env, model_params=model_params)
     o.set_problem(x0[b], glo[b], ghi[b], tf[b])
     return o, x0[b], glo[b], tf[b]
 
 
 @pytest.mark.parametrize("N,mu,s_tr,with_env", [(10, 1.0, 1.0, True), (12, 5.0, 0.25, True), (16, 25.0, 0.0625, False)])
 def test_subproblem_against_slsqp(N, mu, s_tr, with_env):
+    _subproblem_against_slsqp(N, mu, s_tr, with_env)
+
+
+def _subproblem_against_slsqp(N, mu, s_tr, with_env, model_params=None, x_init=None):
+    """the rows below are rebuilt from o.mp: the model's constants, or `model_params`; x_init: another start than the config's.
+    Returns the oracle's result."""
     env = P.freeflyer_env() if with_env else None
-    o, x_init, goal, tf = _ff(N, env)
+    o, x_init, goal, tf = _ff(N, env, model_params=model_params, x_init=x_init)
     Xp, Up = o.init_straightline()
     r = o.subproblem(Xp, Up, mu, s_tr)
     assert r["status"] == 1
@@ -82,6 +90,7 @@ def test_subproblem_against_slsqp(N, mu, s_tr, with_env):
     assert np.abs(Xs - r["X"]).max() < 5e-4 and np.abs(Us - r["U"]).max() < 5e-4
     # the defect variables of the oracle ARE the trapezoid defects of its optimum
     assert np.abs(defects(r["X"], r["U"]) - r["D"][:-1]).max() < 1e-7 and np.abs(r["D"][-1]).max() < 1e-7
+    return r
 
 
 def test_ratio_and_ctol_formulas():

@@ -26,7 +26,7 @@ def test_freeflyer_rollout_jacobians_in_closed_form(nstep):
     tf = 7.3
     dt = tf / 4
     AB = T.linearise(0, X[0], U[0], tf, nstep=nstep)
-    Bv = np.diag([1 / Mo.mass, 1 / Mo.mass, 1 / Mo.J])
+    Bv = np.diag([1 / Mo.mass, 1 / Mo.mass, 1 / Mo.J[2]])
     Ad = np.block([[np.eye(3), dt * np.eye(3)], [np.zeros((3, 3)), np.eye(3)]])
     Bd = np.vstack([0.5 * dt * dt * Bv, dt * Bv])
     for k in range(4):

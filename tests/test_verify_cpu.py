@@ -78,7 +78,7 @@ def test_freeflyer_constant_control_rolls_out_to_the_exact_quadratic():
     Nk, tf = 6, 10.0
     dt = tf / (Nk - 1)
     u = np.array([0.3, -0.2, 0.01])
-    a = np.array([u[0] / Mo.mass, u[1] / Mo.mass, u[2] / Mo.J])
+    a = np.array([u[0] / Mo.mass, u[1] / Mo.mass, u[2] / Mo.J[2]])
     x0 = np.array([0.5, 0.7, 0.1, 0.02, -0.01, 0.003])
     t = dt * np.arange(Nk)[:, None]
     X = np.hstack([x0[:3] + x0[3:] * t + 0.5 * a * t * t, x0[3:] + a * t])
