@@ -61,6 +61,24 @@ constexpr int RS_T = 0, RS_LAM = 1, RS_LAMB = 2, RS_S = 3, RS_DT = 4, RS_DL = 5,
 #ifndef GUSTO_FACTOR_LDS_ROWS
 #define GUSTO_FACTOR_LDS_ROWS 1
 #endif
+// MT::FACTOR_REC (freeflyerSE2's one-wave kernel): only the recursion P_k -> H -> chol(H_uu) -> W -> P_{k-1} (and Pi_k -> Z -> V ->
+// Pi_{k-1}, Gd) stays on the sequential path of the factor stage (factor1w.hpp: factor_sweep_pg2), item by item:
+//   _HUU_DPP    (OFF by default) every row of 16 lanes forms H_uu in its lanes 0 .. 5 and the Cholesky takes it by DPP row_newbcast: no v_readlane
+//               (1: 12 v_mov_b32_dpp the compiler schedules, 2: one block of six v_mov_b64_dpp)
+//   _LAZY_SINV  the stage stores L^-1 where it stored S^-1; S^-1 = L^-T L^-1 is formed by its one reader, the stage-parallel mid phase
+//   _LAZY_D     the stage stores V = L^-1 Z_u where it stored D = L^-T V; the mid phase forms D (needs _LAZY_SINV: L^-1 in the slot)
+// All 0: the stage as it was, instruction for instruction.  Bit-identical either way (the same sums in the same order).
+#ifndef GUSTO_FACTOR_HUU_DPP
+#define GUSTO_FACTOR_HUU_DPP 0   // (built and bit-identical, but slower in place than the 12 v_readlane_b32: profiles/r10_factor_recursion.txt, section 2)
+#endif
+#ifndef GUSTO_FACTOR_LAZY_SINV
+#define GUSTO_FACTOR_LAZY_SINV 1
+#endif
+#ifndef GUSTO_FACTOR_LAZY_D
+#define GUSTO_FACTOR_LAZY_D 1
+#endif
+static_assert(!(GUSTO_FACTOR_LDS_HUU && GUSTO_FACTOR_HUU_DPP), "H_uu to the Cholesky through LDS or by DPP, not both");
+static_assert(!GUSTO_FACTOR_LAZY_D || GUSTO_FACTOR_LAZY_SINV, "GUSTO_FACTOR_LAZY_D forms D from the L^-1 that GUSTO_FACTOR_LAZY_SINV stores");
 #ifndef GUSTO_USE_MFMA
 #define GUSTO_USE_MFMA true   // -DGUSTO_USE_MFMA=false: the VALU two-step contraction instead (A/B measurements)
 #endif
@@ -86,6 +104,7 @@ template <> struct MT<GUSTO_FREEFLYER_SE2> {
     static constexpr bool SWEEP_CALL = false;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool SWEEP_DPP = GUSTO_SWEEP_DPP;   // one-wave vector sweeps on the fp64 DPP broadcast (ipm.hpp:backward_sweep_dpp; needs n = 6, PG2)
     static constexpr bool FACTOR_LDS = GUSTO_FACTOR_LDS;   // factor stage laid out for one-address LDS reads (factor1w.hpp:factor_sweep_pg2; needs n = 6, m = 3, PG2)
+    static constexpr bool FACTOR_REC = true;   // only the recursion on the factor stage's sequential path (GUSTO_FACTOR_HUU_DPP, _LAZY_SINV, _LAZY_D above; one-wave kernel)
     static constexpr bool MFMA = false;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 2;   // default number of one-trip probing slices of the longest-first scheduler
     static constexpr int SCHED_SLICE = 4;   // then slices of 4 trips for problems of penalty level 0 (34.1 vs 34.65 ms; the 12/13-state models lose with any)
@@ -113,6 +132,7 @@ template <> struct MT<GUSTO_DUBINS_CAR> {
     static constexpr bool SWEEP_CALL = false;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool SWEEP_DPP = false;
     static constexpr bool FACTOR_LDS = false;
+    static constexpr bool FACTOR_REC = false;
     static constexpr bool MFMA = false;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (short problems: 2 slices cost more than they order -- 316 vs 211 ms at B = 65 536)
     static constexpr bool LTI = false, HAS_OBS = false;
@@ -133,6 +153,7 @@ template <> struct MT<GUSTO_ASTROBEE_SE3> {
     static constexpr bool SWEEP_CALL = true;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool SWEEP_DPP = false;
     static constexpr bool FACTOR_LDS = false;
+    static constexpr bool FACTOR_REC = false;
     static constexpr bool MFMA = GUSTO_USE_MFMA;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (measured with raised-penalty problems ahead of fresh ones: 123.0 / 127.1 / 132.7 ms for 1 / 2 / 3 slices)
     static constexpr bool LTI = false, HAS_OBS = true;
@@ -158,6 +179,7 @@ template <> struct MT<GUSTO_ASTROBEE_SE3_MANIFOLD> {
     static constexpr bool SWEEP_CALL = true ;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool SWEEP_DPP = false;
     static constexpr bool FACTOR_LDS = false;
+    static constexpr bool FACTOR_REC = false;
     static constexpr bool MFMA = GUSTO_USE_MFMA;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (130.1 / 133.7 / 130.9 ms for 1 / 2 / 3 slices)
     static constexpr bool LTI = false, HAS_OBS = true;
@@ -181,6 +203,7 @@ template <> struct MT<GUSTO_TO_FREEFLYER_SE2> {
     static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_DPP = false;
     static constexpr bool FACTOR_LDS = false;
+    static constexpr bool FACTOR_REC = false;
     static constexpr bool SWEEP_CALL = GUSTO_TO4_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }
@@ -197,6 +220,7 @@ template <> struct MT<GUSTO_TO_ASTROBEE_SE3> {
     static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_DPP = false;
     static constexpr bool FACTOR_LDS = false;
+    static constexpr bool FACTOR_REC = false;
     static constexpr bool SWEEP_CALL = GUSTO_TO_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }
@@ -215,6 +239,7 @@ template <> struct MT<GUSTO_TO_ASTROBEE_SE3_MANIFOLD> {
     static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_DPP = false;
     static constexpr bool FACTOR_LDS = false;
+    static constexpr bool FACTOR_REC = false;
     static constexpr bool SWEEP_CALL = GUSTO_TO_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }
@@ -841,6 +866,37 @@ template <int m> GD bool chol_inv(const double* S, double* Li) {
         }
     }
     return ok;
+}
+// Entry (a, b) = (b, a) of S^-1 = L^-T L^-1 from Li = L^-1 (lower, row-major m x m), b <= a.  One expression for the factor stage
+// (factor_sweep_pg2) and for the mid phase, which forms S^-1 itself under GUSTO_FACTOR_LAZY_SINV.
+template <int m> GD double sinv_entry(const double* Li, int a, int b) {
+    double s1 = 0;
+#pragma unroll
+    for (int l = a; l < m; l++) s1 += Li[l * m + a] * Li[l * m + b];
+    return s1;
+}
+// Entry a of L^-T v from Li = L^-1: a column of D = L^-T V (the goal chain's tail, or the mid phase under GUSTO_FACTOR_LAZY_D)
+template <int m> GD double lt_entry(const double* Li, const double* v, int a) {
+    double s2 = 0;
+#pragma unroll
+    for (int l = a; l < m; l++) s2 += Li[l * m + a] * v[l];
+    return s2;
+}
+// lane Q of this lane's row of 16 lanes (DPP row_newbcast, gfx90a and later): a VALU move, no scalar registers, no LDS
+template <int Q> GD double row_bcast_f64(double v) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const int lo = (int)(u & 0xffffffffu), hi = (int)(u >> 32);
+    const unsigned rl = (unsigned)__builtin_amdgcn_update_dpp(0, lo, 0x150 + Q, 0xf, 0xf, true);
+    const unsigned rh = (unsigned)__builtin_amdgcn_update_dpp(0, hi, 0x150 + Q, 0xf, 0xf, true);
+    return __builtin_bit_cast(double, ((unsigned long long)rh << 32) | rl);
+}
+// ... lanes 0 .. 5 of the row at once as six v_mov_b64_dpp (tools/ub/dpp.hip, k3: 18 ticks per six cheaper than the 12 32-bit moves
+// above in a dependent chain, but one block the compiler can neither open nor cover the DPP read hazard of by scheduling: s_nop 1)
+GD void row_bcast6_b64(double v, double* s) {
+    asm("s_nop 1\n\tv_mov_b64_dpp %0, %6 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\tv_mov_b64_dpp %1, %6 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
+        "v_mov_b64_dpp %2, %6 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\tv_mov_b64_dpp %3, %6 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
+        "v_mov_b64_dpp %4, %6 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\tv_mov_b64_dpp %5, %6 row_newbcast:5 row_mask:0xf bank_mask:0xf"
+        : "=&v"(s[0]), "=&v"(s[1]), "=&v"(s[2]), "=&v"(s[3]), "=&v"(s[4]), "=&v"(s[5]) : "v"(v));
 }
 
 // runtime-size SPD inverse in memory (LDS), single thread; used for the ng x ng goal system

@@ -512,6 +512,15 @@ template <int MODEL> GD void factor_sweep_1w(SweepView<MODEL> K, double* fail, P
 //          (the tail's stores, the head's reads, about 150 cycles) run inside it.  Bit-identical, and measured as no gain on top
 //          of the other two (profiles/r09_factor_stage_lds.txt, section 2), so S = H_uu still comes by v_readlane.
 // All of it stays inside the LDS words this sweep alone uses (the H, Z and T buffers of LdsC): no offset of LdsC moves.
+// MT::FACTOR_REC (freeflyerSE2; common.hpp: GUSTO_FACTOR_HUU_DPP, _LAZY_SINV, _LAZY_D; profiles/r10_factor_recursion.txt) leaves only
+// the recursion on the sequential path -- same sums in the same order:
+//   _HUU_DPP    (OFF by default: measured slower in place than the lane reads) a lane's entry of H follows hmap, not K.lut's order:
+//               lanes 0 .. 5 of EVERY row of 16 lanes form the upper triangle of H_uu (four copies from the same operands: the same bits), lanes 6 .. 15 ten of the other 39 entries, one lane nothing;
+//               S = H_uu then is row_newbcast:sidx(a, b, m) of h -- VALU moves inside the row, no v_readlane, no scalar registers,
+//               no LDS trip -- and the Cholesky runs on values uniform per row, which is all its consumers need
+//   _LAZY_SINV  the six doubles of the K | D | S^-1 slot behind K and D take the lower triangle of L^-1; S^-1 = L^-T L^-1 (10 fp64
+//               instructions per stage) is formed by mid_phase, its one reader, with lane k = knot k: twice per KKT solve, not N times
+//   _LAZY_D     the same for D = L^-T V: the slot of D takes V, mid_phase forms D (6 FMAs per tail against 36 per call)
 template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, Prof& pf) {
     using T = MT<MODEL>;
     using R = Rec<MODEL>;
@@ -525,13 +534,29 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
     constexpr bool F_MV = T::FACTOR_LDS && GUSTO_FACTOR_LDS_MV, F_HUU = T::FACTOR_LDS && GUSTO_FACTOR_LDS_HUU,
                    F_ROWS = T::FACTOR_LDS && GUSTO_FACTOR_LDS_ROWS;
     static_assert(!(F_MV || F_HUU || F_ROWS) || (n == 6 && m == 3), "FACTOR_LDS: rows of three 128-bit reads, m = 2 + 1");
+    // MT::FACTOR_REC, item by item (common.hpp: GUSTO_FACTOR_HUU_DPP, _LAZY_SINV, _LAZY_D; all off: the stage as it was)
+    constexpr bool F_DPP = T::FACTOR_REC && GUSTO_FACTOR_HUU_DPP, F_LSINV = T::FACTOR_REC && GUSTO_FACTOR_LAZY_SINV,
+                   F_LD = T::FACTOR_REC && GUSTO_FACTOR_LAZY_D;
+    constexpr int NHU = m * (m + 1) / 2, NHY = NQ - NHU;   // packed entries of H: [0, NHY) rows 0 .. n-1, [NHY, NQ) the upper triangle of H_uu
+    static_assert(!(F_DPP && F_HUU) && (!F_LD || F_LSINV), "H_uu by DPP or through LDS; D from the stored L^-1");
+    // F_DPP: which packed entry of H a lane forms.  In every row of 16 lanes positions 0 .. NHU-1 form the upper triangle of H_uu (the same
+    // operands at the same LDS addresses, the same expression: the same bits in all four rows), positions NHU .. 15 the other entries,
+    // 16 - NHU per row; what is left over (one lane) forms nothing: -1
+    constexpr auto hmap = [](int t) { const int row = t >> 4, pos = t & 15, e = (16 - NHU) * row + pos - NHU; return pos < NHU ? NHY + pos : (e < NHY ? e : -1); };
+    static_assert(!F_DPP || (NHU == 6 && sidx(n, n, NZ) == NHY && 4 * (16 - NHU) >= NHY), "H_uu is the tail of the packed H; four rows hold the rest");
+    constexpr bool HMAP_ONCE = [&] { for (int e = 0; e < NHY; e++) { int c = 0; for (int t = 0; t < 64; t++) c += hmap(t) == e; if (c != 1) return false; } return true; }();
+    constexpr bool HMAP_HUU = [&] { for (int t = 0; t < 64; t++) if ((t & 15) < NHU ? hmap(t) != NHY + (t & 15) : hmap(t) >= NHY) return false; return true; }();
+    static_assert(!F_DPP || HMAP_ONCE, "every entry of rows 0 .. n-1 of H is formed by exactly one lane");
+    static_assert(!F_DPP || HMAP_HUU, "the upper triangle of H_uu sits at positions 0 .. 5 of each of the four rows of lanes, and nowhere else");
     // F_MV reads the pair (z0, z0 + n/2) of a row of Pi^T at the interleaved positions 2 z0, 2 z0 + 1: every column's first
     // structural row must lie in the upper half, its second n/2 below it
     constexpr bool PG_UPPER = [] { for (int c = 0; c < NZ; c++) if (!(T::pg_r0(c) < h3 && T::pg_r1(c) == T::pg_r0(c) + h3)) return false; return true; }();
     static_assert(!F_MV || PG_UPPER, "F_MV: pg_r0(c) < n/2 and pg_r1(c) = pg_r0(c) + n/2 for every column of [Phi Gam]");
     const int tid = K.tid, N = K.N;
     // ---- lane roles ----
-    const int ijh = K.lut[tid < NQ ? tid : 0], hc = ijh >> 8, hj = ijh & 255, i0 = T::pg_r0(hc), j0 = T::pg_r0(hj);   // H[hc][hj]
+    // (the packed entry of H this lane forms: K.lut's own order, entry tid, or under F_DPP hmap's; lanes without one read entry 0)
+#define HEQ_ (F_DPP ? (hmap(tid) >= 0 ? hmap(tid) : 0) : (tid < NQ ? tid : 0))
+    const int ijh = K.lut[HEQ_], hc = ijh >> 8, hj = ijh & 255, i0 = T::pg_r0(hc), j0 = T::pg_r0(hj);   // H[hc][hj]
     const int zc = tid < NZN ? tid / n : 0, zg = tid < NZN ? tid % n : 0, z0 = T::pg_r0(zc);                       // Z[zc][zg]
     const int ri = tid < n ? tid : 0;                                                                             // r[ri], Pi^T c [ri]
     const bool isnu = tid >= 8 && tid < 8 + n;                                                                    // (F_MV: Pi^T c [tid - 8])
@@ -544,7 +569,7 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
     const int dmy = C::sT0 + (tid & 15);             // dummy slot of this lane (+ immediates < 36 stay inside the T buffer)
     static_assert(n * NZ >= 16 + 36, "dummy slot");
     // F_HUU: the upper triangle of H_uu, six doubles packed row-major behind the dummy slots (its lanes write, every lane reads)
-    constexpr int oHuu = C::sT0 + 46, NHU = m * (m + 1) / 2;
+    constexpr int oHuu = C::sT0 + 46;
     static_assert(oHuu % 2 == 0 && 15 + (2 * m - 1) * n < 46 && 15 + NHU < 46 && 46 + NHU <= n * NZ, "H_uu behind the dummy slots, in the T buffer");
     // F_ROWS: rows of H at an even stride (H_uu is not among them: rows 0 .. n-1 only), Z_u transposed in rows of four doubles
     // on the first even offset of the Z buffer (Z_y is only ever read back by the lane that formed it: zR)
@@ -555,7 +580,7 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
     // (F_MV: the rows of the transposed Pi carry P's column interleave, so the pair a lane of Z needs is adjacent and even)
     const int oPP = C::sP + i0 * n + 2 * j0, oPZ = C::sPi + zg * n + (F_MV ? 2 * z0 : z0), oPr = C::sP + ri * n, oPir = C::sPi + ri * n;
     const int oRow = tid < n ? C::sP + tid * n : (isnu ? C::sPi + (tid - 8) * n : C::sP);   // (F_MV: row of P | of Pi^T of this lane)
-    const int wH1 = tid < NQ ? ((hc >= n && F_HUU) ? oHuu + sidx(hc - n, hj - n, m) : ((hc >= n && F_ROWS) ? dmy : C::sHh + hc * NZH + hj))
+    const int wH1 = (F_DPP ? hmap(tid) >= 0 : tid < NQ) ? ((hc >= n && F_HUU) ? oHuu + sidx(hc - n, hj - n, m) : ((hc >= n && F_ROWS) ? dmy : C::sHh + hc * NZH + hj))
                              : dmy;                                   // (upper triangle only: hc <= hj)
     const int wZ = tid < NZN ? (F_ROWS ? (zc >= n ? oZu + zg * 4 + (zc - n) : dmy) : C::sZ + tid) : dmy;
     const int oHi = C::sHh + i * NZH + n, oHj = C::sHh + j * NZH + n, oPn = C::sHh + (i < j ? i : j) * NZH + (i < j ? j : i);
@@ -591,7 +616,7 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
     L[wP] = 0.0; L[wPi] = 0.0; L[wZ] = 0.0;
     double gdR = 0.0, zR = 0.0;   // this lane's entry of Gd (accumulated over the sweep) and of Z (the Pi' term of the next tail)
     if (tid < R::SNN) K.Paft[(size_t)(N - 1) * R::SNN + tid] = 0.0;
-    double qq = K.kdl[(N - 1) * C::KDS + (tid < NQ ? tid : 0)];
+    double qq = K.kdl[(N - 1) * C::KDS + HEQ_];
     double LiP[m * m], wiP[m];   // L^-1 and this lane's column i of W of the stage before (tail operands)
 #pragma unroll
     for (int e = 0; e < m * m; e++) LiP[e] = 0.0;
@@ -611,19 +636,16 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
             for (int l = 0; l <= a; l++) { s3 += LiP[a * m + l] * zi[l]; s4 += LiP[a * m + l] * zj[l]; }
             vi[a] = s3; vj[a] = s4;
         }
+        if constexpr (!F_LD) {   // (F_LD: D = L^-T V is formed by the mid phase from the V stored below)
 #pragma unroll
-        for (int a = 0; a < m; a++) {
-            double s2 = 0;
-#pragma unroll
-            for (int l = a; l < m; l++) s2 += LiP[l * m + a] * vj[l];
-            dj[a] = s2;
+            for (int a = 0; a < m; a++) dj[a] = lt_entry<m>(LiP, vj, a);
         }
 #pragma unroll
         for (int l = 0; l < m; l++) { pin -= wiP[l] * vj[l]; gd += vi[l] * vj[l]; }
         L[wPi] = pin; gdR = gd;
         K.Paft[(size_t)(kt - 1) * R::SNN + eq] = pin;
 #pragma unroll
-        for (int a = 0; a < m; a++) L[wKD + kt * sKD + (m + a) * n] = dj[a];
+        for (int a = 0; a < m; a++) L[wKD + kt * sKD + (m + a) * n] = F_LD ? vj[a] : dj[a];
     };
 
     // ordering point for LDS traffic between lanes that leaves the ALU work free to move (one wave: the hardware keeps
@@ -670,7 +692,7 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
 #pragma unroll
             for (int l = 0; l < m; l++) { zi[l] = L[oZi + l * n]; zj[l] = L[oZj + l * n]; }
         }
-        const double qqn = K.kdl[((k > 0) ? k - 1 : 0) * C::KDS + (tid < NQ ? tid : 0)];   // (slot k-1 still holds QQ_{k-1})
+        const double qqn = K.kdl[((k > 0) ? k - 1 : 0) * C::KDS + HEQ_];   // (slot k-1 still holds QQ_{k-1})
         // ---- value function chain, first half: H, r_k = P_k c_k ----
         const double h = qq + c.a0 * (c.b0 * p00 + c.b1 * p01) + c.a1 * (c.b0 * p10 + c.b1 * p11);
         L[wH1] = h;
@@ -686,6 +708,17 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
         if constexpr (F_HUU) {   // three broadcast reads of the packed upper triangle its six lanes have just stored
             const v2d s0 = ld2(oHuu), s1 = ld2(oHuu + 2), s2 = ld2(oHuu + 4);
             const double su[NHU] = {s0.x, s0.y, s1.x, s1.y, s2.x, s2.y};
+#pragma unroll
+            for (int a = 0; a < m; a++)
+#pragma unroll
+                for (int b = 0; b < m; b++) S[a * m + b] = su[sidx(a, b, m)];
+        } else if constexpr (F_DPP) {   // lanes 0 .. 5 of this lane's row hold the upper triangle: uniform per row, the same bits in every row
+            double su[NHU];
+            if constexpr (GUSTO_FACTOR_HUU_DPP == 2) row_bcast6_b64(h, su);
+            else {
+                su[0] = row_bcast_f64<0>(h); su[1] = row_bcast_f64<1>(h); su[2] = row_bcast_f64<2>(h);
+                su[3] = row_bcast_f64<3>(h); su[4] = row_bcast_f64<4>(h); su[5] = row_bcast_f64<5>(h);
+            }
 #pragma unroll
             for (int a = 0; a < m; a++)
 #pragma unroll
@@ -761,16 +794,16 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
         K.Paft[(size_t)(k - 1) * R::SNN + ep] = pn;     // (record -1 exists for k == 0)
 #pragma unroll
         for (int a = 0; a < m; a++) L[wKD + k * sKD + a * n] = kj[a];
-        {   // S^-1 = L^-T L^-1, upper triangle (wave-uniform values)
+        if constexpr (F_LSINV) {   // the lower triangle of L^-1 in the slot of S^-1: the mid phase, its one reader, forms S^-1 = L^-T L^-1
 #pragma unroll
             for (int a = 0; a < m; a++)
 #pragma unroll
-                for (int b = 0; b <= a; b++) {
-                    double s1 = 0;
+                for (int b = 0; b <= a; b++) L[wSi + k * sSi + sidx(b, a, m)] = Li[a * m + b];
+        } else {   // S^-1 = L^-T L^-1, upper triangle (wave-uniform values)
 #pragma unroll
-                    for (int l = a; l < m; l++) s1 += Li[l * m + a] * Li[l * m + b];
-                    L[wSi + k * sSi + sidx(b, a, m)] = s1;
-                }
+            for (int a = 0; a < m; a++)
+#pragma unroll
+                for (int b = 0; b <= a; b++) L[wSi + k * sSi + sidx(b, a, m)] = sinv_entry<m>(Li, a, b);
         }
         qq = qqn;
 #pragma unroll
@@ -783,6 +816,7 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
     };
 #undef STAMP
 #undef STAMPS_END
+#undef HEQ_
 
     for (int k = N - 1; k >= 1; k--) stage(k, cN, k == N - 1);
     stage(0, c0, false);

@@ -1929,7 +1929,12 @@ template <int MODEL, class BLK, int NCH = 0> GD void mid_phase(BLK& K, int k, bo
     double th[n], d0[m];
     // (12/13-state models: the D record of the knot, 78 entries from the slot workspace, is walked once and kept for d_k = d0 + D mu_g
     // below -- this phase is a real call with registers of its own -- instead of walked again after the reductions)
-    constexpr bool KEEP_D = T::SWEEP_CALL && BLK::ONE && !BLK::C::KD_LDS;
+    // MT::FACTOR_REC (freeflyerSE2, one wave: factor_sweep_pg2): the slot of S^-1 holds the lower triangle of L^-1 (REC_SINV) and the slot of
+    // D holds V = L^-1 Z_u (REC_D); lane k forms S^-1 = L^-T L^-1 and D = L^-T V of its knot here, twice per KKT solve, with the
+    // expressions the factor stage used 50 times in a row (common.hpp: sinv_entry, lt_entry) -- D once, kept for its second use below
+    constexpr bool REC = T::FACTOR_REC && BLK::ONE && BLK::C::KD_LDS && !SEG, REC_SINV = REC && GUSTO_FACTOR_LAZY_SINV, REC_D = REC && GUSTO_FACTOR_LAZY_D;
+    static_assert(!REC || (T::PG2 && !T::SWEEP_CALL && !T::MFMA), "FACTOR_REC: the kernel whose factor sweep is factor_sweep_pg2");
+    constexpr bool KEEP_D = (T::SWEEP_CALL && BLK::ONE && !BLK::C::KD_LDS) || REC_D;
     double Dk[KEEP_D ? m * n : 1];
 #pragma unroll
     for (int i = 0; i < (KEEP_D ? m * n : 1); i++) Dk[i] = 0;
@@ -1982,12 +1987,37 @@ template <int MODEL, class BLK, int NCH = 0> GD void mid_phase(BLK& K, int k, bo
             for (int l = 0; l < n; l++) if (T::Gnz(l, i)) s += Gamk[l * m + i] * tt[l];
             lu[i] = s;
         }
+        double Lk[REC_SINV ? m * m : 1], Sk[REC_SINV ? m * (m + 1) / 2 : 1];
+        if constexpr (REC_SINV) {
+#pragma unroll
+            for (int a = 0; a < m; a++)
+#pragma unroll
+                for (int b = 0; b < m; b++) Lk[a * m + b] = (b <= a) ? K.kdl[k * BLK::C::KDS + 2 * m * n + sidx(b, a, m)] : 0.0;
+#pragma unroll
+            for (int a = 0; a < m; a++)
+#pragma unroll
+                for (int b = 0; b <= a; b++) Sk[sidx(b, a, m)] = sinv_entry<m>(Lk, a, b);
+        }
 #pragma unroll
         for (int i = 0; i < m; i++) {
             double s = 0;
 #pragma unroll
-            for (int l = 0; l < m; l++) s += K.kdS(k, i, l) * lu[l];
+            for (int l = 0; l < m; l++) {
+                double sil;
+                if constexpr (REC_SINV) sil = Sk[sidx(i, l, m)]; else sil = K.kdS(k, i, l);
+                s += sil * lu[l];
+            }
             d0[i] = s;
+        }
+        if constexpr (REC_D) {
+#pragma unroll
+            for (int j = 0; j < n; j++) {
+                double vj[m];
+#pragma unroll
+                for (int l = 0; l < m; l++) vj[l] = K.kd(k, R::oD + l * n + j);
+#pragma unroll
+                for (int a = 0; a < m; a++) Dk[a * n + j] = lt_entry<m>(Lk, vj, a);
+            }
         }
         // theta_j = sum_k Pi_k^T c_k - D_k^T lu_k  (+ C M rd_{N-1} - rg at the last knot)
         // LTI models: the last knot's goal term is evaluated by EVERY lane on its own knot's data and selected afterwards --
@@ -2026,8 +2056,12 @@ template <int MODEL, class BLK, int NCH = 0> GD void mid_phase(BLK& K, int k, bo
         for (int i = 0; i < m; i++)
 #pragma unroll
             for (int j = 0; j < n; j++) {
-                const double dij = K.kd(k, R::oD + i * n + j);
-                if constexpr (KEEP_D) Dk[i * n + j] = dij;
+                double dij;
+                if constexpr (REC_D) dij = Dk[i * n + j];
+                else {
+                    dij = K.kd(k, R::oD + i * n + j);
+                    if constexpr (KEEP_D) Dk[i * n + j] = dij;
+                }
                 thd[j] -= dij * lu[i];
             }
 #pragma unroll

@@ -206,9 +206,70 @@ __global__ void k2(long long* out, double* sink, double x0) {
         sink[448 + t] = k0; sink[512 + t] = k1;
     }
 }
+// ---- k3: six doubles of a row to every lane of the row (H_uu to the Cholesky of the factor stage) ----
+// One round hands the six doubles held by lanes 0 .. 5 of each row of 16 to every lane of that row and runs three dependent FMAs on
+// them; the value the next round hands on is that result, so eight rounds are one dependent chain.  V = 0: 12 v_readlane_b32 (lanes
+// 39 .. 44 of the wave, what factor_sweep_pg2 does), 1: six v_mov_b64_dpp row_newbcast:q, 2: 12 v_mov_b32_dpp row_newbcast:q as
+// __builtin_amdgcn_update_dpp(.., 0x150 + q, ..) emits them (hazards and order left to the compiler).
+template <int Q> __device__ __forceinline__ double bcast_b32x2(double x) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
+    const int lo = (int)(u & 0xffffffffu), hi = (int)(u >> 32);
+    const unsigned rl = (unsigned)__builtin_amdgcn_update_dpp(0, lo, 0x150 + Q, 0xf, 0xf, true);
+    const unsigned rh = (unsigned)__builtin_amdgcn_update_dpp(0, hi, 0x150 + Q, 0xf, 0xf, true);
+    return __builtin_bit_cast(double, ((unsigned long long)rh << 32) | rl);
+}
+template <int V> __device__ __forceinline__ void six(double x, double* s) {
+    if constexpr (V == 0) {
+        const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
+#pragma unroll
+        for (int q = 0; q < 6; q++)
+            s[q] = __builtin_bit_cast(double, ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(u >> 32), 39 + q) << 32) |
+                                               (unsigned)__builtin_amdgcn_readlane((int)(u & 0xffffffffu), 39 + q));
+    } else if constexpr (V == 1) {
+        asm("s_nop 1\n\tv_mov_b64_dpp %0, %6 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\tv_mov_b64_dpp %1, %6 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
+            "v_mov_b64_dpp %2, %6 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\tv_mov_b64_dpp %3, %6 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
+            "v_mov_b64_dpp %4, %6 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\tv_mov_b64_dpp %5, %6 row_newbcast:5 row_mask:0xf bank_mask:0xf"
+            : "=&v"(s[0]), "=&v"(s[1]), "=&v"(s[2]), "=&v"(s[3]), "=&v"(s[4]), "=&v"(s[5]) : "v"(x));
+    } else {
+        s[0] = bcast_b32x2<0>(x); s[1] = bcast_b32x2<1>(x); s[2] = bcast_b32x2<2>(x);
+        s[3] = bcast_b32x2<3>(x); s[4] = bcast_b32x2<4>(x); s[5] = bcast_b32x2<5>(x);
+    }
+}
+template <int V> __device__ __forceinline__ double rounds8(double x, double w) {
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        double s[6];
+        six<V>(x, s);
+        double f = __builtin_fma(s[0], s[1], s[2]);
+        f = __builtin_fma(f, s[3], s[4]);
+        x = __builtin_fma(f, w, s[5]);   // (every lane's next value: the chain goes on through all six)
+    }
+    return x;
+}
+__global__ void k3(long long* out, double* sink, double x0) {
+    const int t = threadIdx.x;
+    double a = x0 + t * 1e-3, b = 1e-3;
+    long long t0, t1;
+    U0(); a = rounds8<0>(a, b); U1(0);
+    U0(); a = rounds8<1>(a, b); U1(1);
+    U0(); a = rounds8<2>(a, b); U1(2);
+    sink[t] = a;
+    // where the values land: the six doubles of the lane ids
+    double s[6];
+    const double v = (double)t;
+    six<0>(v, s);
+#pragma unroll
+    for (int q = 0; q < 6; q++) sink[64 * (1 + q) + t] = s[q];
+    six<1>(v, s);
+#pragma unroll
+    for (int q = 0; q < 6; q++) sink[64 * (7 + q) + t] = s[q];
+    six<2>(v, s);
+#pragma unroll
+    for (int q = 0; q < 6; q++) sink[64 * (13 + q) + t] = s[q];
+}
 int main() {
     long long* out; double* sink;
-    hipMalloc(&out, 16 * sizeof(long long)); hipMalloc(&sink, 1024 * sizeof(double));
+    hipMalloc(&out, 16 * sizeof(long long)); hipMalloc(&sink, 1280 * sizeof(double));
     for (int rep = 0; rep < 2; rep++) hipLaunchKernelGGL(k, dim3(1), dim3(64), 0, 0, out, sink, 1.0);
     hipDeviceSynchronize();
     long long h[16]; double s[128];
@@ -247,5 +308,20 @@ int main() {
         }
     printf("two chunks with unit operands: %s (group 7 of chunk 1 holds %.0f, expect 16)\n", okc ? "ok" : "WRONG", s2[512 + 16 * 2 + 8]);
     bad += !okc;
+    // ---- k3: six doubles of a row to the whole row ----
+    for (int rep = 0; rep < 2; rep++) hipLaunchKernelGGL(k3, dim3(1), dim3(64), 0, 0, out, sink, 1.0);
+    hipDeviceSynchronize();
+    static double s3[1216];
+    hipMemcpy(h, out, sizeof(h), hipMemcpyDeviceToHost); hipMemcpy(s3, sink, sizeof(s3), hipMemcpyDeviceToHost);
+    const char* nm3[] = {"8 rounds: 12 v_readlane_b32 + 3 fma", "8 rounds: 6 v_mov_b64_dpp row_newbcast + 3 fma", "8 rounds: 12 v_mov_b32_dpp row_newbcast (update_dpp) + 3 fma"};
+    for (int i = 0; i < 3; i++) printf("%-72s %6lld ticks  %.1f per round\n", nm3[i], h[i], (double)h[i] / 8);
+    for (int i = 1; i < 3; i++) printf("  line %d against the readlane form: %+.1f ticks per round\n", i, (double)(h[i] - h[0]) / 8);
+    int ok3 = 1;
+    for (int q = 0; q < 6; q++)
+        for (int l = 0; l < 64; l++)
+            ok3 &= s3[64 * (1 + q) + l] == 39.0 + q && s3[64 * (7 + q) + l] == (double)((l & 48) + q) && s3[64 * (13 + q) + l] == (double)((l & 48) + q);
+    printf("six doubles of a row: %s (readlane: lane 17 holds %.0f, expect 39; b64 dpp q = 5: lane 17 holds %.0f, lane 63 %.0f, expect 21 53; b32 dpp: %.0f %.0f)\n",
+           ok3 ? "ok" : "WRONG", s3[64 + 17], s3[64 * 12 + 17], s3[64 * 12 + 63], s3[64 * 18 + 17], s3[64 * 18 + 63]);
+    bad += !ok3;
     return bad ? 1 : 0;
 }
