@@ -4,12 +4,15 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "gusto_hip.h"
 
 namespace gusto {
 
 #define GD __device__ __forceinline__
 typedef double v4d __attribute__((ext_vector_type(4)));   // accumulator tile of v_mfma_f64_16x16x4_f64
+typedef double v2d __attribute__((ext_vector_type(2)));   // a pair of the row state or an obstacle normal: one 128-bit access (RS_PAIR)
 
 // row kinds of the convex subproblem (scp_gusto.jl:192-314)
 constexpr int ROW_HARD = 0;     // hard inequality (convex_control_ineq, BoxGoal rows)          :213-221,236-245
@@ -77,6 +80,18 @@ constexpr int RS_T = 0, RS_LAM = 1, RS_LAMB = 2, RS_S = 3, RS_DT = 4, RS_DL = 5,
 #ifndef GUSTO_FACTOR_LAZY_D
 #define GUSTO_FACTOR_LAZY_D 1
 #endif
+// The row state of freeflyerSE2's one-wave kernel in PAIRS (RS_PAIR below; rows.hpp: RowState): variables that are always accessed
+// together sit next to each other per knot and move with one 128-bit access -- 26 -> 14 row-state accesses per row and KKT solve.
+//   GUSTO_RS_PAIR      the layout and the pair accesses of the Ops and prefetch buffers (0: RS_ROW, the kernel as it was)
+//   GUSTO_OBS_NH_PAIR  the obstacle normal of a (row, knot) as [obs][N][2]: one 128-bit access where linearize() wrote and the row
+//                      passes read its two components (MT::OBS_NH_PAIR; one-wave kernel, WS = 2)
+// Bit-identical either way (the same values, the same order of operations).
+#ifndef GUSTO_RS_PAIR
+#define GUSTO_RS_PAIR 1
+#endif
+#ifndef GUSTO_OBS_NH_PAIR
+#define GUSTO_OBS_NH_PAIR 0   // (built and bit-identical, a gain alone -- 0.8 % -- but none on top of GUSTO_RS_PAIR: profiles/r11_rowstate_pairs.txt, section 4)
+#endif
 static_assert(!(GUSTO_FACTOR_LDS_HUU && GUSTO_FACTOR_HUU_DPP), "H_uu to the Cholesky through LDS or by DPP, not both");
 static_assert(!GUSTO_FACTOR_LAZY_D || GUSTO_FACTOR_LAZY_SINV, "GUSTO_FACTOR_LAZY_D forms D from the L^-1 that GUSTO_FACTOR_LAZY_SINV stores");
 #ifndef GUSTO_USE_MFMA
@@ -94,13 +109,23 @@ constexpr double TRAJOPT_DEFECT_REG = 1e-4;
 //   RS_ROW       [slot][var][KP], KP = N padded to whole waves, the rows every knot has at compile-time slots; one scalar base, a
 //                32-bit lane offset aimed at the row and the distance of the variable as immediate (one-wave kernels) or scalar
 //   RS_ROW_LANE  as RS_ROW, but kernels with a run-time stride form the whole offset in the lane
-constexpr int RS_EARLIER = 0, RS_ROW = 1, RS_ROW_LANE = 2;
+//   RS_PAIR      [slot][plane][64]: four planes of pairs, [k][2] doubles at 16 bytes per knot -- (T, LAM), (S, LAMB), (DT, DL), (KA, KB) --
+//                then one plane of single doubles, DS: 9 doubles per row and knot as in RS_ROW, no padding.  A pair moves with ONE
+//                128-bit access at scalar base + 32-bit lane offset (k * 16 + a literal) + the plane as immediate.  Compile-time
+//                stride only (MT::RS_PAIRS: the one-wave kernel of the model; its other kernels keep MT::RS_FORM)
+constexpr int RS_EARLIER = 0, RS_ROW = 1, RS_ROW_LANE = 2, RS_PAIR = 3;
+constexpr int RS_NPAIR = 4, RS_PAIR_KP = 64;
+constexpr int RS_PAIR_A[RS_NPAIR] = {RS_T, RS_S, RS_DT, RS_KA}, RS_PAIR_B[RS_NPAIR] = {RS_LAM, RS_LAMB, RS_DL, RS_KB};   // (first, second) of a plane
+constexpr int rs_pair_plane(int var) { return var == RS_T || var == RS_LAM ? 0 : (var == RS_S || var == RS_LAMB ? 1 : (var == RS_DT || var == RS_DL ? 2 : (var == RS_KA || var == RS_KB ? 3 : -1))); }
+constexpr int rs_pair_half(int var) { return (var == RS_LAM || var == RS_LAMB || var == RS_DL || var == RS_KB) ? 1 : 0; }
 template <int MODEL> struct MT;
 template <> struct MT<GUSTO_FREEFLYER_SE2> {
     static constexpr int NDEF = 0;   // (no defect controls: the dynamics are hard rows)
     static constexpr int n = 6, m = 3, WS = 2, NFIX = 3, NHU = 2;
     static constexpr int WAVES_PER_EU = GUSTO_WAVES_PER_EU;   // register budget of the one-wave kernel: 512 / this
     static constexpr int RS_FORM = RS_ROW;   // layout and addressing of the row state, see RS_EARLIER .. RS_ROW_LANE above
+    static constexpr bool RS_PAIRS = GUSTO_RS_PAIR;   // ... of the one-wave kernel: RS_PAIR (common.hpp: rs_form)
+    static constexpr bool OBS_NH_PAIR = GUSTO_OBS_NH_PAIR;   // one-wave kernel: the obstacle normal as [obs][N][2], one 128-bit access (common.hpp: obs_nh_pair)
     static constexpr bool SWEEP_CALL = false;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool SWEEP_DPP = GUSTO_SWEEP_DPP;   // one-wave vector sweeps on the fp64 DPP broadcast (ipm.hpp:backward_sweep_dpp; needs n = 6, PG2)
     static constexpr bool FACTOR_LDS = GUSTO_FACTOR_LDS;   // factor stage laid out for one-address LDS reads (factor1w.hpp:factor_sweep_pg2; needs n = 6, m = 3, PG2)
@@ -356,7 +381,17 @@ template <int MODEL, bool ONE> GD int rs_stride(int N) {
     else return rs_stride_rt<MODEL>(N);
 }
 // the form of a kernel's accesses: RS_ROW_LANE is for run-time strides only
-template <int MODEL, bool ONE> constexpr int rs_form() { return (ONE && MT<MODEL>::RS_FORM == RS_ROW_LANE) ? RS_ROW : MT<MODEL>::RS_FORM; }
+// (the two traits of the paired forms are optional: a model without them has neither)
+template <int MODEL, class = void> struct rs_pair_trait { static constexpr bool value = false; };
+template <int MODEL> struct rs_pair_trait<MODEL, std::void_t<decltype(MT<MODEL>::RS_PAIRS)>> { static constexpr bool value = MT<MODEL>::RS_PAIRS; };
+template <int MODEL, class = void> struct nh_pair_trait { static constexpr bool value = false; };
+template <int MODEL> struct nh_pair_trait<MODEL, std::void_t<decltype(MT<MODEL>::OBS_NH_PAIR)>> { static constexpr bool value = MT<MODEL>::OBS_NH_PAIR; };
+template <int MODEL, bool ONE> constexpr int rs_form() {
+    if (ONE && rs_pair_trait<MODEL>::value) return RS_PAIR;   // (the same slab size as RS_ROW: 9 * 64 doubles per slot)
+    return (ONE && MT<MODEL>::RS_FORM == RS_ROW_LANE) ? RS_ROW : MT<MODEL>::RS_FORM;
+}
+// the obstacle normals of a one-wave kernel as [obs][N][2] (MT::OBS_NH_PAIR; ipm.hpp: linearize, rows.hpp: visit_obs_rows)
+template <int MODEL, bool ONE> constexpr bool obs_nh_pair() { return ONE && MT<MODEL>::WS == 2 && nh_pair_trait<MODEL>::value; }
 
 // per-problem global workspace, offsets in doubles
 struct WsLayout {

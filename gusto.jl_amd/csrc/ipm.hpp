@@ -443,6 +443,12 @@ template <int MODEL, class BLK> GD void linearize(BLK& K, double toggle) {
                 if (dist < toggle) {
                     mask |= (uint64_t)1 << i;
                     double c0 = K.P.mp.clearance - dist;
+                    if constexpr (obs_nh_pair<MODEL, BLK::ONE>()) {   // [obs][N][2]: the two components with one 128-bit store
+                        typedef __attribute__((address_space(1))) v2d GP;
+                        *(GP*)((K.obs_nh + (size_t)i * 2 * K.N).p + 2 * k) = v2d{nh[0], nh[1]};
+#pragma unroll
+                        for (int j = 0; j < T::WS; j++) c0 += nh[j] * xw[j];
+                    } else
 #pragma unroll
                     for (int j = 0; j < T::WS; j++) {
                         K.obs_nh[((size_t)i * T::WS + j) * K.N + k] = nh[j];
@@ -2445,7 +2451,7 @@ GD StepOut step_phase(BLK& K, const RowCtx<MODEL>& ctx, const RS& rs, int k, boo
             segw_rows_step_add<MODEL, NCH>(K.lds, K.P.ll.seg, k, (cs && NCH > 2) ? 1 : 0, op, gAx, gBx);
         } else
 #endif
-        visit_rows<MODEL>(ctx, xs, us, op);
+        visit_rows<MODEL, obs_nh_pair<MODEL, BLK::ONE>()>(ctx, xs, us, op);
         ctx.tick(3);
         if constexpr (ADJ) {
             // v_k = M_k^T (H_x dx_k + gx_k [+ mu_g at the last knot]) -> nun[k], the inhomogeneity of nu_k = Phi_k^T nu_{k+1} + v_k:
@@ -2588,7 +2594,7 @@ GD ResidOut resid_phase(BLK& K, const RowCtx<MODEL>& ctx, const RS& rs, int k, b
             segw_rows_resid_add<MODEL, NCH>(K.lds, K.P.ll.seg, k, NCH - 1, op, Hx, rdx, gx0);
         } else
 #endif
-        visit_rows<MODEL>(ctx, xs, us, op);
+        visit_rows<MODEL, obs_nh_pair<MODEL, BLK::ONE>()>(ctx, xs, us, op);
         ctx.tick(3);
         // row part of the predictor right-hand side, parked in the (currently free) step arrays
 #pragma unroll
@@ -2805,7 +2811,7 @@ template <int MODEL, class BLK, int NCH = 0> GD void ipm_solve(BLK& K, double De
 #pragma unroll
         for (int i = 0; i < m; i++) { us[i] = K.Up[k * m + i]; K.Uw[k * m + i] = us[i]; }
         OpInit<RS> op{rs, muw};
-        visit_rows<MODEL>(ctx, xs, us, op);
+        visit_rows<MODEL, obs_nh_pair<MODEL, BLK::ONE>()>(ctx, xs, us, op);
         ncomp_l = op.ncomp;
     }
     if (k == 0) {
@@ -3108,7 +3114,7 @@ template <int MODEL, class BLK, int NCH = 0> GD void ipm_solve(BLK& K, double De
 #pragma unroll
         for (int i = 0; i < m; i++) l_obj += ((i < m - T::NDEF) ? wk : TRAJOPT_DEFECT_REG * wk) * us[i] * us[i];
         OpSlackSum<RS> op{rs};
-        visit_rows<MODEL>(ctx, xs, us, op);
+        visit_rows<MODEL, obs_nh_pair<MODEL, BLK::ONE>()>(ctx, xs, us, op);
         l_obj += op.sum;
     }
     const double obj = block_reduce<BLK::ONE>(l_obj, OpSum(), red);

@@ -30,7 +30,7 @@ template <int MODEL> struct RowCtx {
     double kappa, omega, Delta;
     GPtr<const double> xp;      // linearisation state of this knot
     uint64_t mask;              // active obstacle rows (dist < obstacle_toggle_distance)
-    GPtr<const double> obs_nh;  // [n_obs][WS][N]
+    GPtr<const double> obs_nh;  // [n_obs][WS][N]  (visit_rows<MODEL, NHP = true>: [n_obs][N][2], common.hpp: obs_nh_pair)
     GPtr<const double> obs_c0;  // [n_obs][N]
     GPtr<const double> goal_lo;
     GPtr<const double> goal_hi;
@@ -102,7 +102,7 @@ template <int MODEL> struct RowSlots {
 // row's loads wait behind the stores of the row before it and a pass pays one memory round trip per active
 // obstacle (3-8 per knot for the freeflyer table, 15-25 in the ISS corner) -- four passes per interior point
 // iteration.  Lanes with fewer rows left aim the spare positions at their last row and skip them.
-template <int MODEL, class Op> GD void visit_obs_rows(const RowCtx<MODEL>& c, const double* xs, Op& op, uint64_t mk) {
+template <int MODEL, bool NHP = false, class Op> GD void visit_obs_rows(const RowCtx<MODEL>& c, const double* xs, Op& op, uint64_t mk) {
     using T = MT<MODEL>;
     const double kw = c.kappa * c.omega;
     const int slot_obs = RowSlots<MODEL>::obs(c.P->n_obs);
@@ -117,6 +117,16 @@ template <int MODEL, class Op> GD void visit_obs_rows(const RowCtx<MODEL>& c, co
             oi[q] = last; oslot[q] = slot_obs + last;
         }
         double ob[OBS_BATCH][T::WS], oc[OBS_BATCH];
+        if constexpr (NHP) {   // obs_nh as [n_obs][N][2]: the normal of (obstacle, knot) with one 128-bit load
+            static_assert(T::WS == 2, "a pair of doubles");
+            typedef __attribute__((address_space(1))) const v2d GP;
+#pragma unroll
+            for (int q = 0; q < OBS_BATCH; q++) {
+                const v2d nh = *(GP*)((c.obs_nh + (size_t)oi[q] * 2 * (size_t)c.N).p + 2 * c.k);
+                ob[q][0] = -nh.x; ob[q][1] = -nh.y;
+                oc[q] = (c.obs_c0 + (size_t)oi[q] * (size_t)c.N)[c.k];
+            }
+        } else
 #pragma unroll
         for (int q = 0; q < OBS_BATCH; q++) {
 #pragma unroll
@@ -160,7 +170,7 @@ template <int MODEL, class Op> GD void visit_ctl_rows(const RowCtx<MODEL>& c, co
 }
 
 // ---- the row programs ------------------------------------------------------------------------------
-template <int MODEL, class Op> GD void visit_rows(const RowCtx<MODEL>& c, const double* xs, const double* us, Op& op) {
+template <int MODEL, bool NHP = false, class Op> GD void visit_rows(const RowCtx<MODEL>& c, const double* xs, const double* us, Op& op) {
     using T = MT<MODEL>;
     constexpr int n = T::n;
     const gusto_model_params& mp = c.P->mp;
@@ -304,7 +314,7 @@ template <int MODEL, class Op> GD void visit_rows(const RowCtx<MODEL>& c, const 
         quad_row<false, 3, nv, GUSTO_FXB(T::NFIX - 2, T::NFIX - 2)>(op, slot++, ROW_PEN, xs, one, nullptr, -mp.hard_limit_vel * mp.hard_limit_vel, kw, 0.0);
         quad_row<false, iw, nw, GUSTO_FXB(T::NFIX - 1, T::NFIX - 1)>(op, slot++, ROW_PEN, xs, one, nullptr, -mp.hard_limit_omega * mp.hard_limit_omega, kw, 0.0);
         c.tick(1);   // fixed state rows; then the obstacle rows (visit_obs_rows)
-        visit_obs_rows<MODEL>(c, xs, op, c.mask);
+        visit_obs_rows<MODEL, NHP>(c, xs, op, c.mask);
         c.tick(2);   // obstacle rows
         if (!c.skip_ctl) visit_ctl_rows<MODEL>(c, us, op);
 #undef GUSTO_FXB
@@ -369,12 +379,32 @@ template <int MODEL, class Op> GD void visit_rows(const RowCtx<MODEL>& c, const 
 //   (32 bits: the block of the largest problem, 9 variables x ~110 slots x 256 knots, is 2 MB)
 // RS_EARLIER: base + (var * nslot + slot) * N + k, a scalar address per (variable, row) and the knot as lane index.
 // The form is a template parameter (common.hpp: rs_form): each kernel holds the code of its own form and nothing of the others.
-template <int FORM> struct RowState {
+// RS_PAIR (compile-time stride 64 only): a row slot is 9 * 64 doubles as in RS_ROW -- four planes of 64 pairs (1 KB each), then the
+//   64 doubles of DS.  The lane offset, slot * 4608 + 2048 + k * 16 (k * 8 for DS), points into the middle of the slot and the
+//   plane is the immediate: -2048, -1024, 0, +1024 for the pairs (+8: the second of a pair on its own), +2048 for DS -- all
+//   within the signed 13 bits.  Every slot, plane and pair is 16-byte aligned when the slab is (launch.hpp asserts it).
+template <int FORM_> struct RowState {
+    static constexpr int FORM = FORM_;
     GPtr<double> base;
     int nslot, kp, k;
+    static constexpr unsigned PSLOT = RS_NVAR * RS_PAIR_KP * 8u, PMID = 2u * RS_PAIR_KP * 16u;   // bytes per slot; the lane offset's literal
+    // the pair of plane pl (RS_PAIR_A[pl], RS_PAIR_B[pl]) of a row: one 128-bit access
+    GD auto& pair(int pl, int slot) const {
+        static_assert(FORM == RS_PAIR, "pairs exist in RS_PAIR only");
+        typedef __attribute__((address_space(1))) char GC;
+        typedef __attribute__((address_space(1))) v2d GP;
+        GC* r = (GC*)base.p + (size_t)((unsigned)slot * PSLOT + PMID + (unsigned)k * 16u);
+        return *(GP*)(r + (ptrdiff_t)((pl - 2) * RS_PAIR_KP * 16));
+    }
     GD auto& at(int var, int slot) const {
         if constexpr (FORM == RS_EARLIER) return (base + (size_t)(var * nslot + slot) * (size_t)kp)[k];
-        else {
+        else if constexpr (FORM == RS_PAIR) {   // one variable: DS, or one half of a pair
+            typedef __attribute__((address_space(1))) char GC;
+            typedef __attribute__((address_space(1))) double GV;
+            const int pl = rs_pair_plane(var);
+            GC* r = (GC*)base.p + (size_t)((unsigned)slot * PSLOT + PMID + (unsigned)k * (pl < 0 ? 8u : 16u));
+            return *(GV*)(r + (ptrdiff_t)(pl < 0 ? 2 * RS_PAIR_KP * 16 : (pl - 2) * RS_PAIR_KP * 16 + rs_pair_half(var) * 8));
+        } else {
             typedef __attribute__((address_space(1))) char GC;
             typedef __attribute__((address_space(1))) double GV;
             const int mid = FORM == RS_ROW_LANE ? var : RS_NVAR / 2;
@@ -390,6 +420,19 @@ template <int FORM> struct RowState {
 template <int NP> struct RowPre {
     double v[RS_NVAR][NP > 0 ? NP : 1];
     template <class RS, class F> GD void load(const RS& rs, int nfix, int slot_u, F&& want) {
+        if constexpr (RS::FORM == RS_PAIR) {   // a pair when either of its variables is wanted
+#pragma unroll
+            for (int pl = 0; pl < RS_NPAIR; pl++)
+#pragma unroll
+                for (int i = 0; i < NP; i++)
+                    if (want(RS_PAIR_A[pl]) || want(RS_PAIR_B[pl])) {
+                        const v2d p = rs.pair(pl, i < nfix ? i : slot_u + (i - nfix));
+                        v[RS_PAIR_A[pl]][i] = p.x; v[RS_PAIR_B[pl]][i] = p.y;
+                    }
+#pragma unroll
+            for (int i = 0; i < NP; i++)
+                if (want(RS_DS)) v[RS_DS][i] = rs.at(RS_DS, i < nfix ? i : slot_u + (i - nfix));
+        } else
 #pragma unroll
         for (int var = 0; var < RS_NVAR; var++)
 #pragma unroll
@@ -403,6 +446,21 @@ template <int NP> struct RowPre {
 struct ObsPre {
     double v[RS_NVAR][OBS_BATCH];
     template <class RS, class F> GD void load(const RS& rs, const int* slot, F&& want) {
+        if constexpr (RS::FORM == RS_PAIR) {
+#pragma unroll
+            for (int pl = 0; pl < RS_NPAIR; pl++)
+                if (want(RS_PAIR_A[pl]) || want(RS_PAIR_B[pl])) {
+#pragma unroll
+                    for (int q = 0; q < OBS_BATCH; q++) {
+                        const v2d p = rs.pair(pl, slot[q]);
+                        v[RS_PAIR_A[pl]][q] = p.x; v[RS_PAIR_B[pl]][q] = p.y;
+                    }
+                }
+            if (want(RS_DS)) {
+#pragma unroll
+                for (int q = 0; q < OBS_BATCH; q++) v[RS_DS][q] = rs.at(RS_DS, slot[q]);
+            }
+        } else
 #pragma unroll
         for (int var = 0; var < RS_NVAR; var++)
             if (want(var)) {
@@ -425,6 +483,26 @@ template <class RS> struct OpInit {
     int ncomp = 0;
     GD void obs_load(const int*) {}
     template <bool ISU, int I0, int CNT, int FX> GD void row(int slot, int kind, const RowEv<CNT>& ev) {
+        if constexpr (RS::FORM == RS_PAIR) {   // the same values, two pair stores per row: (T, LAM), (S, LAMB)
+            if (kind == ROW_EQ) {
+                rs.pair(0, slot) = v2d{1.0, 0.0}; rs.pair(1, slot) = v2d{0.0, 0.0};
+            } else if (row_is_hard(kind)) {
+                const double t = fmax(-ev.g, 1e-2), mu0 = (muw > 0) ? muw : 0.01;
+                rs.pair(0, slot) = v2d{t, mu0 / t}; rs.pair(1, slot) = v2d{0.0, 0.0};
+                ncomp += 1;
+            } else if (muw > 0) {
+                const double g = ev.g, ag = fabs(g), rr = sqrt(g * g + 4 * muw * muw);
+                const double big = muw + 0.5 * (rr + ag), small = muw + 2 * muw * muw / (rr + ag);
+                const double s = (g >= 0) ? big : small, t = (g >= 0) ? small : big;
+                rs.pair(1, slot) = v2d{s, muw / s}; rs.pair(0, slot) = v2d{t, muw / t};
+                ncomp += 2;
+            } else {
+                const double s = fmax(ev.g, 0.0) + 0.01;
+                rs.pair(1, slot) = v2d{s, 0.5}; rs.pair(0, slot) = v2d{s - ev.g, 0.5};
+                ncomp += 2;
+            }
+            return;
+        }
         if (kind == ROW_EQ) {   // (eta = 0; t, s, lamb are not used by an equality row)
             rs.at(RS_T, slot) = 1.0; rs.at(RS_LAM, slot) = 0.0; rs.at(RS_LAMB, slot) = 0.0; rs.at(RS_S, slot) = 0.0;
         } else if (row_is_hard(kind)) {
@@ -480,7 +558,10 @@ template <int n, int m, int NP, bool LRTR, class RS> struct OpResidHess {
             const double dl = get<FX>(RS_DL, slot);
             t += alpha_prev * get<FX>(RS_DT, slot);
             lam += alpha_prev * dl;
+            if constexpr (RS::FORM == RS_PAIR) rs.pair(0, slot) = v2d{t, lam};
+            else {
             rs.at(RS_T, slot) = t; rs.at(RS_LAM, slot) = lam;
+            }
         }
         if (kind == ROW_EQ) {   // (common.hpp: TRAJOPT_EQ_DELTA; lam = the multiplier eta, t is a constant 1)
             rp = ev.g;
@@ -494,7 +575,10 @@ template <int n, int m, int NP, bool LRTR, class RS> struct OpResidHess {
             if (alpha_prev != 0.0) {
                 s += alpha_prev * get<FX>(RS_DS, slot);
                 lamb -= alpha_prev * get<FX>(RS_DL, slot);
+                if constexpr (RS::FORM == RS_PAIR) rs.pair(1, slot) = v2d{s, lamb};
+                else {
                 rs.at(RS_S, slot) = s; rs.at(RS_LAMB, slot) = lamb;
+                }
             }
             rp = ev.g - s + t;
             comp += t * lam + s * lamb;
@@ -583,6 +667,7 @@ template <int NP, bool HDX, class RS> struct OpStep {
         double dt, dl, ds;
         double cA = 0, cB = 0;   // (pass 0) corrector coefficient = cA + mu_t cB
         double sig = 0;          // (HDX) the row's weight in the condensed Hessian, as OpResidHess forms it
+        double kbn = 0.0;        // (RS_PAIR, pass 0) the row's new KB: leaves with KA in one store; a hard row writes 0 into the half nothing reads
         if (kind == ROW_EQ) {    // d_eta = (h + grad' dx) / delta: nothing here has a sign to keep, no step-length test
             sig = 1.0 / TRAJOPT_EQ_DELTA;
             dl = sig * (ev.g + w);
@@ -592,12 +677,16 @@ template <int NP, bool HDX, class RS> struct OpStep {
                 for (int a = 0; a < CNT; a++) hdx[I0 + a] += sw * ev.gr[a];
             }
             if (pass == 0) {     // the corrector's coefficient of an equality row has no second-order term and no mu_t
+                if constexpr (RS::FORM == RS_PAIR) rs.pair(3, slot) = v2d{0.0, 0.0};
+                else
                 rs.at(RS_KA, slot) = 0.0;
                 const double cE = lam + sig * ev.g;
                 double* gA = ISU ? gAu : gAx;
 #pragma unroll
                 for (int a = 0; a < CNT; a++) gA[I0 + a] += cE * ev.gr[a];
             }
+            if constexpr (RS::FORM == RS_PAIR) { if (pass) { rs.pair(2, slot) = v2d{0.0, dl}; rs.at(RS_DS, slot) = 0.0; } }
+            else
             if (pass) { rs.at(RS_DT, slot) = 0.0; rs.at(RS_DL, slot) = dl; rs.at(RS_DS, slot) = 0.0; }
             return;
         }
@@ -624,7 +713,10 @@ template <int NP, bool HDX, class RS> struct OpStep {
             amax.test(s, ds, tau);
             amax.test(lamb, -dl, tau);
             if (pass == 0) {
-                c0 += s * lamb; c1 += ds * lamb - s * dl; c2 -= ds * dl; rs.at(RS_KB, slot) = -ds * dl;
+                c0 += s * lamb; c1 += ds * lamb - s * dl; c2 -= ds * dl;
+                if constexpr (RS::FORM == RS_PAIR) kbn = -ds * dl;
+                else
+                rs.at(RS_KB, slot) = -ds * dl;
                 // with ka = dt dl, kb = -ds dl:  rho0 = mu_t (1 - lol) - t lam - ka + lam rp + lol (s lamb + kb)
                 cA = lam + (lam * rp - t * lam - dt * dl + lol * (s * lamb - ds * dl)) * rD;
                 cB = (1.0 - lol) * rD;
@@ -638,7 +730,10 @@ template <int NP, bool HDX, class RS> struct OpStep {
         amax.test(t, dt, tau);
         amax.test(lam, dl, tau);
         if (pass == 0) {
-            c0 += t * lam; c1 += dt * lam + t * dl; c2 += dt * dl; rs.at(RS_KA, slot) = dt * dl;
+            c0 += t * lam; c1 += dt * lam + t * dl; c2 += dt * dl;
+            if constexpr (RS::FORM == RS_PAIR) rs.pair(3, slot) = v2d{dt * dl, kbn};
+            else
+            rs.at(RS_KA, slot) = dt * dl;
             double* gA = ISU ? gAu : gAx;
             double* gB = ISU ? gBu : gBx;
 #pragma unroll
@@ -646,6 +741,8 @@ template <int NP, bool HDX, class RS> struct OpStep {
         }
         // (the predictor's steps only feed alpha_aff and the second-order terms: the corrector overwrites them, and a
         //  problem without a corrector pass -- ncomp == 0 -- has no rows)
+        if constexpr (RS::FORM == RS_PAIR) { if (pass) { rs.pair(2, slot) = v2d{dt, dl}; rs.at(RS_DS, slot) = ds; } }
+        else
         if (pass) { rs.at(RS_DT, slot) = dt; rs.at(RS_DL, slot) = dl; rs.at(RS_DS, slot) = ds; }
     }
 };
