@@ -12,7 +12,7 @@ namespace gusto {
 
 #define GD __device__ __forceinline__
 typedef double v4d __attribute__((ext_vector_type(4)));   // accumulator tile of v_mfma_f64_16x16x4_f64
-typedef double v2d __attribute__((ext_vector_type(2)));   // a pair of the row state or an obstacle normal: one 128-bit access (RS_PAIR)
+typedef double v2d __attribute__((ext_vector_type(2)));   // a pair of the row state: one 128-bit access (RS_PAIR)
 
 // row kinds of the convex subproblem (scp_gusto.jl:192-314)
 constexpr int ROW_HARD = 0;     // hard inequality (convex_control_ineq, BoxGoal rows)          :213-221,236-245
@@ -43,57 +43,6 @@ constexpr int RS_T = 0, RS_LAM = 1, RS_LAMB = 2, RS_S = 3, RS_DT = 4, RS_DL = 5,
 #ifndef GUSTO_TO4_SWEEP_CALL
 #define GUSTO_TO4_SWEEP_CALL true   // ... of the freeflyer TrajOpt kernel (B = 1024: 58.3 -> 53.4 ms; the same schedule, results within 1e-9: contraction differs across the call)
 #endif
-#ifndef GUSTO_SWEEP_DPP
-// the one-wave vector sweeps of freeflyerSE2 on v_fmac_f64_dpp row_newbcast with row swaps between the rows of 16 lanes
-// (ipm.hpp: backward_sweep_dpp); -DGUSTO_SWEEP_DPP=0: the v_readlane sweeps (A/B measurements).  Bit-identical either way.
-#define GUSTO_SWEEP_DPP 1
-#endif
-#ifndef GUSTO_FACTOR_LDS
-// the factor stage of freeflyerSE2 (factor1w.hpp: factor_sweep_pg2) with fewer LDS instructions: one stream for r_k = P_k c_k and
-// Pi_k^T c_k (_MV) and operand rows laid out for 128-bit reads (_ROWS); H_uu to the Cholesky by broadcast reads instead of
-// v_readlane (_HUU) is built but off, it measured no gain of its own.  -DGUSTO_FACTOR_LDS=0: the stage as it was (A/B
-// measurements); the sub-switches take one item out or put _HUU in.  Bit-identical either way.
-#define GUSTO_FACTOR_LDS 1
-#endif
-#ifndef GUSTO_FACTOR_LDS_MV
-#define GUSTO_FACTOR_LDS_MV 1
-#endif
-#ifndef GUSTO_FACTOR_LDS_HUU
-#define GUSTO_FACTOR_LDS_HUU 0   // (built and bit-identical, but no measured gain on top of the other two: profiles/r09_factor_stage_lds.txt, section 2)
-#endif
-#ifndef GUSTO_FACTOR_LDS_ROWS
-#define GUSTO_FACTOR_LDS_ROWS 1
-#endif
-// MT::FACTOR_REC (freeflyerSE2's one-wave kernel): only the recursion P_k -> H -> chol(H_uu) -> W -> P_{k-1} (and Pi_k -> Z -> V ->
-// Pi_{k-1}, Gd) stays on the sequential path of the factor stage (factor1w.hpp: factor_sweep_pg2), item by item:
-//   _HUU_DPP    (OFF by default) every row of 16 lanes forms H_uu in its lanes 0 .. 5 and the Cholesky takes it by DPP row_newbcast: no v_readlane
-//               (1: 12 v_mov_b32_dpp the compiler schedules, 2: one block of six v_mov_b64_dpp)
-//   _LAZY_SINV  the stage stores L^-1 where it stored S^-1; S^-1 = L^-T L^-1 is formed by its one reader, the stage-parallel mid phase
-//   _LAZY_D     the stage stores V = L^-1 Z_u where it stored D = L^-T V; the mid phase forms D (needs _LAZY_SINV: L^-1 in the slot)
-// All 0: the stage as it was, instruction for instruction.  Bit-identical either way (the same sums in the same order).
-#ifndef GUSTO_FACTOR_HUU_DPP
-#define GUSTO_FACTOR_HUU_DPP 0   // (built and bit-identical, but slower in place than the 12 v_readlane_b32: profiles/r10_factor_recursion.txt, section 2)
-#endif
-#ifndef GUSTO_FACTOR_LAZY_SINV
-#define GUSTO_FACTOR_LAZY_SINV 1
-#endif
-#ifndef GUSTO_FACTOR_LAZY_D
-#define GUSTO_FACTOR_LAZY_D 1
-#endif
-// The row state of freeflyerSE2's one-wave kernel in PAIRS (RS_PAIR below; rows.hpp: RowState): variables that are always accessed
-// together sit next to each other per knot and move with one 128-bit access -- 26 -> 14 row-state accesses per row and KKT solve.
-//   GUSTO_RS_PAIR      the layout and the pair accesses of the Ops and prefetch buffers (0: RS_ROW, the kernel as it was)
-//   GUSTO_OBS_NH_PAIR  the obstacle normal of a (row, knot) as [obs][N][2]: one 128-bit access where linearize() wrote and the row
-//                      passes read its two components (MT::OBS_NH_PAIR; one-wave kernel, WS = 2)
-// Bit-identical either way (the same values, the same order of operations).
-#ifndef GUSTO_RS_PAIR
-#define GUSTO_RS_PAIR 1
-#endif
-#ifndef GUSTO_OBS_NH_PAIR
-#define GUSTO_OBS_NH_PAIR 0   // (built and bit-identical, a gain alone -- 0.8 % -- but none on top of GUSTO_RS_PAIR: profiles/r11_rowstate_pairs.txt, section 4)
-#endif
-static_assert(!(GUSTO_FACTOR_LDS_HUU && GUSTO_FACTOR_HUU_DPP), "H_uu to the Cholesky through LDS or by DPP, not both");
-static_assert(!GUSTO_FACTOR_LAZY_D || GUSTO_FACTOR_LAZY_SINV, "GUSTO_FACTOR_LAZY_D forms D from the L^-1 that GUSTO_FACTOR_LAZY_SINV stores");
 #ifndef GUSTO_USE_MFMA
 #define GUSTO_USE_MFMA true   // -DGUSTO_USE_MFMA=false: the VALU two-step contraction instead (A/B measurements)
 #endif
@@ -111,8 +60,9 @@ constexpr double TRAJOPT_DEFECT_REG = 1e-4;
 //   RS_ROW_LANE  as RS_ROW, but kernels with a run-time stride form the whole offset in the lane
 //   RS_PAIR      [slot][plane][64]: four planes of pairs, [k][2] doubles at 16 bytes per knot -- (T, LAM), (S, LAMB), (DT, DL), (KA, KB) --
 //                then one plane of single doubles, DS: 9 doubles per row and knot as in RS_ROW, no padding.  A pair moves with ONE
-//                128-bit access at scalar base + 32-bit lane offset (k * 16 + a literal) + the plane as immediate.  Compile-time
-//                stride only (MT::RS_PAIRS: the one-wave kernel of the model; its other kernels keep MT::RS_FORM)
+//                128-bit access at scalar base + 32-bit lane offset (k * 16 + a literal) + the plane as immediate: 14 row-state accesses
+//                per row and KKT solve where RS_ROW has 26.  Compile-time stride only (rs_form: the one-wave kernel of freeflyerSE2;
+//                its other kernels keep MT::RS_FORM)
 constexpr int RS_EARLIER = 0, RS_ROW = 1, RS_ROW_LANE = 2, RS_PAIR = 3;
 constexpr int RS_NPAIR = 4, RS_PAIR_KP = 64;
 constexpr int RS_PAIR_A[RS_NPAIR] = {RS_T, RS_S, RS_DT, RS_KA}, RS_PAIR_B[RS_NPAIR] = {RS_LAM, RS_LAMB, RS_DL, RS_KB};   // (first, second) of a plane
@@ -123,13 +73,9 @@ template <> struct MT<GUSTO_FREEFLYER_SE2> {
     static constexpr int NDEF = 0;   // (no defect controls: the dynamics are hard rows)
     static constexpr int n = 6, m = 3, WS = 2, NFIX = 3, NHU = 2;
     static constexpr int WAVES_PER_EU = GUSTO_WAVES_PER_EU;   // register budget of the one-wave kernel: 512 / this
-    static constexpr int RS_FORM = RS_ROW;   // layout and addressing of the row state, see RS_EARLIER .. RS_ROW_LANE above
-    static constexpr bool RS_PAIRS = GUSTO_RS_PAIR;   // ... of the one-wave kernel: RS_PAIR (common.hpp: rs_form)
-    static constexpr bool OBS_NH_PAIR = GUSTO_OBS_NH_PAIR;   // one-wave kernel: the obstacle normal as [obs][N][2], one 128-bit access (common.hpp: obs_nh_pair)
+    static constexpr int RS_FORM = RS_ROW;   // layout and addressing of the row state, see RS_EARLIER .. RS_ROW_LANE above (the one-wave kernel: RS_PAIR, rs_form)
     static constexpr bool SWEEP_CALL = false;   // factor sweep as a function call (ipm.hpp:factor_sweep)
-    static constexpr bool SWEEP_DPP = GUSTO_SWEEP_DPP;   // one-wave vector sweeps on the fp64 DPP broadcast (ipm.hpp:backward_sweep_dpp; needs n = 6, PG2)
-    static constexpr bool FACTOR_LDS = GUSTO_FACTOR_LDS;   // factor stage laid out for one-address LDS reads (factor1w.hpp:factor_sweep_pg2; needs n = 6, m = 3, PG2)
-    static constexpr bool FACTOR_REC = true;   // only the recursion on the factor stage's sequential path (GUSTO_FACTOR_HUU_DPP, _LAZY_SINV, _LAZY_D above; one-wave kernel)
+    static constexpr bool SWEEP_DPP = true;   // one-wave vector sweeps on v_fmac_f64_dpp row_newbcast with row swaps between the rows of 16 lanes (ipm.hpp:backward_sweep_dpp; needs n = 6, PG2)
     static constexpr bool MFMA = false;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 2;   // default number of one-trip probing slices of the longest-first scheduler
     static constexpr int SCHED_SLICE = 4;   // then slices of 4 trips for problems of penalty level 0 (34.1 vs 34.65 ms; the 12/13-state models lose with any)
@@ -156,8 +102,6 @@ template <> struct MT<GUSTO_DUBINS_CAR> {
     static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_CALL = false;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool SWEEP_DPP = false;
-    static constexpr bool FACTOR_LDS = false;
-    static constexpr bool FACTOR_REC = false;
     static constexpr bool MFMA = false;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (short problems: 2 slices cost more than they order -- 316 vs 211 ms at B = 65 536)
     static constexpr bool LTI = false, HAS_OBS = false;
@@ -177,8 +121,6 @@ template <> struct MT<GUSTO_ASTROBEE_SE3> {
     static constexpr int RS_FORM = RS_ROW_LANE;   // (lane form: the only one that adds nothing to the scratch of its multi-wave kernel)
     static constexpr bool SWEEP_CALL = true;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool SWEEP_DPP = false;
-    static constexpr bool FACTOR_LDS = false;
-    static constexpr bool FACTOR_REC = false;
     static constexpr bool MFMA = GUSTO_USE_MFMA;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (measured with raised-penalty problems ahead of fresh ones: 123.0 / 127.1 / 132.7 ms for 1 / 2 / 3 slices)
     static constexpr bool LTI = false, HAS_OBS = true;
@@ -203,8 +145,6 @@ template <> struct MT<GUSTO_ASTROBEE_SE3_MANIFOLD> {
     static constexpr int RS_FORM = RS_EARLIER;   // (config 5 measured 0.9 % slower with RS_ROW: profiles/r07_rowstate_layout.txt)
     static constexpr bool SWEEP_CALL = true ;   // factor sweep as a function call (ipm.hpp:factor_sweep)
     static constexpr bool SWEEP_DPP = false;
-    static constexpr bool FACTOR_LDS = false;
-    static constexpr bool FACTOR_REC = false;
     static constexpr bool MFMA = GUSTO_USE_MFMA;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 1; static constexpr int SCHED_SLICE = 0;   // (130.1 / 133.7 / 130.9 ms for 1 / 2 / 3 slices)
     static constexpr bool LTI = false, HAS_OBS = true;
@@ -227,8 +167,6 @@ template <> struct MT<GUSTO_TO_FREEFLYER_SE2> {
     static constexpr int WAVES_PER_EU = 1, SCHED_PROBE = 0, SCHED_SLICE = 0;
     static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_DPP = false;
-    static constexpr bool FACTOR_LDS = false;
-    static constexpr bool FACTOR_REC = false;
     static constexpr bool SWEEP_CALL = GUSTO_TO4_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }
@@ -244,8 +182,6 @@ template <> struct MT<GUSTO_TO_ASTROBEE_SE3> {
     static constexpr int WAVES_PER_EU = 1, SCHED_PROBE = 0, SCHED_SLICE = 0;
     static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_DPP = false;
-    static constexpr bool FACTOR_LDS = false;
-    static constexpr bool FACTOR_REC = false;
     static constexpr bool SWEEP_CALL = GUSTO_TO_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }
@@ -263,8 +199,6 @@ template <> struct MT<GUSTO_TO_ASTROBEE_SE3_MANIFOLD> {
     static constexpr int WAVES_PER_EU = 1, SCHED_PROBE = 0, SCHED_SLICE = 0;
     static constexpr int RS_FORM = RS_ROW;
     static constexpr bool SWEEP_DPP = false;
-    static constexpr bool FACTOR_LDS = false;
-    static constexpr bool FACTOR_REC = false;
     static constexpr bool SWEEP_CALL = GUSTO_TO_SWEEP_CALL, MFMA = false, LTI = false, HAS_OBS = true, PG2 = false;
     static constexpr int pg_r0(int) { return 0; }
     static constexpr int pg_r1(int) { return 0; }
@@ -381,17 +315,10 @@ template <int MODEL, bool ONE> GD int rs_stride(int N) {
     else return rs_stride_rt<MODEL>(N);
 }
 // the form of a kernel's accesses: RS_ROW_LANE is for run-time strides only
-// (the two traits of the paired forms are optional: a model without them has neither)
-template <int MODEL, class = void> struct rs_pair_trait { static constexpr bool value = false; };
-template <int MODEL> struct rs_pair_trait<MODEL, std::void_t<decltype(MT<MODEL>::RS_PAIRS)>> { static constexpr bool value = MT<MODEL>::RS_PAIRS; };
-template <int MODEL, class = void> struct nh_pair_trait { static constexpr bool value = false; };
-template <int MODEL> struct nh_pair_trait<MODEL, std::void_t<decltype(MT<MODEL>::OBS_NH_PAIR)>> { static constexpr bool value = MT<MODEL>::OBS_NH_PAIR; };
 template <int MODEL, bool ONE> constexpr int rs_form() {
-    if (ONE && rs_pair_trait<MODEL>::value) return RS_PAIR;   // (the same slab size as RS_ROW: 9 * 64 doubles per slot)
+    if (ONE && MODEL == GUSTO_FREEFLYER_SE2) return RS_PAIR;   // (the same slab size as RS_ROW: 9 * 64 doubles per slot)
     return (ONE && MT<MODEL>::RS_FORM == RS_ROW_LANE) ? RS_ROW : MT<MODEL>::RS_FORM;
 }
-// the obstacle normals of a one-wave kernel as [obs][N][2] (MT::OBS_NH_PAIR; ipm.hpp: linearize, rows.hpp: visit_obs_rows)
-template <int MODEL, bool ONE> constexpr bool obs_nh_pair() { return ONE && MT<MODEL>::WS == 2 && nh_pair_trait<MODEL>::value; }
 
 // per-problem global workspace, offsets in doubles
 struct WsLayout {
@@ -471,6 +398,13 @@ template <int MODEL, bool ONE> struct LdsC {
     static constexpr int KDS = (KDW > NZ * (NZ + 1) / 2) ? KDW : NZ * (NZ + 1) / 2;
     static constexpr bool PHICL_LDS = n <= 8 && !PHI_FROM_K;
 };
+// The kernel whose factor sweep is factor_sweep_pg2 (ipm.hpp: factor_sweep; freeflyerSE2, one wave).  That sweep keeps only the
+// recursion on its sequential path: the K | D | S^-1 slot of a knot holds the lower triangle of L^-1 where S^-1 = L^-T L^-1 would be
+// and V = L^-1 Z_u where D = L^-T V would be, and the stage-parallel mid phase (ipm.hpp: mid_phase), the one reader of both, forms
+// S^-1 and D of its knot.  factor_sweep() selects the sweep and mid_phase() its reading of the slot by this one trait.
+template <int MODEL, bool ONE> constexpr bool kd_holds_linv_v() {
+    return ONE && MT<MODEL>::PG2 && LdsC<MODEL, true>::KD_LDS && !MT<MODEL>::SWEEP_CALL && !MT<MODEL>::MFMA;
+}
 // The KKT solve as Riccati segments joined by coarse LQR stages (round 6; segw.hpp).
 //   GUSTO_SEG_W2 (on):  a WAVE PER CHAIN for the matrix-core kernels (astrobeeSE3, astrobeeSE3manifold): scp_kernel_w2, launched for
 //                       batches that leave SIMDs without a wave (launch.hpp: launch_scp)
@@ -902,36 +836,20 @@ template <int m> GD bool chol_inv(const double* S, double* Li) {
     }
     return ok;
 }
-// Entry (a, b) = (b, a) of S^-1 = L^-T L^-1 from Li = L^-1 (lower, row-major m x m), b <= a.  One expression for the factor stage
-// (factor_sweep_pg2) and for the mid phase, which forms S^-1 itself under GUSTO_FACTOR_LAZY_SINV.
+// Entry (a, b) = (b, a) of S^-1 = L^-T L^-1 from Li = L^-1 (lower, row-major m x m), b <= a: the mid phase, from the L^-1 that
+// factor_sweep_pg2 stores (kd_holds_linv_v) -- the sums factor_sweep_1w forms, in its order.
 template <int m> GD double sinv_entry(const double* Li, int a, int b) {
     double s1 = 0;
 #pragma unroll
     for (int l = a; l < m; l++) s1 += Li[l * m + a] * Li[l * m + b];
     return s1;
 }
-// Entry a of L^-T v from Li = L^-1: a column of D = L^-T V (the goal chain's tail, or the mid phase under GUSTO_FACTOR_LAZY_D)
+// Entry a of L^-T v from Li = L^-1: a column of D = L^-T V (the mid phase, from the V that factor_sweep_pg2 stores: kd_holds_linv_v)
 template <int m> GD double lt_entry(const double* Li, const double* v, int a) {
     double s2 = 0;
 #pragma unroll
     for (int l = a; l < m; l++) s2 += Li[l * m + a] * v[l];
     return s2;
-}
-// lane Q of this lane's row of 16 lanes (DPP row_newbcast, gfx90a and later): a VALU move, no scalar registers, no LDS
-template <int Q> GD double row_bcast_f64(double v) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    const int lo = (int)(u & 0xffffffffu), hi = (int)(u >> 32);
-    const unsigned rl = (unsigned)__builtin_amdgcn_update_dpp(0, lo, 0x150 + Q, 0xf, 0xf, true);
-    const unsigned rh = (unsigned)__builtin_amdgcn_update_dpp(0, hi, 0x150 + Q, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, ((unsigned long long)rh << 32) | rl);
-}
-// ... lanes 0 .. 5 of the row at once as six v_mov_b64_dpp (tools/ub/dpp.hip, k3: 18 ticks per six cheaper than the 12 32-bit moves
-// above in a dependent chain, but one block the compiler can neither open nor cover the DPP read hazard of by scheduling: s_nop 1)
-GD void row_bcast6_b64(double v, double* s) {
-    asm("s_nop 1\n\tv_mov_b64_dpp %0, %6 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\tv_mov_b64_dpp %1, %6 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mov_b64_dpp %2, %6 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\tv_mov_b64_dpp %3, %6 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mov_b64_dpp %4, %6 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\tv_mov_b64_dpp %5, %6 row_newbcast:5 row_mask:0xf bank_mask:0xf"
-        : "=&v"(s[0]), "=&v"(s[1]), "=&v"(s[2]), "=&v"(s[3]), "=&v"(s[4]), "=&v"(s[5]) : "v"(v));
 }
 
 // runtime-size SPD inverse in memory (LDS), single thread; used for the ng x ng goal system

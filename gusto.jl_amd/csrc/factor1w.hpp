@@ -478,120 +478,81 @@ template <int MODEL> GD void factor_sweep_1w(SweepView<MODEL> K, double* fail, P
     }
 }
 
-// The factor sweep of the double-integrator model (MT::PG2, one wave, K | D | S^-1 in LDS), software pipelined.
+// The factor sweep of the double-integrator model (MT::PG2, one wave, K | V | L^-1 in LDS: freeflyerSE2), software pipelined.
 // A stage has two chains: the value function (P_k -> H -> chol(H_uu) -> W -> P_{k-1}: the critical path, ~45 dependent
 // flops of a wave-uniform 3 x 3 Cholesky in its middle) and the goal sensitivities (Pi_k -> Z -> V = L^-1 Z_u ->
-// Pi_{k-1}, Gd, D), which needs L_k and W_k of the first chain but nothing the first chain waits for.  Written stage by
+// Pi_{k-1}, Gd), which needs L_k and W_k of the first chain but nothing the first chain waits for.  Written stage by
 // stage (factor_sweep_1w) the second chain sits behind the Cholesky of its own stage and the wave -- one per SIMD, in-order
 // issue -- idles through the factorisation.  Here iteration k runs stage k of the first chain together with the second
-// half of stage k+1 of the second (tail: V, Pi, Gd, D from the L and W kept in registers) and the first half of its stage k
+// half of stage k+1 of the second (tail: V, Pi, Gd from the L and W kept in registers) and the first half of its stage k
 // (head: Z = [Phi Gam]^T Pi_k, Pi_k^T c_k): independent instruction streams in one basic block.  To keep it ONE basic block
 // nothing is predicated: every LDS / global store is unconditional, lanes without an entry aim at a dummy slot (16 doubles
 // of the T buffer, which this path does not use), the last knot's E term is a select, the not-positive-definite flag is
 // accumulated and stored once after the sweep.  [Phi Gam] is constant over the sweep except at knot 0 ([0 | b_0], x_1 is
 // pinned): its entries live in registers and knot 0 is a peeled copy of the stage.  Same arithmetic as factor_sweep_1w,
 // operation for operation: the results are bit-identical.
+// Only the recursion is on the sequential path.  What the vector sweeps and the stage-parallel phases need but the next stage
+// does not is left to its reader: the slot of knot k takes K_k, V_k where D_k = L^-T V would be and the lower triangle of L^-1
+// where S^-1 = L^-T L^-1 would be, and mid_phase forms S^-1 and D with lane k = knot k, twice per KKT solve instead of N times
+// in a row (common.hpp: kd_holds_linv_v).
 // LDS traffic is what bounds a stage (measured: a wave issues one ds_read every ~8 cycles whatever its width up to 128 bits,
-// a ds_read2 costs two, a ds_write ~13, against 4 cycles for an fp64 FMA), so the operands are laid out for 128-bit reads:
-// P is kept with its columns interleaved (j, j + n/2 adjacent: the two entries a lane of H needs from a row are one
-// ds_read_b128) and read by ROWS for r_k = P c (P is exactly symmetric), Pi is kept transposed (the column for Pi^T c is a
-// row), only the upper triangle of H is written, and what a lane reads back from itself (its entry of Gd, its entry of Z)
-// stays in a register.
-// MT::FACTOR_LDS (freeflyerSE2; -DGUSTO_FACTOR_LDS=0 and its sub-switches, common.hpp: the stage without it, A/B measurements)
-// takes the two-address reads and a duplicated stream out of the stage -- same sums in the same order:
-//   _MV    the rows of the transposed Pi carry P's column interleave too, and r_k = P_k c_k (lanes 0 .. n-1) and Pi_k^T c_k (lanes
-//          8 .. 8+n-1) are ONE stream of 3 row reads, 3 reads of c_k, n FMAs and one store, issued where Pi_k (tail) and P_k
-//          (until L[wP]) are both in place; the pair of Pi a lane of Z needs is adjacent: one 128-bit read
-//   _ROWS  the rows of H sit at the even stride NZ + 1 (rows 0 .. n-1 only: H_uu is not read from there) and Z_u is stored
-//          transposed in rows of four doubles (Z_y nowhere: its only reader is the lane that formed it), so the m = 3 operands a
-//          lane needs from H_yu and from Z_u are one 128-bit and one 64-bit read each
-//   _HUU   (OFF by default) the six lanes of the upper triangle of H_uu store it packed (six doubles of the T buffer behind the
-//          dummy slots) and every lane fetches it for the Cholesky with three broadcast 128-bit reads instead of 12 v_readlane_b32.
-//          The store -> read round trip sits on the critical chain h -> chol and nothing arithmetic covers it: hipcc hoists the
-//          FMAs of the goal chain's tail in front of the store of h, so only the issue slots of the LDS instructions behind it
-//          (the tail's stores, the head's reads, about 150 cycles) run inside it.  Bit-identical, and measured as no gain on top
-//          of the other two (profiles/r09_factor_stage_lds.txt, section 2), so S = H_uu still comes by v_readlane.
-// All of it stays inside the LDS words this sweep alone uses (the H, Z and T buffers of LdsC): no offset of LdsC moves.
-// MT::FACTOR_REC (freeflyerSE2; common.hpp: GUSTO_FACTOR_HUU_DPP, _LAZY_SINV, _LAZY_D; profiles/r10_factor_recursion.txt) leaves only
-// the recursion on the sequential path -- same sums in the same order:
-//   _HUU_DPP    (OFF by default: measured slower in place than the lane reads) a lane's entry of H follows hmap, not K.lut's order:
-//               lanes 0 .. 5 of EVERY row of 16 lanes form the upper triangle of H_uu (four copies from the same operands: the same bits), lanes 6 .. 15 ten of the other 39 entries, one lane nothing;
-//               S = H_uu then is row_newbcast:sidx(a, b, m) of h -- VALU moves inside the row, no v_readlane, no scalar registers,
-//               no LDS trip -- and the Cholesky runs on values uniform per row, which is all its consumers need
-//   _LAZY_SINV  the six doubles of the K | D | S^-1 slot behind K and D take the lower triangle of L^-1; S^-1 = L^-T L^-1 (10 fp64
-//               instructions per stage) is formed by mid_phase, its one reader, with lane k = knot k: twice per KKT solve, not N times
-//   _LAZY_D     the same for D = L^-T V: the slot of D takes V, mid_phase forms D (6 FMAs per tail against 36 per call)
+// a ds_read2 costs two, a ds_write ~13, against 4 cycles for an fp64 FMA), so every operand is laid out for one-address reads
+// of up to 128 bits, inside the LDS words this sweep alone uses (the H, Z and T buffers of LdsC):
+//   P     with its columns interleaved (j, j + n/2 adjacent: the two entries a lane of H needs from a row are one ds_read_b128);
+//         r_k = P c reads it by ROWS (P is exactly symmetric)
+//   Pi    transposed (the column for Pi^T c is a row), its rows with P's column interleave: the pair a lane of Z needs is one
+//         128-bit read, and r_k = P_k c_k (lanes 0 .. n-1) and Pi_k^T c_k (lanes 8 .. 8+n-1) are ONE stream of 3 row reads, 3 reads
+//         of c_k, n FMAs and one store, issued where Pi_k (tail) and P_k (until L[wP]) are both in place
+//   H     the upper triangle of rows 0 .. n-1 only, at the even stride NZ + 1: the m = 3 operands a lane needs from H_yu are one
+//         128-bit and one 64-bit read.  H_uu is written nowhere: S = H_uu goes to every lane by 12 v_readlane_b32
+//   Z     Z_u transposed in rows of four doubles (the same two reads); Z_y nowhere, its only reader is the lane that formed it
+// and what a lane reads back from itself (its entry of Gd, its entry of Z) stays in a register.
 template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, Prof& pf) {
     using T = MT<MODEL>;
     using R = Rec<MODEL>;
     using C = LdsC<MODEL, true>;
     constexpr int n = T::n, m = T::m, NZ = n + m, NQ = NZ * (NZ + 1) / 2, NPG = n * NZ, NN = n * n, NZN = NZ * n, h3 = n / 2,
                   NH = n * (n + 1) / 2;
+    static_assert(kd_holds_linv_v<MODEL, true>(), "mid_phase reads L^-1 and V from the slot in exactly the kernel that runs this sweep");
     static_assert(T::PG2 && T::LTI && C::KD_LDS && NQ <= 64 && NZN <= 64 && NN <= 64 && n >= 2 * m, "shape");
+    static_assert(n == 6 && m == 3, "rows of three 128-bit reads, m = 2 + 1");
     static_assert(T::pg_r1(0) == T::pg_r0(0) + h3 && T::pg_r1(n) == T::pg_r0(n) + h3 && T::pg_r1(n - 1) == T::pg_r0(n - 1) + h3, "PG2 row pairs");
     static_assert(NH + NN < R::SNN && !C::BIG, "P | Pi record, dummy slot");
-    // MT::FACTOR_LDS, item by item (common.hpp: GUSTO_FACTOR_LDS*; all off: the stage as it was, instruction for instruction)
-    constexpr bool F_MV = T::FACTOR_LDS && GUSTO_FACTOR_LDS_MV, F_HUU = T::FACTOR_LDS && GUSTO_FACTOR_LDS_HUU,
-                   F_ROWS = T::FACTOR_LDS && GUSTO_FACTOR_LDS_ROWS;
-    static_assert(!(F_MV || F_HUU || F_ROWS) || (n == 6 && m == 3), "FACTOR_LDS: rows of three 128-bit reads, m = 2 + 1");
-    // MT::FACTOR_REC, item by item (common.hpp: GUSTO_FACTOR_HUU_DPP, _LAZY_SINV, _LAZY_D; all off: the stage as it was)
-    constexpr bool F_DPP = T::FACTOR_REC && GUSTO_FACTOR_HUU_DPP, F_LSINV = T::FACTOR_REC && GUSTO_FACTOR_LAZY_SINV,
-                   F_LD = T::FACTOR_REC && GUSTO_FACTOR_LAZY_D;
-    constexpr int NHU = m * (m + 1) / 2, NHY = NQ - NHU;   // packed entries of H: [0, NHY) rows 0 .. n-1, [NHY, NQ) the upper triangle of H_uu
-    static_assert(!(F_DPP && F_HUU) && (!F_LD || F_LSINV), "H_uu by DPP or through LDS; D from the stored L^-1");
-    // F_DPP: which packed entry of H a lane forms.  In every row of 16 lanes positions 0 .. NHU-1 form the upper triangle of H_uu (the same
-    // operands at the same LDS addresses, the same expression: the same bits in all four rows), positions NHU .. 15 the other entries,
-    // 16 - NHU per row; what is left over (one lane) forms nothing: -1
-    constexpr auto hmap = [](int t) { const int row = t >> 4, pos = t & 15, e = (16 - NHU) * row + pos - NHU; return pos < NHU ? NHY + pos : (e < NHY ? e : -1); };
-    static_assert(!F_DPP || (NHU == 6 && sidx(n, n, NZ) == NHY && 4 * (16 - NHU) >= NHY), "H_uu is the tail of the packed H; four rows hold the rest");
-    constexpr bool HMAP_ONCE = [&] { for (int e = 0; e < NHY; e++) { int c = 0; for (int t = 0; t < 64; t++) c += hmap(t) == e; if (c != 1) return false; } return true; }();
-    constexpr bool HMAP_HUU = [&] { for (int t = 0; t < 64; t++) if ((t & 15) < NHU ? hmap(t) != NHY + (t & 15) : hmap(t) >= NHY) return false; return true; }();
-    static_assert(!F_DPP || HMAP_ONCE, "every entry of rows 0 .. n-1 of H is formed by exactly one lane");
-    static_assert(!F_DPP || HMAP_HUU, "the upper triangle of H_uu sits at positions 0 .. 5 of each of the four rows of lanes, and nowhere else");
-    // F_MV reads the pair (z0, z0 + n/2) of a row of Pi^T at the interleaved positions 2 z0, 2 z0 + 1: every column's first
+    // a lane of Z reads the pair (z0, z0 + n/2) of a row of Pi^T at the interleaved positions 2 z0, 2 z0 + 1: every column's first
     // structural row must lie in the upper half, its second n/2 below it
     constexpr bool PG_UPPER = [] { for (int c = 0; c < NZ; c++) if (!(T::pg_r0(c) < h3 && T::pg_r1(c) == T::pg_r0(c) + h3)) return false; return true; }();
-    static_assert(!F_MV || PG_UPPER, "F_MV: pg_r0(c) < n/2 and pg_r1(c) = pg_r0(c) + n/2 for every column of [Phi Gam]");
+    static_assert(PG_UPPER, "pg_r0(c) < n/2 and pg_r1(c) = pg_r0(c) + n/2 for every column of [Phi Gam]");
     const int tid = K.tid, N = K.N;
     // ---- lane roles ----
-    // (the packed entry of H this lane forms: K.lut's own order, entry tid, or under F_DPP hmap's; lanes without one read entry 0)
-#define HEQ_ (F_DPP ? (hmap(tid) >= 0 ? hmap(tid) : 0) : (tid < NQ ? tid : 0))
-    const int ijh = K.lut[HEQ_], hc = ijh >> 8, hj = ijh & 255, i0 = T::pg_r0(hc), j0 = T::pg_r0(hj);   // H[hc][hj]
+    // (the packed entry of H this lane forms: K.lut's order, entry tid; lanes without one read entry 0)
+    const int ijh = K.lut[tid < NQ ? tid : 0], hc = ijh >> 8, hj = ijh & 255, i0 = T::pg_r0(hc), j0 = T::pg_r0(hj);   // H[hc][hj]
     const int zc = tid < NZN ? tid / n : 0, zg = tid < NZN ? tid % n : 0, z0 = T::pg_r0(zc);                       // Z[zc][zg]
-    const int ri = tid < n ? tid : 0;                                                                             // r[ri], Pi^T c [ri]
-    const bool isnu = tid >= 8 && tid < 8 + n;                                                                    // (F_MV: Pi^T c [tid - 8])
+    const bool isnu = tid >= 8 && tid < 8 + n;                                                                    // Pi^T c [tid - 8] (r[tid]: tid < n)
     const bool on = tid < NN;
     const int i = on ? tid / n : 0, j = on ? tid % n : 0;                                                         // P[i][j], Pi[i][j]
     // ---- LDS operands (offsets in doubles from the base of the dynamic LDS) ----
     const LPtr<double> L = K.lds;
-    typedef double v2d __attribute__((ext_vector_type(2)));
     auto ld2 = [&](int off) { return *(const __attribute__((address_space(3))) v2d*)(L.p + off); };   // ds_read_b128 (off even)
     const int dmy = C::sT0 + (tid & 15);             // dummy slot of this lane (+ immediates < 36 stay inside the T buffer)
-    static_assert(n * NZ >= 16 + 36, "dummy slot");
-    // F_HUU: the upper triangle of H_uu, six doubles packed row-major behind the dummy slots (its lanes write, every lane reads)
-    constexpr int oHuu = C::sT0 + 46;
-    static_assert(oHuu % 2 == 0 && 15 + (2 * m - 1) * n < 46 && 15 + NHU < 46 && 46 + NHU <= n * NZ, "H_uu behind the dummy slots, in the T buffer");
-    // F_ROWS: rows of H at an even stride (H_uu is not among them: rows 0 .. n-1 only), Z_u transposed in rows of four doubles
+    static_assert(n * NZ >= 16 + 36 && (2 * m - 1) * n < 36, "dummy slot");
+    // rows of H at an even stride (H_uu is not among them: rows 0 .. n-1 only), Z_u transposed in rows of four doubles
     // on the first even offset of the Z buffer (Z_y is only ever read back by the lane that formed it: zR)
-    constexpr int NZH = F_ROWS ? NZ + 1 : NZ, oZu = (C::sZ + 1) & ~1;
-    static_assert(!F_ROWS || (C::sHh % 2 == 0 && NZH % 2 == 0 && n * NZH <= NZ * NZ && oZu + 4 * n <= C::sZ + NZN), "128-bit rows of H_yu and Z_u");
+    constexpr int NZH = NZ + 1, oZu = (C::sZ + 1) & ~1;
+    static_assert(C::sHh % 2 == 0 && NZH % 2 == 0 && n * NZH <= NZ * NZ && oZu + 4 * n <= C::sZ + NZN, "128-bit rows of H_yu and Z_u");
     auto pcol = [](int j_) { return 2 * (j_ % h3) + j_ / h3; };       // column j of P sits at position pcol(j) of its row
     static_assert(C::sP % 2 == 0 && C::sPi % 2 == 0 && n % 2 == 0 && C::vecs % 2 == 0, "16-byte aligned rows");
-    // (F_MV: the rows of the transposed Pi carry P's column interleave, so the pair a lane of Z needs is adjacent and even)
-    const int oPP = C::sP + i0 * n + 2 * j0, oPZ = C::sPi + zg * n + (F_MV ? 2 * z0 : z0), oPr = C::sP + ri * n, oPir = C::sPi + ri * n;
-    const int oRow = tid < n ? C::sP + tid * n : (isnu ? C::sPi + (tid - 8) * n : C::sP);   // (F_MV: row of P | of Pi^T of this lane)
-    const int wH1 = (F_DPP ? hmap(tid) >= 0 : tid < NQ) ? ((hc >= n && F_HUU) ? oHuu + sidx(hc - n, hj - n, m) : ((hc >= n && F_ROWS) ? dmy : C::sHh + hc * NZH + hj))
-                             : dmy;                                   // (upper triangle only: hc <= hj)
-    const int wZ = tid < NZN ? (F_ROWS ? (zc >= n ? oZu + zg * 4 + (zc - n) : dmy) : C::sZ + tid) : dmy;
+    const int oPP = C::sP + i0 * n + 2 * j0, oPZ = C::sPi + zg * n + 2 * z0;
+    const int oRow = tid < n ? C::sP + tid * n : (isnu ? C::sPi + (tid - 8) * n : C::sP);   // row of P | of Pi^T of this lane
+    const int wH1 = tid < NQ ? (hc >= n ? dmy : C::sHh + hc * NZH + hj) : dmy;   // (upper triangle only: hc <= hj; H_uu nowhere)
+    const int wZ = tid < NZN ? (zc >= n ? oZu + zg * 4 + (zc - n) : dmy) : dmy;   // (Z_u only)
     const int oHi = C::sHh + i * NZH + n, oHj = C::sHh + j * NZH + n, oPn = C::sHh + (i < j ? i : j) * NZH + (i < j ? j : i);
-    const int oZi = F_ROWS ? oZu + i * 4 : C::sZ + n * n + i, oZj = F_ROWS ? oZu + j * 4 : C::sZ + n * n + j;
-    const int wP = on ? C::sP + i * n + pcol(j) : dmy, wPi = on ? C::sPi + j * n + (F_MV ? pcol(i) : i) : dmy, wGd = on ? C::sGd + tid : dmy;
+    const int oZi = oZu + i * 4, oZj = oZu + j * 4;
+    const int wP = on ? C::sP + i * n + pcol(j) : dmy, wPi = on ? C::sPi + j * n + pcol(i) : dmy, wGd = on ? C::sGd + tid : dmy;
     const int vecs = C::vecs, oCv = vecs + 3 * N * n, oRv = vecs + 4 * N * n, oNun = vecs + 6 * N * n;   // (Blk::rebind_lds)
-    const int wRv = tid < n ? oRv + tid : dmy, wNun = tid < n ? oNun + tid : dmy, sRv = tid < n ? n : 0;
-    const int wRN = tid < n ? oRv + tid : (isnu ? oNun + (tid - 8) : dmy), sRN = (tid < n || isnu) ? n : 0;   // (F_MV: both, one store)
+    const int wRN = tid < n ? oRv + tid : (isnu ? oNun + (tid - 8) : dmy), sRN = (tid < n || isnu) ? n : 0;   // r_k | Pi_k^T c_k, one store
     const int kdo = K.kd_off;
-    const int wKD = tid < n ? kdo + tid : dmy, sKD = tid < n ? C::KDS : 0;             // K[a][tid] at + a n, D[a][tid] at + (m + a) n
-    const int wSi = tid == 0 ? kdo + 2 * m * n : dmy, sSi = tid == 0 ? C::KDS : 0;     // S^-1, upper triangle
+    const int wKD = tid < n ? kdo + tid : dmy, sKD = tid < n ? C::KDS : 0;             // K[a][tid] at + a n, V[a][tid] at + (m + a) n
+    const int wSi = tid == 0 ? kdo + 2 * m * n : dmy, sSi = tid == 0 ? C::KDS : 0;     // L^-1, lower triangle
     const int ep = (on && i <= j) ? sidx(i, j, n) : R::SNN - 1, eq = on ? NH + tid : R::SNN - 1;   // packed P | Pi record
     // ---- [Phi Gam] entries of this lane: the block of the sweep and the knot-0 block [0 | b_0] ----
     struct PGC { double a0, a1, b0, b1, zv0, zv1; };
@@ -616,7 +577,7 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
     L[wP] = 0.0; L[wPi] = 0.0; L[wZ] = 0.0;
     double gdR = 0.0, zR = 0.0;   // this lane's entry of Gd (accumulated over the sweep) and of Z (the Pi' term of the next tail)
     if (tid < R::SNN) K.Paft[(size_t)(N - 1) * R::SNN + tid] = 0.0;
-    double qq = K.kdl[(N - 1) * C::KDS + HEQ_];
+    double qq = K.kdl[(N - 1) * C::KDS + (tid < NQ ? tid : 0)];
     double LiP[m * m], wiP[m];   // L^-1 and this lane's column i of W of the stage before (tail operands)
 #pragma unroll
     for (int e = 0; e < m * m; e++) LiP[e] = 0.0;
@@ -625,10 +586,16 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
     bool okall = true;
     K.sync();
 
-    // tail of stage kt (V, Pi_{kt-1}, Gd, D_kt) from (LiP, wiP) and Z of that stage in LDS; returns nothing, writes LDS + record
+    // the m operands of a lane's rows i and j -- H_yu[i][0..m-1] | H_yu[j][..] (at oHi | oHj) or Z_u[0..m-1][i] | Z_u[..][j]
+    // (at oZi | oZj) -- are rows at even offsets: one 128-bit read and one 64-bit read each
+    auto ld3 = [&](int oi, int oj, double* vi, double* vj) {
+        const v2d a2 = ld2(oi), b2 = ld2(oj);
+        vi[0] = a2.x; vi[1] = a2.y; vi[2] = L[oi + 2]; vj[0] = b2.x; vj[1] = b2.y; vj[2] = L[oj + 2];
+    };
+    // tail of stage kt (V, Pi_{kt-1}, Gd) from (LiP, wiP) and Z_u of that stage; returns nothing, writes LDS + record
     auto tail = [&](int kt, const double* zi, const double* zj) {
         double pin = zR, gd = gdR;
-        double vi[m], vj[m], dj[m];
+        double vi[m], vj[m];
 #pragma unroll
         for (int a = 0; a < m; a++) {
             double s3 = 0, s4 = 0;
@@ -636,16 +603,12 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
             for (int l = 0; l <= a; l++) { s3 += LiP[a * m + l] * zi[l]; s4 += LiP[a * m + l] * zj[l]; }
             vi[a] = s3; vj[a] = s4;
         }
-        if constexpr (!F_LD) {   // (F_LD: D = L^-T V is formed by the mid phase from the V stored below)
-#pragma unroll
-            for (int a = 0; a < m; a++) dj[a] = lt_entry<m>(LiP, vj, a);
-        }
 #pragma unroll
         for (int l = 0; l < m; l++) { pin -= wiP[l] * vj[l]; gd += vi[l] * vj[l]; }
         L[wPi] = pin; gdR = gd;
         K.Paft[(size_t)(kt - 1) * R::SNN + eq] = pin;
 #pragma unroll
-        for (int a = 0; a < m; a++) L[wKD + kt * sKD + (m + a) * n] = F_LD ? vj[a] : dj[a];
+        for (int a = 0; a < m; a++) L[wKD + kt * sKD + (m + a) * n] = vj[a];   // (V: the mid phase forms D = L^-T V)
     };
 
     // ordering point for LDS traffic between lanes that leaves the ALU work free to move (one wave: the hardware keeps
@@ -666,96 +629,43 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
 #define STAMP(v) do {} while (0)
 #define STAMPS_END() do {} while (0)
 #endif
-    // F_ROWS: the m operands of a lane's rows i and j -- H_yu[i][0..m-1] | H_yu[j][..] (at oHi | oHj) or Z_u[0..m-1][i] | Z_u[..][j]
-    // (at oZi | oZj) -- are rows at even offsets: one 128-bit read and one 64-bit read each
-    auto ld3 = [&](int oi, int oj, double* vi, double* vj) {
-        const v2d a2 = ld2(oi), b2 = ld2(oj);
-        vi[0] = a2.x; vi[1] = a2.y; vi[2] = L[oi + 2]; vj[0] = b2.x; vj[1] = b2.y; vj[2] = L[oj + 2];
-    };
     auto stage = [&](int k, const PGC& c, bool last) {
         STAMP(t0_);
         // ---- operands of this iteration, one batch ----
         const v2d pA = ld2(oPP), pB = ld2(oPP + h3 * n);
         const double p00 = pA.x, p01 = pA.y, p10 = pB.x, p11 = pB.y;
-        double ra[n], rb[n];
-        if constexpr (!F_MV) {
-#pragma unroll
-            for (int l = 0; l < n; l += 2) {
-                const v2d a2 = ld2(oPr + l), b2 = ld2(oCv + k * n + l);
-                // row ri of P holds the columns in the order 0, n/2, 1, n/2 + 1, ...: ra[] back in natural order
-                ra[l / 2] = a2.x; ra[l / 2 + h3] = a2.y; rb[l] = b2.x; rb[l + 1] = b2.y;
-            }
-        }
         double zi[m], zj[m];
-        if constexpr (F_ROWS) ld3(oZi, oZj, zi, zj);
-        else {
-#pragma unroll
-            for (int l = 0; l < m; l++) { zi[l] = L[oZi + l * n]; zj[l] = L[oZj + l * n]; }
-        }
-        const double qqn = K.kdl[((k > 0) ? k - 1 : 0) * C::KDS + HEQ_];   // (slot k-1 still holds QQ_{k-1})
-        // ---- value function chain, first half: H, r_k = P_k c_k ----
+        ld3(oZi, oZj, zi, zj);
+        const double qqn = K.kdl[((k > 0) ? k - 1 : 0) * C::KDS + (tid < NQ ? tid : 0)];   // (slot k-1 still holds QQ_{k-1})
+        // ---- value function chain, first half: H ----
         const double h = qq + c.a0 * (c.b0 * p00 + c.b1 * p01) + c.a1 * (c.b0 * p10 + c.b1 * p11);
         L[wH1] = h;
-        if constexpr (!F_MV) {
-            double rr = 0;
-#pragma unroll
-            for (int l = 0; l < n; l++) rr += ra[l] * rb[l];
-            L[wRv + k * sRv] = rr;
-        }
         STAMP(t1_);
         msync();
         double S[m * m], Li[m * m];
-        if constexpr (F_HUU) {   // three broadcast reads of the packed upper triangle its six lanes have just stored
-            const v2d s0 = ld2(oHuu), s1 = ld2(oHuu + 2), s2 = ld2(oHuu + 4);
-            const double su[NHU] = {s0.x, s0.y, s1.x, s1.y, s2.x, s2.y};
 #pragma unroll
-            for (int a = 0; a < m; a++)
+        for (int a = 0; a < m; a++)
 #pragma unroll
-                for (int b = 0; b < m; b++) S[a * m + b] = su[sidx(a, b, m)];
-        } else if constexpr (F_DPP) {   // lanes 0 .. 5 of this lane's row hold the upper triangle: uniform per row, the same bits in every row
-            double su[NHU];
-            if constexpr (GUSTO_FACTOR_HUU_DPP == 2) row_bcast6_b64(h, su);
-            else {
-                su[0] = row_bcast_f64<0>(h); su[1] = row_bcast_f64<1>(h); su[2] = row_bcast_f64<2>(h);
-                su[3] = row_bcast_f64<3>(h); su[4] = row_bcast_f64<4>(h); su[5] = row_bcast_f64<5>(h);
+            for (int b = 0; b < m; b++) {
+                const int e = sidx(n + (a < b ? a : b), n + (a < b ? b : a), NZ);
+                S[a * m + b] = readlane_f64(h, e);
             }
-#pragma unroll
-            for (int a = 0; a < m; a++)
-#pragma unroll
-                for (int b = 0; b < m; b++) S[a * m + b] = su[sidx(a, b, m)];
-        } else {
-#pragma unroll
-            for (int a = 0; a < m; a++)
-#pragma unroll
-                for (int b = 0; b < m; b++) {
-                    const int e = sidx(n + (a < b ? a : b), n + (a < b ? b : a), NZ);
-                    S[a * m + b] = readlane_f64(h, e);
-                }
-        }
         double hi[m], hjv[m];
-        if constexpr (F_ROWS) ld3(oHi, oHj, hi, hjv);
-        else {
-#pragma unroll
-            for (int l = 0; l < m; l++) { hi[l] = L[oHi + l]; hjv[l] = L[oHj + l]; }
-        }
+        ld3(oHi, oHj, hi, hjv);
         double pn = L[oPn];
         // ---- goal chain: tail of the stage before, head of this one (independent of the factorisation below) ----
         tail(k + 1 < N ? k + 1 : N - 1, zi, zj);
         STAMP(t2_);
         msync();
         // (operands of the head first, then the factorisation: its ~45 dependent flops run while they are in flight)
-        // F_MV: r_k = P_k c_k (lanes 0 .. n-1) and Pi_k^T c_k (lanes 8 .. 8+n-1) are ONE stream: Pi_k is in place since the tail above,
-        // P_k until L[wP] below, the rows of both hold the columns in the order 0, n/2, 1, n/2 + 1, ..., and the pair of Pi a lane of
-        // Z needs is one 128-bit read
-        const double zb0 = F_MV ? ld2(oPZ).x : L[oPZ], zb1 = F_MV ? ld2(oPZ).y : L[oPZ + h3];
-        double pa[n];
+        // r_k = P_k c_k (lanes 0 .. n-1) and Pi_k^T c_k (lanes 8 .. 8+n-1) are ONE stream: Pi_k is in place since the tail above,
+        // P_k until L[wP] below, the rows of both hold the columns in the order 0, n/2, 1, n/2 + 1, ...
+        const double zb0 = ld2(oPZ).x, zb1 = ld2(oPZ).y;   // (the pair of Pi^T this lane of Z needs: one 128-bit read)
+        double pa[n], rb[n];
 #pragma unroll
         for (int l = 0; l < n; l += 2) {
-            const v2d a2 = ld2((F_MV ? oRow : oPir) + l);
-            if constexpr (F_MV) {
-                const v2d b2 = ld2(oCv + k * n + l);
-                pa[l / 2] = a2.x; pa[l / 2 + h3] = a2.y; rb[l] = b2.x; rb[l + 1] = b2.y;
-            } else { pa[l] = a2.x; pa[l + 1] = a2.y; }
+            const v2d a2 = ld2(oRow + l), b2 = ld2(oCv + k * n + l);
+            pa[l / 2] = a2.x; pa[l / 2 + h3] = a2.y; rb[l] = b2.x; rb[l + 1] = b2.y;
         }
         // ---- value function chain, second half: L = chol(H_uu), W = L^-1 H_uy, K = L^-T W, P_{k-1} = H_yy - W^T W ----
         okall = chol_inv<m>(S, Li) && okall;
@@ -769,8 +679,7 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
             double rr = 0;
 #pragma unroll
             for (int l = 0; l < n; l++) rr += pa[l] * rb[l];
-            if constexpr (F_MV) L[wRN + k * sRN] = rr;
-            else L[wNun + k * sRv] = rr;
+            L[wRN + k * sRN] = rr;
         }
         STAMP(t4_);
         double wi[m], wj[m], kj[m];
@@ -794,17 +703,11 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
         K.Paft[(size_t)(k - 1) * R::SNN + ep] = pn;     // (record -1 exists for k == 0)
 #pragma unroll
         for (int a = 0; a < m; a++) L[wKD + k * sKD + a * n] = kj[a];
-        if constexpr (F_LSINV) {   // the lower triangle of L^-1 in the slot of S^-1: the mid phase, its one reader, forms S^-1 = L^-T L^-1
+        // the lower triangle of L^-1 in the slot of S^-1: the mid phase, its one reader, forms S^-1 = L^-T L^-1
 #pragma unroll
-            for (int a = 0; a < m; a++)
+        for (int a = 0; a < m; a++)
 #pragma unroll
-                for (int b = 0; b <= a; b++) L[wSi + k * sSi + sidx(b, a, m)] = Li[a * m + b];
-        } else {   // S^-1 = L^-T L^-1, upper triangle (wave-uniform values)
-#pragma unroll
-            for (int a = 0; a < m; a++)
-#pragma unroll
-                for (int b = 0; b <= a; b++) L[wSi + k * sSi + sidx(b, a, m)] = sinv_entry<m>(Li, a, b);
-        }
+            for (int b = 0; b <= a; b++) L[wSi + k * sSi + sidx(b, a, m)] = Li[a * m + b];
         qq = qqn;
 #pragma unroll
         for (int e = 0; e < m * m; e++) LiP[e] = Li[e];
@@ -816,17 +719,12 @@ template <int MODEL> GD void factor_sweep_pg2(SweepView<MODEL> K, double* fail, 
     };
 #undef STAMP
 #undef STAMPS_END
-#undef HEQ_
 
     for (int k = N - 1; k >= 1; k--) stage(k, cN, k == N - 1);
     stage(0, c0, false);
-    {   // the goal chain is one half stage behind: tail of stage 0 (Gd, D_0; its Pi lands in record -1)
+    {   // the goal chain is one half stage behind: tail of stage 0 (Gd, V_0; its Pi lands in record -1)
         double zi[m], zj[m];
-        if constexpr (F_ROWS) ld3(oZi, oZj, zi, zj);
-        else {
-#pragma unroll
-            for (int l = 0; l < m; l++) { zi[l] = L[oZi + l * n]; zj[l] = L[oZj + l * n]; }
-        }
+        ld3(oZi, oZj, zi, zj);
         tail(0, zi, zj);
     }
     L[wGd] = gdR;

@@ -443,12 +443,6 @@ template <int MODEL, class BLK> GD void linearize(BLK& K, double toggle) {
                 if (dist < toggle) {
                     mask |= (uint64_t)1 << i;
                     double c0 = K.P.mp.clearance - dist;
-                    if constexpr (obs_nh_pair<MODEL, BLK::ONE>()) {   // [obs][N][2]: the two components with one 128-bit store
-                        typedef __attribute__((address_space(1))) v2d GP;
-                        *(GP*)((K.obs_nh + (size_t)i * 2 * K.N).p + 2 * k) = v2d{nh[0], nh[1]};
-#pragma unroll
-                        for (int j = 0; j < T::WS; j++) c0 += nh[j] * xw[j];
-                    } else
 #pragma unroll
                     for (int j = 0; j < T::WS; j++) {
                         K.obs_nh[((size_t)i * T::WS + j) * K.N + k] = nh[j];
@@ -1791,9 +1785,7 @@ template <int MODEL, class BLK> GD void factor_sweep(BLK& K, double* fail, Prof&
     else if constexpr (!BLK::ONE) factor_sweep_mw<MODEL>(K, fail, pf);
     else if constexpr (MT<MODEL>::SWEEP_CALL) factor_sweep_1w_call<MODEL>(K.args(), &pf);
     else if constexpr (MT<MODEL>::MFMA) factor_sweep_mfma<MODEL, false>(SweepView<MODEL>::make(K), fail, pf);   // (inlined builds, -DGUSTO_SWEEP_INLINE: P | Pi costates)
-    else if constexpr (MT<MODEL>::PG2 && LdsC<MODEL, true>::KD_LDS) {
-        factor_sweep_pg2<MODEL>(SweepView<MODEL>::make(K), fail, pf);
-    }
+    else if constexpr (kd_holds_linv_v<MODEL, BLK::ONE>()) factor_sweep_pg2<MODEL>(SweepView<MODEL>::make(K), fail, pf);
     else factor_sweep_1w<MODEL>(SweepView<MODEL>::make(K), fail, pf);
 }
 template <int MODEL> __device__ __noinline__ void backward_sweep_1w_call(typename Blk<MODEL, true>::Args a) {
@@ -1935,12 +1927,11 @@ template <int MODEL, class BLK, int NCH = 0> GD void mid_phase(BLK& K, int k, bo
     double th[n], d0[m];
     // (12/13-state models: the D record of the knot, 78 entries from the slot workspace, is walked once and kept for d_k = d0 + D mu_g
     // below -- this phase is a real call with registers of its own -- instead of walked again after the reductions)
-    // MT::FACTOR_REC (freeflyerSE2, one wave: factor_sweep_pg2): the slot of S^-1 holds the lower triangle of L^-1 (REC_SINV) and the slot of
-    // D holds V = L^-1 Z_u (REC_D); lane k forms S^-1 = L^-T L^-1 and D = L^-T V of its knot here, twice per KKT solve, with the
-    // expressions the factor stage used 50 times in a row (common.hpp: sinv_entry, lt_entry) -- D once, kept for its second use below
-    constexpr bool REC = T::FACTOR_REC && BLK::ONE && BLK::C::KD_LDS && !SEG, REC_SINV = REC && GUSTO_FACTOR_LAZY_SINV, REC_D = REC && GUSTO_FACTOR_LAZY_D;
-    static_assert(!REC || (T::PG2 && !T::SWEEP_CALL && !T::MFMA), "FACTOR_REC: the kernel whose factor sweep is factor_sweep_pg2");
-    constexpr bool KEEP_D = (T::SWEEP_CALL && BLK::ONE && !BLK::C::KD_LDS) || REC_D;
+    // LV (freeflyerSE2, one wave: factor_sweep_pg2): the slot of S^-1 holds the lower triangle of L^-1 and the slot of D holds
+    // V = L^-1 Z_u; lane k forms S^-1 = L^-T L^-1 and D = L^-T V of its knot here, twice per KKT solve, with the sums a factor
+    // stage would form N times in a row (common.hpp: sinv_entry, lt_entry) -- D once, kept for its second use below
+    constexpr bool LV = kd_holds_linv_v<MODEL, BLK::ONE>();
+    constexpr bool KEEP_D = (T::SWEEP_CALL && BLK::ONE && !BLK::C::KD_LDS) || LV;
     double Dk[KEEP_D ? m * n : 1];
 #pragma unroll
     for (int i = 0; i < (KEEP_D ? m * n : 1); i++) Dk[i] = 0;
@@ -1993,8 +1984,8 @@ template <int MODEL, class BLK, int NCH = 0> GD void mid_phase(BLK& K, int k, bo
             for (int l = 0; l < n; l++) if (T::Gnz(l, i)) s += Gamk[l * m + i] * tt[l];
             lu[i] = s;
         }
-        double Lk[REC_SINV ? m * m : 1], Sk[REC_SINV ? m * (m + 1) / 2 : 1];
-        if constexpr (REC_SINV) {
+        double Lk[LV ? m * m : 1], Sk[LV ? m * (m + 1) / 2 : 1];
+        if constexpr (LV) {
 #pragma unroll
             for (int a = 0; a < m; a++)
 #pragma unroll
@@ -2010,12 +2001,12 @@ template <int MODEL, class BLK, int NCH = 0> GD void mid_phase(BLK& K, int k, bo
 #pragma unroll
             for (int l = 0; l < m; l++) {
                 double sil;
-                if constexpr (REC_SINV) sil = Sk[sidx(i, l, m)]; else sil = K.kdS(k, i, l);
+                if constexpr (LV) sil = Sk[sidx(i, l, m)]; else sil = K.kdS(k, i, l);
                 s += sil * lu[l];
             }
             d0[i] = s;
         }
-        if constexpr (REC_D) {
+        if constexpr (LV) {
 #pragma unroll
             for (int j = 0; j < n; j++) {
                 double vj[m];
@@ -2063,7 +2054,7 @@ template <int MODEL, class BLK, int NCH = 0> GD void mid_phase(BLK& K, int k, bo
 #pragma unroll
             for (int j = 0; j < n; j++) {
                 double dij;
-                if constexpr (REC_D) dij = Dk[i * n + j];
+                if constexpr (LV) dij = Dk[i * n + j];
                 else {
                     dij = K.kd(k, R::oD + i * n + j);
                     if constexpr (KEEP_D) Dk[i * n + j] = dij;
@@ -2451,7 +2442,7 @@ GD StepOut step_phase(BLK& K, const RowCtx<MODEL>& ctx, const RS& rs, int k, boo
             segw_rows_step_add<MODEL, NCH>(K.lds, K.P.ll.seg, k, (cs && NCH > 2) ? 1 : 0, op, gAx, gBx);
         } else
 #endif
-        visit_rows<MODEL, obs_nh_pair<MODEL, BLK::ONE>()>(ctx, xs, us, op);
+        visit_rows<MODEL>(ctx, xs, us, op);
         ctx.tick(3);
         if constexpr (ADJ) {
             // v_k = M_k^T (H_x dx_k + gx_k [+ mu_g at the last knot]) -> nun[k], the inhomogeneity of nu_k = Phi_k^T nu_{k+1} + v_k:
@@ -2594,7 +2585,7 @@ GD ResidOut resid_phase(BLK& K, const RowCtx<MODEL>& ctx, const RS& rs, int k, b
             segw_rows_resid_add<MODEL, NCH>(K.lds, K.P.ll.seg, k, NCH - 1, op, Hx, rdx, gx0);
         } else
 #endif
-        visit_rows<MODEL, obs_nh_pair<MODEL, BLK::ONE>()>(ctx, xs, us, op);
+        visit_rows<MODEL>(ctx, xs, us, op);
         ctx.tick(3);
         // row part of the predictor right-hand side, parked in the (currently free) step arrays
 #pragma unroll
@@ -2811,7 +2802,7 @@ template <int MODEL, class BLK, int NCH = 0> GD void ipm_solve(BLK& K, double De
 #pragma unroll
         for (int i = 0; i < m; i++) { us[i] = K.Up[k * m + i]; K.Uw[k * m + i] = us[i]; }
         OpInit<RS> op{rs, muw};
-        visit_rows<MODEL, obs_nh_pair<MODEL, BLK::ONE>()>(ctx, xs, us, op);
+        visit_rows<MODEL>(ctx, xs, us, op);
         ncomp_l = op.ncomp;
     }
     if (k == 0) {
@@ -3114,7 +3105,7 @@ template <int MODEL, class BLK, int NCH = 0> GD void ipm_solve(BLK& K, double De
 #pragma unroll
         for (int i = 0; i < m; i++) l_obj += ((i < m - T::NDEF) ? wk : TRAJOPT_DEFECT_REG * wk) * us[i] * us[i];
         OpSlackSum<RS> op{rs};
-        visit_rows<MODEL, obs_nh_pair<MODEL, BLK::ONE>()>(ctx, xs, us, op);
+        visit_rows<MODEL>(ctx, xs, us, op);
         l_obj += op.sum;
     }
     const double obj = block_reduce<BLK::ONE>(l_obj, OpSum(), red);

@@ -50,9 +50,9 @@ template <int MODEL> static int fill_params(gusto_handle h, KParams& P, int B, b
     P.tp = h->tp; P.to_mu = h->d_to_mu; P.to_xtol = h->d_to_xtol; P.to_ftol = h->d_to_ftol; P.to_ctol = h->d_to_ctol;
     P.wl = make_ws_layout<MODEL>(h->N, P.n_obs);
     P.ll = make_lds_layout<MODEL>(h->N, launch_waves(h) > (h->N + 63) / 64);
-    // (RS_PAIR, MT::OBS_NH_PAIR: 128-bit accesses to the row state and the obstacle normals -- their slabs at even offsets of a block
-    //  of an even number of doubles; enqueue_solve checks the base)
-    if (P.wl.rowstate % 2 || P.wl.obs_nh % 2 || P.wl.total % 2) { h->err = "workspace layout: row state or obstacle normals not 16-byte aligned"; return GUSTO_ERR_STATE; }
+    // (RS_PAIR: 128-bit accesses to the row state -- its slab at an even offset of a block of an even number of doubles;
+    //  enqueue_solve checks the base)
+    if (P.wl.rowstate % 2 || P.wl.total % 2) { h->err = "workspace layout: row state not 16-byte aligned"; return GUSTO_ERR_STATE; }
     HIPCHK(h, h->d_queue.alloc(SQ_WORDS));
 #ifdef GUSTO_PROFILE
     HIPCHK(h, h->d_prof.alloc((size_t)h->batch_cap * PROF_N));

@@ -30,7 +30,7 @@ template <int MODEL> struct RowCtx {
     double kappa, omega, Delta;
     GPtr<const double> xp;      // linearisation state of this knot
     uint64_t mask;              // active obstacle rows (dist < obstacle_toggle_distance)
-    GPtr<const double> obs_nh;  // [n_obs][WS][N]  (visit_rows<MODEL, NHP = true>: [n_obs][N][2], common.hpp: obs_nh_pair)
+    GPtr<const double> obs_nh;  // [n_obs][WS][N]
     GPtr<const double> obs_c0;  // [n_obs][N]
     GPtr<const double> goal_lo;
     GPtr<const double> goal_hi;
@@ -102,7 +102,7 @@ template <int MODEL> struct RowSlots {
 // row's loads wait behind the stores of the row before it and a pass pays one memory round trip per active
 // obstacle (3-8 per knot for the freeflyer table, 15-25 in the ISS corner) -- four passes per interior point
 // iteration.  Lanes with fewer rows left aim the spare positions at their last row and skip them.
-template <int MODEL, bool NHP = false, class Op> GD void visit_obs_rows(const RowCtx<MODEL>& c, const double* xs, Op& op, uint64_t mk) {
+template <int MODEL, class Op> GD void visit_obs_rows(const RowCtx<MODEL>& c, const double* xs, Op& op, uint64_t mk) {
     using T = MT<MODEL>;
     const double kw = c.kappa * c.omega;
     const int slot_obs = RowSlots<MODEL>::obs(c.P->n_obs);
@@ -117,16 +117,6 @@ template <int MODEL, bool NHP = false, class Op> GD void visit_obs_rows(const Ro
             oi[q] = last; oslot[q] = slot_obs + last;
         }
         double ob[OBS_BATCH][T::WS], oc[OBS_BATCH];
-        if constexpr (NHP) {   // obs_nh as [n_obs][N][2]: the normal of (obstacle, knot) with one 128-bit load
-            static_assert(T::WS == 2, "a pair of doubles");
-            typedef __attribute__((address_space(1))) const v2d GP;
-#pragma unroll
-            for (int q = 0; q < OBS_BATCH; q++) {
-                const v2d nh = *(GP*)((c.obs_nh + (size_t)oi[q] * 2 * (size_t)c.N).p + 2 * c.k);
-                ob[q][0] = -nh.x; ob[q][1] = -nh.y;
-                oc[q] = (c.obs_c0 + (size_t)oi[q] * (size_t)c.N)[c.k];
-            }
-        } else
 #pragma unroll
         for (int q = 0; q < OBS_BATCH; q++) {
 #pragma unroll
@@ -170,7 +160,7 @@ template <int MODEL, class Op> GD void visit_ctl_rows(const RowCtx<MODEL>& c, co
 }
 
 // ---- the row programs ------------------------------------------------------------------------------
-template <int MODEL, bool NHP = false, class Op> GD void visit_rows(const RowCtx<MODEL>& c, const double* xs, const double* us, Op& op) {
+template <int MODEL, class Op> GD void visit_rows(const RowCtx<MODEL>& c, const double* xs, const double* us, Op& op) {
     using T = MT<MODEL>;
     constexpr int n = T::n;
     const gusto_model_params& mp = c.P->mp;
@@ -314,7 +304,7 @@ template <int MODEL, bool NHP = false, class Op> GD void visit_rows(const RowCtx
         quad_row<false, 3, nv, GUSTO_FXB(T::NFIX - 2, T::NFIX - 2)>(op, slot++, ROW_PEN, xs, one, nullptr, -mp.hard_limit_vel * mp.hard_limit_vel, kw, 0.0);
         quad_row<false, iw, nw, GUSTO_FXB(T::NFIX - 1, T::NFIX - 1)>(op, slot++, ROW_PEN, xs, one, nullptr, -mp.hard_limit_omega * mp.hard_limit_omega, kw, 0.0);
         c.tick(1);   // fixed state rows; then the obstacle rows (visit_obs_rows)
-        visit_obs_rows<MODEL, NHP>(c, xs, op, c.mask);
+        visit_obs_rows<MODEL>(c, xs, op, c.mask);
         c.tick(2);   // obstacle rows
         if (!c.skip_ctl) visit_ctl_rows<MODEL>(c, us, op);
 #undef GUSTO_FXB

@@ -167,7 +167,7 @@ template <int MODEL, bool ONEWAVE, int NCH = 0> GD int scp_problem(const KParams
             ctx.xp = K.Xp + k * n; ctx.mask = K.obs_mask[k]; ctx.obs_nh = K.obs_nh; ctx.obs_c0 = K.obs_c0;
             ctx.goal_lo = K.goal_lo; ctx.goal_hi = K.goal_hi; ctx.boxmask = K.boxmask;
             OpCheck op{sp.eps};
-            visit_rows<MODEL, obs_nh_pair<MODEL, ONEWAVE>()>(ctx, xs, us, op);
+            visit_rows<MODEL>(ctx, xs, us, op);
             cvx_l = op.ok;
         }
         tk(1);

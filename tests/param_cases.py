@@ -65,7 +65,7 @@ TF = {SE3: 20.0, MAN: 10.0}
 PROBLEMS = {SE3: (1, 2), MAN: (1, 2), FF: (0, 1), DUB: (0, 3)}     # (dubins 1, 4, 7, 8: infeasible with u_max = 4 at N = 30)
 CASES = {"aniso": (SE3, MAN), "aniso_tight": (SE3, MAN), "freeflyer": (FF,), "dubins": (DUB,)}
 # the horizons the GPU tests run: one wave and the chain kernels at 16, the first multi-wave horizon 65; freeflyerSE2's
-# FACTOR_LDS / SWEEP_DPP path at 5 and 50
+# one-wave kernel (factor_sweep_pg2, the DPP vector sweeps) at 5 and 50
 HORIZONS = {SE3: (16, 65), MAN: (16, 65), FF: (5, 50), DUB: (30,)}
 # gates that were measured, not reused (the way tests/test_gpu_horizons.py treats freeflyerSE2 at N = 3): none
 GATES = {}

@@ -1,11 +1,10 @@
-"""The factor stage of freeflyerSE2 (csrc/factor1w.hpp: factor_sweep_pg2) under MT::FACTOR_REC keeps only the recursion on its
-sequential path: the stage stores L^-1 where it stored S^-1 = L^-T L^-1 (GUSTO_FACTOR_LAZY_SINV) and V = L^-1 Z_u where it stored
-D = L^-T V (GUSTO_FACTOR_LAZY_D), and the stage-parallel mid phase (csrc/ipm.hpp: mid_phase) forms S^-1 and D of its knot with the
-expressions the stage used; with -DGUSTO_FACTOR_HUU_DPP=1 or =2 every row of 16 lanes forms H_uu itself, under a lane map of H
-that is no longer K.lut's, and hands it to the Cholesky by DPP row_newbcast.  No sum and no order of a sum changes, so every solve must stay
-BIT-identical.  The fixtures tests/golden/factorrec_freeflyer_{case}_n{N}.npz were recorded on an MI355X with a build of
--DGUSTO_FACTOR_HUU_DPP=0 -DGUSTO_FACTOR_LAZY_SINV=0 -DGUSTO_FACTOR_LAZY_D=0 whose model_0 code object tools/codeobj_diff.py had shown
-to be that of the library before the change; every case here must reproduce them with np.array_equal, whatever the switches.
+"""The factor stage of freeflyerSE2 (csrc/factor1w.hpp: factor_sweep_pg2) keeps only the recursion on its sequential path: the
+stage stores L^-1 where it once stored S^-1 = L^-T L^-1 and V = L^-1 Z_u where it once stored D = L^-T V, and the stage-parallel
+mid phase (csrc/ipm.hpp: mid_phase; csrc/common.hpp: kd_holds_linv_v) forms S^-1 and D of its knot with the expressions the stage
+used.  No sum and no order of a sum changed, so every solve must stay BIT-identical.  The fixtures
+tests/golden/factorrec_freeflyer_{case}_n{N}.npz were recorded on an MI355X from the code before that change (a build whose
+model_0 code object tools/codeobj_diff.py had shown to be that of the library before it); the library must reproduce them bit for
+bit, np.array_equal on every key.
 
 The sibling files (test_gpu_factor_stage.py, test_gpu_sweep_dpp.py, test_gpu_rowstate_layout.py) hold the stage to those bits with
 a point goal on every coordinate, with none on theta and omega, and with a BoxGoal on x.  What they leave out and this change touches:

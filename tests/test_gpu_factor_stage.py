@@ -1,10 +1,8 @@
-"""The factor stage of freeflyerSE2 (csrc/factor1w.hpp: factor_sweep_pg2) under MT::FACTOR_LDS -- one instruction stream for
-r_k = P_k c_k and Pi_k^T c_k, the rows of H_yu, Z_u and Pi laid out for 128-bit reads and, with -DGUSTO_FACTOR_LDS_HUU=1, H_uu to the
-Cholesky by broadcast LDS reads instead of v_readlane -- forms every sum in the order the stage before formed it, so every solve
-must stay BIT-identical.  The
-fixtures tests/golden/factorstage_freeflyer_{goal}_n{N}.npz were recorded on an MI355X with a -DGUSTO_FACTOR_LDS=0 build whose
-model_0 code object tools/codeobj_diff.py had shown to be that of the library before the change; every case here must reproduce
-them with np.array_equal -- with the default build, with -DGUSTO_FACTOR_LDS_HUU=1 and with a -DGUSTO_FACTOR_LDS=0 build alike.
+"""The factor stage of freeflyerSE2 (csrc/factor1w.hpp: factor_sweep_pg2) -- one instruction stream for r_k = P_k c_k and
+Pi_k^T c_k, the rows of H_yu, Z_u and Pi laid out for 128-bit reads -- forms every sum in the order the stage formed it before it
+had that layout, so every solve must stay BIT-identical.  The fixtures tests/golden/factorstage_freeflyer_{goal}_n{N}.npz were
+recorded on an MI355X from the code before that change (a build whose model_0 code object tools/codeobj_diff.py had shown to be
+that of the library before it); the library must reproduce them bit for bit, np.array_equal on every key.
 
 The fixtures of the sibling files (test_gpu_sweep_dpp.py, test_gpu_rowstate_layout.py) all have a point goal on every coordinate.
 What they leave out of the stage is the last knot's E term of Z = [Phi Gam]^T Pi + E where it differs between the lanes of Z:

@@ -1,9 +1,9 @@
 """The row state of freeflyerSE2's one-wave kernel in pairs (csrc/common.hpp: RS_PAIR, csrc/rows.hpp: RowState::pair) -- (T, LAM),
-(S, LAMB), (DT, DL), (KA, KB) next to each other per knot, one 128-bit access per pair -- and the obstacle normal as [obs][N][2]
-(MT::OBS_NH_PAIR) change where a value lives and how many instructions move it, not one value, sum or order of sums: every solve
-must stay BIT-identical.  The fixtures tests/golden/rowpairs_*.npz were recorded on an MI355X with a -DGUSTO_RS_PAIR=0
--DGUSTO_OBS_NH_PAIR=0 build whose code objects tools/codeobj_diff.py had shown to be those of the library before the change; every
-case here must reproduce them with np.array_equal: trajectories, status, iteration counts and the histories.
+(S, LAMB), (DT, DL), (KA, KB) next to each other per knot, one 128-bit access per pair -- changes where a value lives and how many
+instructions move it, not one value, sum or order of sums: every solve must stay BIT-identical.  The fixtures
+tests/golden/rowpairs_*.npz were recorded on an MI355X from the code before that change (a build whose code objects
+tools/codeobj_diff.py had shown to be those of the library before it); the library must reproduce them bit for bit, np.array_equal
+on every key: trajectories, status, iteration counts and the histories.
 
 Every case is freeflyerSE2, B = 32, solve(30), the table environment.  The shapes are the smallest at which each access pattern
 can go wrong:

@@ -1,7 +1,7 @@
 """The one-wave vector sweeps of freeflyerSE2 (csrc/ipm.hpp: backward_sweep_dpp / forward_sweep_dpp) run the same sums in the same
 order as the v_readlane sweeps they replace (backward_sweep_1w / forward_sweep_1w), so every solve must stay BIT-identical.  The
-fixtures tests/golden/sweepdpp_freeflyer_n{N}.npz were recorded on an MI355X with the library that still had the readlane sweeps;
-every case here must reproduce them with np.array_equal -- with the DPP sweeps and with a -DGUSTO_SWEEP_DPP=0 build alike.
+fixtures tests/golden/sweepdpp_freeflyer_n{N}.npz were recorded on an MI355X with the library that still ran freeflyerSE2 on the
+readlane sweeps; the library must reproduce them bit for bit, np.array_equal on every key.
 
 The DPP sweeps walk the horizon in chunks of 8 knots (two groups of 6 lanes in each of the four rows of 16 lanes, rows in the order
 0, 1, 3, 2, the vector handed from row to row by a row swap and from the last row back to the first at the chunk boundary); the

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Is the device code of two builds the same?  tools/codeobj_diff.py BUILD_DIR_A BUILD_DIR_B [unit ...]
 
-For every unit (default: the twelve objects of gusto.jl_amd/build) the gfx950 code object is taken out of UNIT.o of both
+For every unit (default: the thirteen objects of gusto.jl_amd/build) the gfx950 code object is taken out of UNIT.o of both
 directories and compared symbol by symbol: the instruction bytes of every function of .text, the 64 bytes of every kernel
 descriptor (.kd: VGPR / AGPR / SGPR granules, scratch, LDS, kernarg size) and the kernel's entry of the amdhsa metadata
 note.  Symbol order and addresses may differ, bytes may not; __hip_cuid_<hash>, the one-byte tag hipcc names after a hash of
@@ -14,7 +14,7 @@ import sys
 import tempfile
 
 LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
-UNITS = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate"] + [f"model_{i}" for i in range(7)]
+UNITS = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov"] + [f"model_{i}" for i in range(7)]
 
 
 def run(*cmd):
