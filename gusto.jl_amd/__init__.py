@@ -4,7 +4,7 @@ The package holds the HIP kernels + C ABI (csrc/, libgusto_hip.so) and the host-
 driver interface (host.py: solve_SCP!, solve_gusto_hip!).  Import it through the `gusto_jl_amd` shim at the
 repository root (the directory name contains a dot)."""
 from . import _capi, problems  # noqa: F401
-from ._capi import (ASTROBEE_SE3, ASTROBEE_SE3_MANIFOLD, DUBINS_CAR, FREEFLYER_SE2, BatchSolver, GustoError,  # noqa: F401
+from ._capi import (ASTROBEE_SE3, ASTROBEE_SE3_MANIFOLD, DUBINS_CAR, FREEFLYER_SE2, BatchSolver, DisturbOpts, GustoError,  # noqa: F401
                     IpmOpts, LincovOpts, MODEL_DIMS, ModelParams, ScpParams, SimulateOpts, TrajOptParams, TrajOptSolver, TvlqrOpts, build,
                     default_ipm_opts, default_lincov_opts, default_params, default_simulate_opts, default_trajopt_params, default_tvlqr_opts, lib)
 from . import host  # noqa: F401,E402

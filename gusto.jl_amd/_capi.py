@@ -31,6 +31,7 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_last_verify_ms",
            "gusto_default_tvlqr_opts", "gusto_tvlqr", "gusto_get_tvlqr", "gusto_last_tvlqr_ms",
            "gusto_default_simulate_opts", "gusto_simulate", "gusto_get_simulate", "gusto_get_simulate_knots", "gusto_last_simulate_ms",
+           "gusto_default_disturb_opts", "gusto_simulate_disturbed", "gusto_get_simulate_plant",
            "gusto_default_lincov_opts", "gusto_lincov", "gusto_get_lincov", "gusto_last_lincov_ms",
            "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr"]
 
@@ -81,6 +82,14 @@ class SimulateOpts(C.Structure):
     _fields_ = [("n_samples", C.c_int), ("seed", C.c_ulonglong), ("first_problem", C.c_ulonglong), ("dx0", C.c_double * MAXN),
                 ("du0", C.c_double * MAXM), ("u_lo", C.c_double * MAXM), ("u_hi", C.c_double * MAXM), ("dt_min", C.c_double),
                 ("nstep", C.c_int), ("nstep_cap", C.c_int), ("dense_collision", C.c_int), ("store_knots", C.c_int)]
+
+
+NPLANT = 6   # GUSTO_NPLANT: mass, Jdiag[0], Jdiag[1], Jdiag[2], dubins_v, dubins_k
+
+
+class DisturbOpts(C.Structure):
+    """gusto_disturb_opts: half-widths of the relative plant dispersion and of the per-interval actuator noise"""
+    _fields_ = [("plant_rel", C.c_double * NPLANT), ("dw", C.c_double * MAXM)]
 
 
 # gusto_simulate_report in the header's order: (field, dtype, shape as a function of (B, S, n))
@@ -240,6 +249,9 @@ def lib():
         L.gusto_get_simulate.argtypes = [vp, C.POINTER(SimulateReport)]
         L.gusto_get_simulate_knots.argtypes = [vp, vp]
         L.gusto_last_simulate_ms.argtypes = [vp, C.POINTER(C.c_double)]
+        L.gusto_default_disturb_opts.argtypes = [C.POINTER(DisturbOpts)]
+        L.gusto_simulate_disturbed.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(SimulateOpts), C.POINTER(DisturbOpts)]
+        L.gusto_get_simulate_plant.argtypes = [vp, vp]
         L.gusto_default_lincov_opts.argtypes = [ci, C.POINTER(LincovOpts)]
         L.gusto_lincov.argtypes = [vp, vp, vp, vp, vp, C.POINTER(LincovOpts)]
         L.gusto_get_lincov.argtypes = [vp, C.POINTER(LincovReport)]
@@ -679,6 +691,46 @@ class BatchSolver:
         self._simulate_S = int(o.n_samples)
         return self.get_simulate()
 
+    def disturb_opts(self, disturb=None):
+        """a gusto_disturb_opts from None (zeros), a DisturbOpts, or a dict: plant_rel as a scalar or NPLANT entries, dw as a
+        scalar or the model's u_dim entries"""
+        if isinstance(disturb, DisturbOpts):
+            return disturb
+        d = DisturbOpts()
+        self.L.gusto_default_disturb_opts(C.byref(d))
+        for k, v in (disturb or {}).items():
+            if k not in ("plant_rel", "dw"):
+                raise TypeError(f"unknown disturb option {k!r}")
+            dim = NPLANT if k == "plant_rel" else self.m
+            w = np.broadcast_to(np.asarray(v, dtype=np.float64), (dim,))
+            for i in range(dim):
+                getattr(d, k)[i] = float(w[i])
+        return d
+
+    def simulate_disturbed(self, opts=None, disturb=None, X=None, U=None, K=None, pert=None, plant=None, white=None):
+        """gusto_simulate_disturbed + gusto_get_simulate: simulate() with the nominal law, on a plant whose scalars differ per
+        sample -- plant [B, S, NPLANT] absolute values, default: generated with the relative half-widths disturb["plant_rel"] --
+        and with an actuator noise per hold interval -- white [B, N-1, S, m], default: generated with the half-widths
+        disturb["dw"].  Returns the report as a dict; get_simulate_plant() has the plant scalars that were used."""
+        px, pu, _keep = self._traj_ptrs(X, U, "simulate_disturbed")
+        o, d = self.simulate_opts(opts), self.disturb_opts(disturb)
+        S = int(o.n_samples)
+        Kk = None if K is None else _arr(K).reshape(self.B, self.N - 1, self.m, self.n)
+        pp = None if pert is None else _arr(pert).reshape(self.B, S, self.n + self.m)
+        pl = None if plant is None else _arr(plant).reshape(self.B, S, NPLANT)
+        wh = None if white is None else _arr(white).reshape(self.B, self.N - 1, S, self.m)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._chk(self.L.gusto_simulate_disturbed(self.h, px, pu, ptr(Kk), ptr(pp), ptr(pl), ptr(wh), C.byref(o), C.byref(d)),
+                  "simulate_disturbed")
+        self._simulate_S = S
+        return self.get_simulate()
+
+    def get_simulate_plant(self):
+        """gusto_get_simulate_plant: the plant scalars [B, S, NPLANT] of the last simulate_disturbed()"""
+        plant = np.zeros((self.B, getattr(self, "_simulate_S", 1), NPLANT))
+        self._chk(self.L.gusto_get_simulate_plant(self.h, plant.ctypes.data), "get_simulate_plant")
+        return plant
+
     def get_simulate(self):
         """gusto_get_simulate: the report of the last simulate() as a dict of arrays"""
         S = getattr(self, "_simulate_S", 1)
@@ -813,6 +865,9 @@ class TrajOptSolver(BatchSolver):
 
     def simulate(self, *a, **k):
         raise GustoError("TrajOptSolver: simulate is not supported on TrajOpt handles (gusto_simulate answers GUSTO_ERR_ARG)")
+
+    def simulate_disturbed(self, *a, **k):
+        raise GustoError("TrajOptSolver: simulate_disturbed is not supported on TrajOpt handles (gusto_simulate_disturbed answers GUSTO_ERR_ARG)")
 
     def lincov(self, *a, **k):
         raise GustoError("TrajOptSolver: lincov is not supported on TrajOpt handles (gusto_lincov answers GUSTO_ERR_ARG)")

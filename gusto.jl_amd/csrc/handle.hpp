@@ -124,15 +124,17 @@ struct __attribute__((visibility("hidden"))) TvlqrState {
 // its dense index and the flags (I: [2][batch_cap][S]), [batch_cap][S][n] the final state and the largest deviation per state
 // (Xfin, Dev); the per-problem report (RI: [5][batch_cap] n_free, n_finite, n_clipped, worst_sample, worst_dense_sample; RD:
 // [batch_cap] min_dist, then [batch_cap][n] max_dev, [batch_cap][n] max_final_dev); the knots [batch_cap][N][S][n] (first call
-// with store_knots only); copies of a caller's X / U / K / pert
+// with store_knots only); copies of a caller's X / U / K / pert.  gusto_simulate_disturbed: Plant [batch_cap][S][GUSTO_NPLANT],
+// the plant scalars the kernel used; PlantIn and White, the copies of a caller's plant and noise [batch_cap][N - 1][S][m] (they
+// exist only once one was supplied); disturbed: the last call was a disturbed one
 struct __attribute__((visibility("hidden"))) SimulateState {
-    DevBuf<double> D, Xfin, Dev, RD, Knots, X, U, K, Pert;
+    DevBuf<double> D, Xfin, Dev, RD, Knots, X, U, K, Pert, Plant, PlantIn, White;
     DevBuf<int> I, RI;
     int S = 0;
-    bool have = false, have_knots = false;
+    bool have = false, have_knots = false, disturbed = false;
     DevEvent t0, t1;
     double last_ms = 0.0;
-    void invalidate() { have = false; have_knots = false; }
+    void invalidate() { have = false; have_knots = false; disturbed = false; }
 };
 
 // Linear covariance analysis (lincov.hip): I [6][batch_cap] status, fail_knot, obs_knot, obs_pair, ctl_knot, ctl_entry; D

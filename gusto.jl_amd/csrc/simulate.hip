@@ -14,6 +14,12 @@
 // problem: its report and per-sample arrays do not depend on the batch it sits in.
 // store_knots: the tile's states of a knot are staged in LDS ([lane][i], the layout of Xcl) and copied out by the whole
 // workgroup, consecutive lanes to consecutive addresses (as verify.hip stages its dense samples).
+// gusto_simulate_disturbed is the DIST = true instantiation of the same kernel: a lane carries the plant scalars its model
+// reads (at most 4 doubles, for the whole roll-out) in a copy of the model parameters that f is evaluated with, and adds the
+// noise of the interval to the commanded control -- u_dim integer hashes, or one load from the caller's [B][N-1][S][u_dim]
+// array (a wave's samples of one interval are contiguous), formed ahead of the gain products: inside them the hash chains
+// cost the 12/13-state kernels a resident workgroup (profiles/simulate_disturbed.txt).  DIST = false compiles to what it was:
+// the same gfx950 instructions; what it needs extra is ONE unused local (a second one already moves its schedule).
 #include <hip/hip_runtime.h>
 
 #include "models.hpp"
@@ -41,6 +47,22 @@ struct SimArgs {
     double* knots;                 // [B][N][S][n] (store_knots)
     int *n_free, *n_finite, *n_clipped, *worst_sample, *worst_dense;   // [B]
     double *min_dist, *max_dev, *max_final_dev;                        // [B], [B][n], [B][n]
+};
+
+// gusto_simulate_disturbed: SimArgs and the two disturbances
+struct SimArgsD : SimArgs {
+    const double* plant_in;        // [B][S][GUSTO_NPLANT], or null: generated
+    const double* white;           // [B][N-1][S][m], or null: generated
+    double* plant;                 // [B][S][GUSTO_NPLANT]: the plant scalars used
+    unsigned long long seed_plant, seed_white;   // (hashed on the host: simrng_plant_seed, simrng_white_seed)
+    double plant_rel[GUSTO_NPLANT], dw[GUSTO_MAXM];
+};
+
+// what a lane of the DIST kernel carries besides the state: the model parameters with its own plant scalars (f reads at most
+// four of them) and the noise of the current interval
+template <int M> struct DistLane {
+    gusto_model_params plant;
+    double wk[M];
 };
 
 // smallest signed distance of the robot at state x over components and obstacles
@@ -98,7 +120,8 @@ template <int MODEL> GD void reduce_problem(const SimArgs& V, const double* Xend
     }
 }
 
-template <int MODEL, bool KNOTS> __global__ void __launch_bounds__(TILE) simulate_kernel(const KParams P, const SimArgs V) {
+template <int MODEL, bool KNOTS, bool DIST>
+__global__ void __launch_bounds__(TILE) simulate_kernel(const KParams P, const std::conditional_t<DIST, SimArgsD, SimArgs> V) {
     using T = MT<MODEL>;
     using D = Dyn<MODEL>;
     constexpr int n = T::n, m = T::m, nz = n + m;
@@ -136,6 +159,21 @@ template <int MODEL, bool KNOTS> __global__ void __launch_bounds__(TILE) simulat
 #pragma unroll
         for (int i = 0; i < m; i++) pu[i] = p[n + i];
     }
+    // DIST: the plant of this lane.  All GUSTO_NPLANT scalars are formed and written out; those f reads stay in registers
+    [[maybe_unused]] std::conditional_t<DIST, DistLane<m>, char> L;
+    if constexpr (DIST) {
+        const double nominal[GUSTO_NPLANT] = {P.mp.mass, P.mp.Jdiag[0], P.mp.Jdiag[1], P.mp.Jdiag[2], P.mp.dubins_v, P.mp.dubins_k};
+        double th[GUSTO_NPLANT];
+#pragma unroll
+        for (int j = 0; j < GUSTO_NPLANT; j++) {
+            if (V.plant_in) th[j] = valid ? V.plant_in[((size_t)b * S + s) * GUSTO_NPLANT + j] : nominal[j];
+            else th[j] = simrng_plant(V.seed_plant, V.first_problem + b, S, valid ? s : 0, GUSTO_NPLANT, j, nominal[j], V.plant_rel[j]);
+            if (valid) V.plant[((size_t)b * S + s) * GUSTO_NPLANT + j] = th[j];
+        }
+        L.plant = P.mp;
+        L.plant.mass = th[0]; L.plant.Jdiag[0] = th[1]; L.plant.Jdiag[1] = th[2]; L.plant.Jdiag[2] = th[3];
+        L.plant.dubins_v = th[4]; L.plant.dubins_k = th[5];
+    }
     bool alive = valid, fin = true, clipped = false;
 #pragma unroll
     for (int i = 0; i < n; i++) fin = fin && fabs(x[i]) < INFINITY;
@@ -150,6 +188,13 @@ template <int MODEL, bool KNOTS> __global__ void __launch_bounds__(TILE) simulat
         if (t < n) sX[t] = X[k * n + t];
         if (t < m) sU[t] = U[k * m + t];
         __syncthreads();
+        if constexpr (DIST) {   // the noise of this interval
+#pragma unroll
+            for (int c = 0; c < m; c++) {
+                if (V.white) L.wk[c] = valid ? V.white[(((size_t)b * (N - 1) + k) * S + s) * m + c] : 0.0;
+                else L.wk[c] = simrng_white(V.seed_white, V.first_problem + b, S, valid ? s : 0, N - 1, k, m, c, V.dw[c]);
+            }
+        }
         {
             double d[n];
 #pragma unroll
@@ -162,7 +207,8 @@ template <int MODEL, bool KNOTS> __global__ void __launch_bounds__(TILE) simulat
                 double acc = 0.0;
 #pragma unroll
                 for (int j = 0; j < n; j++) acc += sK[c * n + j] * d[j];
-                const double v = (sU[c] - acc) + pu[c];
+                double v = (sU[c] - acc) + pu[c];
+                if constexpr (DIST) v += L.wk[c];   // the noise of this interval, added last
                 const double lo = sLo[c], hi = sHi[c];
                 if (alive && (v < lo || v > hi)) clipped = true;
                 u[c] = v < lo ? lo : (v > hi ? hi : v);
@@ -184,16 +230,20 @@ template <int MODEL, bool KNOTS> __global__ void __launch_bounds__(TILE) simulat
                     }
                 }
                 double k1[n], kk[n], w[n], xs[n];
-                D::f(P.mp, x, u, k1);
+                if constexpr (DIST) D::f(L.plant, x, u, k1);
+                else D::f(P.mp, x, u, k1);
 #pragma unroll
                 for (int i = 0; i < n; i++) { xs[i] = k1[i]; w[i] = x[i] + 0.5 * h * k1[i]; }
-                D::f(P.mp, w, u, kk);
+                if constexpr (DIST) D::f(L.plant, w, u, kk);
+                else D::f(P.mp, w, u, kk);
 #pragma unroll
                 for (int i = 0; i < n; i++) { xs[i] += 2 * kk[i]; w[i] = x[i] + 0.5 * h * kk[i]; }
-                D::f(P.mp, w, u, kk);
+                if constexpr (DIST) D::f(L.plant, w, u, kk);
+                else D::f(P.mp, w, u, kk);
 #pragma unroll
                 for (int i = 0; i < n; i++) { xs[i] += 2 * kk[i]; w[i] = x[i] + h * kk[i]; }
-                D::f(P.mp, w, u, kk);
+                if constexpr (DIST) D::f(L.plant, w, u, kk);
+                else D::f(P.mp, w, u, kk);
                 fin = true;
 #pragma unroll
                 for (int i = 0; i < n; i++) {
@@ -247,10 +297,14 @@ template <int MODEL> __global__ void __launch_bounds__(TILE) simulate_reduce(con
     reduce_problem<MODEL>(V, xe, b, sred);
 }
 
-template <int MODEL> int launch_simulate(gusto_handle h, const KParams& P, const SimArgs& V, bool knots) {
+// W: null for gusto_simulate, else V with the disturbances (V is its base)
+template <int MODEL> int launch_simulate(gusto_handle h, const KParams& P, const SimArgs& V, const SimArgsD* W, bool knots) {
     const int nt = 64 * ((std::min(V.S, TILE) + 63) / 64);
-    if (knots) hipLaunchKernelGGL((simulate_kernel<MODEL, true>), dim3(h->B, V.tiles), dim3(nt), 0, h->stream, P, V);
-    else hipLaunchKernelGGL((simulate_kernel<MODEL, false>), dim3(h->B, V.tiles), dim3(nt), 0, h->stream, P, V);
+    const dim3 grid(h->B, V.tiles);
+    if (W && knots) hipLaunchKernelGGL((simulate_kernel<MODEL, true, true>), grid, dim3(nt), 0, h->stream, P, *W);
+    else if (W) hipLaunchKernelGGL((simulate_kernel<MODEL, false, true>), grid, dim3(nt), 0, h->stream, P, *W);
+    else if (knots) hipLaunchKernelGGL((simulate_kernel<MODEL, true, false>), grid, dim3(nt), 0, h->stream, P, V);
+    else hipLaunchKernelGGL((simulate_kernel<MODEL, false, false>), grid, dim3(nt), 0, h->stream, P, V);
     HIPCHK(h, hipGetLastError());
     if (V.tiles > 1) {
         hipLaunchKernelGGL((simulate_reduce<MODEL>), dim3(h->B), dim3(TILE), 0, h->stream, P, V);
@@ -259,10 +313,48 @@ template <int MODEL> int launch_simulate(gusto_handle h, const KParams& P, const
     return GUSTO_OK;
 }
 
-int refuse(gusto_handle h, const std::string& text) {
-    h->err = "gusto_simulate: " + text;
+int refuse(gusto_handle h, const std::string& who, const std::string& text) {
+    h->err = who + ": " + text;
     return GUSTO_ERR_ARG;
 }
+
+// which of the GUSTO_NPLANT scalars the model's f reads
+bool plant_entry_read(int model, int j) {
+    if (model == GUSTO_DUBINS_CAR) return j >= 4;
+    if (model == GUSTO_FREEFLYER_SE2) return j == 0 || j == 3;
+    return j < 4;
+}
+
+// The arguments of gusto_simulate_disturbed that gusto_simulate does not have: GUSTO_ERR_ARG and the text, which names the
+// offending problem, sample and entry.  No device
+int disturb_args_host(gusto_handle h, const std::string& who, size_t B, size_t Ns, const gusto_disturb_opts& d, const double* plant,
+                      const double* white) {
+    const size_t N = h->N, m = h->m;
+    for (int j = 0; j < GUSTO_NPLANT; j++)
+        if (!(d.plant_rel[j] >= 0 && d.plant_rel[j] < 1)) return refuse(h, who, "plant_rel must lie in [0, 1) (entry " + std::to_string(j) + ")");
+    for (size_t i = 0; i < m; i++)
+        if (!(d.dw[i] >= 0 && d.dw[i] < INFINITY)) return refuse(h, who, "dw must be finite and >= 0 (entry " + std::to_string(i) + ")");
+    for (size_t e = 0; plant && e < B * Ns * GUSTO_NPLANT; e++) {
+        const int j = (int)(e % GUSTO_NPLANT);
+        if (!plant_entry_read(h->model, j)) continue;
+        const double v = plant[e];
+        const bool ok = j < 4 ? (v > 0 && v < INFINITY) : fabs(v) < INFINITY;
+        if (!ok)
+            return refuse(h, who, std::string(j < 4 ? "plant: mass and Jdiag must be finite and > 0" : "plant: dubins_v and dubins_k must be finite") +
+                                      " (problem " + std::to_string(e / GUSTO_NPLANT / Ns) + ", sample " + std::to_string(e / GUSTO_NPLANT % Ns) +
+                                      ", entry " + std::to_string(j) + ")");
+    }
+    for (size_t e = 0; white && e < B * (N - 1) * Ns * m; e++)
+        if (!(fabs(white[e]) < INFINITY))
+            return refuse(h, who, "white must be finite (problem " + std::to_string(e / m / Ns / (N - 1)) + ", interval " +
+                                      std::to_string(e / m / Ns % (N - 1) + 1) + ", sample " + std::to_string(e / m % Ns) + ", entry " +
+                                      std::to_string(e % m) + ")");
+    return GUSTO_OK;
+}
+
+// gusto_simulate (dist = null) and gusto_simulate_disturbed (dist: the options, never null; plant, white: the caller's or null)
+int simulate_host(gusto_handle h, const char* who_c, const double* X, const double* U, const double* K, const double* pert,
+                  const gusto_simulate_opts* opts, const gusto_disturb_opts* dist, const double* plant, const double* white);
 
 }  // namespace
 
@@ -280,33 +372,58 @@ int gusto_default_simulate_opts(int model_id, gusto_simulate_opts* o) {
 }
 
 int gusto_simulate(gusto_handle h, const double* X, const double* U, const double* K, const double* pert, const gusto_simulate_opts* opts) {
-    if (int rc = post_enter(h, "gusto_simulate", X, U)) return rc;
+    return simulate_host(h, "gusto_simulate", X, U, K, pert, opts, nullptr, nullptr, nullptr);
+}
+
+int gusto_default_disturb_opts(gusto_disturb_opts* d) {
+    if (!d) return GUSTO_ERR_ARG;
+    memset(d, 0, sizeof(*d));
+    return GUSTO_OK;
+}
+
+int gusto_simulate_disturbed(gusto_handle h, const double* X, const double* U, const double* K, const double* pert, const double* plant,
+                             const double* white, const gusto_simulate_opts* opts, const gusto_disturb_opts* d) {
+    gusto_disturb_opts zero;
+    gusto_default_disturb_opts(&zero);
+    return simulate_host(h, "gusto_simulate_disturbed", X, U, K, pert, opts, d ? d : &zero, plant, white);
+}
+
+}  // extern "C"
+
+namespace {
+
+int simulate_host(gusto_handle h, const char* who_c, const double* X, const double* U, const double* K, const double* pert,
+                  const gusto_simulate_opts* opts, const gusto_disturb_opts* dist, const double* plant, const double* white) {
+    if (int rc = post_enter(h, who_c, X, U)) return rc;
+    const std::string who(who_c);
     gusto_simulate_opts o;
     gusto_default_simulate_opts(h->model, &o);
     if (opts) o = *opts;
-    if (o.n_samples < 1 || o.n_samples > 4096) return refuse(h, "n_samples outside 1 .. 4096");
+    if (o.n_samples < 1 || o.n_samples > 4096) return refuse(h, who, "n_samples outside 1 .. 4096");
     if (!nstep_opts_ok(o.dt_min, o.nstep, o.nstep_cap) || (o.dense_collision != 0 && o.dense_collision != 1) ||
         (o.store_knots != 0 && o.store_knots != 1))
-        return refuse(h, "bad options");
+        return refuse(h, who, "bad options");
     for (int i = 0; i < h->n; i++)
-        if (!(o.dx0[i] >= 0 && o.dx0[i] < INFINITY)) return refuse(h, "dx0 must be finite and >= 0 (entry " + std::to_string(i) + ")");
+        if (!(o.dx0[i] >= 0 && o.dx0[i] < INFINITY)) return refuse(h, who, "dx0 must be finite and >= 0 (entry " + std::to_string(i) + ")");
     for (int i = 0; i < h->m; i++) {
-        if (!(o.du0[i] >= 0 && o.du0[i] < INFINITY)) return refuse(h, "du0 must be finite and >= 0 (entry " + std::to_string(i) + ")");
-        if (!(o.u_lo[i] <= o.u_hi[i])) return refuse(h, "u_lo must not exceed u_hi (entry " + std::to_string(i) + ")");
+        if (!(o.du0[i] >= 0 && o.du0[i] < INFINITY)) return refuse(h, who, "du0 must be finite and >= 0 (entry " + std::to_string(i) + ")");
+        if (!(o.u_lo[i] <= o.u_hi[i])) return refuse(h, who, "u_lo must not exceed u_hi (entry " + std::to_string(i) + ")");
     }
+    if (dist)
+        if (int rc = disturb_args_host(h, who, h->B, o.n_samples, *dist, plant, white)) return rc;
     SimulateState& S = h->simulate;
     if (!K && !h->tvlqr.have) {
-        h->err = "gusto_simulate: no gains: pass K or call gusto_tvlqr first";
+        h->err = who + ": no gains: pass K or call gusto_tvlqr first";
         return GUSTO_ERR_STATE;
     }
     const size_t Bc = h->batch_cap, B = h->B, N = h->N, n = h->n, m = h->m, Ns = o.n_samples;
     KParams P = post_params(h);
     if (!fill_env(h, P, model_info(h->model)->has_obs, true)) {
-        h->err = "gusto_simulate: gusto_set_env_batch was called with a different number of problems than gusto_set_problems";
+        h->err = who + ": gusto_set_env_batch was called with a different number of problems than gusto_set_problems";
         return GUSTO_ERR_STATE;
     }
     int nstep_max = 0;   // (as gusto_verify; the largest count is of no use here)
-    if (int rc = resolve_nstep(h, "gusto_simulate", o.dt_min, o.nstep, o.nstep_cap, &nstep_max)) return rc;
+    if (int rc = resolve_nstep(h, who_c, o.dt_min, o.nstep, o.nstep_cap, &nstep_max)) return rc;
     // grow-only; the layout depends on n_samples: results of another layout, or of other problems, are zeros before the launch
     HIPCHK(h, S.D.ensure(Bc * Ns)); HIPCHK(h, S.I.ensure(2 * Bc * Ns));
     HIPCHK(h, S.Xfin.ensure(Bc * Ns * n)); HIPCHK(h, S.Dev.ensure(Bc * Ns * n));
@@ -323,7 +440,11 @@ int gusto_simulate(gusto_handle h, const double* X, const double* U, const doubl
         HIPCHK(h, hipMemsetAsync(S.RD, 0, sizeof(double) * Bc * (1 + 2 * n), h->stream));
     }
     if (o.store_knots && !S.have_knots) HIPCHK(h, hipMemsetAsync(S.Knots, 0, sizeof(double) * Bc * N * Ns * n, h->stream));
-    SimArgs V{};
+    if (dist) {   // (the plant scalars of a problem this call leaves out are those of the last disturbed call, or zeros)
+        HIPCHK(h, S.Plant.ensure(Bc * Ns * GUSTO_NPLANT));
+        if (fresh || !S.disturbed) HIPCHK(h, hipMemsetAsync(S.Plant, 0, sizeof(double) * Bc * Ns * GUSTO_NPLANT, h->stream));
+    }
+    SimArgsD V{};
     if (int rc = stage_traj(h, X, U, Bc, S.X, S.U, &V.X, &V.U)) return rc;
     V.K = h->tvlqr.K;
     if (K) {
@@ -345,15 +466,35 @@ int gusto_simulate(gusto_handle h, const double* X, const double* U, const doubl
     V.smin = S.D; V.xfin = S.Xfin; V.dev = S.Dev; V.sidx = S.I; V.sflags = S.I + Bc * Ns; V.knots = S.Knots;
     V.n_free = S.RI; V.n_finite = S.RI + Bc; V.n_clipped = S.RI + 2 * Bc; V.worst_sample = S.RI + 3 * Bc; V.worst_dense = S.RI + 4 * Bc;
     V.min_dist = S.RD; V.max_dev = S.RD + Bc; V.max_final_dev = S.RD + Bc + Bc * n;
+    if (dist) {
+        if (plant) {
+            HIPCHK(h, S.PlantIn.ensure(Bc * Ns * GUSTO_NPLANT));
+            HIPCHK(h, hipMemcpyAsync(S.PlantIn, plant, sizeof(double) * B * Ns * GUSTO_NPLANT, hipMemcpyHostToDevice, h->stream));
+            V.plant_in = S.PlantIn;
+        }
+        if (white) {
+            HIPCHK(h, S.White.ensure(Bc * (N - 1) * Ns * m));
+            HIPCHK(h, hipMemcpyAsync(S.White, white, sizeof(double) * B * (N - 1) * Ns * m, hipMemcpyHostToDevice, h->stream));
+            V.white = S.White;
+        }
+        V.plant = S.Plant;
+        V.seed_plant = simrng_plant_seed(o.seed); V.seed_white = simrng_white_seed(o.seed);
+        memcpy(V.plant_rel, dist->plant_rel, sizeof(V.plant_rel)); memcpy(V.dw, dist->dw, sizeof(V.dw));
+    }
     HIPCHK(h, S.t0.record(h->stream));
-    if (int rc = for_model(h->model, [&](auto M) { return launch_simulate<M()>(h, P, V, o.store_knots != 0); })) return rc;
+    if (int rc = for_model(h->model, [&](auto M) { return launch_simulate<M()>(h, P, V, dist ? &V : nullptr, o.store_knots != 0); })) return rc;
     HIPCHK(h, S.t1.record(h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, event_ms(S.t0, S.t1, &S.last_ms));
     S.have = true; S.S = o.n_samples;
     S.have_knots = o.store_knots != 0;
+    S.disturbed = dist != nullptr;
     return GUSTO_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int gusto_get_simulate(gusto_handle h, gusto_simulate_report* out) {
     if (!h) return GUSTO_ERR_ARG;
@@ -382,6 +523,14 @@ int gusto_get_simulate_knots(gusto_handle h, double* Xcl) {
     const SimulateState& S = h->simulate;
     if (!S.have_knots) { h->err = "gusto_get_simulate_knots: the last gusto_simulate did not run with store_knots = 1"; return GUSTO_ERR_STATE; }
     return copy_out(h, Xcl, S.Knots, (size_t)h->B * h->N * S.S * h->n);
+}
+
+int gusto_get_simulate_plant(gusto_handle h, double* plant) {
+    if (!h) return GUSTO_ERR_ARG;
+    if (int rc = getter_enter(h, false)) return rc;
+    const SimulateState& S = h->simulate;
+    if (!S.have || !S.disturbed) { h->err = "gusto_get_simulate_plant: the last roll-out was not a gusto_simulate_disturbed"; return GUSTO_ERR_STATE; }
+    return copy_out(h, plant, S.Plant, (size_t)h->B * S.S * GUSTO_NPLANT);
 }
 
 int gusto_last_simulate_ms(gusto_handle h, double* ms) {

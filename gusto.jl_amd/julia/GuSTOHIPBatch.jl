@@ -479,22 +479,38 @@ mutable struct GustoSimulateReport      # gusto_simulate_report
   sample_dense_index::Ptr{Cint}; sample_flags::Ptr{Cint}
   x_final::Ptr{Cdouble}
 end
+struct GustoDisturbOpts       # gusto_disturb_opts
+  plant_rel::NTuple{6,Cdouble}; dw::NTuple{6,Cdouble}
+end
 gusto_bounds(w, dim, cap, off) = (v = w isa Number ? fill(Float64(w), dim) : Float64.(collect(w)); ntuple(i -> i <= dim ? v[i] : off, cap))
 
 # The roll-outs of B problems of handle h (x_dim n, u_dim m, N knots).  X [n,N,B], U [m,N,B] or nothing = the handle's own
 # trajectories; K [n,m,N-1,B] (K[:,:,k,b]' = K_k, as tvlqr_batch! returns it) or nothing = the gains of the last tvlqr_batch!;
 # pert [n+m,S,B] or nothing = generated on the device.  The per-sample arrays come back as [S,B], x_final as [n,S,B], max_dev as
 # [n,B]; with store_knots Xcl is [n,S,N,B].
+# plant_rel (a number or the 6 half-widths of mass, Jdiag[1:3], dubins_v, dubins_k), dw (a number or m half-widths), plant [6,S,B]
+# or white [m,S,N-1,B]: when any of them is given the roll-outs are those of gusto_simulate_disturbed -- the same law on a plant
+# that differs per sample, with an actuator noise per hold interval -- and `plant` [6,S,B] comes back as well.
 function simulate_batch!(h::Ptr{Cvoid}, B::Integer, n::Integer, m::Integer, N::Integer, X=nothing, U=nothing, K=nothing, pert=nothing;
                          n_samples=64, seed=0, first_problem=0, dx0=0.01, du0=0.0, u_lo=-Inf, u_hi=Inf, dt_min=0.1, nstep=0,
-                         nstep_cap=64, dense_collision=true, store_knots=false)
+                         nstep_cap=64, dense_collision=true, store_knots=false, plant_rel=nothing, dw=nothing, plant=nothing,
+                         white=nothing)
   ptr(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
   S = Int(n_samples)
   o = GustoSimulateOpts(S, seed, first_problem, gusto_weights(dx0, n, 13), gusto_weights(du0, m, 6), gusto_bounds(u_lo, m, 6, -Inf),
                         gusto_bounds(u_hi, m, 6, Inf), dt_min, nstep, nstep_cap, dense_collision ? 1 : 0, store_knots ? 1 : 0)
-  GC.@preserve X U K pert gusto_check(ccall((:gusto_simulate, libgusto_hip), Cint,
-                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{GustoSimulateOpts}),
-                    h, ptr(X), ptr(U), ptr(K), ptr(pert), o), h, "simulate")
+  disturbed = !(plant_rel === nothing && dw === nothing && plant === nothing && white === nothing)
+  if disturbed
+    d = GustoDisturbOpts(gusto_weights(plant_rel === nothing ? 0.0 : plant_rel, 6, 6), gusto_weights(dw === nothing ? 0.0 : dw, m, 6))
+    GC.@preserve X U K pert plant white gusto_check(ccall((:gusto_simulate_disturbed, libgusto_hip), Cint,
+                      (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                       Ref{GustoSimulateOpts}, Ref{GustoDisturbOpts}),
+                      h, ptr(X), ptr(U), ptr(K), ptr(pert), ptr(plant), ptr(white), o, d), h, "simulate_disturbed")
+  else
+    GC.@preserve X U K pert gusto_check(ccall((:gusto_simulate, libgusto_hip), Cint,
+                      (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{GustoSimulateOpts}),
+                      h, ptr(X), ptr(U), ptr(K), ptr(pert), o), h, "simulate")
+  end
   nfree, nfin, nclip, worst, wdense = zeros(Cint, B), zeros(Cint, B), zeros(Cint, B), zeros(Cint, B), zeros(Cint, B)
   dmin, dev, fdev = zeros(B), zeros(n, B), zeros(n, B)
   sdist, sidx, sflags, xfin = zeros(S, B), zeros(Cint, S, B), zeros(Cint, S, B), zeros(n, S, B)
@@ -505,9 +521,11 @@ function simulate_batch!(h::Ptr{Cvoid}, B::Integer, n::Integer, m::Integer, N::I
   end
   Xcl = store_knots ? zeros(n, S, N, B) : nothing
   store_knots && gusto_check(ccall((:gusto_get_simulate_knots, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, Xcl), h, "get_simulate_knots")
+  used = disturbed ? zeros(6, S, B) : nothing
+  disturbed && gusto_check(ccall((:gusto_get_simulate_plant, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, used), h, "get_simulate_plant")
   ms = Ref{Cdouble}(0.0)
   gusto_check(ccall((:gusto_last_simulate_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, ms), h, "last_simulate_ms")
   (n_free = Int.(nfree), n_finite = Int.(nfin), n_clipped = Int.(nclip), worst_sample = Int.(worst), worst_dense_sample = Int.(wdense),
    min_dist = dmin, max_dev = dev, max_final_dev = fdev, sample_min_dist = sdist, sample_dense_index = Int.(sidx),
-   sample_flags = Int.(sflags), x_final = xfin, Xcl = Xcl, ms = ms[])
+   sample_flags = Int.(sflags), x_final = xfin, Xcl = Xcl, plant = used, ms = ms[])
 end

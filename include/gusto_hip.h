@@ -398,6 +398,53 @@ int gusto_get_simulate_knots(gusto_handle h, double* Xcl);
 /* GPU time of the last gusto_simulate (roll-out and, for more than 256 samples, the reduction launch), from HIP events */
 int gusto_last_simulate_ms(gusto_handle h, double* ms);
 
+/* gusto_simulate with an uncertain plant and an actuator noise drawn anew in every hold interval (csrc/simulate.hip).  No
+ * counterpart in the reference.  Everything gusto_simulate defines stays as it is -- the roll-out, the dense samples, the
+ * distance, the non-finite rule, pert and its generator, K, X, U, gusto_set_active, stream and timing, the refusals (under this
+ * call's name), the grow-only buffers, "the same bit for bit whatever batch it sits in" -- and the controller is the NOMINAL
+ * one: K, X, U and the law are unchanged, only the plant that is integrated and the control it receives differ.
+ * Plant of sample s of problem b: theta = plant[b][s][0 .. GUSTO_NPLANT-1] = (mass, Jdiag[0], Jdiag[1], Jdiag[2], dubins_v,
+ *   dubins_k), ABSOLUTE values as given by the caller, or (plant = NULL) generated: theta_j = nominal_j (1 + e_j), nominal the
+ *   handle's gusto_model_params, e_j uniform in [-plant_rel_j, plant_rel_j), one rounding for the sum and one for the product;
+ *   sample 0 draws zeros: it is the nominal plant, exactly.  The RK4 stages evaluate f with theta in place of mass, Jdiag,
+ *   dubins_v, dubins_k; nothing else of gusto_model_params changes: radius, clearance and the robot's components are the
+ *   nominal ones.  freeflyerSE2 reads mass and Jdiag[2], DubinsCar dubins_v and dubins_k, both Astrobee models mass and
+ *   Jdiag[0 .. 2]; entries a model does not read are ignored, whatever they hold.
+ * Actuator noise: in interval k = 1 .. N-1
+ *     v = ((U[:,k] - K_k (x - X[:,k])) + p[x_dim:]) + w_k,   u = clip(v, u_lo, u_hi) as in gusto_simulate
+ *   with w_k = white[b][k-1][s][0 .. u_dim-1] as given by the caller -- [B][N-1][S][u_dim], knot-major like Xcl, so a
+ *   wavefront's 64 samples of one interval are one contiguous range -- or (white = NULL) generated: entry i uniform in
+ *   [-dw_i, dw_i), zeros for sample 0.  The clipped flag and n_clipped see v after the noise.  This is the sampled form of
+ *   the du_white of gusto_lincov with du_white_i = dw_i / sqrt(3), the convention of that stage's default S0 (the variances of
+ *   the uniform draws with the same half-widths); gusto_lincov covers dw in this way, but NOT the plant dispersion.
+ * Generator: splitmix64 and the r -> (2 r - 1) w step of gusto_simulate on two streams of their own.  Streams whose seeds
+ *   differ by a multiple of 0x9E3779B97F4A7C15 would be shifted copies of the pert stream, so the stream seeds are hashed, with
+ *   sm(seed, idx) output number idx of splitmix64 started at seed (the z of gusto_simulate's text):
+ *     seed_plant = sm(seed ^ 0x504C414E54, 0),   idx_plant = ((first_problem + b) S + s) 6 + j
+ *     seed_white = sm(seed ^ 0x5748495445, 0),   idx_white = (((first_problem + b) S + s) (N - 1) + (k - 1)) u_dim + i
+ *   (seed, first_problem of gusto_simulate_opts): a shard with first_problem = its offset draws what the whole batch draws.
+ * gusto_get_simulate, gusto_get_simulate_knots and gusto_last_simulate_ms report the last call of either kind;
+ *   gusto_get_simulate_plant returns the theta the kernel used, generated or supplied (the kernel writes them out; an inactive
+ *   problem's are those of the last disturbed call with the same n_samples, zeros if a plain gusto_simulate came between), and
+ *   answers GUSTO_ERR_STATE when the last call was a plain gusto_simulate or there was none.
+ * GUSTO_ERR_ARG, nothing launched, the offending problem, sample and entry in gusto_last_error: a plant_rel outside [0, 1) or
+ *   not finite; a dw that is negative or not finite; a supplied plant whose mass or Jdiag entry, where the model reads it, is
+ *   not finite or not > 0, or whose dubins_v or dubins_k, where read, is not finite; a supplied white with a non-finite entry.
+ * With d NULL or all zeros and plant = white = NULL every output equals that of gusto_simulate with the same remaining
+ *   arguments, as numbers (adding a zero noise can at most turn a -0.0 into +0.0); likewise when the caller supplies the
+ *   nominal theta and zeros as white.
+ * plant_rel[0] = 1.36 / 16.72 = 0.08134 spans the reference free-flyer's 15.36 .. 18.08 kg (robot/freeflyer.jl:32-34). */
+#define GUSTO_NPLANT 6    /* mass, Jdiag[0], Jdiag[1], Jdiag[2], dubins_v, dubins_k */
+typedef struct {
+    double plant_rel[GUSTO_NPLANT]; /* half-widths of the relative dispersion of the plant's scalars; default 0 */
+    double dw[GUSTO_MAXM];          /* half-widths of the actuator noise drawn anew in every hold interval; default 0 */
+} gusto_disturb_opts;
+int gusto_default_disturb_opts(gusto_disturb_opts* d);            /* all zeros */
+int gusto_simulate_disturbed(gusto_handle h, const double* X, const double* U, const double* K, const double* pert,
+                             const double* plant, const double* white,
+                             const gusto_simulate_opts* o, const gusto_disturb_opts* d);
+int gusto_get_simulate_plant(gusto_handle h, double* plant);     /* [B][S][GUSTO_NPLANT] of the last disturbed call */
+
 /* Linear covariance analysis of the tracking law (csrc/lincov.hip): the analytic counterpart of gusto_simulate -- one forward
  * pass per problem carries a covariance through the closed loop and turns it into margins.  No counterpart in the reference;
  * the definitions, for one problem with n = x_dim, m = u_dim:
@@ -408,7 +455,8 @@ int gusto_last_simulate_ms(gusto_handle h, double* ms);
  * Recursion, k = 1 .. N-1, with [Ad_k | Bd_k] of the handle's LAST gusto_tvlqr and G_k = [Ad_k - Bd_k K_k | Bd_k] (n x (n + m)):
  *     Sxx_{k+1} = G_k S_k G_k' + Bd_k diag(du_white^2) Bd_k',   Sxb_{k+1} = G_k S_k[:, n:],   Sbb stays.
  *   Sxx is computed on the upper triangle and mirrored: symmetric to the bit.  du_white is the standard deviation of an
- *   independent actuator noise w_k per hold interval (gusto_simulate has no such term).
+ *   independent actuator noise w_k per hold interval (gusto_simulate has no such term; gusto_simulate_disturbed samples it
+ *   with the half-widths dw = sqrt(3) du_white).
  * Commanded control at knot k: its deviation is dv = [-K_k | I] z + w_k,
  *     sigma_u[k][i] = sqrt(([-K_k I] S_k [-K_k I]' + diag(du_white^2))_ii);   sigma_x[k][i] = sqrt(Sxx_k[i][i]).
  *   Under every square root here and below, a variance that rounding leaves below zero counts as zero: the feedback cancels a

@@ -1,11 +1,13 @@
 """The figures behind the tolerance of tests/test_gpu_simulate.py, one line per quantity.
 
-  python tools/simulate_errors.py [--device]
+  python tools/simulate_errors.py [--device] [--disturbed]
 
 Without a GPU: over exactly the cases of tests/sim_cases.py, the largest relative difference between the float64 and the
 np.longdouble run of the numpy restatement (tests/np_simulate.py) -- what one rounding per operation does to each compared
 quantity.  The test gates at 100 x the largest of them, rounded up to a power of ten.  With --device: the device's errors
-against the float64 restatement fed with the device's own gains, beside them (profiles/simulate.txt holds both)."""
+against the float64 restatement fed with the device's own gains, beside them (profiles/simulate.txt holds both).
+With --disturbed: the same for gusto_simulate_disturbed -- tests/sim_disturbed_cases.py, tests/np_simulate_disturbed.py and
+tests/test_gpu_simulate_disturbed.py (profiles/simulate_disturbed.txt)."""
 import os
 import sys
 
@@ -31,16 +33,19 @@ def rel(a, ref):
 def main():
     worst, dev = {}, {}
     device = "--device" in sys.argv
+    cases = SC
+    if "--disturbed" in sys.argv:
+        import sim_disturbed_cases as cases
     if device:
-        import test_gpu_simulate as G
-    for case in SC.CASES:
-        lo = SC.reference(case, dtype=np.float64)
-        hi = SC.reference(case, dtype=np.longdouble)
+        G = __import__("test_gpu_simulate_disturbed" if cases is not SC else "test_gpu_simulate")
+    for case in cases.CASES:
+        lo = cases.reference(case, dtype=np.float64)
+        hi = cases.reference(case, dtype=np.longdouble)
         for b in range(SC.B):
             for k in FIELDS:
                 worst[k] = max(worst.get(k, 0.0), rel(lo[b][k], hi[b][k]))
         if device:
-            r, Xcl, ref = G.device_and_reference(case)
+            r, Xcl, ref = (lambda out: (out[0], out[1], out[-1]))(G.device_and_reference(case))
             for b in range(SC.B):
                 for k in FIELDS:
                     got = Xcl[b] if k == "Xcl" else r[k][b]
