@@ -75,7 +75,7 @@ template <> struct MT<GUSTO_FREEFLYER_SE2> {
     static constexpr int WAVES_PER_EU = GUSTO_WAVES_PER_EU;   // register budget of the one-wave kernel: 512 / this
     static constexpr int RS_FORM = RS_ROW;   // layout and addressing of the row state, see RS_EARLIER .. RS_ROW_LANE above (the one-wave kernel: RS_PAIR, rs_form)
     static constexpr bool SWEEP_CALL = false;   // factor sweep as a function call (ipm.hpp:factor_sweep)
-    static constexpr bool SWEEP_DPP = true;   // one-wave vector sweeps on v_fmac_f64_dpp row_newbcast with row swaps between the rows of 16 lanes (ipm.hpp:backward_sweep_dpp; needs n = 6, PG2)
+    static constexpr bool SWEEP_DPP = true;   // one-wave vector sweeps on v_fmac_f64_dpp row_newbcast with row swaps between the rows of 16 lanes (sweeps.hpp:backward_sweep_dpp; needs n = 6, PG2)
     static constexpr bool MFMA = false;   // dense per-knot products of the factor sweep on v_mfma_f64_16x16x4_f64
     static constexpr int SCHED_PROBE = 2;   // default number of one-trip probing slices of the longest-first scheduler
     static constexpr int SCHED_SLICE = 4;   // then slices of 4 trips for problems of penalty level 0 (34.1 vs 34.65 ms; the 12/13-state models lose with any)

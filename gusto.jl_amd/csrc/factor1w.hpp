@@ -1062,15 +1062,4 @@ GD void factor_sweep_mfma(SweepView<MODEL> K, double* fail, Prof& pf, int kHi_ =
     K.sync();
 }
 
-// Affine vector recurrences of the one-wave path.  The wave is split into C = 64/n groups of n lanes; group g
-// holds the operands of knot (k0 -+ g) of the current chunk of C knots, so ONE batch of global loads feeds C knots
-// of the dependency chain (the recurrences are memory-latency bound otherwise), and the next chunk is fetched
-// while the current one computes.  The n-vector travels between groups with v_readlane (no LDS on the chain).
-//
-// backward: pt_{k-1} = Phicl_k^T pt_k + qq_k, k = N-1..1, pt := p + r (so qq_k = qt_k + r_{k-1}), pt_{N-1} = r_{N-1}.
-//           pv[k] holds qq_k on entry and pt_k on exit.
-#ifndef GUSTO_SWEEP_RING
-#define GUSTO_SWEEP_RING 4
-#endif
-
 }  // namespace gusto

@@ -624,7 +624,7 @@ struct StepFrac {
 // row pass (6 row-state reads per row) less per interior point iteration.
 // HDX: the pass also leaves hdx = H_x dx of this knot, H_x = sum over the state rows of sigma grad grad^T + lam hess -- the
 // condensed Hessian the residual pass put into the stage cost, applied to the step instead of stored (the adjoint costate
-// recursion of the 12/13-state kernels, ipm.hpp: adjoint_sweep_1w, needs H_x dx_k and nothing else of H_x).
+// recursion of the 12/13-state kernels, sweeps.hpp: adjoint_sweep_1w, needs H_x dx_k and nothing else of H_x).
 template <int NP, bool HDX, class RS> struct OpStep {
     static constexpr bool FIX_BATCH = NP == 0;
     RS rs;

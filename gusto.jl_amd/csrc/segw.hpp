@@ -208,7 +208,8 @@ template <int MODEL, class BLK> GD void seg_fold_tree_level2(BLK& K, double* fai
     seg_fold_finish<MODEL, 4>(K, fail, I1 + SB::PIc);
 }
 
-// ---- the ring-buffered one-wave vector sweeps of ipm.hpp over a RANGE of knots (operands from the global Phicl records) ----
+// ---- the ring paths of backward_sweep_1w / forward_sweep_1w (sweeps.hpp) over a RANGE of knots: a start vector in LDS, and the
+// backward sweep's last vector redirected to last_out.  Same chain step (GUSTO_CHAIN_STEP) ----
 template <int MODEL, class BLK> GD void backward_sweep_ring_rng(const BLK& K, int khi, int klo, int start, int last_out) {
     constexpr int n = BLK::n, C = 64 / n, PS = 4, RING = GUSTO_SWEEP_RING;
     const LPtr<double> L = K.lds;
@@ -235,20 +236,7 @@ template <int MODEL, class BLK> GD void backward_sweep_ring_rng(const BLK& K, in
             if (k0 >= klo) {
 #pragma unroll
                 for (int gs = 0; gs < C; gs++) {
-                    if (k0 - gs >= klo) {
-                        const int sg = (gs == 0) ? C - 1 : gs - 1;
-                        double acc[PS];
-#pragma unroll
-                        for (int q = 0; q < PS; q++) acc[q] = (q == 0) ? qb[d] : 0.0;
-                        double pb[n];
-#pragma unroll
-                        for (int l = 0; l < n; l++) pb[l] = readlane_f64(pval, sg * n + l);
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int l = 0; l < n; l++) acc[l % PS] += cb[d][l] * pb[l];
-                        const double sacc = (acc[0] + acc[1]) + (acc[2] + acc[PS - 1]);
-                        pval = (g == gs) ? sacc : pval;
-                    }
+                    if (k0 - gs >= klo) GUSTO_CHAIN_STEP(pval, qb[d], cb[d], PS)
                 }
                 const int kk = k0 - g;
                 if (tid < C * n && kk >= klo) {
@@ -284,20 +272,7 @@ template <int MODEL, class BLK> GD void forward_sweep_ring_rng(const BLK& K, int
             if (k0 <= khi) {
 #pragma unroll
                 for (int gs = 0; gs < C; gs++) {
-                    if (k0 + gs <= khi) {
-                        const int sg = (gs == 0) ? C - 1 : gs - 1;
-                        double acc[PS];
-#pragma unroll
-                        for (int q = 0; q < PS; q++) acc[q] = (q == 0) ? qb[d] : 0.0;
-                        double pb[n];
-#pragma unroll
-                        for (int l = 0; l < n; l++) pb[l] = readlane_f64(yval, sg * n + l);
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int l = 0; l < n; l++) acc[l % PS] += rb[d][l] * pb[l];
-                        const double sacc = (acc[0] + acc[1]) + (acc[2] + acc[PS - 1]);
-                        yval = (g == gs) ? sacc : yval;
-                    }
+                    if (k0 + gs <= khi) GUSTO_CHAIN_STEP(yval, qb[d], rb[d], PS)
                 }
                 const int kk = k0 + g;
                 if (tid < C * n && kk <= khi) K.dY[kk * n + i] = yval;

@@ -1,4 +1,4 @@
-"""The one-wave vector sweeps of freeflyerSE2 (csrc/ipm.hpp: backward_sweep_dpp / forward_sweep_dpp) run the same sums in the same
+"""The one-wave vector sweeps of freeflyerSE2 (csrc/sweeps.hpp: backward_sweep_dpp / forward_sweep_dpp) run the same sums in the same
 order as the v_readlane sweeps they replace (backward_sweep_1w / forward_sweep_1w), so every solve must stay BIT-identical.  The
 fixtures tests/golden/sweepdpp_freeflyer_n{N}.npz were recorded on an MI355X with the library that still ran freeflyerSE2 on the
 readlane sweeps; the library must reproduce them bit for bit, np.array_equal on every key.

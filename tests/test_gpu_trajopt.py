@@ -69,8 +69,8 @@ def _subproblem_parity(model, N, boxes, spheres, prob, mu, s_tr, Xp=None, Up=Non
 
 @pytest.mark.parametrize("model", [g.FREEFLYER_SE2, g.ASTROBEE_SE3, g.ASTROBEE_SE3_MANIFOLD])
 def test_subproblem_parity_of_the_multi_wave_phases(model):
-    """N > 64: the generic multi-wave phases (factor_sweep_mw, backward / forward_sweep_mw) -- a one-wave problem (every N = 50
-    case of this file) takes factor_sweep_w1 and the one-wave vector sweeps since round 5, so this is the test that keeps the
+    """N > 64: the generic multi-wave phases (factor_sweep_mw; csrc/sweeps.hpp: backward_sweep_mw / forward_sweep_mw) -- a one-wave
+    problem (every N = 50 case of this file) takes factor_sweep_w1 and backward_sweep_1w / forward_sweep_1w since round 5, so this is the test that keeps the
     generic TrajOpt path under parity.  Same tolerances as test_subproblem_parity."""
     _multi_wave_parity(model, 80)
 
