@@ -99,13 +99,14 @@ def test_subproblem_parity_astrobee_manifold():
     _sub_parity(g.ASTROBEE_SE3_MANIFOLD, 50, boxes, sph, x0, glo, ghi, tf, 1e3, 1.0, 1e3 / 8 + 0.03, atol=1e-4, u_atol=1e-6)
 
 
-def _oracle_runs(model, N, env, spheres, x0, glo, ghi, tf, max_iter, cold=True, model_params=None):
+def _oracle_runs(model, N, env, spheres, x0, glo, ghi, tf, max_iter, cold=True, model_params=None, scp_params=None):
     """Oracle solve of every problem with its per-trip trace (traj_prev, subproblem optimum).  The run itself warm-
     starts every interior point solve after the first; the device's lock-step trips start cold, so each traced trip
     is ALSO re-solved cold through the oracle's pieces (same start on both sides): keys Xc, Uc, conv_c, rho_c, J_c, obj_c."""
     g, go = _mods()
     clr = (model_params or g.default_params(model)[1]).clearance
-    o = go.Oracle(model, N, boxes=env, spheres=spheres, model_params=as_params(go.ModelParams, model_params))
+    o = go.Oracle(model, N, boxes=env, spheres=spheres, model_params=as_params(go.ModelParams, model_params),
+                  scp_params=as_params(go.ScpParams, scp_params))
     runs = []
     for b in range(len(x0)):
         o.set_trace(max_iter + 2)
@@ -121,7 +122,7 @@ def _oracle_runs(model, N, env, spheres, x0, glo, ghi, tf, max_iter, cold=True, 
 
 
 def _lockstep_parity(model, N, env, spheres, x0, glo, ghi, tf, max_iter=30, sub_atol=SUB_ATOL, max_flag_mismatch=0.005,
-                     u_atol=SUB_ATOL, q_tight=0.9, min_same_iters=0.9, max_cold_fail=1, model_params=None):
+                     u_atol=SUB_ATOL, q_tight=0.9, min_same_iters=0.9, max_cold_fail=1, model_params=None, scp_params=None, out=None):
     """EVERY trip of EVERY problem (no omega cut-off): the oracle's (traj_prev, Delta, omega) of the trip is fed to
     the device, first through gusto_subproblem (the convex solve alone), then as ONE GuSTO trip of the real state
     machine (gusto_set_trust_state + gusto_solve(1)), whose post-solve quantities -- convergence_measure, rho, the
@@ -131,9 +132,11 @@ def _lockstep_parity(model, N, env, spheres, x0, glo, ghi, tf, max_iter=30, sub_
     point iterations: X, U sub_atol*max(1,omega); convergence_measure 1e-8*max(1,omega) abs; rho 1e-6 rel; J_true
     1e-7 rel; J_full 1e-8*max(1,omega) rel.  A trip where one side stops an iteration earlier (borderline at the 1e-8
     residual test) is gated at 20 x sub_atol.  Verdicts and updates exact on all but `max_flag_mismatch` of the trips
-    (a verdict whose margin is below the solver tolerance may flip)."""
+    (a verdict whose margin is below the solver tolerance may flip).  scp_params: the SCP parameters of both sides (None: the
+    model's defaults); out: a dict that receives runs, trips, the device's history h of step (2) and `same`, the trips whose verdicts
+    and updates agree."""
     g, go = _mods()
-    runs = _oracle_runs(model, N, env, spheres, x0, glo, ghi, tf, max_iter, model_params=model_params)
+    runs = _oracle_runs(model, N, env, spheres, x0, glo, ghi, tf, max_iter, model_params=model_params, scp_params=scp_params)
     all_trips = [(b, t) for b, (r, tr) in enumerate(runs) for t in range(len(tr))]
     # a trip the oracle's warm-started run solved may fail from the cold start both sides use here (subproblems at the
     # edge of feasibility, dubins): such trips are compared by status only -- below -- and are rare
@@ -151,7 +154,8 @@ def _lockstep_parity(model, N, env, spheres, x0, glo, ghi, tf, max_iter=30, sub_
     Delta = np.array([runs[b][0]["Delta"][t] for b, t in trips])
     omega = np.array([runs[b][0]["omega"][t] for b, t in trips])
     mp = model_params or g.default_params(model)[1]
-    s = g.BatchSolver(model, N, T, hist_cap=8, boxes=env, spheres=spheres, model_params=as_params(g.ModelParams, model_params))
+    s = g.BatchSolver(model, N, T, hist_cap=8, boxes=env, spheres=spheres, model_params=as_params(g.ModelParams, model_params),
+                      scp_params=as_params(g.ScpParams, scp_params))
     s.set_schedule(0, 1)
     # (1) the convex subproblem of every trip
     s.set_problems(x0[bi], glo[bi], ghi[bi], tf[bi])
@@ -177,29 +181,44 @@ def _lockstep_parity(model, N, env, spheres, x0, glo, ghi, tf, max_iter=30, sub_
     s.set_problems(x0[bi], glo[bi], ghi[bi], tf[bi], Xp, Up)
     s.set_trust_state(Delta, omega)
     s.solve(1)
-    h, st = s.history(), s.status()
-    assert (h["n_hist"] == 2).all() and (st["iterations"] == 1).all()
     R = lambda k: np.array([runs[b][0][k][t + 1] for b, t in trips])
-    ec = np.abs(h["convergence_measure"][:, 1] - C_("conv_c")) / w
-    same_it = h["ipm_iters"][:, 1] == C_("it_c")
+    ref = dict(conv=C_("conv_c"), obj=C_("obj_c"), iters=C_("it_c"), J=C_("J_c"), rho=C_("rho_c"), tr_sat=R("tr_sat"), cvx_sat=R("cvx_sat"),
+               accept=R("accept"), scp_status=R("scp_status"), Delta=R("Delta"), omega=R("omega"))
+    h = s.history()
+    t2 = _trip_checks(h, s.status(), ref, omega, sub_atol, max_flag_mismatch, trips)
+    if out is not None:
+        out.update(runs=runs, trips=trips, h=h, same=t2["same"])
+    return dict(cold_fail=len(cold_fail), same_iters=float(t2["same_it"].mean()), trips=T, max_omega=float(omega.max()), ex=float(ex.max()), eu=float(eu.max()),
+                conv=float(t2["ec"].max()), rho=t2["worst_rho"], flag_mismatch=int((~t2["same"]).sum()))
+
+
+def _trip_checks(h, st, ref, omega, sub_atol, max_flag_mismatch, trips):
+    """Step (2) of _lockstep_parity: history h and status st of a handle on which every problem took ONE trip from a set trust state
+    with weight omega, against the reference of each trip -- arrays over the trips: conv, obj, iters, J, rho (the cold oracle
+    pieces) and the expected entries tr_sat, cvx_sat, accept, scp_status, Delta, omega.  `trips` labels the trips in messages."""
+    T = len(omega)
+    w = np.maximum(1.0, omega)
+    assert (h["n_hist"] == 2).all() and (st["iterations"] == 1).all()
+    ec = np.abs(h["convergence_measure"][:, 1] - ref["conv"]) / w
+    same_it = h["ipm_iters"][:, 1] == ref["iters"]
     assert ec[same_it].max() < max(1e-8, 0.05 * (sub_atol - SUB_ATOL)) and ec.max() < 20 * sub_atol, (ec[same_it].max(), ec.max(), trips[int(ec.argmax())])
-    eJf = np.abs(h["J_full"][:, 1] - C_("obj_c")) / (w * np.maximum(1.0, np.abs(C_("obj_c"))))
+    eJf = np.abs(h["J_full"][:, 1] - ref["obj"]) / (w * np.maximum(1.0, np.abs(ref["obj"])))
     assert eJf[same_it].max() < 1e-8 and eJf.max() < 1e-6, (eJf[same_it].max(), eJf.max())
     flags = dict(trust_region_satisfied="tr_sat", convex_ineq_satisfied="cvx_sat", accept_solution="accept",
                  scp_status="scp_status")
     same = np.ones(T, bool)
     for kd, ko in flags.items():
-        same &= h[kd][:, 1] == R(ko)
-    same &= (h["Delta"][:, 1] == R("Delta")) & (h["omega"][:, 1] == R("omega"))
+        same &= h[kd][:, 1] == ref[ko]
+    same &= (h["Delta"][:, 1] == ref["Delta"]) & (h["omega"][:, 1] == ref["omega"])
     allowed = int(max_flag_mismatch) if max_flag_mismatch >= 1 else max(1, int(max_flag_mismatch * T))
     assert (~same).sum() <= allowed, ((~same).sum(), T, [trips[i] for i in np.nonzero(~same)[0][:8]])
-    acc = same & (R("accept") == 1)
-    eJ = np.abs(h["J_true"][acc, 1] - C_("J_c")[acc]) / np.maximum(1e-12, np.abs(C_("J_c")[acc]))
+    acc = same & (ref["accept"] == 1)
+    eJ = np.abs(h["J_true"][acc, 1] - ref["J"][acc]) / np.maximum(1e-12, np.abs(ref["J"][acc]))
     assert eJ[same_it[acc]].max() < 2e-6 and eJ.max() < 1e-4, eJ.max()      # J = sum u^2: twice the relative error of u
     # rho of the trip (device: [0] = the constructor's 0, [1] = ratio(traj, traj) of this call, [2] = this trip)
     tr_ok = same & (h["trust_region_satisfied"][:, 1] == 1)
     assert (h["n_rho"][tr_ok] == 3).all()
-    rd, ro = h["rho"][tr_ok, 2], C_("rho_c")[tr_ok]
+    rd, ro = h["rho"][tr_ok, 2], ref["rho"][tr_ok]
     erho = np.abs(rd - ro) / np.maximum(np.abs(ro), 1e-300)
     si = same_it[tr_ok]
     # rho is a ratio of sums of SECOND-order linearisation errors (often 1e-5..1e-3 against thresholds rho0, rho1 of
@@ -210,15 +229,17 @@ def _lockstep_parity(model, N, env, spheres, x0, glo, ghi, tf, max_iter=30, sub_
     assert (np.abs(rd - ro)[si] <= 1e-6 * np.abs(ro)[si] + 3e-8).all(), (np.abs(rd - ro)[si].max(), erho[si].max())
     assert (np.abs(rd - ro) <= 1e-3 * np.abs(ro) + 1e-6).all(), (np.abs(rd - ro).max(), erho.max())
     worst_rho = float(erho.max()) if len(erho) else 0.0
-    return dict(cold_fail=len(cold_fail), same_iters=float(same_it.mean()), trips=T, max_omega=float(omega.max()), ex=float(ex.max()), eu=float(eu.max()), conv=float(ec.max()),
-                rho=worst_rho, flag_mismatch=int((~same).sum()))
+    return dict(ec=ec, same_it=same_it, same=same, worst_rho=worst_rho)
 
 
-def _scp_parity(model, N, env, spheres, x0, glo, ghi, tf, max_iter=30, max_diverged=0, rtol=1e-4, tr_tol=None):
+def _scp_parity(model, N, env, spheres, x0, glo, ghi, tf, max_iter=30, max_diverged=0, rtol=1e-4, tr_tol=None, scp_params=None,
+                force=False, out=None, conv_atol=1e-5):
     """Whole solves, every problem compared (no omega cut-off).  Two implementations of the same algorithm amplify
     their rounding differences along 10-30 trips, so a problem may legitimately take a different branch late in its
     run; such problems are COUNTED (at most `max_diverged`), and up to the first differing entry their histories must
-    still agree.  The lock-step test above is the one that proves no trip hides drift."""
+    still agree.  The lock-step test above is the one that proves no trip hides drift.  scp_params, force: of both sides; out: a
+    dict that receives the device's status st and history h and the oracle's results; conv_atol: the absolute part of the
+    comparison of the convergence measures."""
     g, go = _mods()
     B = len(x0)
     ig = io_ = None
@@ -226,16 +247,20 @@ def _scp_parity(model, N, env, spheres, x0, glo, ghi, tf, max_iter=30, max_diver
         ig = g.default_ipm_opts(); ig.tr_tol = tr_tol
         io_ = go.IpmOpts(tol=ig.tol, tol_acc=ig.tol_acc, mu_floor=ig.mu_floor, tr_tol=tr_tol, mu_warm=ig.mu_warm, max_iter=ig.max_iter,
                          acc_iter=ig.acc_iter, mu_warm_gain=ig.mu_warm_gain, mu_warm_max=ig.mu_warm_max, sigma_max=ig.sigma_max)
-    s = g.BatchSolver(model, N, B, hist_cap=max_iter + 8, boxes=env, spheres=spheres, ipm_opts=ig)
+    s = g.BatchSolver(model, N, B, hist_cap=max_iter + 8, boxes=env, spheres=spheres, ipm_opts=ig, scp_params=as_params(g.ScpParams, scp_params))
     s.set_problems(x0, glo, ghi, tf)
-    s.solve(max_iter)
+    s.solve(max_iter, force)
     X, U = s.traj()
     st, h = s.status(), s.history()
-    o = go.Oracle(model, N, boxes=env, spheres=spheres, ipm_opts=io_)
+    o = go.Oracle(model, N, boxes=env, spheres=spheres, ipm_opts=io_, scp_params=as_params(go.ScpParams, scp_params))
     diverged = []
+    if out is not None:
+        out.update(st=st, h=h, oracle=[], diverged=diverged)
     for b in range(B):
         o.set_problem(x0[b], glo[b], ghi[b], tf[b])
-        r = o.solve(max_iter)
+        r = o.solve(max_iter, force=force)
+        if out is not None:
+            out["oracle"].append(r)
         nh = int(h["n_hist"][b])
         c = min(nh, len(r["omega"]))
         agree = (np.array_equal(h["scp_status"][b, :c], r["scp_status"][:c]) and np.array_equal(h["omega"][b, :c], r["omega"][:c])
@@ -277,7 +302,7 @@ def _scp_parity(model, N, env, spheres, x0, glo, ghi, tf, max_iter=30, max_diver
         # on convergence_measure, whose threshold is 1e-2..1e-4); the per-trip agreement is the lock-step test's
         np.testing.assert_allclose(h["J_true"][b, :nJ][:ch], r["J_true"][:ch], rtol=rtol * wh, atol=1e-9)
         np.testing.assert_allclose(h["J_full"][b, :nJ][:ch], r["J_full"][:ch], rtol=rtol * wh, atol=1e-9)
-        np.testing.assert_allclose(h["convergence_measure"][b, :nh][:ch], r["conv"][:ch], rtol=rtol * wh, atol=1e-5 * wh)
+        np.testing.assert_allclose(h["convergence_measure"][b, :nh][:ch], r["conv"][:ch], rtol=rtol * wh, atol=conv_atol * wh)
         nr = h["n_rho"][b]
         np.testing.assert_allclose(h["rho"][b, :nr][:ch], r["rho"][:ch], rtol=100 * rtol * wh, atol=1e-7 * wh)
     assert len(diverged) <= max_diverged, diverged
@@ -650,18 +675,24 @@ def test_longest_first_schedule_is_bit_identical(model):
         s.set_problems(x0, glo, ghi, tf)
         s.solve(30)
         out.append((s.traj(), s.status(), s.history()))
-    (X, U), st, hist = out[0]
+    for o in out[1:]:
+        _assert_same_runs(out[0], o)
+
+
+def _assert_same_runs(a, b):
+    """(traj(), status(), history()) of two solves: trajectories, statuses and the set entries of the histories bit for bit"""
+    (X, U), st, hist = a
+    (X2, U2), st2, h2 = b
     valid = np.arange(hist["Delta"].shape[1])[None, :] < hist["n_hist"][:, None]
     validJ = np.arange(hist["J_true"].shape[1])[None, :] < hist["nJ"][:, None]
-    for (X2, U2), st2, h2 in out[1:]:
-        assert np.array_equal(X, X2) and np.array_equal(U, U2)
-        for k in st:
-            assert np.array_equal(st[k], st2[k]), k
-        for k in ("n_hist", "nJ", "n_rho"):
-            assert np.array_equal(hist[k], h2[k]), k
-        for k in ("Delta", "omega", "accept_solution", "scp_status", "solver_status", "convergence_measure", "ipm_iters"):
-            assert np.array_equal(np.asarray(hist[k])[valid], np.asarray(h2[k])[valid]), k
-        assert np.array_equal(hist["J_true"][validJ], h2["J_true"][validJ])
+    assert np.array_equal(X, X2) and np.array_equal(U, U2)
+    for k in st:
+        assert np.array_equal(st[k], st2[k]), k
+    for k in ("n_hist", "nJ", "n_rho"):
+        assert np.array_equal(hist[k], h2[k]), k
+    for k in ("Delta", "omega", "accept_solution", "scp_status", "solver_status", "convergence_measure", "ipm_iters"):
+        assert np.array_equal(np.asarray(hist[k])[valid], np.asarray(h2[k])[valid]), k
+    assert np.array_equal(hist["J_true"][validJ], h2["J_true"][validJ])
 
 
 GOLDEN = ["freeflyer_se2_n50", "freeflyer_se2_n200_notebook", "dubins_car_n30", "astrobee_se3_n50",
