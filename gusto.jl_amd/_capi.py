@@ -33,6 +33,7 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_default_simulate_opts", "gusto_simulate", "gusto_get_simulate", "gusto_get_simulate_knots", "gusto_last_simulate_ms",
            "gusto_default_disturb_opts", "gusto_simulate_disturbed", "gusto_get_simulate_plant",
            "gusto_default_lincov_opts", "gusto_lincov", "gusto_get_lincov", "gusto_last_lincov_ms",
+           "gusto_lincov_disturbed", "gusto_get_lincov_plant",
            "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr"]
 
 
@@ -256,6 +257,8 @@ def lib():
         L.gusto_lincov.argtypes = [vp, vp, vp, vp, vp, C.POINTER(LincovOpts)]
         L.gusto_get_lincov.argtypes = [vp, C.POINTER(LincovReport)]
         L.gusto_last_lincov_ms.argtypes = [vp, C.POINTER(C.c_double)]
+        L.gusto_lincov_disturbed.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(LincovOpts), C.POINTER(DisturbOpts)]
+        L.gusto_get_lincov_plant.argtypes = [vp, vp, vp]
         L.gusto_default_trajopt_params.argtypes = [ci, C.POINTER(TrajOptParams)]
         L.gusto_create_trajopt.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci]
         L.gusto_set_trajopt_params.argtypes = [vp, C.POINTER(TrajOptParams)]
@@ -781,6 +784,31 @@ class BatchSolver:
         self._lincov_store_S = bool(o.store_S)
         return self.get_lincov()
 
+    def lincov_disturbed(self, opts=None, disturb=None, X=None, U=None, K=None, S0=None, Sth=None):
+        """gusto_lincov_disturbed + gusto_get_lincov: lincov() with the deviation augmented by the constant plant deviation
+        theta - theta_nom, to first order -- Sth [B, NPLANT, NPLANT] its covariance, default: the variances of the uniform draws
+        of simulate_disturbed() with the relative half-widths disturb["plant_rel"] -- and with disturb["dw"] added to du_white as
+        dw^2 / 3.  Returns the report as a dict like lincov(); get_lincov_plant() has Cd and the x-theta block of S."""
+        px, pu, _keep = self._traj_ptrs(X, U, "lincov_disturbed")
+        o, d = self.lincov_opts(opts), self.disturb_opts(disturb)
+        Kk = None if K is None else _arr(K).reshape(self.B, self.N - 1, self.m, self.n)
+        Ss = None if S0 is None else _arr(S0).reshape(self.B, self.n + self.m, self.n + self.m)
+        St = None if Sth is None else _arr(Sth).reshape(self.B, NPLANT, NPLANT)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._chk(self.L.gusto_lincov_disturbed(self.h, px, pu, ptr(Kk), ptr(Ss), ptr(St), C.byref(o), C.byref(d)), "lincov_disturbed")
+        self._lincov_store_S = bool(o.store_S)
+        return self.get_lincov()
+
+    def get_lincov_plant(self, Sxt=None):
+        """gusto_get_lincov_plant: (Cd [B, N-1, n, NPLANT], Sxt [B, N, n, NPLANT]) of the last lincov_disturbed().  Sxt: None = the
+        array if the last call kept it, else None in its place; True = ask for it (refused with -3 after a call without
+        store_S); False = without."""
+        want = getattr(self, "_lincov_store_S", False) if Sxt is None else bool(Sxt)
+        Cd = np.zeros((self.B, self.N - 1, self.n, NPLANT))
+        St = np.zeros((self.B, self.N, self.n, NPLANT)) if want else None
+        self._chk(self.L.gusto_get_lincov_plant(self.h, Cd.ctypes.data, None if St is None else St.ctypes.data), "get_lincov_plant")
+        return Cd, St
+
     def get_lincov(self, Sxx=None):
         """gusto_get_lincov: the report of the last lincov() as a dict of arrays.  Sxx: None = with Sxx [B, N, n, n] if the last
         call kept it; True = ask for it (refused with -3 after a call without store_S); False = without."""
@@ -871,3 +899,6 @@ class TrajOptSolver(BatchSolver):
 
     def lincov(self, *a, **k):
         raise GustoError("TrajOptSolver: lincov is not supported on TrajOpt handles (gusto_lincov answers GUSTO_ERR_ARG)")
+
+    def lincov_disturbed(self, *a, **k):
+        raise GustoError("TrajOptSolver: lincov_disturbed is not supported on TrajOpt handles (gusto_lincov_disturbed answers GUSTO_ERR_ARG)")

@@ -11,6 +11,7 @@
 namespace gusto {
 
 #define GD __device__ __forceinline__
+#define GHD __host__ __device__ __forceinline__   // the model traits f, A, B, dfdth: also callable from the host programs of tests/c
 typedef double v4d __attribute__((ext_vector_type(4)));   // accumulator tile of v_mfma_f64_16x16x4_f64
 typedef double v2d __attribute__((ext_vector_type(2)));   // a pair of the row state: one 128-bit access (RS_PAIR)
 

@@ -110,11 +110,14 @@ struct __attribute__((visibility("hidden"))) VerifyState {
 // Time-varying LQR gains (tvlqr.hip), B the batch of the call that allocated them: [B][N - 1][n][n + m] rows of [Ad | Bd],
 // [B][N - 1][m][n] gains, [B][n][n] P of knot 1, [B][N][n][n] P of every knot (first call with store_P only), [2][B] status and
 // fail_knot, copies of a caller's X / U.  A later call with a larger batch grows them, contents discarded.  `mid` is recorded
-// between the two launches (gusto_dev_tvlqr).  have_Pall outlives invalidate(): the next gusto_tvlqr resets it
+// between the two launches (gusto_dev_tvlqr).  have_Pall outlives invalidate(): the next gusto_tvlqr resets it.  dt_min, nstep:
+// the roll-out options of the last call, which its [Ad | Bd] belong to (gusto_lincov_disturbed rolls out with the same)
 struct __attribute__((visibility("hidden"))) TvlqrState {
     DevBuf<double> AB, K, P1, Pall, X, U;
     DevBuf<int> St;
     bool have = false, store_P = false, have_Pall = false;
+    double dt_min = 0.0;
+    int nstep = 0;
     DevEvent t0, mid, t1;
     double last_ms = 0.0, lin_ms = 0.0, ric_ms = 0.0;
     void invalidate() { have = false; }
@@ -140,14 +143,16 @@ struct __attribute__((visibility("hidden"))) SimulateState {
 // Linear covariance analysis (lincov.hip): I [6][batch_cap] status, fail_knot, obs_knot, obs_pair, ctl_knot, ctl_entry; D
 // [3][batch_cap] min_z_obs, p_collision_bound, min_z_ctl; Sx [batch_cap][N][n], Su [batch_cap][N - 1][m], Z [batch_cap][N] the
 // per-knot rows; Sxx [batch_cap][N][n][n] (first call with store_S only); copies of a caller's X / U / K / S0.  have_Sxx
-// outlives invalidate(): the next gusto_lincov resets it
+// outlives invalidate(): the next gusto_lincov resets it.  gusto_lincov_disturbed: Cd [batch_cap][N - 1][n][GUSTO_NPLANT], Sxt
+// [batch_cap][N][n][GUSTO_NPLANT] (first call with store_S only), Sth the copy of a caller's [batch_cap][GUSTO_NPLANT]
+// [GUSTO_NPLANT]; plant: the last call was a disturbed one
 struct __attribute__((visibility("hidden"))) LincovState {
-    DevBuf<double> D, Sx, Su, Z, Sxx, X, U, K, S0;
+    DevBuf<double> D, Sx, Su, Z, Sxx, X, U, K, S0, Cd, Sxt, Sth;
     DevBuf<int> I;
-    bool have = false, store_S = false, have_Sxx = false;
+    bool have = false, store_S = false, have_Sxx = false, plant = false;
     DevEvent t0, t1;
     double last_ms = 0.0;
-    void invalidate() { have = false; }
+    void invalidate() { have = false; plant = false; }
 };
 
 struct gusto_handle_s {

@@ -14,6 +14,16 @@
 // the lanes' minima, its ordinal a second one over the lanes that hold that minimum: the lowest ordinal of equal minima.
 // Over the knots a strict < keeps the lowest knot.  The control margins (m <= 6) are walked by every lane on the same LDS values.
 // No atomics, nothing crosses a problem: a problem's outputs are the same bit for bit whatever batch it sits in.
+// gusto_lincov_disturbed is the PLANT = true instantiation of the same kernel (as DIST is in simulate.hip): the deviation is
+// augmented by the constant plant deviation, z = [dx; b; theta~], so S, G = [Ad - Bd K | Bd | Cd] and T gain GUSTO_NPLANT columns
+// (11.8 KB of LDS for n = 13) and every dot product the theta terms BEHIND the terms it has; PLANT = false is what it was.  Cd
+// comes from a launch ahead of it on the same stream:
+//   lincov_plant_sens  grid (problem, tile of IPB intervals), 256 lanes.  Work item (k, c) = lane: interval k and the c-th plant
+//     scalar the model reads (2 or 4 of them: IPB = 128 or 64).  A lane carries the nominal state and ONE tangent column
+//     d = dx/dtheta_j through the four RK4 stages of every substep, kd = A(stage point) d + dfdth_j(stage point, u), forward mode
+//     as tvlqr_linearise with the model's own A over its structural nonzeros.  The tile is staged in LDS ([interval][row][6],
+//     the layout of Cd, zeros in the columns the model does not read) and copied out by the whole workgroup, consecutive lanes
+//     to consecutive addresses.
 #include <hip/hip_runtime.h>
 
 #include "models.hpp"
@@ -37,6 +47,34 @@ struct LcArgs {
     double *sigma_x, *sigma_u, *z_obs, *Sxx;   // [B][N][n], [B][N-1][m], [B][N], [B][N][n][n] (store_S)
 };
 
+// gusto_lincov_disturbed: LcArgs and the plant dispersion
+struct LcArgsP : LcArgs {
+    const double* Cd;              // [B][N-1][n][GUSTO_NPLANT]: lincov_plant_sens
+    const double* Sth;             // [B][GUSTO_NPLANT][GUSTO_NPLANT], or null: diag((nominal plant_rel)^2 / 3)
+    double plant_rel[GUSTO_NPLANT], dw[GUSTO_MAXM];
+    double* Sxt;                   // [B][N][n][GUSTO_NPLANT] (store_S)
+};
+
+struct SensArgs {
+    const double *X, *U;           // [B][N][n], [B][N][m]
+    const int* active;
+    double dt_min;                 // the roll-out options of the handle's last gusto_tvlqr
+    int nstep;
+    double* Cd;
+};
+
+// the plant scalars a model reads: their number and the GUSTO_NPLANT entry of the c-th of them
+template <int MODEL> struct PlantCols {
+    static constexpr int count() { int c = 0; for (int j = 0; j < GUSTO_NPLANT; j++) c += plant_entry_read(MODEL, j) ? 1 : 0; return c; }
+    static constexpr int NR = count();
+    static constexpr int IPB = 256 / NR;   // whole intervals per workgroup: its slice of Cd is one contiguous range
+    static constexpr int entry(int c) {
+        for (int j = 0; j < GUSTO_NPLANT; j++)
+            if (plant_entry_read(MODEL, j) && c-- == 0) return j;
+        return 0;
+    }
+};
+
 // the standard deviation of a variance: what rounding leaves below zero counts as zero (a NaN stays one)
 GD double sigma_of(double var) { return sqrt(var < 0.0 ? 0.0 : var); }
 
@@ -47,10 +85,10 @@ GD double margin_z(double d, double sigma) {
 }
 
 // z_obs of one knot and the ordinal of the pair it occurs at (NO_ORD: +inf), the same in every lane.  xk: the knot's state;
-// sS: S_k, whose leading WS x WS block is the covariance of the workspace location (the component offsets are translations)
-template <int MODEL> GD void obstacle_margin(const KParams& P, const Env& E, const double* xk, const double* sS, int lane, double* zk, int* pk) {
+// sS: S_k in rows of nz doubles, whose leading WS x WS block is the covariance of the workspace location (the component offsets are translations)
+template <int MODEL, int nz> GD void obstacle_margin(const KParams& P, const Env& E, const double* xk, const double* sS, int lane, double* zk, int* pk) {
     using T = MT<MODEL>;
-    constexpr int WS = T::WS, nz = T::n + T::m;
+    constexpr int WS = T::WS;   // (nz: the row length of sS)
     double zb = INFINITY;
     int ob = NO_ORD;
     if constexpr (T::HAS_OBS) {
@@ -82,15 +120,100 @@ template <int MODEL> GD void obstacle_margin(const KParams& P, const Env& E, con
     *zk = zmin;
 }
 
-template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const KParams P, const LcArgs V) {
+// kd = A d + g over the structural nonzeros of A (as tvlqr.hip: tangent)
+template <int MODEL> GD void plant_tangent(const double* A, const double* d, const double* g, double* kd) {
+    constexpr int n = MT<MODEL>::n;
+#pragma unroll
+    for (int i = 0; i < n; i++) {
+        double s = g[i];
+#pragma unroll
+        for (int j = 0; j < n; j++)
+            if (MT<MODEL>::Anz(i, j)) s += A[i * n + j] * d[j];
+        kd[i] = s;
+    }
+}
+
+template <int MODEL> __global__ void __launch_bounds__(256) lincov_plant_sens(const KParams P, const SensArgs V) {
+    using D = Dyn<MODEL>;
+    using PC = PlantCols<MODEL>;
+    constexpr int n = MT<MODEL>::n, m = MT<MODEL>::m, NT = GUSTO_NPLANT, NR = PC::NR, IPB = PC::IPB;
+    static_assert(IPB * NR == 256, "every lane has a work item");
+    __shared__ double stage[IPB * n * NT];
+    const int b = blockIdx.x, k0 = blockIdx.y * IPB, t = threadIdx.x, N = P.N;
+    if (V.active && !V.active[b]) return;   // (the whole workgroup)
+    const double dt = P.tf[b] / (N - 1);
+    const int nstep = V.nstep > 0 ? V.nstep : (int)ceil(dt / V.dt_min);   // (gusto_tvlqr has checked 1 <= nstep <= nstep_cap)
+    const double h = dt / nstep;
+    const int kl = t / NR, c = t % NR;
+    const bool valid = k0 + kl < N - 1;
+    const int k = valid ? k0 + kl : 0;   // (idle lanes roll interval 0 out and store nothing)
+    int j = 0;
+#pragma unroll
+    for (int q = 0; q < NR; q++)
+        if (c == q) j = PC::entry(q);
+    const double* Xk = V.X + ((size_t)b * N + k) * n;
+    const double* Uk = V.U + ((size_t)b * N + k) * m;
+    double x[n], u[m], d[n];
+#pragma unroll
+    for (int i = 0; i < n; i++) { x[i] = Xk[i]; d[i] = 0.0; }
+#pragma unroll
+    for (int i = 0; i < m; i++) u[i] = Uk[i];
+    for (int s = 0; s < nstep; s++) {
+        double A[n * n], g[n], w[n], dw[n], k1[n], kk[n], kd1[n], kdk[n], xs[n], ds[n];
+        D::f(P.mp, x, u, k1);
+        D::A(P.mp, x, u, A);
+        D::dfdth(P.mp, x, u, j, g);
+        plant_tangent<MODEL>(A, d, g, kd1);
+#pragma unroll
+        for (int i = 0; i < n; i++) { xs[i] = k1[i]; ds[i] = kd1[i]; w[i] = x[i] + 0.5 * h * k1[i]; dw[i] = d[i] + 0.5 * h * kd1[i]; }
+        D::f(P.mp, w, u, kk);
+        D::A(P.mp, w, u, A);
+        D::dfdth(P.mp, w, u, j, g);
+        plant_tangent<MODEL>(A, dw, g, kdk);
+#pragma unroll
+        for (int i = 0; i < n; i++) { xs[i] += 2 * kk[i]; ds[i] += 2 * kdk[i]; w[i] = x[i] + 0.5 * h * kk[i]; dw[i] = d[i] + 0.5 * h * kdk[i]; }
+        D::f(P.mp, w, u, kk);
+        D::A(P.mp, w, u, A);
+        D::dfdth(P.mp, w, u, j, g);
+        plant_tangent<MODEL>(A, dw, g, kdk);
+#pragma unroll
+        for (int i = 0; i < n; i++) { xs[i] += 2 * kk[i]; ds[i] += 2 * kdk[i]; w[i] = x[i] + h * kk[i]; dw[i] = d[i] + h * kdk[i]; }
+        D::f(P.mp, w, u, kk);
+        D::A(P.mp, w, u, A);
+        D::dfdth(P.mp, w, u, j, g);
+        plant_tangent<MODEL>(A, dw, g, kdk);
+#pragma unroll
+        for (int i = 0; i < n; i++) {
+            x[i] = x[i] + 1.0 / 6.0 * h * (xs[i] + kk[i]);
+            d[i] = d[i] + 1.0 / 6.0 * h * (ds[i] + kdk[i]);
+        }
+    }
+    // the columns the model does not read are zeros; a lane writes column j of its interval (disjoint addresses)
+    for (int e = t; e < IPB * n * NT; e += 256)
+        if (!plant_entry_read(MODEL, e % NT)) stage[e] = 0.0;
+    if (valid)
+#pragma unroll
+        for (int i = 0; i < n; i++) stage[(kl * n + i) * NT + j] = d[i];
+    __syncthreads();
+    const int cnt = min(IPB, N - 1 - k0) * n * NT;   // (the lanes past it hold nothing: never read)
+    double* out = V.Cd + ((size_t)b * (N - 1) + k0) * n * NT;
+    for (int e = t; e < cnt; e += 256) out[e] = stage[e];
+}
+
+// NZ: the size of the augmented deviation, the row length of S, G and T.  PLANT = false: NZ = nz, NGZ = NG, NT = 0 -- the loops
+// over the theta entries are empty
+template <int MODEL, bool PLANT>
+__global__ void __launch_bounds__(64) lincov_kernel(const KParams P, const std::conditional_t<PLANT, LcArgsP, LcArgs> V) {
     using T = MT<MODEL>;
-    constexpr int n = T::n, m = T::m, nz = n + m;
-    constexpr int NG = n * nz, RG = (NG + 63) / 64;                 // entries of [Ad | Bd], of G and of T, per lane
+    constexpr int n = T::n, m = T::m, nz = n + m, NT = PLANT ? GUSTO_NPLANT : 0, NZ = nz + NT;
+    constexpr int NG = n * nz, RG = (NG + 63) / 64;                 // entries of [Ad | Bd], per lane
+    constexpr int NGZ = n * NZ, RGZ = (NGZ + 63) / 64;              // entries of G and of T
+    constexpr int NC = n * NT, RC = (NC + 63) / 64;                 // entries of Cd
     constexpr int NK = m * n, RK = (NK + 63) / 64;
     constexpr int NV = m * nz, RV = (NV + 63) / 64;                 // V = [-K I] S
     constexpr int NP = n * (n + 1) / 2, RP = (NP + 63) / 64;        // upper triangle of Sxx
-    constexpr int NS = nz * nz, RS = (NS + 63) / 64, NPF = n * n, RPF = (NPF + 63) / 64;
-    __shared__ double sS[NS], sG[NG], sT[NG], sK[NK], sV[NV], sSu[m];
+    constexpr int NS = NZ * NZ, RS = (NS + 63) / 64, NPF = n * n, RPF = (NPF + 63) / 64;
+    __shared__ double sS[NS], sG[NGZ], sT[NGZ], sK[NK], sV[NV], sSu[m];
     const int b = blockIdx.x, lane = threadIdx.x, N = P.N;
     if (V.active && !V.active[b]) return;   // (an inactive problem's outputs are left as they are)
     const double* X = V.X + (size_t)b * N * n;
@@ -101,6 +224,12 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const K
     double* su = V.sigma_u + (size_t)b * (N - 1) * m;
     double* zo = V.z_obs + (size_t)b * N;
     double* Sall = V.store_S ? V.Sxx + (size_t)b * N * NPF : nullptr;
+    [[maybe_unused]] const double* Cd = nullptr;
+    [[maybe_unused]] double* Tall = nullptr;   // Sxt of every knot
+    if constexpr (PLANT) {
+        Cd = V.Cd + (size_t)b * (N - 1) * NC;
+        if (V.store_S) Tall = V.Sxt + (size_t)b * N * NC;
+    }
     const Env E = problem_env(P, b);
 
     // gains of a failed gusto_tvlqr: its fail_knot, every output zero
@@ -119,23 +248,46 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const K
     }
     double w2[m];
 #pragma unroll
-    for (int q = 0; q < m; q++) w2[q] = V.du_white[q] * V.du_white[q];
+    for (int q = 0; q < m; q++) {
+        w2[q] = V.du_white[q] * V.du_white[q];
+        if constexpr (PLANT) w2[q] += V.dw[q] * V.dw[q] / 3.0;   // the variance of the uniform draw with the half-width dw
+    }
 
-    // S_1 = S0
+    // S_1 = S0; PLANT: blockdiag(S0, Stheta), Stheta on the entries the model reads
 #pragma unroll
     for (int r = 0; r < RS; r++) {
         const int e = lane + 64 * r;
         if (e < NS) {
-            const int i = e / nz, c = e % nz;
+            const int i = e / NZ, c = e % NZ;
             double v = 0.0;
-            if (V.S0) v = V.S0[(size_t)b * NS + e];
-            else if (i == c) { const double w = i < n ? V.dx0[i] : V.du0[i - n]; v = w * w / 3.0; }
+            if constexpr (!PLANT) {
+                if (V.S0) v = V.S0[(size_t)b * NS + e];
+                else if (i == c) { const double w = i < n ? V.dx0[i] : V.du0[i - n]; v = w * w / 3.0; }
+            } else {
+                if (i < nz && c < nz) {
+                    if (V.S0) v = V.S0[(size_t)b * nz * nz + i * nz + c];
+                    else if (i == c) { const double w = i < n ? V.dx0[i] : V.du0[i - n]; v = w * w / 3.0; }
+                }
+                const double nominal[GUSTO_NPLANT] = {P.mp.mass, P.mp.Jdiag[0], P.mp.Jdiag[1], P.mp.Jdiag[2], P.mp.dubins_v, P.mp.dubins_k};
+#pragma unroll
+                for (int ji = 0; ji < NT; ji++)
+#pragma unroll
+                    for (int jc = 0; jc < NT; jc++)
+                        if (plant_entry_read(MODEL, ji) && plant_entry_read(MODEL, jc) && i == nz + ji && c == nz + jc) {
+                            if (V.Sth) v = V.Sth[(size_t)b * NT * NT + ji * NT + jc];
+                            else if (ji == jc) { const double t = nominal[ji] * V.plant_rel[ji]; v = (t * t) / 3.0; }
+                        }
+            }
             sS[e] = v;
         }
     }
     double g[RG], kr[RK];
+    [[maybe_unused]] double cd[RC > 0 ? RC : 1];
 #pragma unroll
     for (int r = 0; r < RG; r++) { const int e = lane + 64 * r; g[r] = (!dead && e < NG) ? AB[e] : 0.0; }
+    if constexpr (PLANT)
+#pragma unroll
+        for (int r = 0; r < RC; r++) { const int e = lane + 64 * r; cd[r] = (!dead && e < NC) ? Cd[e] : 0.0; }
 #pragma unroll
     for (int r = 0; r < RK; r++) { const int e = lane + 64 * r; kr[r] = (!dead && e < NK) ? K[e] : 0.0; }
     __syncthreads();
@@ -145,12 +297,16 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const K
 
     // rows of knot k from S_k: sigma_x, z_obs, Sxx; sigma_u on the knots that have a control
     auto emit = [&](int k, double zk, bool with_u) {
-        if (lane < n) sx[(size_t)(k - 1) * n + lane] = sigma_of(sS[lane * nz + lane]);
+        if (lane < n) sx[(size_t)(k - 1) * n + lane] = sigma_of(sS[lane * NZ + lane]);
         if (with_u && lane < m) su[(size_t)(k - 1) * m + lane] = sSu[lane];
         if (lane == 0) zo[k - 1] = zk;
         if (Sall)
 #pragma unroll
-            for (int r = 0; r < RPF; r++) { const int e = lane + 64 * r; if (e < NPF) Sall[(size_t)(k - 1) * NPF + e] = sS[(e / n) * nz + e % n]; }
+            for (int r = 0; r < RPF; r++) { const int e = lane + 64 * r; if (e < NPF) Sall[(size_t)(k - 1) * NPF + e] = sS[(e / n) * NZ + e % n]; }
+        if constexpr (PLANT)
+            if (Tall)
+#pragma unroll
+                for (int r = 0; r < RC; r++) { const int e = lane + 64 * r; if (e < NC) Tall[(size_t)(k - 1) * NC + e] = sS[(e / NT) * NZ + nz + e % NT]; }
     };
     auto note_obstacles = [&](int k, double zk, int pk) {
         if (zk < zo_min) { zo_min = zk; zo_knot = k; zo_pair = pk; }   // (strict: the lowest knot of equal minima)
@@ -159,12 +315,19 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const K
 
     for (int k = 1; k <= N - 1 && !dead; k++) {   // knot k (1-based): interval k - 1 of the arrays
 #pragma unroll
-        for (int r = 0; r < RG; r++) { const int e = lane + 64 * r; if (e < NG) sG[e] = g[r]; }
+        for (int r = 0; r < RG; r++) { const int e = lane + 64 * r; if (e < NG) sG[PLANT ? (e / nz) * NZ + e % nz : e] = g[r]; }
+        if constexpr (PLANT)
+#pragma unroll
+            for (int r = 0; r < RC; r++) { const int e = lane + 64 * r; if (e < NC) sG[(e / NT) * NZ + nz + e % NT] = cd[r]; }
 #pragma unroll
         for (int r = 0; r < RK; r++) { const int e = lane + 64 * r; if (e < NK) sK[e] = kr[r]; }
         __syncthreads();
         // [Ad | Bd] and K of the next knot, in flight while this one computes
         double gp[RG], kp[RK];
+        [[maybe_unused]] double cdp[RC > 0 ? RC : 1];
+        if constexpr (PLANT)
+#pragma unroll
+            for (int r = 0; r < RC; r++) { const int e = lane + 64 * r; cdp[r] = (k < N - 1 && e < NC) ? Cd[(size_t)k * NC + e] : 0.0; }
 #pragma unroll
         for (int r = 0; r < RG; r++) { const int e = lane + 64 * r; gp[r] = (k < N - 1 && e < NG) ? AB[(size_t)k * NG + e] : 0.0; }
 #pragma unroll
@@ -177,8 +340,8 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const K
                 const int i = e / nz, c = e % nz;
                 double s = g[r];
 #pragma unroll
-                for (int q = 0; q < m; q++) s -= sG[i * nz + n + q] * sK[q * n + c];
-                sG[e] = s;
+                for (int q = 0; q < m; q++) s -= sG[i * NZ + n + q] * sK[q * n + c];
+                sG[PLANT ? i * NZ + c : e] = s;
             }
         }
         // V = [-K I] S
@@ -187,23 +350,23 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const K
             const int e = lane + 64 * r;
             if (e < NV) {
                 const int i = e / nz, c = e % nz;
-                double s = sS[(n + i) * nz + c];
+                double s = sS[(n + i) * NZ + c];
 #pragma unroll
-                for (int j = 0; j < n; j++) s -= sK[i * n + j] * sS[j * nz + c];
+                for (int j = 0; j < n; j++) s -= sK[i * n + j] * sS[j * NZ + c];
                 sV[e] = s;
             }
         }
         __syncthreads();
         bool bad = false;
-        // T = G S; its last m columns are Sxb of the next knot
+        // T = G S; its columns from n on are Sxb (PLANT: and Sx-theta) of the next knot
 #pragma unroll
-        for (int r = 0; r < RG; r++) {
+        for (int r = 0; r < RGZ; r++) {
             const int e = lane + 64 * r;
-            if (e < NG) {
-                const int i = e / nz, c = e % nz;
+            if (e < NGZ) {
+                const int i = e / NZ, c = e % NZ;
                 double s = 0.0;
 #pragma unroll
-                for (int p = 0; p < nz; p++) s += sG[i * nz + p] * sS[p * nz + c];
+                for (int p = 0; p < NZ; p++) s += sG[i * NZ + p] * sS[p * NZ + c];
                 sT[e] = s;
                 if (c >= n && !(fabs(s) < INFINITY)) bad = true;
             }
@@ -215,6 +378,7 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const K
             for (int j = 0; j < n; j++) s -= sV[lane * nz + j] * sK[lane * n + j];
             const double w = V.du_white[lane];
             s += w * w;
+            if constexpr (PLANT) { const double hw = V.dw[lane]; s += hw * hw / 3.0; }   // (after gusto_lincov's terms: a zero dw changes nothing)
             const double sd = sigma_of(s);
             sSu[lane] = sd;
             if (!(fabs(sd) < INFINITY)) bad = true;
@@ -229,9 +393,11 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const K
                 const int a = pa[r], c = pb[r];
                 double s = 0.0;
 #pragma unroll
-                for (int p = 0; p < nz; p++) s += sT[a * nz + p] * sG[c * nz + p];
+                for (int p = 0; p < nz; p++) s += sT[a * NZ + p] * sG[c * NZ + p];
 #pragma unroll
-                for (int q = 0; q < m; q++) s += sG[a * nz + n + q] * w2[q] * sG[c * nz + n + q];
+                for (int q = 0; q < m; q++) s += sG[a * NZ + n + q] * w2[q] * sG[c * NZ + n + q];
+#pragma unroll
+                for (int p = nz; p < NZ; p++) s += sT[a * NZ + p] * sG[c * NZ + p];   // (PLANT: the theta terms, last)
                 pn[r] = s;
                 if (!(fabs(s) < INFINITY)) bad = true;
             }
@@ -240,7 +406,7 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const K
         // the margins of knot k on S_k
         double zk;
         int pk;
-        obstacle_margin<MODEL>(P, E, X + (size_t)(k - 1) * n, sS, lane, &zk, &pk);
+        obstacle_margin<MODEL, NZ>(P, E, X + (size_t)(k - 1) * n, sS, lane, &zk, &pk);
         note_obstacles(k, zk, pk);
         {
             double zc = INFINITY;
@@ -258,13 +424,16 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const K
         // S_{k+1}: Sxx mirrored, Sxb and its transpose; Sbb stays
 #pragma unroll
         for (int r = 0; r < RP; r++) {
-            if (lane + 64 * r < NP) { sS[pa[r] * nz + pb[r]] = pn[r]; sS[pb[r] * nz + pa[r]] = pn[r]; }
+            if (lane + 64 * r < NP) { sS[pa[r] * NZ + pb[r]] = pn[r]; sS[pb[r] * NZ + pa[r]] = pn[r]; }
         }
 #pragma unroll
-        for (int r = 0; r < RG; r++) {
+        for (int r = 0; r < RGZ; r++) {
             const int e = lane + 64 * r;
-            if (e < NG && e % nz >= n) { const int i = e / nz, c = e % nz; const double v = sT[e]; sS[i * nz + c] = v; sS[c * nz + i] = v; }
+            if (e < NGZ && e % NZ >= n) { const int i = e / NZ, c = e % NZ; const double v = sT[e]; sS[i * NZ + c] = v; sS[c * NZ + i] = v; }
         }
+        if constexpr (PLANT)
+#pragma unroll
+            for (int r = 0; r < RC; r++) cd[r] = cdp[r];
 #pragma unroll
         for (int r = 0; r < RG; r++) g[r] = gp[r];
 #pragma unroll
@@ -274,7 +443,7 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const K
     if (!dead && !fail) {   // knot N: no control
         double zk;
         int pk;
-        obstacle_margin<MODEL>(P, E, X + (size_t)(N - 1) * n, sS, lane, &zk, &pk);
+        obstacle_margin<MODEL, NZ>(P, E, X + (size_t)(N - 1) * n, sS, lane, &zk, &pk);
         note_obstacles(N, zk, pk);
         emit(N, zk, false);
     }
@@ -285,6 +454,10 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const K
         if (Sall)
 #pragma unroll
             for (int r = 0; r < RPF; r++) { const int e = lane + 64 * r; if (e < NPF) Sall[(size_t)(k - 1) * NPF + e] = 0.0; }
+        if constexpr (PLANT)
+            if (Tall)
+#pragma unroll
+                for (int r = 0; r < RC; r++) { const int e = lane + 64 * r; if (e < NC) Tall[(size_t)(k - 1) * NC + e] = 0.0; }
     }
     if (lane == 0) {
         V.status[b] = (dead || fail) ? 0 : 1;
@@ -299,11 +472,23 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_kernel(const K
     }
 }
 
-template <int MODEL> int launch_lincov(gusto_handle h, const KParams& P, const LcArgs& V) {
-    hipLaunchKernelGGL((lincov_kernel<MODEL>), dim3(h->B), dim3(64), 0, h->stream, P, V);
+// W: null for gusto_lincov, else V with the dispersion (V is its base) and A, the sensitivity launch ahead of the recursion
+template <int MODEL> int launch_lincov(gusto_handle h, const KParams& P, const LcArgs& V, const LcArgsP* W, const SensArgs& A) {
+    if (W) {
+        const int tiles = (h->N - 1 + PlantCols<MODEL>::IPB - 1) / PlantCols<MODEL>::IPB;
+        hipLaunchKernelGGL((lincov_plant_sens<MODEL>), dim3(h->B, tiles), dim3(256), 0, h->stream, P, A);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL((lincov_kernel<MODEL, true>), dim3(h->B), dim3(64), 0, h->stream, P, *W);
+    } else {
+        hipLaunchKernelGGL((lincov_kernel<MODEL, false>), dim3(h->B), dim3(64), 0, h->stream, P, V);
+    }
     HIPCHK(h, hipGetLastError());
     return GUSTO_OK;
 }
+
+// gusto_lincov (dist = null) and gusto_lincov_disturbed (dist: the options, never null; Sth: the caller's or null)
+int lincov_host(gusto_handle h, const char* who_c, const double* X, const double* U, const double* K, const double* S0,
+                const gusto_lincov_opts* opts, const gusto_disturb_opts* dist, const double* Sth);
 
 }  // namespace
 
@@ -319,20 +504,39 @@ int gusto_default_lincov_opts(int model_id, gusto_lincov_opts* o) {
 }
 
 int gusto_lincov(gusto_handle h, const double* X, const double* U, const double* K, const double* S0, const gusto_lincov_opts* opts) {
-    if (int rc = post_enter(h, "gusto_lincov", X, U)) return rc;
+    return lincov_host(h, "gusto_lincov", X, U, K, S0, opts, nullptr, nullptr);
+}
+
+int gusto_lincov_disturbed(gusto_handle h, const double* X, const double* U, const double* K, const double* S0, const double* Sth,
+                           const gusto_lincov_opts* opts, const gusto_disturb_opts* d) {
+    gusto_disturb_opts zero;
+    gusto_default_disturb_opts(&zero);
+    return lincov_host(h, "gusto_lincov_disturbed", X, U, K, S0, opts, d ? d : &zero, Sth);
+}
+
+}  // extern "C"
+
+namespace {
+
+int lincov_host(gusto_handle h, const char* who_c, const double* X, const double* U, const double* K, const double* S0,
+                const gusto_lincov_opts* opts, const gusto_disturb_opts* dist, const double* Sth) {
+    if (int rc = post_enter(h, who_c, X, U)) return rc;
+    const std::string who(who_c);
     gusto_lincov_opts o;
     gusto_default_lincov_opts(h->model, &o);
     if (opts) o = *opts;
-    if (int rc = lincov_args_host(h->n, h->m, h->B, &o, S0, &h->err)) return rc;
+    if (int rc = lincov_args_host(h->n, h->m, h->B, &o, S0, &h->err, who_c)) return rc;
+    if (dist)
+        if (int rc = lincov_plant_args_host(h->model, h->m, h->B, dist, Sth, &h->err)) return rc;
     if (!h->tvlqr.have) {
-        h->err = "gusto_lincov: no discrete Jacobians: call gusto_tvlqr first";
+        h->err = who + ": no discrete Jacobians: call gusto_tvlqr first";
         return GUSTO_ERR_STATE;
     }
     LincovState& S = h->lincov;
-    const size_t Bc = h->batch_cap, B = h->B, N = h->N, n = h->n, m = h->m, nz = n + m;
+    const size_t Bc = h->batch_cap, B = h->B, N = h->N, n = h->n, m = h->m, nz = n + m, NT = GUSTO_NPLANT;
     KParams P = post_params(h);
     if (!fill_env(h, P, model_info(h->model)->has_obs, true)) {
-        h->err = "gusto_lincov: gusto_set_env_batch was called with a different number of problems than gusto_set_problems";
+        h->err = who + ": gusto_set_env_batch was called with a different number of problems than gusto_set_problems";
         return GUSTO_ERR_STATE;
     }
     // grow-only, zeroed when (re)allocated
@@ -352,7 +556,16 @@ int gusto_lincov(gusto_handle h, const double* X, const double* U, const double*
         }
         if (o.store_S && !S.have_Sxx) HIPCHK(h, hipMemsetAsync(S.Sxx, 0, sizeof(double) * S.Sxx.count(), h->stream));
     }
-    LcArgs V{};
+    if (dist) {   // (Cd and Sxt of a problem this call leaves out are those of the last disturbed call, or zeros)
+        HIPCHK(h, S.Cd.ensure_zeroed(Bc * (N - 1) * n * NT, h->stream));
+        if (o.store_S) HIPCHK(h, S.Sxt.ensure_zeroed(Bc * N * n * NT, h->stream));
+        if (h->n_active >= 0 && !(S.have && S.plant)) {
+            HIPCHK(h, hipMemsetAsync(S.Cd, 0, sizeof(double) * S.Cd.count(), h->stream));
+            if (S.Sxt.count()) HIPCHK(h, hipMemsetAsync(S.Sxt, 0, sizeof(double) * S.Sxt.count(), h->stream));
+        }
+    }
+    LcArgsP V{};
+    SensArgs A{};
     if (int rc = stage_traj(h, X, U, Bc, S.X, S.U, &V.X, &V.U)) return rc;
     V.AB = h->tvlqr.AB;
     V.K = h->tvlqr.K;
@@ -375,15 +588,42 @@ int gusto_lincov(gusto_handle h, const double* X, const double* U, const double*
     V.ctl_entry = S.I + 5 * Bc;
     V.min_z_obs = S.D; V.p_bound = S.D + Bc; V.min_z_ctl = S.D + 2 * Bc;
     V.sigma_x = S.Sx; V.sigma_u = S.Su; V.z_obs = S.Z; V.Sxx = S.Sxx;
+    if (dist) {
+        if (Sth) {
+            HIPCHK(h, S.Sth.ensure(Bc * NT * NT));
+            HIPCHK(h, hipMemcpyAsync(S.Sth, Sth, sizeof(double) * B * NT * NT, hipMemcpyHostToDevice, h->stream));
+            V.Sth = S.Sth;
+        }
+        memcpy(V.plant_rel, dist->plant_rel, sizeof(V.plant_rel)); memcpy(V.dw, dist->dw, sizeof(V.dw));
+        V.Cd = S.Cd; V.Sxt = S.Sxt;
+        A.X = V.X; A.U = V.U; A.active = V.active; A.Cd = S.Cd;
+        A.dt_min = h->tvlqr.dt_min; A.nstep = h->tvlqr.nstep;
+    }
     HIPCHK(h, S.t0.record(h->stream));
-    if (int rc = for_model(h->model, [&](auto M) { return launch_lincov<M()>(h, P, V); })) return rc;
+    if (int rc = for_model(h->model, [&](auto M) { return launch_lincov<M()>(h, P, V, dist ? &V : nullptr, A); })) return rc;
     HIPCHK(h, S.t1.record(h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, event_ms(S.t0, S.t1, &S.last_ms));
     if (o.store_S) S.have_Sxx = true;
     S.have = true;
     S.store_S = o.store_S != 0;
+    S.plant = dist != nullptr;
     return GUSTO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gusto_get_lincov_plant(gusto_handle h, double* Cd, double* Sxt) {
+    if (!h) return GUSTO_ERR_ARG;
+    if (int rc = getter_enter(h, false)) return rc;
+    const LincovState& S = h->lincov;
+    if (!S.have || !S.plant) { h->err = "gusto_get_lincov_plant: the last covariance analysis was not a gusto_lincov_disturbed"; return GUSTO_ERR_STATE; }
+    if (Sxt && !S.store_S) { h->err = "gusto_get_lincov_plant: the last gusto_lincov_disturbed did not run with store_S = 1"; return GUSTO_ERR_STATE; }
+    const size_t B = h->B, N = h->N, n = h->n;
+    if (int rc = copy_out(h, Cd, S.Cd, B * (N - 1) * n * GUSTO_NPLANT)) return rc;
+    return copy_out(h, Sxt, S.Sxt, B * N * n * GUSTO_NPLANT);
 }
 
 int gusto_get_lincov(gusto_handle h, gusto_lincov_report* out) {

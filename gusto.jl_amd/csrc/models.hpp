@@ -1,4 +1,4 @@
-// models.hpp -- per-model dynamics f, A = df/dx, B = df/du and the analytic signed distances.
+// models.hpp -- per-model dynamics f, A = df/dx, B = df/du, dfdth = df/dtheta_j and the analytic signed distances.
 // The reference's model plug-in surface (multiple dispatch on the model type) becomes a compile-time
 // trait: f_dyn/update_f!, A_dyn/update_A!, B_dyn of src/dynamics/<model>.jl.
 #pragma once
@@ -6,46 +6,58 @@
 
 namespace gusto {
 
-GD void cross3(double* c, const double* a, const double* b) {
+GHD void cross3(double* c, const double* a, const double* b) {
     c[0] = a[1] * b[2] - a[2] * b[1];
     c[1] = a[2] * b[0] - a[0] * b[2];
     c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
+// dfdth: the derivative of f with respect to entry j of the plant scalars theta = (mass, Jdiag[0], Jdiag[1], Jdiag[2], dubins_v,
+// dubins_k) of gusto_simulate_disturbed (GUSTO_NPLANT); an entry the model's f does not read gives zeros (no counterpart in the
+// reference; csrc/lincov.hip carries it through the RK4 stages)
 template <int MODEL> struct Dyn;
 
 // freeflyer_se2.jl:182-206 : x = (r, th, v, w), u = (F, M); exactly linear
 template <> struct Dyn<GUSTO_FREEFLYER_SE2> {
     static constexpr int n = 6, m = 3;
-    GD static void f(const gusto_model_params& mp, const double* x, const double* u, double* f) {
+    GHD static void f(const gusto_model_params& mp, const double* x, const double* u, double* f) {
         f[0] = x[3]; f[1] = x[4]; f[2] = x[5];
         f[3] = u[0] / mp.mass; f[4] = u[1] / mp.mass; f[5] = u[2] * (1.0 / mp.Jdiag[2]);
     }
-    GD static void A(const gusto_model_params&, const double*, const double*, double* A) {
+    GHD static void A(const gusto_model_params&, const double*, const double*, double* A) {
 #pragma unroll
         for (int i = 0; i < n * n; i++) A[i] = 0;
         A[0 * n + 3] = 1; A[1 * n + 4] = 1; A[2 * n + 5] = 1;
     }
-    GD static void B(const gusto_model_params& mp, double* B) {
+    GHD static void B(const gusto_model_params& mp, double* B) {
 #pragma unroll
         for (int i = 0; i < n * m; i++) B[i] = 0;
         B[3 * m + 0] = 1.0 / mp.mass; B[4 * m + 1] = 1.0 / mp.mass; B[5 * m + 2] = 1.0 / mp.Jdiag[2];
+    }
+    GHD static void dfdth(const gusto_model_params& mp, const double*, const double* u, int j, double* g) {
+#pragma unroll
+        for (int i = 0; i < n; i++) g[i] = 0;
+        if (j == 0) { g[3] = -u[0] / (mp.mass * mp.mass); g[4] = -u[1] / (mp.mass * mp.mass); }
+        if (j == 3) g[5] = -u[2] / (mp.Jdiag[2] * mp.Jdiag[2]);
     }
 };
 
 // dubins_car.jl:161-181 : x = (x, y, th), u = turn rate
 template <> struct Dyn<GUSTO_DUBINS_CAR> {
     static constexpr int n = 3, m = 1;
-    GD static void f(const gusto_model_params& mp, const double* x, const double* u, double* f) {
+    GHD static void f(const gusto_model_params& mp, const double* x, const double* u, double* f) {
         f[0] = mp.dubins_v * cos(x[2]); f[1] = mp.dubins_v * sin(x[2]); f[2] = mp.dubins_k * u[0];
     }
-    GD static void A(const gusto_model_params& mp, const double* x, const double*, double* A) {
+    GHD static void A(const gusto_model_params& mp, const double* x, const double*, double* A) {
 #pragma unroll
         for (int i = 0; i < n * n; i++) A[i] = 0;
         A[0 * n + 2] = -mp.dubins_v * sin(x[2]);
         A[1 * n + 2] = mp.dubins_v * cos(x[2]);
     }
-    GD static void B(const gusto_model_params& mp, double* B) { B[0] = 0; B[1] = 0; B[2] = mp.dubins_k; }
+    GHD static void B(const gusto_model_params& mp, double* B) { B[0] = 0; B[1] = 0; B[2] = mp.dubins_k; }
+    GHD static void dfdth(const gusto_model_params&, const double* x, const double* u, int j, double* g) {
+        g[0] = j == 4 ? cos(x[2]) : 0.0; g[1] = j == 4 ? sin(x[2]) : 0.0; g[2] = j == 5 ? u[0] : 0.0;
+    }
     // f and A at a fixed point from two cached numbers (v cos th, v sin th): the same values as f() and A() -- a negation
     // is exact -- without their sin / cos (~140 instructions apiece in double precision)
     GD static void lin_cache(const gusto_model_params& mp, const double* x, double* c) {
@@ -62,10 +74,26 @@ template <> struct Dyn<GUSTO_DUBINS_CAR> {
     }
 };
 
+// mass and Jdiag of the rigid body with angular rate w and its derivative wd = f[W .. W+2] (the Astrobee models: W = 9, 10):
+// f[3 + i] = u[i] / mass, wd = (u[3:6] - w x (J w)) / J
+template <int n, int W> GHD void rigid_body_dfdth(const gusto_model_params& mp, const double* x, const double* u, int j, double* g) {
+    const double Jx = mp.Jdiag[0], Jy = mp.Jdiag[1], Jz = mp.Jdiag[2], wx = x[W], wy = x[W + 1], wz = x[W + 2];
+#pragma unroll
+    for (int i = 0; i < n; i++) g[i] = 0;
+    if (j == 0) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) g[3 + i] = -u[i] / (mp.mass * mp.mass);
+    }
+    // w x (J w) = ((Jz - Jy) wy wz, (Jx - Jz) wx wz, (Jy - Jx) wx wy)
+    if (j == 1) { g[W] = -(u[3] - (Jz - Jy) * wy * wz) / (Jx * Jx); g[W + 1] = -wx * wz / Jy; g[W + 2] = wx * wy / Jz; }
+    if (j == 2) { g[W] = wy * wz / Jx; g[W + 1] = -(u[4] - (Jx - Jz) * wx * wz) / (Jy * Jy); g[W + 2] = -wx * wy / Jz; }
+    if (j == 3) { g[W] = -wy * wz / Jx; g[W + 1] = wx * wz / Jy; g[W + 2] = -(u[5] - (Jy - Jx) * wx * wy) / (Jz * Jz); }
+}
+
 // astrobee_se3.jl:180-241 + quat_functions.jl:253-257 : x = (r, v, p_MRP, w), u = (F, M)
 template <> struct Dyn<GUSTO_ASTROBEE_SE3> {
     static constexpr int n = 12, m = 6;
-    GD static void f(const gusto_model_params& mp, const double* x, const double* u, double* f) {
+    GHD static void f(const gusto_model_params& mp, const double* x, const double* u, double* f) {
         const double* pp = x + 6; const double* w = x + 9;
         const double Jx = mp.Jdiag[0], Jy = mp.Jdiag[1], Jz = mp.Jdiag[2];
 #pragma unroll
@@ -79,7 +107,7 @@ template <> struct Dyn<GUSTO_ASTROBEE_SE3> {
         cross3(c2, w, Jw);
         f[9] = (u[3] - c2[0]) / Jx; f[10] = (u[4] - c2[1]) / Jy; f[11] = (u[5] - c2[2]) / Jz;
     }
-    GD static void A(const gusto_model_params& mp, const double* x, const double*, double* A) {
+    GHD static void A(const gusto_model_params& mp, const double* x, const double*, double* A) {
         const double Jx = mp.Jdiag[0], Jy = mp.Jdiag[1], Jz = mp.Jdiag[2];
         const double px = x[6], py = x[7], pz = x[8], wx = x[9], wy = x[10], wz = x[11];
 #pragma unroll
@@ -113,19 +141,20 @@ template <> struct Dyn<GUSTO_ASTROBEE_SE3> {
         AA(12, 11) = (Jx - Jy) * wx / Jz;
 #undef AA
     }
-    GD static void B(const gusto_model_params& mp, double* B) {
+    GHD static void B(const gusto_model_params& mp, double* B) {
 #pragma unroll
         for (int i = 0; i < n * m; i++) B[i] = 0;
 #pragma unroll
         for (int i = 0; i < 3; i++) B[(3 + i) * m + i] = 1.0 / mp.mass;
         B[9 * m + 3] = 1.0 / mp.Jdiag[0]; B[10 * m + 4] = 1.0 / mp.Jdiag[1]; B[11 * m + 5] = 1.0 / mp.Jdiag[2];
     }
+    GHD static void dfdth(const gusto_model_params& mp, const double* x, const double* u, int j, double* g) { rigid_body_dfdth<n, 9>(mp, x, u, j, g); }
 };
 
 // astrobee_se3_manifold.jl:231-304 : x = (r, v, q scalar-first, w)
 template <> struct Dyn<GUSTO_ASTROBEE_SE3_MANIFOLD> {
     static constexpr int n = 13, m = 6;
-    GD static void f(const gusto_model_params& mp, const double* x, const double* u, double* f) {
+    GHD static void f(const gusto_model_params& mp, const double* x, const double* u, double* f) {
         const double qw = x[6], qx = x[7], qy = x[8], qz = x[9], wx = x[10], wy = x[11], wz = x[12];
         const double Jx = mp.Jdiag[0], Jy = mp.Jdiag[1], Jz = mp.Jdiag[2];
 #pragma unroll
@@ -138,7 +167,7 @@ template <> struct Dyn<GUSTO_ASTROBEE_SE3_MANIFOLD> {
         cross3(c2, w, Jw);
         f[10] = (u[3] - c2[0]) / Jx; f[11] = (u[4] - c2[1]) / Jy; f[12] = (u[5] - c2[2]) / Jz;
     }
-    GD static void A(const gusto_model_params& mp, const double* x, const double*, double* A) {
+    GHD static void A(const gusto_model_params& mp, const double* x, const double*, double* A) {
         const double qw = x[6], qx = x[7], qy = x[8], qz = x[9], wx = x[10], wy = x[11], wz = x[12];
         const double Jx = mp.Jdiag[0], Jy = mp.Jdiag[1], Jz = mp.Jdiag[2];
 #pragma unroll
@@ -162,13 +191,14 @@ template <> struct Dyn<GUSTO_ASTROBEE_SE3_MANIFOLD> {
         AA(13, 12) = (Jx - Jy) * wx / Jz;
 #undef AA
     }
-    GD static void B(const gusto_model_params& mp, double* B) {
+    GHD static void B(const gusto_model_params& mp, double* B) {
 #pragma unroll
         for (int i = 0; i < n * m; i++) B[i] = 0;
 #pragma unroll
         for (int i = 0; i < 3; i++) B[(3 + i) * m + i] = 1.0 / mp.mass;
         B[10 * m + 3] = 1.0 / mp.Jdiag[0]; B[11 * m + 4] = 1.0 / mp.Jdiag[1]; B[12 * m + 5] = 1.0 / mp.Jdiag[2];
     }
+    GHD static void dfdth(const gusto_model_params& mp, const double* x, const double* u, int j, double* g) { rigid_body_dfdth<n, 10>(mp, x, u, j, g); }
 };
 
 // ---- signed distance: replaces BulletCollision.distance(env, rb_idx, r, env_idx) -------------------
@@ -216,9 +246,9 @@ template <int WS> GD double sdf_box(const double* q, const double* lo, const dou
 template <int MODEL, int BASE> struct DynTO {
     using D0 = Dyn<BASE>;
     static constexpr int n = D0::n, m0 = D0::m, m = m0 + n;
-    GD static void f(const gusto_model_params& mp, const double* x, const double* u, double* f) { D0::f(mp, x, u, f); }
-    GD static void A(const gusto_model_params& mp, const double* x, const double* u, double* A) { D0::A(mp, x, u, A); }
-    GD static void B(const gusto_model_params& mp, double* B) {
+    GHD static void f(const gusto_model_params& mp, const double* x, const double* u, double* f) { D0::f(mp, x, u, f); }
+    GHD static void A(const gusto_model_params& mp, const double* x, const double* u, double* A) { D0::A(mp, x, u, A); }
+    GHD static void B(const gusto_model_params& mp, double* B) {
         double B0[n * m0];
         D0::B(mp, B0);
 #pragma unroll

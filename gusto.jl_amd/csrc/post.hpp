@@ -56,8 +56,9 @@ static inline int resolve_nstep(gusto_handle h, const char* who, double dt_min, 
 // The arguments of gusto_lincov for a model of n states and m controls: the options, and the caller's S0 [B][n + m][n + m]
 // (null: the default start).  GUSTO_ERR_ARG and the text, which names the offending entry (and problem), in *err.  Whether S0
 // is positive semi-definite is the caller's business.  No device, no handle.
-static inline int lincov_args_host(int n, int m, size_t B, const gusto_lincov_opts* o, const double* S0, std::string* err) {
-    const std::string w("gusto_lincov: ");
+static inline int lincov_args_host(int n, int m, size_t B, const gusto_lincov_opts* o, const double* S0, std::string* err,
+                                   const char* who = "gusto_lincov") {
+    const std::string w = std::string(who) + ": ";
     const auto width_ok = [](double v) { return v >= 0 && v < INFINITY; };
     if (o->store_S != 0 && o->store_S != 1) { *err = w + "store_S must be 0 or 1"; return GUSTO_ERR_ARG; }
     for (int i = 0; i < n; i++)
@@ -80,6 +81,41 @@ static inline int lincov_args_host(int n, int m, size_t B, const gusto_lincov_op
                 if (i == j && v < 0) { *err = w + "S0 has a negative diagonal entry" + where(i, j); return GUSTO_ERR_ARG; }
                 if (j > i && memcmp(&S[i * nz + j], &S[j * nz + i], sizeof(double)) != 0) {
                     *err = w + "S0 must be symmetric to the bit" + where(i, j);
+                    return GUSTO_ERR_ARG;
+                }
+            }
+    }
+    return GUSTO_OK;
+}
+
+// which of the GUSTO_NPLANT scalars (mass, Jdiag[0 .. 2], dubins_v, dubins_k) the f of the public model `model` reads
+constexpr bool plant_entry_read(int model, int j) {
+    return model == GUSTO_DUBINS_CAR ? j >= 4 : (model == GUSTO_FREEFLYER_SE2 ? (j == 0 || j == 3) : j < 4);
+}
+
+// The arguments of gusto_lincov_disturbed that gusto_lincov does not have: the dispersion d and the caller's Sth
+// [B][GUSTO_NPLANT][GUSTO_NPLANT] (null: the default), of which only the entries the model reads are looked at.  GUSTO_ERR_ARG
+// and the text, which names the offending entry (and problem), in *err.  No device, no handle.
+static inline int lincov_plant_args_host(int model, int m, size_t B, const gusto_disturb_opts* d, const double* Sth, std::string* err) {
+    const std::string w("gusto_lincov_disturbed: ");
+    constexpr size_t NT = GUSTO_NPLANT;
+    for (size_t j = 0; j < NT; j++)
+        if (!(d->plant_rel[j] >= 0 && d->plant_rel[j] < 1)) { *err = w + "plant_rel must lie in [0, 1) (entry " + std::to_string(j) + ")"; return GUSTO_ERR_ARG; }
+    for (int i = 0; i < m; i++)
+        if (!(d->dw[i] >= 0 && d->dw[i] < INFINITY)) { *err = w + "dw must be finite and >= 0 (entry " + std::to_string(i) + ")"; return GUSTO_ERR_ARG; }
+    for (size_t b = 0; Sth && b < B; b++) {
+        const double* S = Sth + b * NT * NT;
+        const auto where = [&](size_t i, size_t j) {
+            return " (problem " + std::to_string(b) + ", entry " + std::to_string(i) + ", " + std::to_string(j) + ")";
+        };
+        for (size_t i = 0; i < NT; i++)
+            for (size_t j = 0; j < NT; j++) {
+                if (!plant_entry_read(model, (int)i) || !plant_entry_read(model, (int)j)) continue;
+                const double v = S[i * NT + j];
+                if (!(fabs(v) < INFINITY)) { *err = w + "Sth must be finite" + where(i, j); return GUSTO_ERR_ARG; }
+                if (i == j && v < 0) { *err = w + "Sth has a negative diagonal entry" + where(i, j); return GUSTO_ERR_ARG; }
+                if (j > i && memcmp(&S[i * NT + j], &S[j * NT + i], sizeof(double)) != 0) {
+                    *err = w + "Sth must be symmetric to the bit" + where(i, j);
                     return GUSTO_ERR_ARG;
                 }
             }

@@ -318,15 +318,8 @@ int refuse(gusto_handle h, const std::string& who, const std::string& text) {
     return GUSTO_ERR_ARG;
 }
 
-// which of the GUSTO_NPLANT scalars the model's f reads
-bool plant_entry_read(int model, int j) {
-    if (model == GUSTO_DUBINS_CAR) return j >= 4;
-    if (model == GUSTO_FREEFLYER_SE2) return j == 0 || j == 3;
-    return j < 4;
-}
-
 // The arguments of gusto_simulate_disturbed that gusto_simulate does not have: GUSTO_ERR_ARG and the text, which names the
-// offending problem, sample and entry.  No device
+// offending problem, sample and entry (plant_entry_read: post.hpp).  No device
 int disturb_args_host(gusto_handle h, const std::string& who, size_t B, size_t Ns, const gusto_disturb_opts& d, const double* plant,
                       const double* white) {
     const size_t N = h->N, m = h->m;

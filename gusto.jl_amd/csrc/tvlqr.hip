@@ -360,6 +360,7 @@ int gusto_tvlqr(gusto_handle h, const double* X, const double* U, const gusto_tv
     if (o.store_P) S.have_Pall = true;
     S.have = true;
     S.store_P = o.store_P != 0;
+    S.dt_min = o.dt_min; S.nstep = o.nstep;
     return GUSTO_OK;
 }
 

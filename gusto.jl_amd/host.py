@@ -625,6 +625,25 @@ def lincov(traj, SCPP, K=None, S0=None, Q=1.0, R=1.0, Qf=1.0, dt_min=0.1, **opts
     return {k: v[0] for k, v in r.items()}
 
 
+def lincov_disturbed(traj, SCPP, K=None, S0=None, Sth=None, disturb=None, Q=1.0, R=1.0, Qf=1.0, dt_min=0.1, **opts):
+    """lincov() with an uncertain plant (gusto_lincov_disturbed; no counterpart in the reference): the deviation is augmented by
+    the constant deviation of the plant scalars (mass, Jdiag, dubins_v, dubins_k) from the model's, to first order, and the
+    per-interval noise disturb["dw"] joins du_white.  Sth [6, 6]: the covariance of the plant deviation, default the variances of
+    the uniform draws of simulate()'s disturb["plant_rel"].  Returns lincov()'s report with Cd [N-1, x_dim, 6], the sensitivity
+    of the roll-out map, and -- with store_S = 1 -- Sxt [N, x_dim, 6], the state / plant block of the covariance."""
+    bs = _verify_handle(traj, SCPP)
+    try:
+        bs.tvlqr(dict(Q=Q, R=R, Qf=Qf, dt_min=dt_min, nstep_cap=max(64, int(np.ceil(traj.dt / dt_min)))))
+        one = lambda a: None if a is None else np.asarray(a, float)[None]
+        r = bs.lincov_disturbed(opts, disturb, K=one(K), S0=one(S0), Sth=one(Sth))
+        r["Cd"], Sxt = bs.get_lincov_plant()
+        if Sxt is not None:
+            r["Sxt"] = Sxt
+    finally:
+        bs.close()
+    return {k: v[0] for k, v in r.items()}
+
+
 def shard_bounds(B, world_size, rank):
     """Contiguous block of ceil(B/G) problems per rank; the tail rank may get fewer."""
     per = -(-B // world_size)

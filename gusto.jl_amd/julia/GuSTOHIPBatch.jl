@@ -529,3 +529,53 @@ function simulate_batch!(h::Ptr{Cvoid}, B::Integer, n::Integer, m::Integer, N::I
    min_dist = dmin, max_dev = dev, max_final_dev = fdev, sample_min_dist = sdist, sample_dense_index = Int.(sidx),
    sample_flags = Int.(sflags), x_final = xfin, Xcl = Xcl, plant = used, ms = ms[])
 end
+
+# ---- linear covariance analysis with an uncertain plant (gusto_lincov_disturbed, csrc/lincov.hip) -------------------------------
+# The covariance of z = [dx; b; theta - theta_nom] carried through the closed loop of every trajectory of a handle, to first order
+# in the plant deviation (include/gusto_hip.h states the definitions; the reference has no counterpart).  After tvlqr_batch! on the
+# same X, U.  GuSTO handles only.  These wrappers have not been run.
+struct GustoLincovOpts      # gusto_lincov_opts
+  dx0::NTuple{13,Cdouble}; du0::NTuple{6,Cdouble}; du_white::NTuple{6,Cdouble}
+  u_lo::NTuple{6,Cdouble}; u_hi::NTuple{6,Cdouble}
+  store_S::Cint
+end
+mutable struct GustoLincovReport      # gusto_lincov_report
+  status::Ptr{Cint}; fail_knot::Ptr{Cint}; obs_knot::Ptr{Cint}; obs_pair::Ptr{Cint}; ctl_knot::Ptr{Cint}; ctl_entry::Ptr{Cint}
+  min_z_obs::Ptr{Cdouble}; p_collision_bound::Ptr{Cdouble}; min_z_ctl::Ptr{Cdouble}
+  sigma_x::Ptr{Cdouble}; sigma_u::Ptr{Cdouble}; z_obs::Ptr{Cdouble}; Sxx::Ptr{Cdouble}
+end
+
+# X [n,N,B], U [m,N,B] or nothing = the handle's own trajectories; K [n,m,N-1,B] or nothing = the gains of the last tvlqr_batch!;
+# S0 [n+m,n+m,B] and Sth [6,6,B] (symmetric, so the transposes are themselves) or nothing = the default diagonals of dx0, du0 and
+# plant_rel (a number or the 6 half-widths of mass, Jdiag[1:3], dubins_v, dubins_k); dw: a number or m half-widths of the noise per
+# hold interval.  sigma_x comes back as [n,N,B], sigma_u as [m,N-1,B], z_obs as [N,B], Cd as [6,n,N-1,B] (Cd[:,:,k,b]' = Cd_k);
+# with store_S Sxx [n,n,N,B] and Sxt [6,n,N,B].
+function lincov_disturbed_batch!(h::Ptr{Cvoid}, B::Integer, n::Integer, m::Integer, N::Integer, X=nothing, U=nothing, K=nothing,
+                                 S0=nothing, Sth=nothing; dx0=0.01, du0=0.0, du_white=0.0, u_lo=-Inf, u_hi=Inf, store_S=false,
+                                 plant_rel=0.0, dw=0.0)
+  ptr(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+  o = GustoLincovOpts(gusto_weights(dx0, n, 13), gusto_weights(du0, m, 6), gusto_weights(du_white, m, 6), gusto_bounds(u_lo, m, 6, -Inf),
+                      gusto_bounds(u_hi, m, 6, Inf), store_S ? 1 : 0)
+  d = GustoDisturbOpts(gusto_weights(plant_rel, 6, 6), gusto_weights(dw, m, 6))
+  GC.@preserve X U K S0 Sth gusto_check(ccall((:gusto_lincov_disturbed, libgusto_hip), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{GustoLincovOpts}, Ref{GustoDisturbOpts}),
+                    h, ptr(X), ptr(U), ptr(K), ptr(S0), ptr(Sth), o, d), h, "lincov_disturbed")
+  status, fail_knot, obs_knot, obs_pair, ctl_knot, ctl_entry = (zeros(Cint, B) for _ in 1:6)
+  zo, pb, zc = zeros(B), zeros(B), zeros(B)
+  sx, su, z = zeros(n, N, B), zeros(m, N - 1, B), zeros(N, B)
+  Sxx = store_S ? zeros(n, n, N, B) : nothing
+  GC.@preserve status fail_knot obs_knot obs_pair ctl_knot ctl_entry zo pb zc sx su z Sxx begin
+    rep = GustoLincovReport(pointer(status), pointer(fail_knot), pointer(obs_knot), pointer(obs_pair), pointer(ctl_knot), pointer(ctl_entry),
+                            pointer(zo), pointer(pb), pointer(zc), pointer(sx), pointer(su), pointer(z), ptr(Sxx))
+    gusto_check(ccall((:gusto_get_lincov, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoLincovReport}), h, rep), h, "get_lincov")
+  end
+  Cd = zeros(6, n, N - 1, B)
+  Sxt = store_S ? zeros(6, n, N, B) : nothing
+  GC.@preserve Cd Sxt gusto_check(ccall((:gusto_get_lincov_plant, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    h, Cd, ptr(Sxt)), h, "get_lincov_plant")
+  ms = Ref{Cdouble}(0.0)
+  gusto_check(ccall((:gusto_last_lincov_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, ms), h, "last_lincov_ms")
+  (status = Int.(status), fail_knot = Int.(fail_knot), obs_knot = Int.(obs_knot), obs_pair = Int.(obs_pair), ctl_knot = Int.(ctl_knot),
+   ctl_entry = Int.(ctl_entry), min_z_obs = zo, p_collision_bound = pb, min_z_ctl = zc, sigma_x = sx, sigma_u = su, z_obs = z,
+   Sxx = Sxx, Cd = Cd, Sxt = Sxt, ms = ms[])
+end

@@ -416,7 +416,8 @@ int gusto_last_simulate_ms(gusto_handle h, double* ms);
  *   wavefront's 64 samples of one interval are one contiguous range -- or (white = NULL) generated: entry i uniform in
  *   [-dw_i, dw_i), zeros for sample 0.  The clipped flag and n_clipped see v after the noise.  This is the sampled form of
  *   the du_white of gusto_lincov with du_white_i = dw_i / sqrt(3), the convention of that stage's default S0 (the variances of
- *   the uniform draws with the same half-widths); gusto_lincov covers dw in this way, but NOT the plant dispersion.
+ *   the uniform draws with the same half-widths); gusto_lincov covers dw in this way; gusto_lincov_disturbed also the plant dispersion,
+ *   to first order.
  * Generator: splitmix64 and the r -> (2 r - 1) w step of gusto_simulate on two streams of their own.  Streams whose seeds
  *   differ by a multiple of 0x9E3779B97F4A7C15 would be shifted copies of the pert stream, so the stream seeds are hashed, with
  *   sm(seed, idx) output number idx of splitmix64 started at seed (the z of gusto_simulate's text):
@@ -510,8 +511,53 @@ typedef struct {
     double *Sxx;       /* [B][N][x_dim][x_dim] */
 } gusto_lincov_report;
 int gusto_get_lincov(gusto_handle h, gusto_lincov_report* out);
-/* GPU time of the last gusto_lincov (one launch), from HIP events on the handle's stream */
+/* GPU time of the last gusto_lincov (one launch) or gusto_lincov_disturbed (both launches), from HIP events on the handle's
+ * stream */
 int gusto_last_lincov_ms(gusto_handle h, double* ms);
+
+/* gusto_lincov with an uncertain plant (csrc/lincov.hip): the analytic counterpart of gusto_simulate_disturbed.  No counterpart
+ * in the reference.  Everything gusto_lincov defines stays as it is, word for word -- sigma_x, sigma_u and the variance-below-
+ * zero rule, the obstacle and control margins and their tie rules, min_z_obs / min_z_ctl with their indices, p_collision_bound,
+ * status and fail_knot (K = NULL with a failed gusto_tvlqr; a non-finite entry at knot k, where Sxb now reads S_{x,[b theta]}),
+ * X, U, K, S0, gusto_set_active, stream and timing, the refusals (under this call's name), the grow-only buffers, "the same bit
+ * for bit in any batch and under any mask" -- and the deviation carries the plant with it:
+ * Plant deviation: theta = (mass, Jdiag[0], Jdiag[1], Jdiag[2], dubins_v, dubins_k), the GUSTO_NPLANT vector of
+ *   gusto_simulate_disturbed; theta_nom comes from the handle's gusto_model_params, theta~ = theta - theta_nom is constant per
+ *   flight.  freeflyerSE2 reads mass and Jdiag[2], DubinsCar dubins_v and dubins_k, both Astrobee models mass and Jdiag[0 .. 2].
+ * Sensitivity of the roll-out map: Cd_k = dF_k/dtheta at (X[:,k], U[:,k], theta_nom), n x GUSTO_NPLANT, k = 1 .. N-1, F_k the map
+ *   of gusto_tvlqr (Nstep_b classical RK4 steps under the held control).  It is the EXACT derivative of that discrete map,
+ *   forward mode through the four stages of every substep, kd = A(stage point) d + df/dtheta_j(stage point, u) with the model's
+ *   own A -- not a finite difference.  Columns of entries the model does not read are zeros.  Nstep_b, dt_min and nstep are
+ *   those of the handle's last gusto_tvlqr, which the call remembers.
+ * Augmented deviation z = [dx; b; theta~], of size n + m + GUSTO_NPLANT, with the covariance S_k.
+ * Start: S_1 = blockdiag(S0, Stheta).  S0 exactly as in gusto_lincov, the caller's or the default diagonal.  Stheta is the
+ *   caller's Sth [B][GUSTO_NPLANT][GUSTO_NPLANT], or (Sth = NULL) diag((theta_nom_j plant_rel_j)^2 / 3) on the entries the
+ *   model reads -- the variance of the uniform draw of gusto_simulate_disturbed with the same half-width, computed as
+ *   t = nominal * rel; (t * t) / 3.  Rows and columns of entries the model does not read are zero, whatever a supplied Sth
+ *   holds there.
+ * Recursion, k = 1 .. N-1, with G^_k = [Ad_k - Bd_k K_k | Bd_k | Cd_k] (n x (n + m + GUSTO_NPLANT)):
+ *     Sxx_{k+1} = G^_k S_k G^_k' + Bd_k diag(sw2) Bd_k',   S_{x,[b theta]}_{k+1} = G^_k S_k[:, n:],   the [b theta] block stays,
+ *   sw2_i = du_white_i^2 + dw_i^2 / 3: du_white of gusto_lincov_opts, dw of gusto_disturb_opts, the convention stated for
+ *   gusto_simulate_disturbed.  Sxx is computed on the upper triangle and mirrored.  In every dot product the terms gusto_lincov
+ *   adds come first, in its order, the theta terms after them.
+ * Commanded control: dv = [-K_k | I | 0] z + w_k, sigma_u with sw2 in place of du_white^2.
+ * What the stage is NOT: it is first order in theta~ around (X, U, theta_nom).  1 / mass and 1 / J are not linear in theta:
+ *   at plant_rel = 0.08 the neglected term is of relative order plant_rel^2; gusto_simulate_disturbed samples the full plant.
+ * gusto_get_lincov and gusto_last_lincov_ms report the last call of either kind (the time covers both launches);
+ *   gusto_get_lincov_plant answers GUSTO_ERR_STATE when the last call was a plain gusto_lincov or there was none.  Cd and Sxt
+ *   of a problem that gusto_set_active leaves out are those of the last disturbed call, zeros if there was none since
+ *   gusto_set_problems or a plain gusto_lincov came between.
+ * GUSTO_ERR_ARG, nothing launched, the offending problem and entry in gusto_last_error: everything gusto_lincov refuses; a
+ *   plant_rel outside [0, 1) or not finite; a dw that is negative or not finite; an Sth that, on the entries the model reads,
+ *   is not finite, has a negative diagonal entry or is not symmetric to the bit; TrajOpt handles.  GUSTO_ERR_STATE: no
+ *   problems, or no gusto_tvlqr since gusto_set_problems.
+ * With d NULL or all zeros and Sth = NULL every output of gusto_get_lincov equals that of gusto_lincov with the same remaining
+ *   arguments, as numbers (adding exact zeros can at most turn a -0.0 into +0.0). */
+int gusto_lincov_disturbed(gusto_handle h, const double* X, const double* U, const double* K, const double* S0,
+                           const double* Sth, const gusto_lincov_opts* o, const gusto_disturb_opts* d);
+/* Cd [B][N-1][n][GUSTO_NPLANT]; Sxt [B][N][n][GUSTO_NPLANT], the x-theta block of S_k, after a call with store_S = 1
+ * (asked for after a call without: GUSTO_ERR_STATE).  Either may be NULL. */
+int gusto_get_lincov_plant(gusto_handle h, double* Cd, double* Sxt);
 
 /* One convex subproblem per problem (what scp_gusto.jl:82-104 builds and solves in one trip), linearised at
  * (Xp,Up)[b] with the given Delta/omega/obstacle_toggle_distance[b].  Used by the parity tests.
