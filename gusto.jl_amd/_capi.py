@@ -33,7 +33,7 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_default_simulate_opts", "gusto_simulate", "gusto_get_simulate", "gusto_get_simulate_knots", "gusto_last_simulate_ms",
            "gusto_default_disturb_opts", "gusto_simulate_disturbed", "gusto_get_simulate_plant",
            "gusto_default_lincov_opts", "gusto_lincov", "gusto_get_lincov", "gusto_last_lincov_ms",
-           "gusto_lincov_disturbed", "gusto_get_lincov_plant",
+           "gusto_lincov_disturbed", "gusto_get_lincov_plant", "gusto_lincov_dense", "gusto_get_lincov_dense",
            "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr"]
 
 
@@ -123,6 +123,19 @@ LINCOV_FIELDS = tuple((k, np.int32, lambda B, N, n, m: (B,)) for k in ("status",
 class LincovReport(C.Structure):
     """gusto_lincov_report: caller-owned arrays"""
     _fields_ = [(k, C.c_void_p) for k, _, _ in LINCOV_FIELDS]
+
+
+# gusto_lincov_dense_report in the header's order: (field, dtype, shape as a function of (B, nfull_max, WS)); the last three
+# only after a call with store_dense = 1
+LINCOV_DENSE_FIELDS = tuple((k, np.int32, lambda B, R, ws: (B,)) for k in ("nfull", "dense_sample", "dense_pair")) + \
+                      (("min_z_dense", np.float64, lambda B, R, ws: (B,)), ("z_dense", np.float64, lambda B, R, ws: (B, R)),
+                       ("pair_dense", np.int32, lambda B, R, ws: (B, R)), ("Spos", np.float64, lambda B, R, ws: (B, R, ws, ws)))
+WS_DIM = {0: 2, 1: 2, 2: 3, 3: 3}   # workspace dimension of the public models (csrc/common.hpp: MT<MODEL>::WS)
+
+
+class LincovDenseReport(C.Structure):
+    """gusto_lincov_dense_report: caller-owned arrays"""
+    _fields_ = [(k, C.c_void_p) for k, _, _ in LINCOV_DENSE_FIELDS]
 
 
 VERIFY_FIELDS = (("collision_free", np.int32), ("first_knot", np.int32), ("first_dist", np.float64),
@@ -259,6 +272,8 @@ def lib():
         L.gusto_last_lincov_ms.argtypes = [vp, C.POINTER(C.c_double)]
         L.gusto_lincov_disturbed.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(LincovOpts), C.POINTER(DisturbOpts)]
         L.gusto_get_lincov_plant.argtypes = [vp, vp, vp]
+        L.gusto_lincov_dense.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(LincovOpts), C.POINTER(DisturbOpts), ci]
+        L.gusto_get_lincov_dense.argtypes = [vp, C.POINTER(LincovDenseReport), C.POINTER(ci)]
         L.gusto_default_trajopt_params.argtypes = [ci, C.POINTER(TrajOptParams)]
         L.gusto_create_trajopt.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci]
         L.gusto_set_trajopt_params.argtypes = [vp, C.POINTER(TrajOptParams)]
@@ -799,6 +814,37 @@ class BatchSolver:
         self._lincov_store_S = bool(o.store_S)
         return self.get_lincov()
 
+    def lincov_dense(self, opts=None, disturb=None, X=None, U=None, K=None, S0=None, Sth=None, store_dense=1):
+        """gusto_lincov_dense + gusto_get_lincov_dense: lincov_disturbed() (its knot pass is what get_lincov() and
+        get_lincov_plant() then report) and the obstacle margins at the dense samples between the knots -- the samples of
+        simulate() and interpolate(), with the roll-out options of the last tvlqr().  Returns the dense report as a dict: nfull,
+        dense_sample, dense_pair, min_z_dense [B] and, with store_dense = 1, z_dense, pair_dense [B, nfull_max] and Spos
+        [B, nfull_max, WS, WS]."""
+        px, pu, _keep = self._traj_ptrs(X, U, "lincov_dense")
+        o, d = self.lincov_opts(opts), self.disturb_opts(disturb)
+        Kk = None if K is None else _arr(K).reshape(self.B, self.N - 1, self.m, self.n)
+        Ss = None if S0 is None else _arr(S0).reshape(self.B, self.n + self.m, self.n + self.m)
+        St = None if Sth is None else _arr(Sth).reshape(self.B, NPLANT, NPLANT)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._chk(self.L.gusto_lincov_dense(self.h, px, pu, ptr(Kk), ptr(Ss), ptr(St), C.byref(o), C.byref(d), int(store_dense)),
+                  "lincov_dense")
+        self._lincov_store_S = bool(o.store_S)
+        self._lincov_store_dense = bool(store_dense)
+        return self.get_lincov_dense()
+
+    def get_lincov_dense(self, rows=None):
+        """gusto_get_lincov_dense: the dense report of the last lincov_dense() as a dict of arrays.  rows: None = with the
+        per-sample arrays if the last call kept them; True = ask for them (refused with -3 after a call without store_dense);
+        False = without."""
+        want = getattr(self, "_lincov_store_dense", False) if rows is None else bool(rows)
+        R = C.c_int(0)
+        self._chk(self.L.gusto_get_lincov_dense(self.h, None, C.byref(R)), "get_lincov_dense")
+        out = {k: np.zeros(shape(self.B, R.value, WS_DIM[self.model]), dtype=t) for k, t, shape in LINCOV_DENSE_FIELDS
+               if want or k not in ("z_dense", "pair_dense", "Spos")}
+        rep = LincovDenseReport(**{k: v.ctypes.data for k, v in out.items()})
+        self._chk(self.L.gusto_get_lincov_dense(self.h, C.byref(rep), None), "get_lincov_dense")
+        return out
+
     def get_lincov_plant(self, Sxt=None):
         """gusto_get_lincov_plant: (Cd [B, N-1, n, NPLANT], Sxt [B, N, n, NPLANT]) of the last lincov_disturbed().  Sxt: None = the
         array if the last call kept it, else None in its place; True = ask for it (refused with -3 after a call without
@@ -902,3 +948,6 @@ class TrajOptSolver(BatchSolver):
 
     def lincov_disturbed(self, *a, **k):
         raise GustoError("TrajOptSolver: lincov_disturbed is not supported on TrajOpt handles (gusto_lincov_disturbed answers GUSTO_ERR_ARG)")
+
+    def lincov_dense(self, *a, **k):
+        raise GustoError("TrajOptSolver: lincov_dense is not supported on TrajOpt handles (gusto_lincov_dense answers GUSTO_ERR_ARG)")

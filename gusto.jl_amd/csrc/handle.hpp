@@ -117,7 +117,7 @@ struct __attribute__((visibility("hidden"))) TvlqrState {
     DevBuf<int> St;
     bool have = false, store_P = false, have_Pall = false;
     double dt_min = 0.0;
-    int nstep = 0;
+    int nstep = 0, nstep_max = 0;   // nstep_max: the largest Nstep_b of that call (the row count of gusto_lincov_dense)
     DevEvent t0, mid, t1;
     double last_ms = 0.0, lin_ms = 0.0, ric_ms = 0.0;
     void invalidate() { have = false; }
@@ -145,14 +145,21 @@ struct __attribute__((visibility("hidden"))) SimulateState {
 // per-knot rows; Sxx [batch_cap][N][n][n] (first call with store_S only); copies of a caller's X / U / K / S0.  have_Sxx
 // outlives invalidate(): the next gusto_lincov resets it.  gusto_lincov_disturbed: Cd [batch_cap][N - 1][n][GUSTO_NPLANT], Sxt
 // [batch_cap][N][n][GUSTO_NPLANT] (first call with store_S only), Sth the copy of a caller's [batch_cap][GUSTO_NPLANT]
-// [GUSTO_NPLANT]; plant: the last call was a disturbed one
+// [GUSTO_NPLANT]; plant: the last call was a disturbed one.  gusto_lincov_dense: Srow [batch_cap][N][n][n + m + GUSTO_NPLANT] the
+// x-rows of S_k and Sbt [batch_cap][m + GUSTO_NPLANT][m + GUSTO_NPLANT] its constant block, from the knot pass to the dense one;
+// Zint [batch_cap][N - 1] and Jint [2][batch_cap][N - 1] the minimum, sample and pair of every interval; DI [3][batch_cap] nfull,
+// dense_sample, dense_pair; DD [batch_cap] min_z_dense; with store_dense Zd, Pd [batch_cap][dense_rows] and Spos
+// [batch_cap][dense_rows][dense_nsp = WS WS].  dense: the last call was a dense one; have_dense: DI, DD belong to these problems
+// and to dense_rows; have_dense_rows: so do Zd, Pd, Spos
 struct __attribute__((visibility("hidden"))) LincovState {
-    DevBuf<double> D, Sx, Su, Z, Sxx, X, U, K, S0, Cd, Sxt, Sth;
-    DevBuf<int> I;
+    DevBuf<double> D, Sx, Su, Z, Sxx, X, U, K, S0, Cd, Sxt, Sth, Srow, Sbt, Zint, DD, Zd, Spos;
+    DevBuf<int> I, Jint, DI, Pd;
     bool have = false, store_S = false, have_Sxx = false, plant = false;
+    bool dense = false, store_dense = false, have_dense = false, have_dense_rows = false;
+    size_t dense_rows = 0, dense_nsp = 0;
     DevEvent t0, t1;
     double last_ms = 0.0;
-    void invalidate() { have = false; plant = false; }
+    void invalidate() { have = false; plant = false; dense = false; have_dense = false; have_dense_rows = false; }
 };
 
 struct gusto_handle_s {

@@ -24,6 +24,11 @@
 //     as tvlqr_linearise with the model's own A over its structural nonzeros.  The tile is staged in LDS ([interval][row][6],
 //     the layout of Cd, zeros in the columns the model does not read) and copied out by the whole workgroup, consecutive lanes
 //     to consecutive addresses.
+// gusto_lincov_dense is gusto_lincov_disturbed with DENSE = true -- the knot pass also writes the x-rows of S_k of every knot and
+// the [b theta] block, which stays -- and two launches behind it on the same stream:
+//   lincov_dense         grid (problem, tile of 4 intervals), one wave per interval: the margins at the dense samples inside it
+//     (the comment at the kernel has the mapping)
+//   lincov_dense_reduce  one wave per problem: the minimum over the intervals in their order, zeros behind nfull_b
 #include <hip/hip_runtime.h>
 
 #include "models.hpp"
@@ -53,6 +58,12 @@ struct LcArgsP : LcArgs {
     const double* Sth;             // [B][GUSTO_NPLANT][GUSTO_NPLANT], or null: diag((nominal plant_rel)^2 / 3)
     double plant_rel[GUSTO_NPLANT], dw[GUSTO_MAXM];
     double* Sxt;                   // [B][N][n][GUSTO_NPLANT] (store_S)
+};
+
+// gusto_lincov_dense: what its knot pass leaves for the dense pass
+struct LcArgsD : LcArgsP {
+    double* Srow;                  // [B][N][n][NZ]: the x-rows of S_k, NZ = n + m + GUSTO_NPLANT
+    double* Sbt;                   // [B][m + GUSTO_NPLANT][m + GUSTO_NPLANT]: the [b theta] block, which stays
 };
 
 struct SensArgs {
@@ -201,9 +212,11 @@ template <int MODEL> __global__ void __launch_bounds__(256) lincov_plant_sens(co
 }
 
 // NZ: the size of the augmented deviation, the row length of S, G and T.  PLANT = false: NZ = nz, NGZ = NG, NT = 0 -- the loops
-// over the theta entries are empty
-template <int MODEL, bool PLANT>
-__global__ void __launch_bounds__(64) lincov_kernel(const KParams P, const std::conditional_t<PLANT, LcArgsP, LcArgs> V) {
+// over the theta entries are empty.  DENSE (gusto_lincov_dense, with PLANT): the x-rows of S_k of every knot and the [b theta]
+// block go out for lincov_dense; DENSE = false is what it was
+template <int MODEL, bool PLANT, bool DENSE = false>
+__global__ void __launch_bounds__(64) lincov_kernel(const KParams P, const std::conditional_t<DENSE, LcArgsD, std::conditional_t<PLANT, LcArgsP, LcArgs>> V) {
+    static_assert(PLANT || !DENSE, "the dense pass reads the augmented S");
     using T = MT<MODEL>;
     constexpr int n = T::n, m = T::m, nz = n + m, NT = PLANT ? GUSTO_NPLANT : 0, NZ = nz + NT;
     constexpr int NG = n * nz, RG = (NG + 63) / 64;                 // entries of [Ad | Bd], per lane
@@ -230,6 +243,8 @@ __global__ void __launch_bounds__(64) lincov_kernel(const KParams P, const std::
         Cd = V.Cd + (size_t)b * (N - 1) * NC;
         if (V.store_S) Tall = V.Sxt + (size_t)b * N * NC;
     }
+    [[maybe_unused]] double* Rall = nullptr;   // the x-rows of S of every knot
+    if constexpr (DENSE) Rall = V.Srow + (size_t)b * N * NGZ;
     const Env E = problem_env(P, b);
 
     // gains of a failed gusto_tvlqr: its fail_knot, every output zero
@@ -279,6 +294,8 @@ __global__ void __launch_bounds__(64) lincov_kernel(const KParams P, const std::
                         }
             }
             sS[e] = v;
+            if constexpr (DENSE)
+                if (i >= n && c >= n) V.Sbt[((size_t)b * (NZ - n) + (i - n)) * (NZ - n) + (c - n)] = v;
         }
     }
     double g[RG], kr[RK];
@@ -307,6 +324,9 @@ __global__ void __launch_bounds__(64) lincov_kernel(const KParams P, const std::
             if (Tall)
 #pragma unroll
                 for (int r = 0; r < RC; r++) { const int e = lane + 64 * r; if (e < NC) Tall[(size_t)(k - 1) * NC + e] = sS[(e / NT) * NZ + nz + e % NT]; }
+        if constexpr (DENSE)
+#pragma unroll
+            for (int r = 0; r < RGZ; r++) { const int e = lane + 64 * r; if (e < NGZ) Rall[(size_t)(k - 1) * NGZ + e] = sS[e]; }
     };
     auto note_obstacles = [&](int k, double zk, int pk) {
         if (zk < zo_min) { zo_min = zk; zo_knot = k; zo_pair = pk; }   // (strict: the lowest knot of equal minima)
@@ -458,6 +478,9 @@ __global__ void __launch_bounds__(64) lincov_kernel(const KParams P, const std::
             if (Tall)
 #pragma unroll
                 for (int r = 0; r < RC; r++) { const int e = lane + 64 * r; if (e < NC) Tall[(size_t)(k - 1) * NC + e] = 0.0; }
+        if constexpr (DENSE)
+#pragma unroll
+            for (int r = 0; r < RGZ; r++) { const int e = lane + 64 * r; if (e < NGZ) Rall[(size_t)(k - 1) * NGZ + e] = 0.0; }
     }
     if (lane == 0) {
         V.status[b] = (dead || fail) ? 0 : 1;
@@ -472,9 +495,238 @@ __global__ void __launch_bounds__(64) lincov_kernel(const KParams P, const std::
     }
 }
 
-// W: null for gusto_lincov, else V with the dispersion (V is its base) and A, the sensitivity launch ahead of the recursion
-template <int MODEL> int launch_lincov(gusto_handle h, const KParams& P, const LcArgs& V, const LcArgsP* W, const SensArgs& A) {
-    if (W) {
+// gusto_lincov_dense: the margins at the dense samples between the knots, from what the DENSE knot pass left
+struct DnArgs {
+    const double *X, *U, *K;       // K: the gains the knot pass used
+    const double *Srow, *Sbt;      // LcArgsD
+    const int* active;
+    const int* tv_status;          // as LcArgs: null with a caller's K
+    const int* fail_knot;          // of the knot pass
+    double dt_min;                 // the roll-out options of the handle's last gusto_tvlqr
+    int nstep;
+    double du_white[GUSTO_MAXM], dw[GUSTO_MAXM];
+    int store_dense, rows;         // rows = nfull_max: the row count of the per-sample arrays
+    double* zint;                  // [B][N-1]: the smallest z of every interval (knot N belongs to the last one),
+    int *jint, *pint;              // its dense sample and pair ordinal (-1: +inf)
+    double* z_dense;               // [B][rows]
+    int* pair_dense;               // [B][rows]
+    double* Spos;                  // [B][rows][WS][WS]
+    int *nfull, *dense_sample, *dense_pair;   // [B]
+    double* min_z_dense;                      // [B]
+};
+
+// grid (problem, tile of 4 intervals), 256 lanes: one wave per interval.  Lane j < NZ carries the nominal state and column j of
+// G_{k,i} = [Phi - Gamma K | Gamma | C] through the RK4 stages (tvlqr_linearise's statements; the theta columns take dfdth as their
+// source, as lincov_plant_sens): the closed loop sits in the seed -- x-columns start at e_j with the control direction -K e_j, b-
+// columns at 0 with e_c, theta-columns at 0 -- and B du is formed once.  After every substep the first WS entries of the columns
+// go to LDS, the wave forms T = Gp S_k and the upper triangle of Spos = T Gp' + Gammap diag(sw2) Gammap' in a fixed order (S_k:
+// the interval's x-rows of the knot pass, completed by symmetry and the constant block, in LDS throughout), and all 64 lanes
+// take the pairs through obstacle_margin.  At i = 0 and at knot N Spos is the knot pass's Sxx block, by definition.  Every wave
+// of a workgroup walks the same number of substeps (Nstep is the problem's), so the barriers are the workgroup's; a wave past
+// the last interval rolls interval 0 out and stores nothing.  z and the pair of sample i wait in lane i mod 64 and go out 64
+// at a time, consecutive lanes to consecutive addresses.
+template <int MODEL> __global__ void __launch_bounds__(256) lincov_dense(const KParams P, const DnArgs V) {
+    using T = MT<MODEL>;
+    using D = Dyn<MODEL>;
+    constexpr int n = T::n, m = T::m, nz = n + m, NT = GUSTO_NPLANT, NZ = nz + NT, NB = m + NT, WS = T::WS, IPB = 4;
+    constexpr int NS = NZ * NZ, RS = (NS + 63) / 64, NGP = WS * NZ, RGP = (NGP + 63) / 64, NSP = WS * WS, NGZ = n * NZ;
+    static_assert(NZ <= 64 && NSP <= 64, "a lane per column and per entry of Spos");
+    __shared__ double sS[IPB][NS], sGp[IPB][NGP], sT[IPB][NGP], sSp[IPB][NSP], sX[IPB][WS];
+    const int b = blockIdx.x, wv = threadIdx.x >> 6, lane = threadIdx.x & 63, N = P.N;
+    if (V.active && !V.active[b]) return;   // (the whole workgroup)
+    const double dt = P.tf[b] / (N - 1);
+    const int nstep = V.nstep > 0 ? V.nstep : (int)ceil(dt / V.dt_min);   // (gusto_tvlqr has checked 1 <= nstep <= nstep_cap)
+    const double h = dt / nstep;
+    const bool valid = (int)blockIdx.y * IPB + wv < N - 1;
+    const int k = valid ? blockIdx.y * IPB + wv : 0;          // interval k (0-based): knot k + 1
+    const bool has_last = blockIdx.y == gridDim.y - 1, last = valid && k == N - 2;
+    const bool dead = V.tv_status && !V.tv_status[b];
+    const int fail = V.fail_knot[b];
+    const bool live = valid && !dead && (fail == 0 || k + 1 < fail);   // (wave-uniform) else: zeros
+    const Env E = problem_env(P, b);
+    const double* Xk = V.X + ((size_t)b * N + k) * n;
+    const double* Uk = V.U + ((size_t)b * N + k) * m;
+    const double* Kk = V.K + ((size_t)b * (N - 1) + k) * m * n;
+    const double* Sr = V.Srow + ((size_t)b * N + k) * NGZ;
+    const double* Sb = V.Sbt + (size_t)b * NB * NB;
+#pragma unroll
+    for (int r = 0; r < RS; r++) {
+        const int e = lane + 64 * r;
+        if (e < NS) {
+            const int i = e / NZ, c = e % NZ;
+            sS[wv][e] = i < n ? Sr[e] : (c < n ? Sr[c * NZ + i] : Sb[(i - n) * NB + (c - n)]);
+        }
+    }
+    double w2[m];
+#pragma unroll
+    for (int q = 0; q < m; q++) w2[q] = V.du_white[q] * V.du_white[q] + V.dw[q] * V.dw[q] / 3.0;
+    const bool col = lane < NZ;
+    const int j = col ? lane : 0;             // (idle lanes carry column 0 and store nothing)
+    const int jx = j < n ? j : 0, jt = j >= nz ? j - nz : 0;
+    double x[n], u[m], d[n], bu[n];
+#pragma unroll
+    for (int i = 0; i < n; i++) { x[i] = Xk[i]; d[i] = i == j ? 1.0 : 0.0; }
+#pragma unroll
+    for (int i = 0; i < m; i++) u[i] = Uk[i];
+    {   // B du: B does not depend on the state in any model
+        double Bm[n * m], du[m];
+        D::B(P.mp, Bm);
+#pragma unroll
+        for (int c = 0; c < m; c++) du[c] = j < n ? -Kk[c * n + jx] : (n + c == j ? 1.0 : 0.0);
+#pragma unroll
+        for (int i = 0; i < n; i++) {
+            double s = 0.0;
+#pragma unroll
+            for (int c = 0; c < m; c++)
+                if (T::Bnz(i, c)) s += Bm[i * m + c] * du[c];
+            bu[i] = s;
+        }
+    }
+    // the source of a stage: B du, and behind the controls df/dtheta_jt at the stage point
+    auto source = [&](const double* xp, double* g) {
+        D::dfdth(P.mp, xp, u, jt, g);
+#pragma unroll
+        for (int i = 0; i < n; i++) g[i] = j >= nz ? g[i] : bu[i];
+    };
+    __syncthreads();
+
+    double zi = INFINITY, zreg = 0.0;
+    int ji = -1, pi = -1, preg = 0;
+    const int iend = nstep - 1 + (has_last ? 1 : 0);   // (uniform in the workgroup) the sample at i = nstep is knot N
+    for (int i = 0; i <= iend; i++) {
+        const bool end = i == nstep;
+        if (end) {   // knot N, kept by the last interval's wave: X[:,N] and the knot pass's Sxx
+            if (lane < WS) sX[wv][lane] = Xk[n + lane];
+            if (lane < NSP) sSp[wv][lane] = Sr[NGZ + (lane / WS) * NZ + lane % WS];
+        } else if (i == 0) {
+            if (lane < WS) sX[wv][lane] = Xk[lane];
+            if (lane < NSP) sSp[wv][lane] = sS[wv][(lane / WS) * NZ + lane % WS];
+        } else {
+            if (lane == 0)
+#pragma unroll
+                for (int a = 0; a < WS; a++) sX[wv][a] = x[a];
+            if (col)
+#pragma unroll
+                for (int a = 0; a < WS; a++) sGp[wv][a * NZ + j] = d[a];
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < RGP; r++) {
+                const int e = lane + 64 * r;
+                if (e < NGP) {
+                    const int a = e / NZ, c = e % NZ;
+                    double s = 0.0;
+#pragma unroll
+                    for (int p = 0; p < NZ; p++) s += sGp[wv][a * NZ + p] * sS[wv][p * NZ + c];
+                    sT[wv][e] = s;
+                }
+            }
+            __syncthreads();
+            if (lane < NSP && lane / WS <= lane % WS) {
+                const int a = lane / WS, c = lane % WS;
+                double s = 0.0;
+#pragma unroll
+                for (int p = 0; p < NZ; p++) s += sT[wv][a * NZ + p] * sGp[wv][c * NZ + p];
+#pragma unroll
+                for (int q = 0; q < m; q++) s += sGp[wv][a * NZ + n + q] * w2[q] * sGp[wv][c * NZ + n + q];
+                sSp[wv][a * WS + c] = s;
+                sSp[wv][c * WS + a] = s;
+            }
+        }
+        __syncthreads();
+        double zk;
+        int pk;
+        obstacle_margin<MODEL, WS>(P, E, sX[wv], sSp[wv], lane, &zk, &pk);
+        const bool mine = valid && (!end || last);   // the sample is a row of this wave
+        if (mine && live && zk < zi) { zi = zk; ji = k * nstep + i; pi = pk; }   // (strict: the first sample of equal minima)
+        if (V.store_dense) {
+            const size_t row = (size_t)b * V.rows + (size_t)k * nstep;
+            if (mine && lane < NSP) V.Spos[(row + i) * NSP + lane] = live ? sSp[wv][lane] : 0.0;
+            if (lane == (i & 63)) { zreg = live ? zk : 0.0; preg = live ? (pk == NO_ORD ? -1 : pk) : 0; }
+            if ((i & 63) == 63 || i == iend) {
+                const int i0 = i & ~63, il = i0 + lane;
+                if (valid && il <= i && (il != nstep || last)) { V.z_dense[row + il] = zreg; V.pair_dense[row + il] = preg; }
+            }
+        }
+        __syncthreads();   // (the readers of sX, sGp and sSp are done)
+        if (i >= nstep - 1) continue;   // no substep behind the interval's last sample: the next interval restarts at its knot
+        double A[n * n], g[n], w[n], dw[n], k1[n], kk[n], kd1[n], kdk[n], xs[n], ds[n];
+        D::f(P.mp, x, u, k1);
+        D::A(P.mp, x, u, A);
+        source(x, g);
+        plant_tangent<MODEL>(A, d, g, kd1);
+#pragma unroll
+        for (int q = 0; q < n; q++) { xs[q] = k1[q]; ds[q] = kd1[q]; w[q] = x[q] + 0.5 * h * k1[q]; dw[q] = d[q] + 0.5 * h * kd1[q]; }
+        D::f(P.mp, w, u, kk);
+        D::A(P.mp, w, u, A);
+        source(w, g);
+        plant_tangent<MODEL>(A, dw, g, kdk);
+#pragma unroll
+        for (int q = 0; q < n; q++) { xs[q] += 2 * kk[q]; ds[q] += 2 * kdk[q]; w[q] = x[q] + 0.5 * h * kk[q]; dw[q] = d[q] + 0.5 * h * kdk[q]; }
+        D::f(P.mp, w, u, kk);
+        D::A(P.mp, w, u, A);
+        source(w, g);
+        plant_tangent<MODEL>(A, dw, g, kdk);
+#pragma unroll
+        for (int q = 0; q < n; q++) { xs[q] += 2 * kk[q]; ds[q] += 2 * kdk[q]; w[q] = x[q] + h * kk[q]; dw[q] = d[q] + h * kdk[q]; }
+        D::f(P.mp, w, u, kk);
+        D::A(P.mp, w, u, A);
+        source(w, g);
+        plant_tangent<MODEL>(A, dw, g, kdk);
+#pragma unroll
+        for (int q = 0; q < n; q++) {
+            x[q] = x[q] + 1.0 / 6.0 * h * (xs[q] + kk[q]);
+            d[q] = d[q] + 1.0 / 6.0 * h * (ds[q] + kdk[q]);
+        }
+    }
+    if (valid && lane == 0) {
+        V.zint[(size_t)b * (N - 1) + k] = zi;
+        V.jint[(size_t)b * (N - 1) + k] = ji;
+        V.pint[(size_t)b * (N - 1) + k] = ji < 0 || pi == NO_ORD ? -1 : pi;
+    }
+}
+
+// one wave per problem: the minimum over the intervals in their order (lane 0; a strict <, so the first sample of equal minima
+// stays), and zeros in the rows behind nfull_b
+template <int MODEL> __global__ void __launch_bounds__(64) lincov_dense_reduce(const KParams P, const DnArgs V) {
+    constexpr int NSP = MT<MODEL>::WS * MT<MODEL>::WS;
+    const int b = blockIdx.x, lane = threadIdx.x, N = P.N;
+    if (V.active && !V.active[b]) return;
+    const double dt = P.tf[b] / (N - 1);
+    const int nstep = V.nstep > 0 ? V.nstep : (int)ceil(dt / V.dt_min);
+    const int nfull = nstep * (N - 1) + 1;
+    const bool dead = V.tv_status && !V.tv_status[b];
+    if (lane == 0) {
+        double zb = INFINITY;
+        int jb = -1, pb = -1;
+        for (int k = 0; k < N - 1; k++) {
+            const double z = V.zint[(size_t)b * (N - 1) + k];
+            if (z < zb) { zb = z; jb = V.jint[(size_t)b * (N - 1) + k]; pb = V.pint[(size_t)b * (N - 1) + k]; }
+        }
+        V.nfull[b] = nfull;
+        V.min_z_dense[b] = dead ? 0.0 : zb;
+        V.dense_sample[b] = dead ? 0 : jb;
+        V.dense_pair[b] = dead ? 0 : pb;
+    }
+    if (V.store_dense) {
+        for (int r = nfull + lane; r < V.rows; r += 64) { V.z_dense[(size_t)b * V.rows + r] = 0.0; V.pair_dense[(size_t)b * V.rows + r] = 0; }
+        for (size_t e = (size_t)nfull * NSP + lane; e < (size_t)V.rows * NSP; e += 64) V.Spos[(size_t)b * V.rows * NSP + e] = 0.0;
+    }
+}
+
+// W: null for gusto_lincov, else V with the dispersion (V is its base) and A, the sensitivity launch ahead of the recursion;
+// Dn: null, or (gusto_lincov_dense; V is an LcArgsD) the dense pass and its reduction behind the DENSE recursion
+template <int MODEL> int launch_lincov(gusto_handle h, const KParams& P, const LcArgs& V, const LcArgsP* W, const SensArgs& A,
+                                       const DnArgs* Dn = nullptr) {
+    if (Dn) {
+        const int tiles = (h->N - 1 + PlantCols<MODEL>::IPB - 1) / PlantCols<MODEL>::IPB;
+        hipLaunchKernelGGL((lincov_plant_sens<MODEL>), dim3(h->B, tiles), dim3(256), 0, h->stream, P, A);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL((lincov_kernel<MODEL, true, true>), dim3(h->B), dim3(64), 0, h->stream, P, static_cast<const LcArgsD&>(V));
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL((lincov_dense<MODEL>), dim3(h->B, (h->N - 1 + 3) / 4), dim3(256), 0, h->stream, P, *Dn);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL((lincov_dense_reduce<MODEL>), dim3(h->B), dim3(64), 0, h->stream, P, *Dn);
+    } else if (W) {
         const int tiles = (h->N - 1 + PlantCols<MODEL>::IPB - 1) / PlantCols<MODEL>::IPB;
         hipLaunchKernelGGL((lincov_plant_sens<MODEL>), dim3(h->B, tiles), dim3(256), 0, h->stream, P, A);
         HIPCHK(h, hipGetLastError());
@@ -486,9 +738,10 @@ template <int MODEL> int launch_lincov(gusto_handle h, const KParams& P, const L
     return GUSTO_OK;
 }
 
-// gusto_lincov (dist = null) and gusto_lincov_disturbed (dist: the options, never null; Sth: the caller's or null)
+// gusto_lincov (dist = null) and gusto_lincov_disturbed (dist: the options, never null; Sth: the caller's or null);
+// gusto_lincov_dense: dense = its store_dense (0 / 1), else -1
 int lincov_host(gusto_handle h, const char* who_c, const double* X, const double* U, const double* K, const double* S0,
-                const gusto_lincov_opts* opts, const gusto_disturb_opts* dist, const double* Sth);
+                const gusto_lincov_opts* opts, const gusto_disturb_opts* dist, const double* Sth, int dense = -1);
 
 }  // namespace
 
@@ -514,12 +767,21 @@ int gusto_lincov_disturbed(gusto_handle h, const double* X, const double* U, con
     return lincov_host(h, "gusto_lincov_disturbed", X, U, K, S0, opts, d ? d : &zero, Sth);
 }
 
+int gusto_lincov_dense(gusto_handle h, const double* X, const double* U, const double* K, const double* S0, const double* Sth,
+                       const gusto_lincov_opts* opts, const gusto_disturb_opts* d, int store_dense) {
+    gusto_disturb_opts zero;
+    gusto_default_disturb_opts(&zero);
+    if (int rc = post_enter(h, "gusto_lincov_dense", X, U)) return rc;   // (the handle first: the refusals of every stage)
+    if (int rc = lincov_dense_args_host(store_dense, &h->err)) return rc;
+    return lincov_host(h, "gusto_lincov_dense", X, U, K, S0, opts, d ? d : &zero, Sth, store_dense);
+}
+
 }  // extern "C"
 
 namespace {
 
 int lincov_host(gusto_handle h, const char* who_c, const double* X, const double* U, const double* K, const double* S0,
-                const gusto_lincov_opts* opts, const gusto_disturb_opts* dist, const double* Sth) {
+                const gusto_lincov_opts* opts, const gusto_disturb_opts* dist, const double* Sth, int dense) {
     if (int rc = post_enter(h, who_c, X, U)) return rc;
     const std::string who(who_c);
     gusto_lincov_opts o;
@@ -527,7 +789,7 @@ int lincov_host(gusto_handle h, const char* who_c, const double* X, const double
     if (opts) o = *opts;
     if (int rc = lincov_args_host(h->n, h->m, h->B, &o, S0, &h->err, who_c)) return rc;
     if (dist)
-        if (int rc = lincov_plant_args_host(h->model, h->m, h->B, dist, Sth, &h->err)) return rc;
+        if (int rc = lincov_plant_args_host(h->model, h->m, h->B, dist, Sth, &h->err, who_c)) return rc;
     if (!h->tvlqr.have) {
         h->err = who + ": no discrete Jacobians: call gusto_tvlqr first";
         return GUSTO_ERR_STATE;
@@ -564,8 +826,37 @@ int lincov_host(gusto_handle h, const char* who_c, const double* X, const double
             if (S.Sxt.count()) HIPCHK(h, hipMemsetAsync(S.Sxt, 0, sizeof(double) * S.Sxt.count(), h->stream));
         }
     }
-    LcArgsP V{};
+    // gusto_lincov_dense: the x-rows of S and the per-interval minima; the per-sample arrays with store_dense.  A first call since
+    // gusto_set_problems, or another row count: zeros everywhere (what an inactive problem then reads)
+    const size_t NZ = nz + NT, NB = m + NT;
+    size_t rows = 0, nsp = 0;
+    if (dense >= 0) {
+        int ws = 0;
+        for_model(h->model, [&](auto M) { ws = MT<M()>::WS; return GUSTO_OK; });
+        nsp = (size_t)ws * ws;
+        rows = (size_t)h->tvlqr.nstep_max * (N - 1) + 1;
+        const bool fresh = !S.have_dense || S.dense_rows != rows;
+        HIPCHK(h, S.Srow.ensure_zeroed(Bc * N * n * NZ, h->stream)); HIPCHK(h, S.Sbt.ensure_zeroed(Bc * NB * NB, h->stream));
+        HIPCHK(h, S.Zint.ensure_zeroed(Bc * (N - 1), h->stream)); HIPCHK(h, S.Jint.ensure_zeroed(2 * Bc * (N - 1), h->stream));
+        HIPCHK(h, S.DI.ensure_zeroed(3 * Bc, h->stream)); HIPCHK(h, S.DD.ensure_zeroed(Bc, h->stream));
+        if (fresh) {
+            HIPCHK(h, hipMemsetAsync(S.DI, 0, sizeof(int) * S.DI.count(), h->stream));
+            HIPCHK(h, hipMemsetAsync(S.DD, 0, sizeof(double) * S.DD.count(), h->stream));
+            S.have_dense_rows = false;
+        }
+        if (dense) {
+            HIPCHK(h, S.Zd.ensure_zeroed(Bc * rows, h->stream)); HIPCHK(h, S.Pd.ensure_zeroed(Bc * rows, h->stream));
+            HIPCHK(h, S.Spos.ensure_zeroed(Bc * rows * nsp, h->stream));
+            if (!S.have_dense_rows) {
+                HIPCHK(h, hipMemsetAsync(S.Zd, 0, sizeof(double) * S.Zd.count(), h->stream));
+                HIPCHK(h, hipMemsetAsync(S.Pd, 0, sizeof(int) * S.Pd.count(), h->stream));
+                HIPCHK(h, hipMemsetAsync(S.Spos, 0, sizeof(double) * S.Spos.count(), h->stream));
+            }
+        }
+    }
+    LcArgsD V{};
     SensArgs A{};
+    DnArgs Dn{};
     if (int rc = stage_traj(h, X, U, Bc, S.X, S.U, &V.X, &V.U)) return rc;
     V.AB = h->tvlqr.AB;
     V.K = h->tvlqr.K;
@@ -599,8 +890,18 @@ int lincov_host(gusto_handle h, const char* who_c, const double* X, const double
         A.X = V.X; A.U = V.U; A.active = V.active; A.Cd = S.Cd;
         A.dt_min = h->tvlqr.dt_min; A.nstep = h->tvlqr.nstep;
     }
+    if (dense >= 0) {
+        V.Srow = S.Srow; V.Sbt = S.Sbt;
+        Dn.X = V.X; Dn.U = V.U; Dn.K = V.K; Dn.Srow = S.Srow; Dn.Sbt = S.Sbt; Dn.active = V.active; Dn.tv_status = V.tv_status;
+        Dn.fail_knot = V.fail_knot; Dn.dt_min = A.dt_min; Dn.nstep = A.nstep;
+        memcpy(Dn.du_white, V.du_white, sizeof(Dn.du_white)); memcpy(Dn.dw, V.dw, sizeof(Dn.dw));
+        Dn.store_dense = dense; Dn.rows = (int)rows;
+        Dn.zint = S.Zint; Dn.jint = S.Jint; Dn.pint = S.Jint + Bc * (N - 1);
+        Dn.z_dense = S.Zd; Dn.pair_dense = S.Pd; Dn.Spos = S.Spos;
+        Dn.nfull = S.DI; Dn.dense_sample = S.DI + Bc; Dn.dense_pair = S.DI + 2 * Bc; Dn.min_z_dense = S.DD;
+    }
     HIPCHK(h, S.t0.record(h->stream));
-    if (int rc = for_model(h->model, [&](auto M) { return launch_lincov<M()>(h, P, V, dist ? &V : nullptr, A); })) return rc;
+    if (int rc = for_model(h->model, [&](auto M) { return launch_lincov<M()>(h, P, V, dist ? &V : nullptr, A, dense >= 0 ? &Dn : nullptr); })) return rc;
     HIPCHK(h, S.t1.record(h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, event_ms(S.t0, S.t1, &S.last_ms));
@@ -608,6 +909,11 @@ int lincov_host(gusto_handle h, const char* who_c, const double* X, const double
     S.have = true;
     S.store_S = o.store_S != 0;
     S.plant = dist != nullptr;
+    S.dense = dense >= 0;
+    if (dense >= 0) {
+        S.have_dense = true; S.dense_rows = rows; S.dense_nsp = nsp; S.store_dense = dense != 0;
+        if (dense) S.have_dense_rows = true;
+    }
     return GUSTO_OK;
 }
 
@@ -647,6 +953,27 @@ int gusto_get_lincov(gusto_handle h, gusto_lincov_report* out) {
     if (int rc = copy_out(h, out->sigma_u, S.Su, B * (N - 1) * m)) return rc;
     if (int rc = copy_out(h, out->z_obs, S.Z, B * N)) return rc;
     return copy_out(h, out->Sxx, S.Sxx, B * N * n * n);
+}
+
+int gusto_get_lincov_dense(gusto_handle h, gusto_lincov_dense_report* out, int* nfull_max) {
+    if (!h) return GUSTO_ERR_ARG;
+    if (int rc = getter_enter(h, false)) return rc;
+    const LincovState& S = h->lincov;
+    if (!S.have || !S.dense) { h->err = "gusto_get_lincov_dense: the last covariance analysis was not a gusto_lincov_dense"; return GUSTO_ERR_STATE; }
+    if (nfull_max) *nfull_max = (int)S.dense_rows;
+    if (!out) return GUSTO_OK;
+    if ((out->z_dense || out->pair_dense || out->Spos) && !S.store_dense) {
+        h->err = "gusto_get_lincov_dense: the last gusto_lincov_dense did not run with store_dense = 1";
+        return GUSTO_ERR_STATE;
+    }
+    const size_t B = h->B, Bc = h->batch_cap, rows = S.dense_rows;
+    if (int rc = copy_out(h, out->nfull, S.DI, B)) return rc;
+    if (int rc = copy_out(h, out->dense_sample, S.DI + Bc, B)) return rc;
+    if (int rc = copy_out(h, out->dense_pair, S.DI + 2 * Bc, B)) return rc;
+    if (int rc = copy_out(h, out->min_z_dense, S.DD, B)) return rc;
+    if (int rc = copy_out(h, out->z_dense, S.Zd, B * rows)) return rc;
+    if (int rc = copy_out(h, out->pair_dense, S.Pd, B * rows)) return rc;
+    return copy_out(h, out->Spos, S.Spos, B * rows * S.dense_nsp);
 }
 
 int gusto_last_lincov_ms(gusto_handle h, double* ms) {

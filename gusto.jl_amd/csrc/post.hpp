@@ -96,8 +96,9 @@ constexpr bool plant_entry_read(int model, int j) {
 // The arguments of gusto_lincov_disturbed that gusto_lincov does not have: the dispersion d and the caller's Sth
 // [B][GUSTO_NPLANT][GUSTO_NPLANT] (null: the default), of which only the entries the model reads are looked at.  GUSTO_ERR_ARG
 // and the text, which names the offending entry (and problem), in *err.  No device, no handle.
-static inline int lincov_plant_args_host(int model, int m, size_t B, const gusto_disturb_opts* d, const double* Sth, std::string* err) {
-    const std::string w("gusto_lincov_disturbed: ");
+static inline int lincov_plant_args_host(int model, int m, size_t B, const gusto_disturb_opts* d, const double* Sth, std::string* err,
+                                         const char* who = "gusto_lincov_disturbed") {
+    const std::string w = std::string(who) + ": ";
     constexpr size_t NT = GUSTO_NPLANT;
     for (size_t j = 0; j < NT; j++)
         if (!(d->plant_rel[j] >= 0 && d->plant_rel[j] < 1)) { *err = w + "plant_rel must lie in [0, 1) (entry " + std::to_string(j) + ")"; return GUSTO_ERR_ARG; }
@@ -120,6 +121,13 @@ static inline int lincov_plant_args_host(int model, int m, size_t B, const gusto
                 }
             }
     }
+    return GUSTO_OK;
+}
+
+// The argument of gusto_lincov_dense that gusto_lincov_disturbed does not have (its others go through the two checks above,
+// under this call's name).  No device, no handle.
+static inline int lincov_dense_args_host(int store_dense, std::string* err) {
+    if (store_dense != 0 && store_dense != 1) { *err = "gusto_lincov_dense: store_dense must be 0 or 1"; return GUSTO_ERR_ARG; }
     return GUSTO_OK;
 }
 

@@ -321,7 +321,7 @@ int gusto_tvlqr(gusto_handle h, const double* X, const double* U, const gusto_tv
         }
     TvlqrState& S = h->tvlqr;
     const size_t B = h->B, N = h->N, n = h->n, m = h->m;
-    int nstep_max = 0;   // (as gusto_verify; the largest count is of no use here)
+    int nstep_max = 0;   // (as gusto_verify; gusto_lincov_dense sizes its per-sample arrays by the largest count)
     if (int rc = resolve_nstep(h, "gusto_tvlqr", o.dt_min, o.nstep, o.nstep_cap, &nstep_max)) return rc;
     const KParams P = post_params(h);
     // grow-only, zeroed when (re)allocated.  Growing discards the contents: it happens only after a gusto_set_problems with a
@@ -360,7 +360,7 @@ int gusto_tvlqr(gusto_handle h, const double* X, const double* U, const gusto_tv
     if (o.store_P) S.have_Pall = true;
     S.have = true;
     S.store_P = o.store_P != 0;
-    S.dt_min = o.dt_min; S.nstep = o.nstep;
+    S.dt_min = o.dt_min; S.nstep = o.nstep; S.nstep_max = nstep_max;
     return GUSTO_OK;
 }
 

@@ -644,6 +644,27 @@ def lincov_disturbed(traj, SCPP, K=None, S0=None, Sth=None, disturb=None, Q=1.0,
     return {k: v[0] for k, v in r.items()}
 
 
+def lincov_dense(traj, SCPP, K=None, S0=None, Sth=None, disturb=None, Q=1.0, R=1.0, Qf=1.0, dt_min=0.1, store_dense=True, **opts):
+    """lincov_disturbed() with the obstacle margins at the dense samples between the knots (gusto_lincov_dense; no counterpart in
+    the reference): the samples of interpolate_traj / simulate() with the roll-out of tvlqr(traj, SCPP, Q, R, Qf, dt_min), the
+    position covariance carried inside every hold interval by the exact derivative of the RK4 substeps.  Returns
+    lincov_disturbed()'s report of the knot pass with nfull, min_z_dense, dense_sample, dense_pair and -- with store_dense --
+    z_dense, pair_dense [nfull] and Spos [nfull, WS, WS]."""
+    bs = _verify_handle(traj, SCPP)
+    try:
+        bs.tvlqr(dict(Q=Q, R=R, Qf=Qf, dt_min=dt_min, nstep_cap=max(64, int(np.ceil(traj.dt / dt_min)))))
+        one = lambda a: None if a is None else np.asarray(a, float)[None]
+        dense = bs.lincov_dense(opts, disturb, K=one(K), S0=one(S0), Sth=one(Sth), store_dense=int(bool(store_dense)))
+        r = bs.get_lincov()
+        r["Cd"], Sxt = bs.get_lincov_plant()
+        if Sxt is not None:
+            r["Sxt"] = Sxt
+        r.update(dense)
+    finally:
+        bs.close()
+    return {k: v[0] for k, v in r.items()}
+
+
 def shard_bounds(B, world_size, rank):
     """Contiguous block of ceil(B/G) problems per rank; the tail rank may get fewer."""
     per = -(-B // world_size)

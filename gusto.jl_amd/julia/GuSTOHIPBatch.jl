@@ -579,3 +579,46 @@ function lincov_disturbed_batch!(h::Ptr{Cvoid}, B::Integer, n::Integer, m::Integ
    ctl_entry = Int.(ctl_entry), min_z_obs = zo, p_collision_bound = pb, min_z_ctl = zc, sigma_x = sx, sigma_u = su, z_obs = z,
    Sxx = Sxx, Cd = Cd, Sxt = Sxt, ms = ms[])
 end
+
+# ---- obstacle margins at the dense samples between the knots (gusto_lincov_dense, csrc/lincov.hip) ------------------------------
+# lincov_disturbed_batch!'s knot pass and, inside every hold interval, the position covariance at the samples of gusto_simulate /
+# gusto_interpolate (the roll-out of the last tvlqr_batch!), turned into margins.  Same arguments; ws = 2 in the plane, 3 in space.
+# Returns nfull, dense_sample (0-based, as the C ABI), dense_pair, min_z_dense [B] and, with store_dense, z_dense and pair_dense
+# as [nfull_max,B] and Spos as [ws,ws,nfull_max,B]; gusto_get_lincov / gusto_get_lincov_plant then report the knot pass.  This
+# wrapper has not been run.
+mutable struct GustoLincovDenseReport      # gusto_lincov_dense_report
+  nfull::Ptr{Cint}; dense_sample::Ptr{Cint}; dense_pair::Ptr{Cint}
+  min_z_dense::Ptr{Cdouble}
+  z_dense::Ptr{Cdouble}; pair_dense::Ptr{Cint}
+  Spos::Ptr{Cdouble}
+end
+function lincov_dense_batch!(h::Ptr{Cvoid}, B::Integer, n::Integer, m::Integer, N::Integer, ws::Integer, X=nothing, U=nothing, K=nothing,
+                             S0=nothing, Sth=nothing; dx0=0.01, du0=0.0, du_white=0.0, u_lo=-Inf, u_hi=Inf, store_S=false,
+                             plant_rel=0.0, dw=0.0, store_dense=true)
+  ptr(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+  o = GustoLincovOpts(gusto_weights(dx0, n, 13), gusto_weights(du0, m, 6), gusto_weights(du_white, m, 6), gusto_bounds(u_lo, m, 6, -Inf),
+                      gusto_bounds(u_hi, m, 6, Inf), store_S ? 1 : 0)
+  d = GustoDisturbOpts(gusto_weights(plant_rel, 6, 6), gusto_weights(dw, m, 6))
+  GC.@preserve X U K S0 Sth gusto_check(ccall((:gusto_lincov_dense, libgusto_hip), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{GustoLincovOpts}, Ref{GustoDisturbOpts}, Cint),
+                    h, ptr(X), ptr(U), ptr(K), ptr(S0), ptr(Sth), o, d, store_dense ? 1 : 0), h, "lincov_dense")
+  rows = Ref{Cint}(0)
+  gusto_check(ccall((:gusto_get_lincov_dense, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{GustoLincovDenseReport}, Ref{Cint}), h, C_NULL, rows),
+              h, "get_lincov_dense")
+  R = Int(rows[])
+  nfull, js, jp = (zeros(Cint, B) for _ in 1:3)
+  zmin = zeros(B)
+  z = store_dense ? zeros(R, B) : nothing
+  pr = store_dense ? zeros(Cint, R, B) : nothing
+  Sp = store_dense ? zeros(ws, ws, R, B) : nothing
+  GC.@preserve nfull js jp zmin z pr Sp begin
+    rep = GustoLincovDenseReport(pointer(nfull), pointer(js), pointer(jp), pointer(zmin), ptr(z),
+                                 pr === nothing ? Ptr{Cint}(C_NULL) : pointer(pr), ptr(Sp))
+    gusto_check(ccall((:gusto_get_lincov_dense, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoLincovDenseReport}, Ptr{Cint}), h, rep, C_NULL),
+                h, "get_lincov_dense")
+  end
+  ms = Ref{Cdouble}(0.0)
+  gusto_check(ccall((:gusto_last_lincov_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, ms), h, "last_lincov_ms")
+  (nfull = Int.(nfull), dense_sample = Int.(js), dense_pair = Int.(jp), min_z_dense = zmin, z_dense = z,
+   pair_dense = pr === nothing ? nothing : Int.(pr), Spos = Sp, nfull_max = R, ms = ms[])
+end

@@ -511,8 +511,8 @@ typedef struct {
     double *Sxx;       /* [B][N][x_dim][x_dim] */
 } gusto_lincov_report;
 int gusto_get_lincov(gusto_handle h, gusto_lincov_report* out);
-/* GPU time of the last gusto_lincov (one launch) or gusto_lincov_disturbed (both launches), from HIP events on the handle's
- * stream */
+/* GPU time of the last gusto_lincov (one launch), gusto_lincov_disturbed (both launches) or gusto_lincov_dense (all four), from
+ * HIP events on the handle's stream */
 int gusto_last_lincov_ms(gusto_handle h, double* ms);
 
 /* gusto_lincov with an uncertain plant (csrc/lincov.hip): the analytic counterpart of gusto_simulate_disturbed.  No counterpart
@@ -558,6 +558,57 @@ int gusto_lincov_disturbed(gusto_handle h, const double* X, const double* U, con
 /* Cd [B][N-1][n][GUSTO_NPLANT]; Sxt [B][N][n][GUSTO_NPLANT], the x-theta block of S_k, after a call with store_S = 1
  * (asked for after a call without: GUSTO_ERR_STATE).  Either may be NULL. */
 int gusto_get_lincov_plant(gusto_handle h, double* Cd, double* Sxt);
+
+/* gusto_lincov_disturbed with the obstacle margins at the dense samples between the knots (csrc/lincov.hip): what
+ * min_dist_dense is to gusto_verify and worst_dense_sample to gusto_simulate.  No counterpart in the reference.  Everything
+ * gusto_lincov_disturbed defines stays as it is, word for word; the call runs that knot pass and adds a dense pass:
+ * Dense samples: the index of gusto_simulate and gusto_interpolate, j = (k - 1) Nstep_b + i (0-based), i = 0 .. Nstep_b - 1;
+ *   j = (N - 1) Nstep_b is knot N, so nfull_b = Nstep_b (N - 1) + 1.  Nstep_b, dt_min and nstep are those of the handle's last
+ *   gusto_tvlqr, as gusto_lincov_disturbed takes them.
+ * Nominal point of sample (k, i): xbar_{k,i}, the state after i classical RK4 substeps from X[:,k] under the held U[:,k] and
+ *   theta_nom.  Every interval is restarted at its knot; the arithmetic is that of gusto_tvlqr's nominal roll-out.
+ * Sensitivities inside an interval: Phi_{k,i} = d xbar_{k,i} / d x_k, Gamma_{k,i} = d / d u_k, C_{k,i} = d / d theta: the EXACT
+ *   derivative of the discrete map after i substeps, forward mode through the four stages with the models' own A, B and
+ *   df/dtheta -- no finite differences.  At i = 0 they are I, 0, 0.
+ * Deviation at the sample: the closed loop holds u = U_k - K_k dx_k + b + w_k for the whole interval.  With z_k = [dx_k; b; theta~]
+ *     dx_{k,i} = G_{k,i} z_k + Gamma_{k,i} w_k,   G_{k,i} = [Phi - Gamma K_k | Gamma | C]   (n x (n + m + GUSTO_NPLANT)),
+ *     Spos_{k,i} = Gp S_k Gp' + Gammap diag(sw2) Gammap'   (WS x WS; Gp, Gammap: the first WS rows of G_{k,i}, Gamma_{k,i}),
+ *   computed on the upper triangle and mirrored; S_k and sw2 are those of the knot pass.  At i = 0, and at knot N, Spos is BY
+ *   DEFINITION the leading WS x WS block of the knot pass's Sxx.
+ * Margin: for every pair (robot component c, keep-out component o), in gusto_lincov's order, ordinal c n_obs + o: d and nh from
+ *   the signed distance at xbar_{k,i}, sigma_d = sqrt(nh' Spos nh) under the variance-below-zero rule, z = d / sigma_d with the
+ *   sigma_d == 0 rule.  z_dense[j] is the smallest over the pairs, pair_dense[j] its lowest ordinal; a NaN never wins.
+ *   DubinsCar, or an empty keep-out set: +inf and -1.
+ * Per problem: min_z_dense, the smallest z_dense[j]; dense_sample, the first j it occurs at (0-based; -1 when it is +inf);
+ *   dense_pair, the pair there (-1 likewise); nfull.  z_dense at every i = 0 sample and at knot N is z_obs of that knot, to the
+ *   bit, so min_z_dense <= min_z_obs, and dense_sample sets against gusto_simulate's worst_dense_sample.
+ * NO Boole bound is formed over the dense samples: neighbouring samples are strongly correlated, the sum grows with Nstep
+ *   without saying more, and it would look like a probability.  p_collision_bound stays the knots' (gusto_get_lincov).
+ * Status: that of the knot pass (gusto_get_lincov).  A problem with status 0 and fail_knot f from the recursion: the per-sample
+ *   rows from sample (f - 1) Nstep_b on are zeros, the summary covers the samples before (none: +inf, -1, -1).  A problem dead
+ *   from gusto_tvlqr: every per-sample row and min_z_dense, dense_sample, dense_pair are zero; nfull is the layout's, as ever.
+ * store_dense = 1 keeps z_dense, pair_dense [B][nfull_max] and Spos [B][nfull_max][WS][WS], nfull_max = the largest nfull_b of
+ *   the handle's last gusto_tvlqr (gusto_get_lincov_dense returns it); rows behind nfull[b] are zeros.
+ * d NULL or all zeros with Sth = NULL gives the dense form of plain gusto_lincov.  X, U, K, S0, Sth, o, d, gusto_set_active (an
+ *   inactive problem keeps what the last call with the same nfull_max wrote; zeros after new problems), stream and events, the
+ *   grow-only buffers and the refusals are gusto_lincov_disturbed's, under this call's name; store_dense other than 0 / 1:
+ *   GUSTO_ERR_ARG; TrajOpt handles: GUSTO_ERR_ARG.  After the call gusto_get_lincov and gusto_get_lincov_plant report its knot
+ *   pass, which equals gusto_lincov_disturbed's with the same arguments bit for bit, and gusto_last_lincov_ms covers all four
+ *   launches (sensitivities, knot pass, dense pass, reduction).  gusto_get_lincov_dense answers GUSTO_ERR_STATE before the
+ *   first gusto_lincov_dense, after a gusto_lincov or gusto_lincov_disturbed came between, and for a per-sample array after a
+ *   call without store_dense.  All reductions run in a fixed order without atomics: every dense output of a problem is the
+ *   same bit for bit whatever batch it sits in and under any mask. */
+int gusto_lincov_dense(gusto_handle h, const double* X, const double* U, const double* K, const double* S0,
+                       const double* Sth, const gusto_lincov_opts* o, const gusto_disturb_opts* d, int store_dense);
+/* Caller-owned arrays; any pointer may be NULL */
+typedef struct {
+    int *nfull, *dense_sample, *dense_pair;   /* [B] */
+    double *min_z_dense;                      /* [B] */
+    double *z_dense; int *pair_dense;         /* [B][nfull_max], store_dense = 1 */
+    double *Spos;                             /* [B][nfull_max][WS][WS], store_dense = 1 */
+} gusto_lincov_dense_report;
+/* out and nfull_max may each be NULL */
+int gusto_get_lincov_dense(gusto_handle h, gusto_lincov_dense_report* out, int* nfull_max);
 
 /* One convex subproblem per problem (what scp_gusto.jl:82-104 builds and solves in one trip), linearised at
  * (Xp,Up)[b] with the given Delta/omega/obstacle_toggle_distance[b].  Used by the parity tests.
