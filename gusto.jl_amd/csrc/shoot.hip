@@ -330,8 +330,8 @@ template <int MODEL, int G> __global__ void __launch_bounds__(64) shoot_group_ke
     }
 }
 
-// out[b][r] = in[r][b] for the problems whose shooting converged (R = N n or N m rows, B columns): 32 x 32 tiles through
-// LDS, reads and writes both coalesced; the rows of the other problems are left as they are
+// out[b][r] = in[r][b] for the problems whose shooting converged, 0 for the others -- the staging holds nothing of theirs from
+// this call (R = N n or N m rows, B columns): 32 x 32 tiles through LDS, reads and writes both coalesced
 __global__ void __launch_bounds__(256) shoot_transpose_kernel(const double* in, double* out, const int* status, int R, int B) {
     __shared__ double tile[32][33];
     const int b0 = blockIdx.x * 32, r0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
@@ -342,7 +342,7 @@ __global__ void __launch_bounds__(256) shoot_transpose_kernel(const double* in, 
     __syncthreads();
     for (int j = ty; j < 32; j += 8) {
         const int b = b0 + j, r = r0 + tx;
-        if (b < B && r < R && status[b]) out[(size_t)b * R + r] = tile[tx][j];
+        if (b < B && r < R) out[(size_t)b * R + r] = status[b] ? tile[tx][j] : 0.0;
     }
 }
 

@@ -235,7 +235,9 @@ typedef struct {
 int gusto_default_shoot_opts(gusto_shoot_opts* o);
 int gusto_shoot(gusto_handle h, const double* p0, const gusto_shoot_opts* opts);
 /* status [B]: 1 = :Optimal (sol_newton.f_converged), 0 = :Diverged; p0 [B][n] the converged initial costate; X [B][N][n],
- * U [B][N][m] the recovered trajectory of the :Optimal problems (shooting.jl:26-36).  Any pointer may be NULL. */
+ * U [B][N][m] the recovered trajectory of the :Optimal problems (shooting.jl:26-36); the X and U of a problem that is not
+ * :Optimal in the last gusto_shoot are zeros.  A problem that gusto_set_active left out of that call reports status 0, 0 Newton
+ * iterations, a NaN residual and its seed as p0.  Any pointer may be NULL. */
 int gusto_get_shoot(gusto_handle h, int* status, int* newton_iters, double* resid, double* p0, double* X, double* U);
 
 /* Post-solve verification of every problem of the batch (csrc/verify.hip): interpolate_traj, dynamics_constraint_satisfaction

@@ -1,6 +1,7 @@
 """Indirect shooting seeded by the SCP dual (src/shooting.jl, src/traj_opt.jl:4-45): DubinsCar and
 AstrobeeSE3Manifold, the two models with a shooting ODE in the reference.
-CPU: the oracle's restatement against scipy.  GPU: gusto_shoot against the oracle, and solve_SCPshooting! end to end."""
+CPU: the oracle's restatement against scipy.  GPU: gusto_shoot against the oracle, and solve_SCPshooting! end to end.
+tests/test_gpu_shoot.py holds the tight checks of gusto_shoot against an independent restatement (tests/np_shoot.py)."""
 import numpy as np
 import pytest
 
