@@ -20,10 +20,9 @@
 // comes from a launch ahead of it on the same stream:
 //   lincov_plant_sens  grid (problem, tile of IPB intervals), 256 lanes.  Work item (k, c) = lane: interval k and the c-th plant
 //     scalar the model reads (2 or 4 of them: IPB = 128 or 64).  A lane carries the nominal state and ONE tangent column
-//     d = dx/dtheta_j through the four RK4 stages of every substep, kd = A(stage point) d + dfdth_j(stage point, u), forward mode
-//     as tvlqr_linearise with the model's own A over its structural nonzeros.  The tile is staged in LDS ([interval][row][6],
-//     the layout of Cd, zeros in the columns the model does not read) and copied out by the whole workgroup, consecutive lanes
-//     to consecutive addresses.
+//     d = dx/dtheta_j through every substep: tvlqr_linearise's step (rk4_tangent.inc) with the source dfdth_j(stage point, u).  The
+//     tile is staged in LDS ([interval][row][6], the layout of Cd, zeros in the columns the model does not read) and copied out
+//     by the whole workgroup, consecutive lanes to consecutive addresses.
 // gusto_lincov_dense is gusto_lincov_disturbed with DENSE = true -- the knot pass also writes the x-rows of S_k of every knot and
 // the [b theta] block, which stays -- and two launches behind it on the same stream:
 //   lincov_dense         grid (problem, tile of 4 intervals), one wave per interval: the margins at the dense samples inside it
@@ -31,8 +30,8 @@
 //   lincov_dense_reduce  one wave per problem: the minimum over the intervals in their order, zeros behind nfull_b
 #include <hip/hip_runtime.h>
 
-#include "models.hpp"
 #include "post.hpp"
+#include "rollout.hpp"
 
 using namespace gusto;
 
@@ -131,19 +130,6 @@ template <int MODEL, int nz> GD void obstacle_margin(const KParams& P, const Env
     *zk = zmin;
 }
 
-// kd = A d + g over the structural nonzeros of A (as tvlqr.hip: tangent)
-template <int MODEL> GD void plant_tangent(const double* A, const double* d, const double* g, double* kd) {
-    constexpr int n = MT<MODEL>::n;
-#pragma unroll
-    for (int i = 0; i < n; i++) {
-        double s = g[i];
-#pragma unroll
-        for (int j = 0; j < n; j++)
-            if (MT<MODEL>::Anz(i, j)) s += A[i * n + j] * d[j];
-        kd[i] = s;
-    }
-}
-
 template <int MODEL> __global__ void __launch_bounds__(256) lincov_plant_sens(const KParams P, const SensArgs V) {
     using D = Dyn<MODEL>;
     using PC = PlantCols<MODEL>;
@@ -153,7 +139,7 @@ template <int MODEL> __global__ void __launch_bounds__(256) lincov_plant_sens(co
     const int b = blockIdx.x, k0 = blockIdx.y * IPB, t = threadIdx.x, N = P.N;
     if (V.active && !V.active[b]) return;   // (the whole workgroup)
     const double dt = P.tf[b] / (N - 1);
-    const int nstep = V.nstep > 0 ? V.nstep : (int)ceil(dt / V.dt_min);   // (gusto_tvlqr has checked 1 <= nstep <= nstep_cap)
+    const int nstep = rollout_nstep(dt, V.nstep, V.dt_min);
     const double h = dt / nstep;
     const int kl = t / NR, c = t % NR;
     const bool valid = k0 + kl < N - 1;
@@ -170,34 +156,8 @@ template <int MODEL> __global__ void __launch_bounds__(256) lincov_plant_sens(co
 #pragma unroll
     for (int i = 0; i < m; i++) u[i] = Uk[i];
     for (int s = 0; s < nstep; s++) {
-        double A[n * n], g[n], w[n], dw[n], k1[n], kk[n], kd1[n], kdk[n], xs[n], ds[n];
-        D::f(P.mp, x, u, k1);
-        D::A(P.mp, x, u, A);
-        D::dfdth(P.mp, x, u, j, g);
-        plant_tangent<MODEL>(A, d, g, kd1);
-#pragma unroll
-        for (int i = 0; i < n; i++) { xs[i] = k1[i]; ds[i] = kd1[i]; w[i] = x[i] + 0.5 * h * k1[i]; dw[i] = d[i] + 0.5 * h * kd1[i]; }
-        D::f(P.mp, w, u, kk);
-        D::A(P.mp, w, u, A);
-        D::dfdth(P.mp, w, u, j, g);
-        plant_tangent<MODEL>(A, dw, g, kdk);
-#pragma unroll
-        for (int i = 0; i < n; i++) { xs[i] += 2 * kk[i]; ds[i] += 2 * kdk[i]; w[i] = x[i] + 0.5 * h * kk[i]; dw[i] = d[i] + 0.5 * h * kdk[i]; }
-        D::f(P.mp, w, u, kk);
-        D::A(P.mp, w, u, A);
-        D::dfdth(P.mp, w, u, j, g);
-        plant_tangent<MODEL>(A, dw, g, kdk);
-#pragma unroll
-        for (int i = 0; i < n; i++) { xs[i] += 2 * kk[i]; ds[i] += 2 * kdk[i]; w[i] = x[i] + h * kk[i]; dw[i] = d[i] + h * kdk[i]; }
-        D::f(P.mp, w, u, kk);
-        D::A(P.mp, w, u, A);
-        D::dfdth(P.mp, w, u, j, g);
-        plant_tangent<MODEL>(A, dw, g, kdk);
-#pragma unroll
-        for (int i = 0; i < n; i++) {
-            x[i] = x[i] + 1.0 / 6.0 * h * (xs[i] + kk[i]);
-            d[i] = d[i] + 1.0 / 6.0 * h * (ds[i] + kdk[i]);
-        }
+#define RK4_TANGENT_SOURCE(xp, g) (D::dfdth(P.mp, xp, u, j, g), g)
+#include "rk4_tangent.inc"
     }
     // the columns the model does not read are zeros; a lane writes column j of its interval (disjoint addresses)
     for (int e = t; e < IPB * n * NT; e += 256)
@@ -283,14 +243,14 @@ __global__ void __launch_bounds__(64) lincov_kernel(const KParams P, const std::
                     if (V.S0) v = V.S0[(size_t)b * nz * nz + i * nz + c];
                     else if (i == c) { const double w = i < n ? V.dx0[i] : V.du0[i - n]; v = w * w / 3.0; }
                 }
-                const double nominal[GUSTO_NPLANT] = {P.mp.mass, P.mp.Jdiag[0], P.mp.Jdiag[1], P.mp.Jdiag[2], P.mp.dubins_v, P.mp.dubins_k};
+                const PlantNominal nominal(P.mp);
 #pragma unroll
                 for (int ji = 0; ji < NT; ji++)
 #pragma unroll
                     for (int jc = 0; jc < NT; jc++)
                         if (plant_entry_read(MODEL, ji) && plant_entry_read(MODEL, jc) && i == nz + ji && c == nz + jc) {
                             if (V.Sth) v = V.Sth[(size_t)b * NT * NT + ji * NT + jc];
-                            else if (ji == jc) { const double t = nominal[ji] * V.plant_rel[ji]; v = (t * t) / 3.0; }
+                            else if (ji == jc) { const double t = nominal.v[ji] * V.plant_rel[ji]; v = (t * t) / 3.0; }
                         }
             }
             sS[e] = v;
@@ -312,21 +272,10 @@ __global__ void __launch_bounds__(64) lincov_kernel(const KParams P, const std::
     double zo_min = INFINITY, zc_min = INFINITY, psum = 0.0;
     int zo_knot = 0, zo_pair = -1, zc_knot = 0, zc_entry = -1;
 
-    // rows of knot k from S_k: sigma_x, z_obs, Sxx; sigma_u on the knots that have a control
+    // the rows of knot k (lincov_knot_rows.inc has the list) from S_k
     auto emit = [&](int k, double zk, bool with_u) {
-        if (lane < n) sx[(size_t)(k - 1) * n + lane] = sigma_of(sS[lane * NZ + lane]);
-        if (with_u && lane < m) su[(size_t)(k - 1) * m + lane] = sSu[lane];
-        if (lane == 0) zo[k - 1] = zk;
-        if (Sall)
-#pragma unroll
-            for (int r = 0; r < RPF; r++) { const int e = lane + 64 * r; if (e < NPF) Sall[(size_t)(k - 1) * NPF + e] = sS[(e / n) * NZ + e % n]; }
-        if constexpr (PLANT)
-            if (Tall)
-#pragma unroll
-                for (int r = 0; r < RC; r++) { const int e = lane + 64 * r; if (e < NC) Tall[(size_t)(k - 1) * NC + e] = sS[(e / NT) * NZ + nz + e % NT]; }
-        if constexpr (DENSE)
-#pragma unroll
-            for (int r = 0; r < RGZ; r++) { const int e = lane + 64 * r; if (e < NGZ) Rall[(size_t)(k - 1) * NGZ + e] = sS[e]; }
+#define KNOT_ROWS_LIVE true
+#include "lincov_knot_rows.inc"
     };
     auto note_obstacles = [&](int k, double zk, int pk) {
         if (zk < zo_min) { zo_min = zk; zo_knot = k; zo_pair = pk; }   // (strict: the lowest knot of equal minima)
@@ -467,20 +416,11 @@ __global__ void __launch_bounds__(64) lincov_kernel(const KParams P, const std::
         note_obstacles(N, zk, pk);
         emit(N, zk, false);
     }
-    for (int k = zero_from; k <= N; k++) {
-        if (lane < n) sx[(size_t)(k - 1) * n + lane] = 0.0;
-        if (k <= N - 1 && lane < m) su[(size_t)(k - 1) * m + lane] = 0.0;
-        if (lane == 0) zo[k - 1] = 0.0;
-        if (Sall)
-#pragma unroll
-            for (int r = 0; r < RPF; r++) { const int e = lane + 64 * r; if (e < NPF) Sall[(size_t)(k - 1) * NPF + e] = 0.0; }
-        if constexpr (PLANT)
-            if (Tall)
-#pragma unroll
-                for (int r = 0; r < RC; r++) { const int e = lane + 64 * r; if (e < NC) Tall[(size_t)(k - 1) * NC + e] = 0.0; }
-        if constexpr (DENSE)
-#pragma unroll
-            for (int r = 0; r < RGZ; r++) { const int e = lane + 64 * r; if (e < NGZ) Rall[(size_t)(k - 1) * NGZ + e] = 0.0; }
+    for (int k = zero_from; k <= N; k++) {   // zeros from a failed knot on
+        const bool with_u = k <= N - 1;
+        const double zk = 0.0;
+#define KNOT_ROWS_LIVE false
+#include "lincov_knot_rows.inc"
     }
     if (lane == 0) {
         V.status[b] = (dead || fail) ? 0 : 1;
@@ -516,8 +456,8 @@ struct DnArgs {
 };
 
 // grid (problem, tile of 4 intervals), 256 lanes: one wave per interval.  Lane j < NZ carries the nominal state and column j of
-// G_{k,i} = [Phi - Gamma K | Gamma | C] through the RK4 stages (tvlqr_linearise's statements; the theta columns take dfdth as their
-// source, as lincov_plant_sens): the closed loop sits in the seed -- x-columns start at e_j with the control direction -K e_j, b-
+// G_{k,i} = [Phi - Gamma K | Gamma | C] through the RK4 stages (rk4_tangent.inc, as tvlqr_linearise; the theta columns take dfdth as
+// their source, as lincov_plant_sens): the closed loop sits in the seed -- x-columns start at e_j with the control direction -K e_j, b-
 // columns at 0 with e_c, theta-columns at 0 -- and B du is formed once.  After every substep the first WS entries of the columns
 // go to LDS, the wave forms T = Gp S_k and the upper triangle of Spos = T Gp' + Gammap diag(sw2) Gammap' in a fixed order (S_k:
 // the interval's x-rows of the knot pass, completed by symmetry and the constant block, in LDS throughout), and all 64 lanes
@@ -535,7 +475,7 @@ template <int MODEL> __global__ void __launch_bounds__(256) lincov_dense(const K
     const int b = blockIdx.x, wv = threadIdx.x >> 6, lane = threadIdx.x & 63, N = P.N;
     if (V.active && !V.active[b]) return;   // (the whole workgroup)
     const double dt = P.tf[b] / (N - 1);
-    const int nstep = V.nstep > 0 ? V.nstep : (int)ceil(dt / V.dt_min);   // (gusto_tvlqr has checked 1 <= nstep <= nstep_cap)
+    const int nstep = rollout_nstep(dt, V.nstep, V.dt_min);
     const double h = dt / nstep;
     const bool valid = (int)blockIdx.y * IPB + wv < N - 1;
     const int k = valid ? blockIdx.y * IPB + wv : 0;          // interval k (0-based): knot k + 1
@@ -649,34 +589,8 @@ template <int MODEL> __global__ void __launch_bounds__(256) lincov_dense(const K
         }
         __syncthreads();   // (the readers of sX, sGp and sSp are done)
         if (i >= nstep - 1) continue;   // no substep behind the interval's last sample: the next interval restarts at its knot
-        double A[n * n], g[n], w[n], dw[n], k1[n], kk[n], kd1[n], kdk[n], xs[n], ds[n];
-        D::f(P.mp, x, u, k1);
-        D::A(P.mp, x, u, A);
-        source(x, g);
-        plant_tangent<MODEL>(A, d, g, kd1);
-#pragma unroll
-        for (int q = 0; q < n; q++) { xs[q] = k1[q]; ds[q] = kd1[q]; w[q] = x[q] + 0.5 * h * k1[q]; dw[q] = d[q] + 0.5 * h * kd1[q]; }
-        D::f(P.mp, w, u, kk);
-        D::A(P.mp, w, u, A);
-        source(w, g);
-        plant_tangent<MODEL>(A, dw, g, kdk);
-#pragma unroll
-        for (int q = 0; q < n; q++) { xs[q] += 2 * kk[q]; ds[q] += 2 * kdk[q]; w[q] = x[q] + 0.5 * h * kk[q]; dw[q] = d[q] + 0.5 * h * kdk[q]; }
-        D::f(P.mp, w, u, kk);
-        D::A(P.mp, w, u, A);
-        source(w, g);
-        plant_tangent<MODEL>(A, dw, g, kdk);
-#pragma unroll
-        for (int q = 0; q < n; q++) { xs[q] += 2 * kk[q]; ds[q] += 2 * kdk[q]; w[q] = x[q] + h * kk[q]; dw[q] = d[q] + h * kdk[q]; }
-        D::f(P.mp, w, u, kk);
-        D::A(P.mp, w, u, A);
-        source(w, g);
-        plant_tangent<MODEL>(A, dw, g, kdk);
-#pragma unroll
-        for (int q = 0; q < n; q++) {
-            x[q] = x[q] + 1.0 / 6.0 * h * (xs[q] + kk[q]);
-            d[q] = d[q] + 1.0 / 6.0 * h * (ds[q] + kdk[q]);
-        }
+#define RK4_TANGENT_SOURCE(xp, g) (source(xp, g), g)
+#include "rk4_tangent.inc"
     }
     if (valid && lane == 0) {
         V.zint[(size_t)b * (N - 1) + k] = zi;
@@ -692,7 +606,7 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_dense_reduce(c
     const int b = blockIdx.x, lane = threadIdx.x, N = P.N;
     if (V.active && !V.active[b]) return;
     const double dt = P.tf[b] / (N - 1);
-    const int nstep = V.nstep > 0 ? V.nstep : (int)ceil(dt / V.dt_min);
+    const int nstep = rollout_nstep(dt, V.nstep, V.dt_min);
     const int nfull = nstep * (N - 1) + 1;
     const bool dead = V.tv_status && !V.tv_status[b];
     if (lane == 0) {
@@ -713,35 +627,33 @@ template <int MODEL> __global__ void __launch_bounds__(64) lincov_dense_reduce(c
     }
 }
 
-// W: null for gusto_lincov, else V with the dispersion (V is its base) and A, the sensitivity launch ahead of the recursion;
-// Dn: null, or (gusto_lincov_dense; V is an LcArgsD) the dense pass and its reduction behind the DENSE recursion
+// The launches of one call, in their order on the handle's stream.  W: null for gusto_lincov, else V with the dispersion (V is
+// its base) and A for the sensitivity launch; Dn: null, or (gusto_lincov_dense: W is set and V is an LcArgsD) the dense pass
 template <int MODEL> int launch_lincov(gusto_handle h, const KParams& P, const LcArgs& V, const LcArgsP* W, const SensArgs& A,
                                        const DnArgs* Dn = nullptr) {
-    if (Dn) {
+    if (W) {   // the sensitivities Cd of the dispersion
         const int tiles = (h->N - 1 + PlantCols<MODEL>::IPB - 1) / PlantCols<MODEL>::IPB;
         hipLaunchKernelGGL((lincov_plant_sens<MODEL>), dim3(h->B, tiles), dim3(256), 0, h->stream, P, A);
         HIPCHK(h, hipGetLastError());
-        hipLaunchKernelGGL((lincov_kernel<MODEL, true, true>), dim3(h->B), dim3(64), 0, h->stream, P, static_cast<const LcArgsD&>(V));
-        HIPCHK(h, hipGetLastError());
+    }
+    // the knot pass
+    if (Dn) hipLaunchKernelGGL((lincov_kernel<MODEL, true, true>), dim3(h->B), dim3(64), 0, h->stream, P, static_cast<const LcArgsD&>(V));
+    else if (W) hipLaunchKernelGGL((lincov_kernel<MODEL, true>), dim3(h->B), dim3(64), 0, h->stream, P, *W);
+    else hipLaunchKernelGGL((lincov_kernel<MODEL, false>), dim3(h->B), dim3(64), 0, h->stream, P, V);
+    HIPCHK(h, hipGetLastError());
+    if (Dn) {   // the dense pass and its reduction
         hipLaunchKernelGGL((lincov_dense<MODEL>), dim3(h->B, (h->N - 1 + 3) / 4), dim3(256), 0, h->stream, P, *Dn);
         HIPCHK(h, hipGetLastError());
         hipLaunchKernelGGL((lincov_dense_reduce<MODEL>), dim3(h->B), dim3(64), 0, h->stream, P, *Dn);
-    } else if (W) {
-        const int tiles = (h->N - 1 + PlantCols<MODEL>::IPB - 1) / PlantCols<MODEL>::IPB;
-        hipLaunchKernelGGL((lincov_plant_sens<MODEL>), dim3(h->B, tiles), dim3(256), 0, h->stream, P, A);
         HIPCHK(h, hipGetLastError());
-        hipLaunchKernelGGL((lincov_kernel<MODEL, true>), dim3(h->B), dim3(64), 0, h->stream, P, *W);
-    } else {
-        hipLaunchKernelGGL((lincov_kernel<MODEL, false>), dim3(h->B), dim3(64), 0, h->stream, P, V);
     }
-    HIPCHK(h, hipGetLastError());
     return GUSTO_OK;
 }
 
 // gusto_lincov (dist = null) and gusto_lincov_disturbed (dist: the options, never null; Sth: the caller's or null);
-// gusto_lincov_dense: dense = its store_dense (0 / 1), else -1
+// gusto_lincov_dense: store_dense = the caller's, not yet checked; else null
 int lincov_host(gusto_handle h, const char* who_c, const double* X, const double* U, const double* K, const double* S0,
-                const gusto_lincov_opts* opts, const gusto_disturb_opts* dist, const double* Sth, int dense = -1);
+                const gusto_lincov_opts* opts, const gusto_disturb_opts* dist, const double* Sth, const int* store_dense = nullptr);
 
 }  // namespace
 
@@ -771,9 +683,7 @@ int gusto_lincov_dense(gusto_handle h, const double* X, const double* U, const d
                        const gusto_lincov_opts* opts, const gusto_disturb_opts* d, int store_dense) {
     gusto_disturb_opts zero;
     gusto_default_disturb_opts(&zero);
-    if (int rc = post_enter(h, "gusto_lincov_dense", X, U)) return rc;   // (the handle first: the refusals of every stage)
-    if (int rc = lincov_dense_args_host(store_dense, &h->err)) return rc;
-    return lincov_host(h, "gusto_lincov_dense", X, U, K, S0, opts, d ? d : &zero, Sth, store_dense);
+    return lincov_host(h, "gusto_lincov_dense", X, U, K, S0, opts, d ? d : &zero, Sth, &store_dense);
 }
 
 }  // extern "C"
@@ -781,8 +691,11 @@ int gusto_lincov_dense(gusto_handle h, const double* X, const double* U, const d
 namespace {
 
 int lincov_host(gusto_handle h, const char* who_c, const double* X, const double* U, const double* K, const double* S0,
-                const gusto_lincov_opts* opts, const gusto_disturb_opts* dist, const double* Sth, int dense) {
-    if (int rc = post_enter(h, who_c, X, U)) return rc;
+                const gusto_lincov_opts* opts, const gusto_disturb_opts* dist, const double* Sth, const int* store_dense) {
+    if (int rc = post_enter(h, who_c, X, U)) return rc;   // (the handle first: the refusals of every stage)
+    if (store_dense)
+        if (int rc = lincov_dense_args_host(*store_dense, &h->err)) return rc;
+    const int dense = store_dense ? *store_dense : -1;    // 0 / 1: gusto_lincov_dense; -1: the knot pass alone
     const std::string who(who_c);
     gusto_lincov_opts o;
     gusto_default_lincov_opts(h->model, &o);

@@ -1,7 +1,7 @@
 // post.hpp -- the host path of the post-solve stages (shoot.hip, verify.hip, tvlqr.hip, simulate.hip, lincov.hip; nothing else includes it).  Plain
 // functions that answer a GUSTO_* code and leave the text in h->err: `if (int rc = ...) return rc;` at the call site.  A new
-// stage starts from these and from a struct of its own next to ShootState / VerifyState / TvlqrState / SimulateState / LincovState
-// (handle.hpp).
+// stage starts from these, from a struct of its own next to ShootState / VerifyState / TvlqrState / SimulateState / LincovState
+// (handle.hpp) and, on the device, from rollout.hpp: the roll-out every stage but shoot.hip shares.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -92,6 +92,12 @@ static inline int lincov_args_host(int n, int m, size_t B, const gusto_lincov_op
 constexpr bool plant_entry_read(int model, int j) {
     return model == GUSTO_DUBINS_CAR ? j >= 4 : (model == GUSTO_FREEFLYER_SE2 ? (j == 0 || j == 3) : j < 4);
 }
+
+// their nominal values, from the handle's model parameters (device code: simulate.hip, lincov.hip)
+struct PlantNominal {
+    double v[GUSTO_NPLANT];
+    GD explicit PlantNominal(const gusto_model_params& mp) : v{mp.mass, mp.Jdiag[0], mp.Jdiag[1], mp.Jdiag[2], mp.dubins_v, mp.dubins_k} {}
+};
 
 // The arguments of gusto_lincov_disturbed that gusto_lincov does not have: the dispersion d and the caller's Sth
 // [B][GUSTO_NPLANT][GUSTO_NPLANT] (null: the default), of which only the entries the model reads are looked at.  GUSTO_ERR_ARG

@@ -22,8 +22,8 @@
 // the same gfx950 instructions; what it needs extra is ONE unused local (a second one already moves its schedule).
 #include <hip/hip_runtime.h>
 
-#include "models.hpp"
 #include "post.hpp"
+#include "rollout.hpp"
 #include "simrng.hpp"
 
 using namespace gusto;
@@ -64,18 +64,6 @@ template <int M> struct DistLane {
     gusto_model_params plant;
     double wk[M];
 };
-
-// smallest signed distance of the robot at state x over components and obstacles
-template <int MODEL> GD double robot_distance(const KParams& P, const Env& E, const double* x) {
-    using T = MT<MODEL>;
-    double dmin = INFINITY;
-    for (int c = 0; c < P.mp.n_robot_comp; c++)
-        for (int i = 0; i < E.n_obs; i++) {
-            double nh[T::WS];
-            dmin = fmin(dmin, signed_distance<T::WS>(P, E, c, x, i, nh));
-        }
-    return dmin;
-}
 
 // The report of problem b from its per-sample arrays; every thread of the workgroup calls.  Thread t walks the samples
 // t, t + blockDim, ... in ascending order, the partial results meet in block_reduce: minima, maxima and exact counts, so the
@@ -133,7 +121,7 @@ __global__ void __launch_bounds__(TILE) simulate_kernel(const KParams P, const s
     const int s = s0 + t;
     const bool valid = s < S;
     const double dt = P.tf[b] / (N - 1);
-    const int nstep = V.nstep > 0 ? V.nstep : (int)ceil(dt / V.dt_min);   // (the host has checked 1 <= nstep <= nstep_cap)
+    const int nstep = rollout_nstep(dt, V.nstep, V.dt_min);
     const double h = dt / nstep;
     const double* X = V.X + (size_t)b * N * n;
     const double* U = V.U + (size_t)b * N * m;
@@ -162,12 +150,12 @@ __global__ void __launch_bounds__(TILE) simulate_kernel(const KParams P, const s
     // DIST: the plant of this lane.  All GUSTO_NPLANT scalars are formed and written out; those f reads stay in registers
     [[maybe_unused]] std::conditional_t<DIST, DistLane<m>, char> L;
     if constexpr (DIST) {
-        const double nominal[GUSTO_NPLANT] = {P.mp.mass, P.mp.Jdiag[0], P.mp.Jdiag[1], P.mp.Jdiag[2], P.mp.dubins_v, P.mp.dubins_k};
+        const PlantNominal nominal(P.mp);
         double th[GUSTO_NPLANT];
 #pragma unroll
         for (int j = 0; j < GUSTO_NPLANT; j++) {
-            if (V.plant_in) th[j] = valid ? V.plant_in[((size_t)b * S + s) * GUSTO_NPLANT + j] : nominal[j];
-            else th[j] = simrng_plant(V.seed_plant, V.first_problem + b, S, valid ? s : 0, GUSTO_NPLANT, j, nominal[j], V.plant_rel[j]);
+            if (V.plant_in) th[j] = valid ? V.plant_in[((size_t)b * S + s) * GUSTO_NPLANT + j] : nominal.v[j];
+            else th[j] = simrng_plant(V.seed_plant, V.first_problem + b, S, valid ? s : 0, GUSTO_NPLANT, j, nominal.v[j], V.plant_rel[j]);
             if (valid) V.plant[((size_t)b * S + s) * GUSTO_NPLANT + j] = th[j];
         }
         L.plant = P.mp;
@@ -225,30 +213,19 @@ __global__ void __launch_bounds__(TILE) simulate_kernel(const KParams P, const s
             if (alive) {
                 if constexpr (T::HAS_OBS) {
                     if (V.dense_collision || q == 0) {
-                        const double dq = robot_distance<MODEL>(P, E, x);
+                        const double dq = robot_min_distance<MODEL>(P, E, x);
                         if (dq < dmin) { dmin = dq; dj = k * nstep + q; }
                     }
                 }
-                double k1[n], kk[n], w[n], xs[n];
-                if constexpr (DIST) D::f(L.plant, x, u, k1);
-                else D::f(P.mp, x, u, k1);
-#pragma unroll
-                for (int i = 0; i < n; i++) { xs[i] = k1[i]; w[i] = x[i] + 0.5 * h * k1[i]; }
-                if constexpr (DIST) D::f(L.plant, w, u, kk);
-                else D::f(P.mp, w, u, kk);
-#pragma unroll
-                for (int i = 0; i < n; i++) { xs[i] += 2 * kk[i]; w[i] = x[i] + 0.5 * h * kk[i]; }
-                if constexpr (DIST) D::f(L.plant, w, u, kk);
-                else D::f(P.mp, w, u, kk);
-#pragma unroll
-                for (int i = 0; i < n; i++) { xs[i] += 2 * kk[i]; w[i] = x[i] + h * kk[i]; }
-                if constexpr (DIST) D::f(L.plant, w, u, kk);
-                else D::f(P.mp, w, u, kk);
                 fin = true;
-#pragma unroll
-                for (int i = 0; i < n; i++) {
-                    x[i] = x[i] + 1.0 / 6.0 * h * (xs[i] + kk[i]);
-                    fin = fin && fabs(x[i]) < INFINITY;
+                if constexpr (DIST) {
+#define RK4_STEP_MP L.plant
+#define RK4_STEP_NEW(i) fin = fin && fabs(x[i]) < INFINITY
+#include "rk4_step.inc"
+                } else {
+#define RK4_STEP_MP P.mp
+#define RK4_STEP_NEW(i) fin = fin && fabs(x[i]) < INFINITY
+#include "rk4_step.inc"
                 }
                 alive = fin;
             }
@@ -262,7 +239,7 @@ __global__ void __launch_bounds__(TILE) simulate_kernel(const KParams P, const s
 #pragma unroll
         for (int i = 0; i < n; i++) dev[i] = fmax(dev[i], fabs(x[i] - sX[i]));
         if constexpr (T::HAS_OBS) {
-            const double dq = robot_distance<MODEL>(P, E, x);
+            const double dq = robot_min_distance<MODEL>(P, E, x);
             if (dq < dmin) { dmin = dq; dj = (N - 1) * nstep; }
         }
     }

@@ -3,7 +3,8 @@
 // Two launches on the handle's stream:
 //   tvlqr_linearise  grid (problem, tile of IPB intervals), 256 lanes.  Work item (k, j) = lane: interval k, column j of
 //     [dF_k/dx | dF_k/du].  A lane carries the nominal state (every lane of an interval recomputes the cheap nominal roll-out)
-//     and ONE tangent column, 2 n doubles, through the four RK4 stages of every substep: kd = A(stage point) d + B e_j, with
+//     and ONE tangent column, 2 n doubles, through the four RK4 stages of every substep (rk4_tangent.inc, the text lincov.hip's
+//     linearising kernels include too): kd = A(stage point) d + B e_j, with
 //     Dyn<MODEL>::A written into a local array that full unrolling dissolves -- only its structural nonzeros (MT<MODEL>::Anz) are
 //     multiplied, nothing indexes it at run time.  A lane owns column j of the n rows of its interval, n + m doubles apart: the tile is staged in LDS
 //     ([interval][row][column], the layout of AB) and copied out by the whole workgroup, consecutive lanes to consecutive
@@ -20,8 +21,8 @@
 // No atomics, nothing crosses a problem: a problem's output is the same bit for bit whatever batch it sits in.
 #include <hip/hip_runtime.h>
 
-#include "models.hpp"
 #include "post.hpp"
+#include "rollout.hpp"
 
 using namespace gusto;
 
@@ -37,20 +38,6 @@ struct TvArgs {
     int *status, *fail_knot;
 };
 
-// kd = A d + bu over the structural nonzeros of A (MT<MODEL>::Anz: the loops are unrolled, so the pattern is a compile-time
-// choice per product -- a product with a constant 0.0 is not something the compiler may drop on its own in IEEE arithmetic)
-template <int MODEL> GD void tangent(const double* A, const double* d, const double* bu, double* kd) {
-    constexpr int n = MT<MODEL>::n;
-#pragma unroll
-    for (int i = 0; i < n; i++) {
-        double s = bu[i];
-#pragma unroll
-        for (int j = 0; j < n; j++)
-            if (MT<MODEL>::Anz(i, j)) s += A[i * n + j] * d[j];
-        kd[i] = s;
-    }
-}
-
 template <int MODEL> struct LinTile {
     static constexpr int n = MT<MODEL>::n, m = MT<MODEL>::m, nz = n + m;
     static constexpr int IPB = 256 / nz;   // whole intervals per workgroup: its slice of AB is one contiguous range
@@ -64,7 +51,7 @@ template <int MODEL> __global__ void __launch_bounds__(256) tvlqr_linearise(cons
     const int b = blockIdx.x, k0 = blockIdx.y * IPB, t = threadIdx.x, N = P.N;
     if (V.active && !V.active[b]) return;   // (the whole workgroup)
     const double dt = P.tf[b] / (N - 1);
-    const int nstep = V.nstep > 0 ? V.nstep : (int)ceil(dt / V.dt_min);   // (the host has checked 1 <= nstep <= nstep_cap)
+    const int nstep = rollout_nstep(dt, V.nstep, V.dt_min);
     const double h = dt / nstep;
     const int kl = t / nz, j = t % nz;
     const bool valid = kl < IPB && k0 + kl < N - 1;
@@ -89,30 +76,8 @@ template <int MODEL> __global__ void __launch_bounds__(256) tvlqr_linearise(cons
         }
     }
     for (int s = 0; s < nstep; s++) {
-        double A[n * n], w[n], dw[n], k1[n], kk[n], kd1[n], kdk[n], xs[n], ds[n];
-        D::f(P.mp, x, u, k1);
-        D::A(P.mp, x, u, A);
-        tangent<MODEL>(A, d, bu, kd1);
-#pragma unroll
-        for (int i = 0; i < n; i++) { xs[i] = k1[i]; ds[i] = kd1[i]; w[i] = x[i] + 0.5 * h * k1[i]; dw[i] = d[i] + 0.5 * h * kd1[i]; }
-        D::f(P.mp, w, u, kk);
-        D::A(P.mp, w, u, A);
-        tangent<MODEL>(A, dw, bu, kdk);
-#pragma unroll
-        for (int i = 0; i < n; i++) { xs[i] += 2 * kk[i]; ds[i] += 2 * kdk[i]; w[i] = x[i] + 0.5 * h * kk[i]; dw[i] = d[i] + 0.5 * h * kdk[i]; }
-        D::f(P.mp, w, u, kk);
-        D::A(P.mp, w, u, A);
-        tangent<MODEL>(A, dw, bu, kdk);
-#pragma unroll
-        for (int i = 0; i < n; i++) { xs[i] += 2 * kk[i]; ds[i] += 2 * kdk[i]; w[i] = x[i] + h * kk[i]; dw[i] = d[i] + h * kdk[i]; }
-        D::f(P.mp, w, u, kk);
-        D::A(P.mp, w, u, A);
-        tangent<MODEL>(A, dw, bu, kdk);
-#pragma unroll
-        for (int i = 0; i < n; i++) {
-            x[i] = x[i] + 1.0 / 6.0 * h * (xs[i] + kk[i]);
-            d[i] = d[i] + 1.0 / 6.0 * h * (ds[i] + kdk[i]);
-        }
+#define RK4_TANGENT_SOURCE(xp, g) bu   // B e_j, the same at every stage point
+#include "rk4_tangent.inc"
     }
     if (valid)
 #pragma unroll

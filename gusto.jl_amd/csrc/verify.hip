@@ -24,15 +24,15 @@
 // lane's DENSE_TILE n doubles; the held controls are copied straight from U (thread e writes double e of the problem).
 #include <hip/hip_runtime.h>
 
-#include "models.hpp"
 #include "post.hpp"
+#include "rollout.hpp"
 
 using namespace gusto;
 
 namespace {
 
 constexpr int DENSE_TILE = 4;      // substeps staged in LDS per copy-out: 4 n doubles per lane (26.6 KB for N <= 64, n = 13)
-constexpr int NO_HIT = 1 << 30;    // (keys stay below 2 * 64 * 256)
+// (NO_HIT, rollout.hpp: the keys below stay under 2 * 64 * 256)
 
 struct VerifyArgs {
     const double *X, *U;           // [B][N][n], [B][N][m]: the handle's trajectories or the caller's copies
@@ -45,21 +45,6 @@ struct VerifyArgs {
     double *Xfull, *Ufull;         // [B][nfull_max][n], [B][nfull_max - 1][m]
 };
 
-// smallest signed distance of the robot at state x over components and obstacles; with `hit`: the first penetrating pair in
-// loop order (its ordinal and distance)
-template <int MODEL> GD double min_distance(const KParams& P, const Env& E, const double* x, int* hit, double* hit_d) {
-    using T = MT<MODEL>;
-    double dmin = INFINITY;
-    for (int c = 0; c < P.mp.n_robot_comp; c++)
-        for (int i = 0; i < E.n_obs; i++) {
-            double nh[T::WS];
-            const double d = signed_distance<T::WS>(P, E, c, x, i, nh);
-            dmin = fmin(dmin, d);
-            if (hit && d < 0 && *hit == NO_HIT) { *hit = c * E.n_obs + i; *hit_d = d; }
-        }
-    return dmin;
-}
-
 template <int MODEL, bool DENSE> __global__ void __launch_bounds__(256) verify_kernel(const KParams P, const VerifyArgs V) {
     using T = MT<MODEL>;
     constexpr int n = T::n, m = T::m;
@@ -68,7 +53,7 @@ template <int MODEL, bool DENSE> __global__ void __launch_bounds__(256) verify_k
     const int b = blockIdx.x, k = threadIdx.x, N = P.N, nt = blockDim.x;
     if (V.active && !V.active[b]) return;   // (the whole workgroup: an inactive problem's report is left as it is)
     const double dt = P.tf[b] / (N - 1);
-    const int nstep = V.nstep > 0 ? V.nstep : (int)ceil(dt / V.dt_min);   // (the host has checked 1 <= nstep <= nstep_cap)
+    const int nstep = rollout_nstep(dt, V.nstep, V.dt_min);
     const int nfull = nstep * (N - 1) + 1;
     if (DENSE && nfull > V.nfull_max) return;
     const double h = dt / nstep;
@@ -87,7 +72,7 @@ template <int MODEL, bool DENSE> __global__ void __launch_bounds__(256) verify_k
     int hit = NO_HIT;
     if constexpr (T::HAS_OBS) {
         if (knot) {
-            dk = min_distance<MODEL>(P, E, x, &hit, &hit_d);
+            dk = robot_min_distance<MODEL, true>(P, E, x, &hit, &hit_d);
             if (hit != NO_HIT) hit = hit * N + k;
         }
     }
@@ -109,7 +94,7 @@ template <int MODEL, bool DENSE> __global__ void __launch_bounds__(256) verify_k
             const bool samp = ival || (k == N - 1 && s == 0);   // (the last dense sample is the last knot)
             if constexpr (T::HAS_OBS) {
                 if (samp && V.dense_collision) {
-                    const double d = min_distance<MODEL>(P, E, x, nullptr, nullptr);
+                    const double d = robot_min_distance<MODEL, true>(P, E, x, nullptr, nullptr);   // (rollout.hpp: why HIT)
                     if (d < dd) { dd = d; di = k * nstep + s; }
                 }
             }
@@ -118,21 +103,7 @@ template <int MODEL, bool DENSE> __global__ void __launch_bounds__(256) verify_k
 #pragma unroll
                     for (int i = 0; i < n; i++) stage[(k * DENSE_TILE + (s - s0)) * n + i] = x[i];
             }
-            if (ival) {
-                double k1[n], k2[n], k3[n], k4[n], w[n];
-                Dyn<MODEL>::f(P.mp, x, u, k1);
-#pragma unroll
-                for (int i = 0; i < n; i++) w[i] = x[i] + 0.5 * h * k1[i];
-                Dyn<MODEL>::f(P.mp, w, u, k2);
-#pragma unroll
-                for (int i = 0; i < n; i++) w[i] = x[i] + 0.5 * h * k2[i];
-                Dyn<MODEL>::f(P.mp, w, u, k3);
-#pragma unroll
-                for (int i = 0; i < n; i++) w[i] = x[i] + h * k3[i];
-                Dyn<MODEL>::f(P.mp, w, u, k4);
-#pragma unroll
-                for (int i = 0; i < n; i++) x[i] = x[i] + 1.0 / 6.0 * h * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
-            }
+            if (ival) rk4_step<MODEL>(P.mp, x, u, h);
         }
         if constexpr (DENSE) {
             __syncthreads();
