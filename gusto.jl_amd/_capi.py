@@ -34,6 +34,7 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_default_disturb_opts", "gusto_simulate_disturbed", "gusto_get_simulate_plant",
            "gusto_default_lincov_opts", "gusto_lincov", "gusto_get_lincov", "gusto_last_lincov_ms",
            "gusto_lincov_disturbed", "gusto_get_lincov_plant", "gusto_lincov_dense", "gusto_get_lincov_dense",
+           "gusto_set_problems_multistart", "gusto_select_best", "gusto_get_best", "gusto_get_best_dev",
            "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr"]
 
 
@@ -138,6 +139,18 @@ class LincovDenseReport(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in LINCOV_DENSE_FIELDS]
 
 
+MAX_STARTS = 64   # GUSTO_MAX_STARTS
+# gusto_best_report in the header's order: (field, dtype, shape as a function of (Bq, N, n, m))
+BEST_FIELDS = (("winner", np.int32, lambda Q, N, n, m: (Q,)), ("winner_problem", np.int32, lambda Q, N, n, m: (Q,)),
+               ("n_eligible", np.int32, lambda Q, N, n, m: (Q,)), ("best_score", np.float64, lambda Q, N, n, m: (Q,)),
+               ("X", np.float64, lambda Q, N, n, m: (Q, N, n)), ("U", np.float64, lambda Q, N, n, m: (Q, N, m)))
+
+
+class BestReport(C.Structure):
+    """gusto_best_report: caller-owned arrays"""
+    _fields_ = [(k, C.c_void_p) for k, _, _ in BEST_FIELDS]
+
+
 VERIFY_FIELDS = (("collision_free", np.int32), ("first_knot", np.int32), ("first_dist", np.float64),
                  ("min_dist_knots", np.float64), ("dyn_defect_l1", np.float64), ("min_dist_dense", np.float64),
                  ("min_dense_sample", np.int32), ("max_gap", np.float64))
@@ -179,7 +192,7 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(_ROOT, "include"), "-fPIC",
              "-Wno-unused-value", "-Wno-pass-failed"]
-    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
+    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
     bdir = os.path.join(_HERE, "build")
     os.makedirs(bdir, exist_ok=True)
 
@@ -274,6 +287,10 @@ def lib():
         L.gusto_get_lincov_plant.argtypes = [vp, vp, vp]
         L.gusto_lincov_dense.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(LincovOpts), C.POINTER(DisturbOpts), ci]
         L.gusto_get_lincov_dense.argtypes = [vp, C.POINTER(LincovDenseReport), C.POINTER(ci)]
+        L.gusto_set_problems_multistart.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp]
+        L.gusto_select_best.argtypes = [vp, ci, vp, vp]
+        L.gusto_get_best.argtypes = [vp, C.POINTER(BestReport)]
+        L.gusto_get_best_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.gusto_default_trajopt_params.argtypes = [ci, C.POINTER(TrajOptParams)]
         L.gusto_create_trajopt.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci]
         L.gusto_set_trajopt_params.argtypes = [vp, C.POINTER(TrajOptParams)]
@@ -346,15 +363,16 @@ def _arr(a, dtype=np.float64):
 
 
 class _View:
-    """__cuda_array_interface__ v2 of a float64 device array: lets torch wrap a raw device pointer without a copy"""
+    """__cuda_array_interface__ v2 of a device array (float64 unless typestr says otherwise): lets torch wrap a raw device
+    pointer without a copy"""
 
-    def __init__(self, ptr, shape):
-        self.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(int(ptr), False), version=2)
+    def __init__(self, ptr, shape, typestr="<f8"):
+        self.__cuda_array_interface__ = dict(shape=shape, typestr=typestr, data=(int(ptr), False), version=2)
 
 
-def _dev_view(ptr, shape, device):
+def _dev_view(ptr, shape, device, typestr="<f8"):
     import torch
-    return torch.as_tensor(_View(ptr, shape), device=torch.device("cuda", device))
+    return torch.as_tensor(_View(ptr, shape, typestr), device=torch.device("cuda", device))
 
 
 class GustoError(RuntimeError):
@@ -442,6 +460,48 @@ class BatchSolver:
                                             tf.ctypes.data, None if X0 is None else self._keep[4].ctypes.data,
                                             None if U0 is None else self._keep[5].ctypes.data), "set_problems")
         self.B = B
+
+    def set_problems_multistart(self, x_init, goal_lo, goal_hi, tf, fan, boxes=None, spheres=None):
+        """gusto_set_problems_multistart: Bq queries x K = len(fan) starts become the B = Bq K problems of the handle, problem
+        q K + j = start j of query q; fan [K, 2] the lateral offsets (a2, a3) in metres, (0, 0) the straight line.  boxes / spheres:
+        one keep-out set PER QUERY (lists of Bq tables), repeated K times into set_env_batch; None leaves the environment as it is."""
+        x_init, goal_lo, goal_hi = _arr(x_init).reshape(-1, self.n), _arr(goal_lo).reshape(-1, self.n), \
+            _arr(goal_hi).reshape(-1, self.n)
+        Bq = x_init.shape[0]
+        tf = _arr(np.broadcast_to(np.asarray(tf, dtype=np.float64), (Bq,)))
+        fan = _arr(fan).reshape(-1, 2)
+        K = fan.shape[0]
+        self._chk(self.L.gusto_set_problems_multistart(self.h, Bq, K, x_init.ctypes.data, goal_lo.ctypes.data, goal_hi.ctypes.data,
+                                                       tf.ctypes.data, fan.ctypes.data), "set_problems_multistart")
+        self.B = Bq * K
+        if boxes is not None or spheres is not None:
+            rep = lambda tables: None if tables is None else [t for t in tables for _ in range(K)]
+            self.set_env_batch(rep(boxes) if boxes is not None else [None] * self.B, rep(spheres))
+
+    def select_best(self, K, score=None, eligible=None):
+        """gusto_select_best + gusto_get_best: per group of K consecutive problems the eligible one with the smallest score (ties:
+        the lowest; NaN never wins).  score [B] (None: the last true cost), eligible [B] (None: converged and successful).  A dict of
+        winner, winner_problem, n_eligible [Bq] (-1: no winner), best_score [Bq] (+inf likewise), X [Bq, N, n], U [Bq, N, m]."""
+        sc = None if score is None else _arr(score).reshape(self.B)
+        el = None if eligible is None else _arr(np.asarray(eligible).astype(bool), np.int32).reshape(self.B)
+        self._chk(self.L.gusto_select_best(self.h, int(K), None if sc is None else sc.ctypes.data,
+                                           None if el is None else el.ctypes.data), "select_best")
+        return self.get_best(self.B // int(K))
+
+    def get_best(self, Bq):
+        """gusto_get_best: the report of the last select_best, which had Bq groups"""
+        out = {k: np.zeros(shape(Bq, self.N, self.n, self.m), dtype=t) for k, t, shape in BEST_FIELDS}
+        rep = BestReport(**{k: v.ctypes.data for k, v in out.items()})
+        self._chk(self.L.gusto_get_best(self.h, C.byref(rep)), "get_best")
+        return out
+
+    def best_dev(self, Bq):
+        """gusto_get_best_dev as zero-copy torch views of the compact buffers of the last select_best: X [Bq, N, n], U [Bq, N, m]
+        and winner_problem [Bq] (int32); valid until the next select_best"""
+        px, pu, pw = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._chk(self.L.gusto_get_best_dev(self.h, C.byref(px), C.byref(pu), C.byref(pw)), "get_best_dev")
+        return (_dev_view(px.value, (Bq, self.N, self.n), self.device), _dev_view(pu.value, (Bq, self.N, self.m), self.device),
+                _dev_view(pw.value, (Bq,), self.device, "<i4"))
 
     def set_trust_state(self, Delta=None, omega=None):
         """gusto_set_trust_state: the caller's own Delta_vec[end] / omega_vec[end] for the next trip of every problem."""
@@ -951,3 +1011,9 @@ class TrajOptSolver(BatchSolver):
 
     def lincov_dense(self, *a, **k):
         raise GustoError("TrajOptSolver: lincov_dense is not supported on TrajOpt handles (gusto_lincov_dense answers GUSTO_ERR_ARG)")
+
+    def set_problems_multistart(self, *a, **k):
+        raise GustoError("TrajOptSolver: multi-start problems are not supported on TrajOpt handles (gusto_set_problems_multistart answers GUSTO_ERR_ARG)")
+
+    def select_best(self, *a, **k):
+        raise GustoError("TrajOptSolver: select_best is not supported on TrajOpt handles (gusto_select_best answers GUSTO_ERR_ARG)")

@@ -285,6 +285,16 @@ template <class T> static int copy_hist(gusto_handle h, T* dst, const T* src, si
     return GUSTO_OK;
 }
 
+int gusto_problems_loaded(gusto_handle h, bool straight) {
+    int rc = do_init(h, straight);
+    if (rc) return rc;
+    h->have_problems = true;
+    h->shoot.invalidate(); h->verify.invalidate(); h->tvlqr.invalidate(); h->simulate.invalidate(); h->lincov.invalidate();
+    h->select.invalidate();
+    h->n_active = -1;   // (gusto_set_active belongs to the problems it was set for)
+    return GUSTO_OK;
+}
+
 extern "C" {
 
 static int set_problems_impl(gusto_handle h, int B, const double* x_init, const double* glo, const double* ghi,
@@ -306,12 +316,7 @@ static int set_problems_impl(gusto_handle h, int B, const double* x_init, const 
         HIPCHK(h, hipMemcpyAsync(h->d_X, X0, sizeof(double) * B * N * n, kind, h->stream));
         HIPCHK(h, copy_U(h, h->d_U, U0, true, kind));
     }
-    int rc = do_init(h, X0 == nullptr);
-    if (rc) return rc;
-    h->have_problems = true;
-    h->shoot.invalidate(); h->verify.invalidate(); h->tvlqr.invalidate(); h->simulate.invalidate(); h->lincov.invalidate();
-    h->n_active = -1;   // (gusto_set_active belongs to the problems it was set for)
-    return GUSTO_OK;
+    return gusto_problems_loaded(h, X0 == nullptr);
 }
 
 int gusto_set_problems(gusto_handle h, int B, const double* x_init, const double* glo, const double* ghi, const double* tf,

@@ -162,6 +162,18 @@ struct __attribute__((visibility("hidden"))) LincovState {
     void invalidate() { have = false; plant = false; dense = false; have_dense = false; have_dense_rows = false; }
 };
 
+// Multi-start solves (multistart.hip).  In: the [Bq] inputs of gusto_set_problems_multistart as the fan kernel reads them
+// (x_init, goal_lo, goal_hi [Bq][n] each, tf [Bq], fan [K][2]).  gusto_select_best with K starts per query, Bq = B / K: Score,
+// Elig [B] the copies of a caller's arrays; Rep [3][Bq] winner, winner_problem, n_eligible; Best [Bq] the winners' scores; X
+// [Bq][N][n], U [Bq][N][m] their trajectories
+struct __attribute__((visibility("hidden"))) SelectState {
+    DevBuf<double> In, Score, Best, X, U;
+    DevBuf<int> Elig, Rep;
+    int K = 0, Bq = 0;
+    bool have = false;
+    void invalidate() { have = false; }
+};
+
 struct gusto_handle_s {
     int model = 0, n = 0, m = 0, N = 0, batch_cap = 0, hist_cap = 0, device = 0, B = 0;
     // TrajOpt handles (gusto_create_trajopt): `model` is the internal variant (common.hpp: GUSTO_TO_*), `m` its control
@@ -213,6 +225,7 @@ struct gusto_handle_s {
     DevBuf<double> d_gX, d_gU;     // gusto_gather_peer: the shards of several handles, one after the other, on this handle's GPU
     DevBuf<double> d_Upub;         // TrajOpt handles: U compacted to the public [B][N][u_dim] layout for gusto_get_traj_dev
     ShootState shoot; VerifyState verify; TvlqrState tvlqr; SimulateState simulate; LincovState lincov;   // the post-solve stages
+    SelectState select;
     std::string err;
 
     // (the buffers and events free themselves; the caller has made `device` current: gusto_destroy)
@@ -309,3 +322,7 @@ struct ModelOps {
     int (*trajopt)(gusto_handle, int mode, int max_iter);
 };
 template <int MODEL> __attribute__((visibility("hidden"))) const ModelOps& model_ops();
+
+// What gusto_set_problems does once the inputs, X and U of h->B problems are on the device or enqueued on the handle's stream
+// (gusto_hip.hip): the straight line when asked for, the history reset, the post-solve stages invalidated, every problem active
+__attribute__((visibility("hidden"))) int gusto_problems_loaded(gusto_handle h, bool straight);

@@ -1,4 +1,4 @@
-// post.hpp -- the host path of the post-solve stages (shoot.hip, verify.hip, tvlqr.hip, simulate.hip, lincov.hip; nothing else includes it).  Plain
+// post.hpp -- the host path of the post-solve stages (shoot.hip, verify.hip, tvlqr.hip, simulate.hip, lincov.hip) and of multistart.hip; nothing else includes it.  Plain
 // functions that answer a GUSTO_* code and leave the text in h->err: `if (int rc = ...) return rc;` at the call site.  A new
 // stage starts from these, from a struct of its own next to ShootState / VerifyState / TvlqrState / SimulateState / LincovState
 // (handle.hpp) and, on the device, from rollout.hpp: the roll-out every stage but shoot.hip shares.

@@ -787,6 +787,95 @@ def solve_SCP_batch(TOSs, TOPs, solve_method=None, init_method=init_traj_straigh
     return out
 
 
+def default_fan(model_id):
+    """The lateral detours of a multi-start solve, in metres, start 0 the straight line: 0, +-0.5, +-1 across the direction of
+    travel in the plane; +-0.5 along each of the two axes across it in space."""
+    if _capi.WS_DIM[model_id] == 2:
+        return np.array([(0.0, 0.0), (0.5, 0.0), (-0.5, 0.0), (1.0, 0.0), (-1.0, 0.0)])
+    return np.array([(0.0, 0.0), (0.5, 0.0), (-0.5, 0.0), (0.0, 0.5), (0.0, -0.5)])
+
+
+def solve_SCP_multistart_batch(TOSs, TOPs, fan=None, policy="all", solver="hip", max_iter=30, force=False, device=0):
+    """Every TOP is one planning QUERY, started from a fan of K initial trajectories (gusto_set_problems_multistart: the straight
+    line bent sideways by fan[j] = (a2, a3) metres; None = default_fan) and answered with the best start that is converged and
+    successful (gusto_select_best on the last true cost).  All TOPs share model and N; each may bring its own environment.
+
+    policy="all": one launch of len(TOPs) K problems.  policy="retry": a plain straight-line solve of the queries first, then
+    the fan for the queries that are not successful only, on the same handle (sized for the larger batch; a retry that does not
+    fit runs in several launches); a query solved in the first pass keeps that result untouched.
+
+    Returns one dict per query: `winner` (the start's index in the fan, -1 when no start qualified), `cost` (its last J_true,
+    +inf likewise) and `SCPS`, the filled SCPSolution of the winner -- without one, of the straight line's solve.  TOSs[q].traj
+    and TOSs[q].SCPS are set as by solve_SCP_batch."""
+    if policy not in ("all", "retry"):
+        raise ValueError("solve_SCP_multistart_batch!: policy is 'all' or 'retry'")
+    if len(TOSs) != len(TOPs) or not TOPs:
+        raise ValueError("solve_SCP_multistart_batch!: need as many solutions as problems, at least one")
+    TOP0 = TOPs[0]
+    model, N = TOP0.PD.model, TOP0.N
+    n = model.x_dim
+    Q = len(TOPs)
+    for t in TOPs[1:]:
+        if type(t.PD.model) is not type(model) or t.N != N:
+            raise ValueError("solve_SCP_multistart_batch!: all problems must share the model type and N")
+    fan = default_fan(model.model_id) if fan is None else np.asarray(fan, float).reshape(-1, 2)
+    K = len(fan)
+    same_env = all(np.array_equal(t.PD.env.boxes, TOP0.PD.env.boxes) and np.array_equal(t.PD.env.spheres, TOP0.PD.env.spheres)
+                   for t in TOPs[1:])
+    sp, mp = _capi.default_params(model.model_id)
+    x0 = np.stack([t.PD.x_init for t in TOPs])
+    bounds = [_goal_bounds(t.PD.goal_set, n, t.tf_guess) for t in TOPs]
+    lo, hi = np.stack([b[0] for b in bounds]), np.stack([b[1] for b in bounds])
+    tf = np.array([t.tf_guess for t in TOPs])
+    cap = Q * K if policy == "all" else max(Q, K)
+    bs = BatchSolver(model.model_id, N, cap, hist_cap=_hist_cap(max_iter), device=device, boxes=TOP0.PD.env.boxes,
+                     spheres=TOP0.PD.env.spheres, scp_params=sp, model_params=mp)
+    out = [None] * Q
+
+    def take(q, snap, b, per, winner, cost):
+        SCPP = SCPProblem(TOPs[q])
+        SCPS = SCPSolution(SCPP, init_traj_straightline(TOPs[q]))
+        _fill_solution(SCPS, SCPP, snap, b, per)
+        TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
+        out[q] = dict(winner=int(winner), cost=float(cost), SCPS=SCPS)
+
+    def fanned(qs, keep_loser):
+        """the queries qs through one fanned launch; a query without a winner is taken from start 0 when keep_loser"""
+        qs = np.asarray(qs)
+        env = {} if same_env else dict(boxes=[TOPs[q].PD.env.boxes for q in qs], spheres=[TOPs[q].PD.env.spheres for q in qs])
+        bs.set_problems_multistart(x0[qs], lo[qs], hi[qs], tf[qs], fan, **env)
+        bs.solve(max_iter, force)
+        best = bs.select_best(K)
+        snap = _fetch(bs)
+        per = bs.last_solve_ms() * 1e-3 / len(qs)
+        for i, q in enumerate(qs):
+            if best["winner"][i] >= 0:
+                take(q, snap, best["winner_problem"][i], per, best["winner"][i], best["best_score"][i])
+            elif keep_loser:
+                take(q, snap, i * K, per, -1, np.inf)
+
+    try:
+        if policy == "all":
+            fanned(np.arange(Q), True)
+        else:
+            if not same_env:
+                bs.set_env_batch([t.PD.env.boxes for t in TOPs], [t.PD.env.spheres for t in TOPs])
+            bs.set_problems(x0, lo, hi, tf)
+            bs.solve(max_iter, force)
+            snap = _fetch(bs)
+            per = bs.last_solve_ms() * 1e-3 / Q
+            ok = snap["st"]["converged"] & snap["st"]["successful"]
+            for q in range(Q):
+                last = snap["h"]["J_true"][q, snap["h"]["nJ"][q] - 1]
+                take(q, snap, q, per, 0 if ok[q] else -1, last if ok[q] else np.inf)
+            again = np.flatnonzero(~ok)
+            for c in range(0, len(again), cap // K):
+                fanned(again[c:c + cap // K], False)
+    finally:
+        bs.close()
+    return out
+
+
 def solve_batch_sharded(model_id, N, x_init, goal_lo, goal_hi, tf, world_size, rank, device=0, max_iter=30, boxes=None,
                         spheres=None, group=None, solver=None):
     """The multi-GPU path of SURVEY.md 8(e) in one call (one process per GPU, launched by torch.distributed.run):

@@ -622,3 +622,114 @@ function lincov_dense_batch!(h::Ptr{Cvoid}, B::Integer, n::Integer, m::Integer, 
   (nfull = Int.(nfull), dense_sample = Int.(js), dense_pair = Int.(jp), min_z_dense = zmin, z_dense = z,
    pair_dense = pr === nothing ? nothing : Int.(pr), Spos = Sp, nfull_max = R, ms = ms[])
 end
+
+# ---- multi-start solves: a fan of detour starts per query, best-of-K select (csrc/multistart.hip) ------------------------------
+# GuSTO is a local method: every TOP is one planning QUERY, started from K initial trajectories in the same launch -- the straight
+# line bent sideways by fan[:, j] = (a2, a3) metres (gusto_set_problems_multistart; include/gusto_hip.h states the definitions, the
+# reference has no counterpart) -- and answered with the best start that is converged and successful (gusto_select_best on the last
+# true cost).  policy = :all: one launch of B K problems; :retry: a plain straight-line solve first, then the fan for the queries
+# that are not successful only, on the same handle; a query solved in the first pass keeps that result.  Returns per query
+# (winner, cost): the winning start (1-based; 0 = none qualified) and its cost (Inf likewise); TOSs[q] receives the winner's
+# solution, without one the straight line's.  All TOPs share model, N and the environment.  Mirrors gusto.jl_amd/host.py:
+# solve_SCP_multistart_batch.  This wrapper has not been run.
+const GUSTO_MAX_STARTS = 64
+mutable struct GustoBestReport      # gusto_best_report
+  winner::Ptr{Cint}; winner_problem::Ptr{Cint}; n_eligible::Ptr{Cint}
+  best_score::Ptr{Cdouble}
+  X::Ptr{Cdouble}; U::Ptr{Cdouble}
+end
+gusto_default_fan(model) = gusto_model_id(model) in (0, 1) ? [0. .5 -.5 1. -1.; 0. 0. 0. 0. 0.] : [0. .5 -.5 0. 0.; 0. 0. 0. .5 -.5]
+
+function solve_SCP_multistart_batch!(TOSs::Vector, TOPs::Vector; fan=nothing, policy=:all, max_iter=30, force=false, device=0)
+  policy in (:all, :retry) || error("solve_SCP_multistart_batch!: policy is :all or :retry")
+  TOP0 = TOPs[1]; model, N = TOP0.PD.model, TOP0.N
+  n, m, Q = model.x_dim, model.u_dim, length(TOPs)
+  all(T -> typeof(T.PD.model) == typeof(model) && T.N == N && T.PD.env === TOP0.PD.env, TOPs) ||
+    error("solve_SCP_multistart_batch!: all problems must share the model type, N and the environment")
+  F = fan === nothing ? gusto_default_fan(model) : Matrix{Float64}(fan)      # [2, K]: column j = (a2, a3) of start j
+  K = size(F, 2)
+  cap = policy == :all ? Q * K : max(Q, K)
+  alg0 = SCPParam_GuSTO(model)
+  sp = GustoScpParams(alg0.Δ0, alg0.ω0, alg0.ω_max, alg0.ε, alg0.ρ0, alg0.ρ1, alg0.β_succ, alg0.β_fail, alg0.γ_fail,
+                      SCPParam(model, TOP0.fixed_final_time).convergence_threshold)
+  href = Ref{Ptr{Cvoid}}(C_NULL)
+  gusto_check(ccall((:gusto_create, libgusto_hip), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Cint),
+                    href, gusto_model_id(model), N, cap, gusto_hist_cap(max_iter), device), href[], "create")
+  h = href[]
+  gusto_check(ccall((:gusto_set_params, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoScpParams}, Ref{GustoModelParams}),
+                    h, sp, gusto_model_params(TOP0.PD.robot, model)), h, "set_params")
+  boxes, spheres = gusto_env_tables(TOP0.PD.env)
+  gusto_check(ccall((:gusto_set_env, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+                    h, length(boxes) ÷ 6, boxes, length(spheres) ÷ 4, spheres), h, "set_env")
+  x0 = hcat((Float64.(T.PD.x_init) for T in TOPs)...)
+  bounds = [gusto_goal_bounds(T.PD.goal_set, n, T.tf_guess) for T in TOPs]
+  lo, hi = hcat(first.(bounds)...), hcat(last.(bounds)...)
+  tf = Float64[T.tf_guess for T in TOPs]
+  result = [(0, Inf) for _ in 1:Q]
+
+  # everything a solution needs from the B problems the handle holds now, after gusto_solve(max_iter)
+  function solve_and_fetch(B)
+    gusto_check(ccall((:gusto_solve, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Cint), h, max_iter, force), h, "solve")
+    X, U = zeros(n, N, B), zeros(m, N, B)
+    gusto_check(ccall((:gusto_get_traj, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), h, X, U), h, "get_traj")
+    its, conv, succ, stop = zeros(Cint, B), zeros(Cint, B), zeros(Cint, B), zeros(Cint, B)
+    gusto_check(ccall((:gusto_get_status, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ptr{Cvoid}),
+                      h, its, conv, succ, stop, C_NULL), h, "get_status")
+    duals = zeros(n, B)
+    gusto_check(ccall((:gusto_get_dual, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, duals), h, "get_dual")
+    msec = Ref{Cdouble}(0.)
+    ccall((:gusto_last_solve_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, msec)
+    (X = X, U = U, its = its, conv = conv, succ = succ, stop = stop, duals = duals, Hs = gusto_histories(h, B), per = msec[] / 1e3 / B)
+  end
+  function take!(q, S, j, winner, cost)       # problem j of the snapshot S answers query q
+    SCPP = SCPProblem(TOPs[q])
+    SCPP.param.alg = SCPParam_GuSTO(model)
+    SCPS = SCPSolution(SCPP, Trajectory(S.X[:, :, j], S.U[:, :, j], TOPs[q].tf_guess))
+    gusto_fill_solution!(SCPS, SCPP.param.alg, S.Hs, j, S.its[j], S.conv[j], S.succ[j], S.stop[j], S.duals[:, j])
+    SCPS.total_time = S.per
+    SCPS.iter_elapsed_times = vcat(0., fill(SCPS.total_time / max(1, S.its[j]), S.its[j]))
+    SCPP.param.obstacle_toggle_distance = SCPP.param.alg.Δ_vec[end] / 8 + model.clearance
+    TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
+    result[q] = (winner, cost)
+  end
+  function fanned!(qs, keep_loser)             # the queries qs through one fanned launch
+    Bq = length(qs)
+    gusto_check(ccall((:gusto_set_problems_multistart, libgusto_hip), Cint,
+                      (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                      h, Bq, K, x0[:, qs], lo[:, qs], hi[:, qs], tf[qs], F), h, "set_problems_multistart")
+    S = solve_and_fetch(Bq * K)
+    gusto_check(ccall((:gusto_select_best, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cint}), h, K, C_NULL, C_NULL), h, "select_best")
+    win, wp, best = zeros(Cint, Bq), zeros(Cint, Bq), zeros(Bq)
+    GC.@preserve win wp best begin
+      rep = GustoBestReport(pointer(win), pointer(wp), C_NULL, pointer(best), C_NULL, C_NULL)
+      gusto_check(ccall((:gusto_get_best, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoBestReport}), h, rep), h, "get_best")
+    end
+    for (i, q) in enumerate(qs)
+      if win[i] >= 0
+        take!(q, S, wp[i] + 1, win[i] + 1, best[i])
+      elseif keep_loser
+        take!(q, S, (i - 1) * K + 1, 0, Inf)
+      end
+    end
+  end
+
+  if policy == :all
+    fanned!(collect(1:Q), true)
+  else
+    gusto_check(ccall((:gusto_set_problems, libgusto_hip), Cint,
+                      (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                      h, Q, x0, lo, hi, tf, C_NULL, C_NULL), h, "set_problems")      # X0 = NULL: init_traj_straightline on the device
+    S = solve_and_fetch(Q)
+    ok = [S.conv[q] != 0 && S.succ[q] != 0 for q in 1:Q]
+    for q in 1:Q
+      take!(q, S, q, ok[q] ? 1 : 0, ok[q] ? TOSs[q].SCPS.J_true[end] : Inf)
+    end
+    again = findall(.!ok)
+    per = cap ÷ K
+    for c in 1:per:length(again)
+      fanned!(again[c:min(c + per - 1, length(again))], false)
+    end
+  end
+  ccall((:gusto_destroy, libgusto_hip), Cint, (Ptr{Cvoid},), h)
+  result
+end

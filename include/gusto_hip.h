@@ -612,6 +612,58 @@ typedef struct {
 /* out and nfull_max may each be NULL */
 int gusto_get_lincov_dense(gusto_handle h, gusto_lincov_dense_report* out, int* nfull_max);
 
+/* Multi-start solves (csrc/multistart.hip): GuSTO is a local method, so one planning query is started from a fan of K initial
+ * trajectories in the same launch and the best result is handed back.  No counterpart in the reference; its
+ * init_traj_straightline is the start with a zero offset.  The definitions:
+ * Layout: Bq queries with K starts each become the B = Bq K problems of the handle; problem b = q K + j is start j of query q.
+ *   x_init, goal_lo, goal_hi [Bq][x_dim] and tf [Bq] are HOST arrays with the meaning they have in gusto_set_problems; a kernel
+ *   replicates them into the handle's [B] arrays and writes the K initial trajectories of every query.  Everything
+ *   gusto_set_problems does afterwards happens unchanged: the history reset, the post-solve stages (and the selection below)
+ *   invalidated, every problem active again, the end of a latched scheduler error.
+ * Workspace dimension: WS = 2 for freeflyerSE2 and DubinsCar, 3 for the Astrobee models.
+ * End points: p_i = x_init[0:WS]; p_g the goal centre on the same entries by the straight line's rule, (lo + hi) / 2 where
+ *   both are finite, else 0.  Direction d = p_g - p_i, L = |d| (hypot in the plane, sqrt(dx dx + dy dy + dz dz) in space).
+ * Frame: e1 = d / L, or the first axis when L == 0.  Plane: e2 = (-e1_y, e1_x).  Space: h = hypot(e1_x, e1_y);
+ *   e2 = (-e1_y, e1_x, 0) / h if h > 1e-9, else (1, 0, 0); e3 = e1 x e2.  (For 0 < h <= 1e-9 the frame is orthogonal up to h.)
+ * Detour of start j: (a2, a3) = fan[j], in metres; w = a2 e2 + a3 e3.  a3 is not read in the plane.
+ * Trajectory: X0[k] is the straight line's knot, (1 - t_k) x_init + t_k centre with t_k = k / (N - 1), k = 0 .. N-1, the exact
+ *   expression of init_traj_straightline here; on the entries i < WS only, tent(t_k) w_i is added, tent(t) = 1 - |2 t - 1|: zero
+ *   at both ends, one in the middle.  Velocities, attitude and rates stay the straight line's.  U0 = 0.
+ * Zero offset: a start with a2 == a3 == 0 (in the plane: a2 == 0) skips the addition: it is the straight line bit for bit.
+ * GUSTO_ERR_ARG, nothing launched, the handle left as it was: K outside 1 .. GUSTO_MAX_STARTS, Bq < 1, Bq K > batch_cap, a null
+ *   array, a fan entry that is not finite, a TrajOpt handle.  All four models.
+ * Keep-out sets: gusto_set_env applies as ever; gusto_set_env_batch needs B = Bq K sets, each query's repeated K times. */
+#define GUSTO_MAX_STARTS 64
+int gusto_set_problems_multistart(gusto_handle h, int Bq, int K, const double* x_init, const double* goal_lo,
+                                  const double* goal_hi, const double* tf, const double* fan /* [K][2] */);
+/* The winner of every group of K consecutive problems, selected and gathered on the device (csrc/multistart.hip).  K must lie in
+ * 1 .. GUSTO_MAX_STARTS and divide the handle's B (else GUSTO_ERR_ARG); Bq = B / K.  The problems need not come from
+ * gusto_set_problems_multistart.  The call completes a pending gusto_solve_async, runs on the handle's stream and changes
+ * nothing else on the handle.
+ * eligible [B] (HOST; nonzero = may win), or NULL = converged && successful as gusto_get_status reports them.
+ * score [B] (HOST), or NULL = the last true cost, J_true[b][nJ[b] - 1] of gusto_get_history (a problem with nJ[b] == 0: NaN).
+ * Winner of a query: the eligible start with the smallest score under a strict `<` in ascending j -- ties go to the lowest
+ *   start; a NaN score never wins.  A query without such a start reports winner = winner_problem = -1, best_score = +inf and
+ *   zero rows, the convention of gusto_get_shoot for problems that are not :Optimal.  n_eligible counts the eligible starts,
+ *   whatever their scores.
+ * With a caller's score and eligible the call is a general best-of-group: the report of gusto_verify, a min_z_obs of
+ *   gusto_lincov or anything else the caller has can decide.  To run the post-solve stages on the winners only, pass the mask
+ *   built from winner_problem to gusto_set_active.
+ * One wavefront per query, reductions in a fixed order, no atomics: a query's report is the same bit for bit in any batch.
+ * Both getters: GUSTO_ERR_STATE before the first gusto_select_best since the problems were set and on a handle without
+ *   problems, GUSTO_ERR_ARG on a TrajOpt handle. */
+int gusto_select_best(gusto_handle h, int K, const double* score /* [B] or NULL */, const int* eligible /* [B] or NULL */);
+typedef struct {
+    int *winner;          /* [Bq] start index j, -1: no eligible start        */
+    int *winner_problem;  /* [Bq] q K + j, -1 likewise                          */
+    int *n_eligible;      /* [Bq]                                               */
+    double *best_score;   /* [Bq] +inf when there is no winner                  */
+    double *X, *U;        /* [Bq][N][x_dim], [Bq][N][u_dim]: the winners' trajectories, zeros without a winner */
+} gusto_best_report;      /* caller-owned, any pointer may be NULL */
+int gusto_get_best(gusto_handle h, gusto_best_report* out);
+/* the same compact buffers on the device (valid until the next gusto_select_best on the handle); any pointer may be NULL */
+int gusto_get_best_dev(gusto_handle h, const double** X_dev, const double** U_dev, const int** winner_problem_dev);
+
 /* One convex subproblem per problem (what scp_gusto.jl:82-104 builds and solves in one trip), linearised at
  * (Xp,Up)[b] with the given Delta/omega/obstacle_toggle_distance[b].  Used by the parity tests.
  * Outputs: Xn,Un [B][N][.], obj [B] (JuMP.objective_value), status [B] (GUSTO_SOLVER_*), iters [B]. */
