@@ -35,7 +35,10 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_default_lincov_opts", "gusto_lincov", "gusto_get_lincov", "gusto_last_lincov_ms",
            "gusto_lincov_disturbed", "gusto_get_lincov_plant", "gusto_lincov_dense", "gusto_get_lincov_dense",
            "gusto_set_problems_multistart", "gusto_select_best", "gusto_get_best", "gusto_get_best_dev",
-           "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr"]
+           "gusto_default_trajlib_opts", "gusto_trajlib_create", "gusto_trajlib_destroy", "gusto_trajlib_last_error", "gusto_trajlib_size",
+           "gusto_trajlib_clear", "gusto_trajlib_add", "gusto_trajlib_add_host", "gusto_trajlib_get", "gusto_set_problems_trajlib",
+           "gusto_get_trajlib_seeds", "gusto_last_trajlib_ms",
+           "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr", "gusto_dev_trajlib"]
 
 
 class ScpParams(C.Structure):
@@ -151,6 +154,14 @@ class BestReport(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in BEST_FIELDS]
 
 
+TRAJLIB_MAX_K, TRAJLIB_MAX_CAP = 8, 1 << 20   # GUSTO_TRAJLIB_MAX_K, GUSTO_TRAJLIB_MAX_CAP
+
+
+class TrajLibOpts(C.Structure):
+    """gusto_trajlib_opts"""
+    _fields_ = [("w_init", C.c_double * MAXN), ("w_goal", C.c_double * MAXN), ("w_tf", C.c_double), ("lds_tile", C.c_int)]
+
+
 VERIFY_FIELDS = (("collision_free", np.int32), ("first_knot", np.int32), ("first_dist", np.float64),
                  ("min_dist_knots", np.float64), ("dyn_defect_l1", np.float64), ("min_dist_dense", np.float64),
                  ("min_dense_sample", np.int32), ("max_gap", np.float64))
@@ -192,7 +203,7 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(_ROOT, "include"), "-fPIC",
              "-Wno-unused-value", "-Wno-pass-failed"]
-    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
+    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "trajlib", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
     bdir = os.path.join(_HERE, "build")
     os.makedirs(bdir, exist_ok=True)
 
@@ -291,6 +302,20 @@ def lib():
         L.gusto_select_best.argtypes = [vp, ci, vp, vp]
         L.gusto_get_best.argtypes = [vp, C.POINTER(BestReport)]
         L.gusto_get_best_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.gusto_default_trajlib_opts.argtypes = [ci, C.POINTER(TrajLibOpts)]
+        L.gusto_trajlib_create.argtypes = [C.POINTER(vp), ci, ci, ci, ci, C.POINTER(TrajLibOpts)]
+        L.gusto_trajlib_destroy.argtypes = [vp]
+        L.gusto_trajlib_last_error.restype = C.c_char_p
+        L.gusto_trajlib_last_error.argtypes = [vp]
+        L.gusto_trajlib_size.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
+        L.gusto_trajlib_clear.argtypes = [vp]
+        L.gusto_trajlib_add.argtypes = [vp, vp, vp, vp, C.POINTER(ci)]
+        L.gusto_trajlib_add_host.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
+        L.gusto_trajlib_get.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.gusto_set_problems_trajlib.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp]
+        L.gusto_get_trajlib_seeds.argtypes = [vp, vp, vp, vp]
+        L.gusto_last_trajlib_ms.argtypes = [vp, C.POINTER(C.c_double)]
+        L.gusto_dev_trajlib.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.gusto_default_trajopt_params.argtypes = [ci, C.POINTER(TrajOptParams)]
         L.gusto_create_trajopt.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci]
         L.gusto_set_trajopt_params.argtypes = [vp, C.POINTER(TrajOptParams)]
@@ -355,6 +380,14 @@ def default_lincov_opts(model):
     rc = lib().gusto_default_lincov_opts(model, C.byref(o))
     if rc:
         raise ValueError(f"gusto_default_lincov_opts({model}) -> {rc}")
+    return o
+
+
+def default_trajlib_opts(model):
+    o = TrajLibOpts()
+    rc = lib().gusto_default_trajlib_opts(model, C.byref(o))
+    if rc:
+        raise ValueError(f"gusto_default_trajlib_opts({model}) -> {rc}")
     return o
 
 
@@ -502,6 +535,43 @@ class BatchSolver:
         self._chk(self.L.gusto_get_best_dev(self.h, C.byref(px), C.byref(pu), C.byref(pw)), "get_best_dev")
         return (_dev_view(px.value, (Bq, self.N, self.n), self.device), _dev_view(pu.value, (Bq, self.N, self.m), self.device),
                 _dev_view(pw.value, (Bq,), self.device, "<i4"))
+
+    def set_problems_trajlib(self, lib, x_init, goal_lo, goal_hi, tf, K=1, tag=None, boxes=None, spheres=None):
+        """gusto_set_problems_trajlib: Bq queries seeded from their K nearest entries of the TrajLib `lib` become the B = Bq K problems
+        of the handle, problem q K + j = neighbour j of query q (a start without a neighbour is the straight line).  tag [Bq]: only
+        the entries with the query's tag are eligible (None: all).  boxes / spheres: one keep-out set PER QUERY, repeated K times
+        into set_env_batch; None leaves the environment as it is.  The seeds: trajlib_seeds()."""
+        x_init, goal_lo, goal_hi = _arr(x_init).reshape(-1, self.n), _arr(goal_lo).reshape(-1, self.n), \
+            _arr(goal_hi).reshape(-1, self.n)
+        Bq, K = x_init.shape[0], int(K)
+        tf = _arr(np.broadcast_to(np.asarray(tf, dtype=np.float64), (Bq,)))
+        tg = None if tag is None else _arr(tag, np.int32).reshape(Bq)
+        self._chk(self.L.gusto_set_problems_trajlib(self.h, lib.h, Bq, K, x_init.ctypes.data, goal_lo.ctypes.data, goal_hi.ctypes.data,
+                                                    tf.ctypes.data, None if tg is None else tg.ctypes.data), "set_problems_trajlib")
+        self.B, self._trajlib_K = Bq * K, K
+        if boxes is not None or spheres is not None:
+            rep = lambda tables: None if tables is None else [t for t in tables for _ in range(K)]
+            self.set_env_batch(rep(boxes) if boxes is not None else [None] * self.B, rep(spheres))
+
+    def trajlib_seeds(self):
+        """gusto_get_trajlib_seeds: a dict of entry [Bq, K] (-1: the straight line), dist2 [Bq, K] (+inf likewise), n_found [Bq]"""
+        K = self._trajlib_K
+        out = dict(entry=np.zeros((self.B // K, K), np.int32), dist2=np.zeros((self.B // K, K)), n_found=np.zeros(self.B // K, np.int32))
+        self._chk(self.L.gusto_get_trajlib_seeds(self.h, out["entry"].ctypes.data, out["dist2"].ctypes.data, out["n_found"].ctypes.data),
+                  "get_trajlib_seeds")
+        return out
+
+    def last_trajlib_ms(self):
+        """gusto_last_trajlib_ms: GPU time of search plus retargeting of the last set_problems_trajlib"""
+        ms = C.c_double()
+        self._chk(self.L.gusto_last_trajlib_ms(self.h, C.byref(ms)), "last_trajlib_ms")
+        return ms.value
+
+    def trajlib_phase_ms(self):
+        """gusto_dev_trajlib: (search_ms, retarget_ms) of the last set_problems_trajlib"""
+        a, b = C.c_double(), C.c_double()
+        self._chk(self.L.gusto_dev_trajlib(self.h, C.byref(a), C.byref(b)), "dev_trajlib")
+        return a.value, b.value
 
     def set_trust_state(self, Delta=None, omega=None):
         """gusto_set_trust_state: the caller's own Delta_vec[end] / omega_vec[end] for the next trip of every problem."""
@@ -1017,3 +1087,103 @@ class TrajOptSolver(BatchSolver):
 
     def select_best(self, *a, **k):
         raise GustoError("TrajOptSolver: select_best is not supported on TrajOpt handles (gusto_select_best answers GUSTO_ERR_ARG)")
+
+    def set_problems_trajlib(self, *a, **k):
+        raise GustoError("TrajOptSolver: library seeds are not supported on TrajOpt handles (gusto_set_problems_trajlib answers GUSTO_ERR_ARG)")
+
+
+class TrajLib:
+    """Thin owner of one gusto_trajlib: solved trajectories of one model and horizon on one GPU, the seeds of later queries
+    (BatchSolver.set_problems_trajlib).  w_init / w_goal [x_dim], w_tf: the weights of the distance (None: the library's defaults,
+    1 on every state of both vectors and 0 -- a placeholder, the states have different units)."""
+
+    def __init__(self, model, N, cap, device=0, w_init=None, w_goal=None, w_tf=None, lds_tile=None):
+        self.L = lib()
+        self.model, self.N, self.cap, self.device = model, N, cap, device
+        self.n, self.m = MODEL_DIMS[model]
+        o = default_trajlib_opts(model)
+        for name, w in (("w_init", w_init), ("w_goal", w_goal)):
+            if w is not None:
+                w = np.broadcast_to(np.asarray(w, dtype=np.float64), (self.n,))
+                for i in range(self.n):
+                    getattr(o, name)[i] = w[i]
+        if w_tf is not None:
+            o.w_tf = float(w_tf)
+        if lds_tile is not None:
+            o.lds_tile = int(lds_tile)
+        self.opts = o
+        self.h = C.c_void_p()
+        rc = self.L.gusto_trajlib_create(C.byref(self.h), model, N, cap, device, C.byref(o))
+        if rc:
+            msg = self.L.gusto_trajlib_last_error(None)
+            self.h = C.c_void_p()
+            raise GustoError(f"gusto_trajlib_create -> {rc}: {msg.decode() if msg else ''}")
+
+    def _chk(self, rc, what):
+        if rc:
+            msg = self.L.gusto_trajlib_last_error(self.h)
+            raise GustoError(f"gusto_trajlib_{what} -> {rc}: {msg.decode() if msg else ''}")
+
+    def close(self):
+        if getattr(self, "h", None) and self.h:
+            self.L.gusto_trajlib_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        c, cap = C.c_int(), C.c_int()
+        self._chk(self.L.gusto_trajlib_size(self.h, C.byref(c), C.byref(cap)), "size")
+        return c.value
+
+    def clear(self):
+        self._chk(self.L.gusto_trajlib_clear(self.h), "clear")
+
+    def add_from(self, solver, mask=None, tag=None):
+        """gusto_trajlib_add: appends the problems of the BatchSolver whose mask is nonzero (None: converged and successful), in
+        ascending order, device to device; tag [B] or one integer for all (None: 0).  Returns the number appended."""
+        mk = None if mask is None else _arr(np.asarray(mask).astype(bool), np.int32).reshape(solver.B)
+        tg = None if tag is None else _arr(np.broadcast_to(np.asarray(tag, dtype=np.int32), (solver.B,)), np.int32)
+        n = C.c_int()
+        self._chk(self.L.gusto_trajlib_add(self.h, solver.h, None if mk is None else mk.ctypes.data, None if tg is None else tg.ctypes.data,
+                                           C.byref(n)), "add")
+        return n.value
+
+    def add_host(self, x_init, goal_lo, goal_hi, tf, X, U, tag=None):
+        """gusto_trajlib_add_host: appends entries from host arrays ([n, x_dim] each, tf [n], X [n, N, x_dim], U [n, N, u_dim])"""
+        x_init, goal_lo, goal_hi = (_arr(a).reshape(-1, self.n) for a in (x_init, goal_lo, goal_hi))
+        n = x_init.shape[0]
+        tf = _arr(np.broadcast_to(np.asarray(tf, dtype=np.float64), (n,)))
+        X, U = _arr(X).reshape(n, self.N, self.n), _arr(U).reshape(n, self.N, self.m)
+        tg = None if tag is None else _arr(np.broadcast_to(np.asarray(tag, dtype=np.int32), (n,)), np.int32)
+        self._chk(self.L.gusto_trajlib_add_host(self.h, n, x_init.ctypes.data, goal_lo.ctypes.data, goal_hi.ctypes.data, tf.ctypes.data,
+                                                None if tg is None else tg.ctypes.data, X.ctypes.data, U.ctypes.data), "add_host")
+
+    def get(self):
+        """gusto_trajlib_get: a dict of x_init, goal_c [L, x_dim], tf [L], tag [L], X [L, N, x_dim], U [L, N, u_dim]"""
+        c = len(self)
+        out = dict(x_init=np.zeros((c, self.n)), goal_c=np.zeros((c, self.n)), tf=np.zeros(c), tag=np.zeros(c, np.int32),
+                   X=np.zeros((c, self.N, self.n)), U=np.zeros((c, self.N, self.m)))
+        self._chk(self.L.gusto_trajlib_get(self.h, *(out[k].ctypes.data for k in ("x_init", "goal_c", "tf", "tag", "X", "U"))), "get")
+        return out
+
+    def save(self, path):
+        """the entries and the weights as an .npz (numpy appends the suffix when it is missing)"""
+        o = self.opts
+        np.savez(path, model=self.model, N=self.N, w_init=np.array(o.w_init[:self.n]), w_goal=np.array(o.w_goal[:self.n]), w_tf=o.w_tf,
+                 **self.get())
+
+    @classmethod
+    def load(cls, path, cap=None, device=0):
+        """a library from save(): the same entries in the same order, the same weights; cap: at least the entries (None: exactly)"""
+        d = np.load(path)
+        c = len(d["tf"])
+        out = cls(int(d["model"]), int(d["N"]), max(c, 1) if cap is None else cap, device=device, w_init=d["w_init"], w_goal=d["w_goal"],
+                  w_tf=float(d["w_tf"]))
+        if c:
+            out.add_host(d["x_init"], d["goal_c"], d["goal_c"], d["tf"], d["X"], d["U"], tag=d["tag"])
+        return out

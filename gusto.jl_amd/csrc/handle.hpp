@@ -174,6 +174,34 @@ struct __attribute__((visibility("hidden"))) SelectState {
     void invalidate() { have = false; }
 };
 
+// Trajectory library (trajlib.hip), on the handle: In the [Bq] inputs of gusto_set_problems_trajlib as its kernels read them
+// (x_init, goal_lo, goal_hi [Bq][n] each, tf [Bq]) and Tag their tags [Bq]; Entry, Dist [B] the seeds, Found [Bq]; Mask [2][B]
+// the copies of mask and tag of gusto_trajlib_add
+struct __attribute__((visibility("hidden"))) TrajlibState {
+    DevBuf<double> In, Dist;
+    DevBuf<int> Tag, Entry, Found, Mask;
+    int K = 0, Bq = 0;
+    bool have = false;
+    DevEvent t0, mid, t1;   // `mid` is recorded between the two launches (gusto_dev_trajlib)
+    double last_ms = 0.0, search_ms = 0.0, retarget_ms = 0.0;
+    void invalidate() { have = false; }
+};
+
+// The library itself: `count` of `cap` entries on `device`, entry e at row e of xi, c [cap][n], tf, tag [cap], X [cap][N][n], U
+// [cap][N][m].  The features are the F positive-weight terms of the distance, in its order of summation: term f has the weight
+// w[f] and reads entry fmap[f] & 15 of x_init (fmap[f] >> 4 == 0), of the goal centre (1) or tf (2).  Feat is feature-major,
+// [F][cap]: consecutive lanes read consecutive entries of one feature.
+constexpr int TRAJLIB_MAX_F = 2 * GUSTO_MAXN + 1;
+struct gusto_trajlib_s {
+    int model = 0, n = 0, m = 0, N = 0, cap = 0, device = 0, count = 0, F = 0, lds_tile = 1;
+    int fmap[TRAJLIB_MAX_F] = {0};
+    double w[TRAJLIB_MAX_F] = {0};
+    DevBuf<double> xi, c, tf, X, U, Feat;
+    DevBuf<int> tag;
+    std::string err;
+    __attribute__((visibility("hidden"))) ~gusto_trajlib_s() = default;
+};
+
 struct gusto_handle_s {
     int model = 0, n = 0, m = 0, N = 0, batch_cap = 0, hist_cap = 0, device = 0, B = 0;
     // TrajOpt handles (gusto_create_trajopt): `model` is the internal variant (common.hpp: GUSTO_TO_*), `m` its control
@@ -226,6 +254,7 @@ struct gusto_handle_s {
     DevBuf<double> d_Upub;         // TrajOpt handles: U compacted to the public [B][N][u_dim] layout for gusto_get_traj_dev
     ShootState shoot; VerifyState verify; TvlqrState tvlqr; SimulateState simulate; LincovState lincov;   // the post-solve stages
     SelectState select;
+    TrajlibState trajlib;
     std::string err;
 
     // (the buffers and events free themselves; the caller has made `device` current: gusto_destroy)

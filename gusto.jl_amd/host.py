@@ -876,6 +876,97 @@ def solve_SCP_multistart_batch(TOSs, TOPs, fan=None, policy="all", solver="hip",
     return out
 
 
+class TrajLib(_capi.TrajLib):
+    """A device-resident library of solved trajectories (gusto_trajlib): TrajLib(model_id, N, cap, device=0, w_init=None,
+    w_goal=None, w_tf=None).  add_from(solver, mask=None, tag=None) appends the converged and successful (or the masked) problems
+    of a BatchSolver device to device, save(path) / TrajLib.load(path, cap=None, device=0) move a library through an .npz with its
+    weights, len() is its fill; solve_SCP_trajlib_batch seeds queries from it."""
+
+
+def solve_SCP_trajlib_batch(TOSs, TOPs, lib, K=1, fallback_fan=None, learn=False, solver="hip", max_iter=30, force=False, device=0):
+    """Every TOP is one planning QUERY, seeded from its K nearest entries of the TrajLib `lib` (gusto_set_problems_trajlib: the
+    entry's trajectory retargeted to the query's end points; a start without a neighbour is the straight line), solved in one
+    launch of len(TOPs) K problems and answered with the best start that is converged and successful (gusto_select_best on the
+    last true cost).  All TOPs share the library's model and N; each may bring its own environment.
+
+    fallback_fan: the queries without a winner go through the multi-start path afterwards (gusto_set_problems_multistart with this
+    fan [Kf, 2]; True = default_fan), on the same handle.  learn: the winners are appended to the library, device to device, so a
+    later batch is seeded from them too (a full library refuses: GustoError, the solutions of this batch are filled by then).
+
+    Returns one dict per query: `winner` (the start's index, -1 when no start qualified), `cost` (its last J_true, +inf
+    likewise), `source` ("library", "fan", or None without a winner), `entry` (the library entry the winning start was seeded
+    from; -1 for a straight line or a fan start) and `SCPS`, the filled SCPSolution of the winner -- without one, of start 0.
+    TOSs[q].traj and TOSs[q].SCPS are set as by solve_SCP_batch."""
+    if len(TOSs) != len(TOPs) or not TOPs:
+        raise ValueError("solve_SCP_trajlib_batch!: need as many solutions as problems, at least one")
+    TOP0 = TOPs[0]
+    model, N = TOP0.PD.model, TOP0.N
+    n = model.x_dim
+    Q, K = len(TOPs), int(K)
+    for t in TOPs[1:]:
+        if type(t.PD.model) is not type(model) or t.N != N:
+            raise ValueError("solve_SCP_trajlib_batch!: all problems must share the model type and N")
+    if lib.model != model.model_id or lib.N != N:
+        raise ValueError("solve_SCP_trajlib_batch!: the library belongs to another model or N")
+    fan = None
+    if fallback_fan is not None and fallback_fan is not False:
+        fan = default_fan(model.model_id) if fallback_fan is True else np.asarray(fallback_fan, float).reshape(-1, 2)
+    same_env = all(np.array_equal(t.PD.env.boxes, TOP0.PD.env.boxes) and np.array_equal(t.PD.env.spheres, TOP0.PD.env.spheres)
+                   for t in TOPs[1:])
+    sp, mp = _capi.default_params(model.model_id)
+    x0 = np.stack([t.PD.x_init for t in TOPs])
+    bounds = [_goal_bounds(t.PD.goal_set, n, t.tf_guess) for t in TOPs]
+    lo, hi = np.stack([b[0] for b in bounds]), np.stack([b[1] for b in bounds])
+    tf = np.array([t.tf_guess for t in TOPs])
+    cap = Q * K if fan is None else max(Q * K, len(fan))
+    bs = BatchSolver(model.model_id, N, cap, hist_cap=_hist_cap(max_iter), device=lib.device, boxes=TOP0.PD.env.boxes,
+                     spheres=TOP0.PD.env.spheres, scp_params=sp, model_params=mp)
+    out = [None] * Q
+
+    def take(q, snap, b, per, winner, cost, source, entry):
+        SCPP = SCPProblem(TOPs[q])
+        SCPS = SCPSolution(SCPP, init_traj_straightline(TOPs[q]))
+        _fill_solution(SCPS, SCPP, snap, b, per)
+        TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
+        out[q] = dict(winner=int(winner), cost=float(cost), source=source, entry=int(entry), SCPS=SCPS)
+
+    def finish(qs, Ks, source, entries, keep_loser):
+        """solve what is set, select, fill the queries qs; with learn the winners join the library.  Returns the losers"""
+        bs.solve(max_iter, force)
+        best = bs.select_best(Ks)
+        snap = _fetch(bs)
+        per = bs.last_solve_ms() * 1e-3 / len(qs)
+        lost = []
+        for i, q in enumerate(qs):
+            w = best["winner"][i]
+            if w >= 0:
+                take(q, snap, best["winner_problem"][i], per, w, best["best_score"][i], source, -1 if entries is None else entries[i, w])
+            else:
+                lost.append(q)
+                if keep_loser:
+                    take(q, snap, i * Ks, per, -1, np.inf, None, -1)
+        if learn and (best["winner"] >= 0).any():
+            mask = np.zeros(bs.B, bool)
+            mask[best["winner_problem"][best["winner"] >= 0]] = True
+            lib.add_from(bs, mask)
+        return np.array(lost, dtype=int)
+
+    try:
+        env = {} if same_env else dict(boxes=[t.PD.env.boxes for t in TOPs], spheres=[t.PD.env.spheres for t in TOPs])
+        bs.set_problems_trajlib(lib, x0, lo, hi, tf, K, **env)
+        again = finish(np.arange(Q), K, "library", bs.trajlib_seeds()["entry"], True)
+        if fan is not None:
+            Kf = len(fan)
+            for c in range(0, len(again), cap // Kf):
+                qs = again[c:c + cap // Kf]
+                env = {} if same_env else dict(boxes=[TOPs[q].PD.env.boxes for q in qs], spheres=[TOPs[q].PD.env.spheres for q in qs])
+                bs.set_problems_multistart(x0[qs], lo[qs], hi[qs], tf[qs], fan, **env)
+                finish(qs, Kf, "fan", None, False)
+    finally:
+        bs.close()
+    return out
+
+
 def solve_batch_sharded(model_id, N, x_init, goal_lo, goal_hi, tf, world_size, rank, device=0, max_iter=30, boxes=None,
                         spheres=None, group=None, solver=None):
     """The multi-GPU path of SURVEY.md 8(e) in one call (one process per GPU, launched by torch.distributed.run):

@@ -733,3 +733,149 @@ function solve_SCP_multistart_batch!(TOSs::Vector, TOPs::Vector; fan=nothing, po
   ccall((:gusto_destroy, libgusto_hip), Cint, (Ptr{Cvoid},), h)
   result
 end
+
+# ---- trajectory library: every query seeded from its nearest solved neighbours (csrc/trajlib.hip) ------------------------------
+# GuSTO is warm-started at its previous iterate: a query that starts from the solved trajectory of a similar query needs fewer
+# trips than one that starts from the straight line.  A gusto_trajlib keeps solved trajectories on the device;
+# gusto_set_problems_trajlib finds the K nearest entries of every query and retargets them to its end points (include/gusto_hip.h
+# states the definitions, the reference has no counterpart).  TrajLib owns one library; trajlib_add! appends the converged and
+# successful (or the masked) problems of a handle device to device, trajlib_get / trajlib_add_host! move a library through host
+# arrays ([x_dim, L], [x_dim, N, L], [u_dim, N, L]: the column-major images of the C rows).  solve_SCP_trajlib_batch! seeds,
+# solves and selects; with fallback_fan the queries without a winner go through solve_SCP_multistart_batch!'s fan afterwards;
+# with learn the winners join the library.  Returns per query (winner, cost, entry): the winning start (1-based; 0 = none
+# qualified), its cost (Inf likewise) and the library entry it was seeded from (1-based; 0 = a straight line or a fan start).
+# Mirrors gusto.jl_amd/host.py: TrajLib, solve_SCP_trajlib_batch.  This wrapper has not been run.
+const GUSTO_TRAJLIB_MAX_K = 8
+struct GustoTrajlibOpts      # gusto_trajlib_opts
+  w_init::NTuple{13,Cdouble}; w_goal::NTuple{13,Cdouble}
+  w_tf::Cdouble
+  lds_tile::Cint
+end
+mutable struct TrajLib
+  h::Ptr{Cvoid}; model_id::Int; n::Int; m::Int; N::Int; cap::Int; device::Int
+end
+trajlib_check(rc, lib, what) = rc == 0 || error("gusto_trajlib_$what -> $rc: " *
+  unsafe_string(ccall((:gusto_trajlib_last_error, libgusto_hip), Cstring, (Ptr{Cvoid},), lib)))
+
+function TrajLib(model, N::Integer, cap::Integer; device=0, w_init=nothing, w_goal=nothing, w_tf=nothing)
+  id, n, m = gusto_model_id(model), model.x_dim, model.u_dim
+  o = Ref(GustoTrajlibOpts(ntuple(_ -> 0., 13), ntuple(_ -> 0., 13), 0., 1))
+  ccall((:gusto_default_trajlib_opts, libgusto_hip), Cint, (Cint, Ref{GustoTrajlibOpts}), id, o) == 0 || error("gusto_default_trajlib_opts")
+  pad(w, d) = w === nothing ? d : ntuple(i -> i <= n ? Float64(w isa Number ? w : w[i]) : 0., 13)
+  o[] = GustoTrajlibOpts(pad(w_init, o[].w_init), pad(w_goal, o[].w_goal), w_tf === nothing ? o[].w_tf : Float64(w_tf), o[].lds_tile)
+  href = Ref{Ptr{Cvoid}}(C_NULL)
+  trajlib_check(ccall((:gusto_trajlib_create, libgusto_hip), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Ref{GustoTrajlibOpts}),
+                      href, id, N, cap, device, o), C_NULL, "create")
+  TrajLib(href[], id, n, m, N, cap, device)
+end
+trajlib_destroy!(lib::TrajLib) = (ccall((:gusto_trajlib_destroy, libgusto_hip), Cint, (Ptr{Cvoid},), lib.h); lib.h = C_NULL; nothing)
+trajlib_clear!(lib::TrajLib) = trajlib_check(ccall((:gusto_trajlib_clear, libgusto_hip), Cint, (Ptr{Cvoid},), lib.h), lib.h, "clear")
+function Base.length(lib::TrajLib)
+  c = Ref{Cint}(0)
+  trajlib_check(ccall((:gusto_trajlib_size, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cint}, Ptr{Cint}), lib.h, c, C_NULL), lib.h, "size")
+  Int(c[])
+end
+# the problems of handle h (B of them) whose mask is nonzero (nothing: converged and successful); returns the number appended
+function trajlib_add!(lib::TrajLib, h::Ptr{Cvoid}, B::Integer; mask=nothing, tag=nothing)
+  mk = mask === nothing ? C_NULL : Cint.(mask .!= 0)
+  tg = tag === nothing ? C_NULL : (tag isa Number ? fill(Cint(tag), B) : Cint.(tag))
+  added = Ref{Cint}(0)
+  trajlib_check(ccall((:gusto_trajlib_add, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Ref{Cint}),
+                      lib.h, h, mk, tg, added), lib.h, "add")
+  Int(added[])
+end
+function trajlib_add_host!(lib::TrajLib, x_init, goal_lo, goal_hi, tf, X, U; tag=nothing)
+  L = length(tf)
+  tg = tag === nothing ? C_NULL : Cint.(tag)
+  trajlib_check(ccall((:gusto_trajlib_add_host, libgusto_hip), Cint,
+                      (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}),
+                      lib.h, L, Matrix{Float64}(x_init), Matrix{Float64}(goal_lo), Matrix{Float64}(goal_hi), Vector{Float64}(tf), tg,
+                      Array{Float64}(X), Array{Float64}(U)), lib.h, "add_host")
+end
+function trajlib_get(lib::TrajLib)
+  L = length(lib)
+  x_init, goal_c, tf, tag = zeros(lib.n, L), zeros(lib.n, L), zeros(L), zeros(Cint, L)
+  X, U = zeros(lib.n, lib.N, L), zeros(lib.m, lib.N, L)
+  trajlib_check(ccall((:gusto_trajlib_get, libgusto_hip), Cint,
+                      (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}),
+                      lib.h, x_init, goal_c, tf, tag, X, U), lib.h, "get")
+  (x_init = x_init, goal_c = goal_c, tf = tf, tag = Int.(tag), X = X, U = U)
+end
+
+function solve_SCP_trajlib_batch!(TOSs::Vector, TOPs::Vector, lib::TrajLib; K=1, fallback_fan=nothing, learn=false, max_iter=30,
+                                  force=false)
+  TOP0 = TOPs[1]; model, N = TOP0.PD.model, TOP0.N
+  n, m, Q = model.x_dim, model.u_dim, length(TOPs)
+  all(T -> typeof(T.PD.model) == typeof(model) && T.N == N && T.PD.env === TOP0.PD.env, TOPs) ||
+    error("solve_SCP_trajlib_batch!: all problems must share the model type, N and the environment")
+  (gusto_model_id(model) == lib.model_id && N == lib.N) || error("solve_SCP_trajlib_batch!: the library belongs to another model or N")
+  1 <= K <= GUSTO_TRAJLIB_MAX_K || error("solve_SCP_trajlib_batch!: K outside 1 .. GUSTO_TRAJLIB_MAX_K")
+  alg0 = SCPParam_GuSTO(model)
+  sp = GustoScpParams(alg0.Δ0, alg0.ω0, alg0.ω_max, alg0.ε, alg0.ρ0, alg0.ρ1, alg0.β_succ, alg0.β_fail, alg0.γ_fail,
+                      SCPParam(model, TOP0.fixed_final_time).convergence_threshold)
+  href = Ref{Ptr{Cvoid}}(C_NULL)
+  gusto_check(ccall((:gusto_create, libgusto_hip), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Cint),
+                    href, gusto_model_id(model), N, Q * K, gusto_hist_cap(max_iter), lib.device), href[], "create")
+  h = href[]
+  gusto_check(ccall((:gusto_set_params, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoScpParams}, Ref{GustoModelParams}),
+                    h, sp, gusto_model_params(TOP0.PD.robot, model)), h, "set_params")
+  boxes, spheres = gusto_env_tables(TOP0.PD.env)
+  gusto_check(ccall((:gusto_set_env, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+                    h, length(boxes) ÷ 6, boxes, length(spheres) ÷ 4, spheres), h, "set_env")
+  x0 = hcat((Float64.(T.PD.x_init) for T in TOPs)...)
+  bounds = [gusto_goal_bounds(T.PD.goal_set, n, T.tf_guess) for T in TOPs]
+  lo, hi = hcat(first.(bounds)...), hcat(last.(bounds)...)
+  tf = Float64[T.tf_guess for T in TOPs]
+  B = Q * K
+  gusto_check(ccall((:gusto_set_problems_trajlib, libgusto_hip), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+                    h, lib.h, Q, K, x0, lo, hi, tf, C_NULL), h, "set_problems_trajlib")
+  entry, nfound = zeros(Cint, K, Q), zeros(Cint, Q)
+  gusto_check(ccall((:gusto_get_trajlib_seeds, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}),
+                    h, entry, C_NULL, nfound), h, "get_trajlib_seeds")
+  gusto_check(ccall((:gusto_solve, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Cint), h, max_iter, force), h, "solve")
+  X, U = zeros(n, N, B), zeros(m, N, B)
+  gusto_check(ccall((:gusto_get_traj, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), h, X, U), h, "get_traj")
+  its, conv, succ, stop = zeros(Cint, B), zeros(Cint, B), zeros(Cint, B), zeros(Cint, B)
+  gusto_check(ccall((:gusto_get_status, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ptr{Cvoid}),
+                    h, its, conv, succ, stop, C_NULL), h, "get_status")
+  duals = zeros(n, B)
+  gusto_check(ccall((:gusto_get_dual, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, duals), h, "get_dual")
+  msec = Ref{Cdouble}(0.)
+  ccall((:gusto_last_solve_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, msec)
+  Hs = gusto_histories(h, B)
+  gusto_check(ccall((:gusto_select_best, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cint}), h, K, C_NULL, C_NULL), h, "select_best")
+  win, wp, best = zeros(Cint, Q), zeros(Cint, Q), zeros(Q)
+  GC.@preserve win wp best begin
+    rep = GustoBestReport(pointer(win), pointer(wp), C_NULL, pointer(best), C_NULL, C_NULL)
+    gusto_check(ccall((:gusto_get_best, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoBestReport}), h, rep), h, "get_best")
+  end
+  result = Vector{Any}(undef, Q)
+  for q in 1:Q
+    j = win[q] >= 0 ? wp[q] + 1 : (q - 1) * K + 1      # without a winner: start 1 of the query
+    SCPP = SCPProblem(TOPs[q])
+    SCPP.param.alg = SCPParam_GuSTO(model)
+    SCPS = SCPSolution(SCPP, Trajectory(X[:, :, j], U[:, :, j], TOPs[q].tf_guess))
+    gusto_fill_solution!(SCPS, SCPP.param.alg, Hs, j, its[j], conv[j], succ[j], stop[j], duals[:, j])
+    SCPS.total_time = msec[] / 1e3 / B
+    SCPS.iter_elapsed_times = vcat(0., fill(SCPS.total_time / max(1, its[j]), its[j]))
+    SCPP.param.obstacle_toggle_distance = SCPP.param.alg.Δ_vec[end] / 8 + model.clearance
+    TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
+    result[q] = win[q] >= 0 ? (win[q] + 1, best[q], entry[win[q] + 1, q] + 1) : (0, Inf, 0)
+  end
+  if learn && any(win .>= 0)
+    mask = zeros(Cint, B)
+    mask[wp[win .>= 0] .+ 1] .= 1
+    trajlib_add!(lib, h, B; mask=mask)
+  end
+  ccall((:gusto_destroy, libgusto_hip), Cint, (Ptr{Cvoid},), h)
+  lost = findall(win .< 0)
+  if fallback_fan !== nothing && !isempty(lost)      # the multi-start path for the queries the library could not answer
+    fan = fallback_fan === true ? nothing : fallback_fan
+    again = solve_SCP_multistart_batch!(TOSs[lost], TOPs[lost]; fan=fan, policy=:all, max_iter=max_iter, force=force, device=lib.device)
+    for (i, q) in enumerate(lost)
+      again[i][1] > 0 && (result[q] = (again[i][1], again[i][2], 0))
+    end
+  end
+  result
+end

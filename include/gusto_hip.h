@@ -664,6 +664,87 @@ int gusto_get_best(gusto_handle h, gusto_best_report* out);
 /* the same compact buffers on the device (valid until the next gusto_select_best on the handle); any pointer may be NULL */
 int gusto_get_best_dev(gusto_handle h, const double** X_dev, const double** U_dev, const int** winner_problem_dev);
 
+/* Trajectory library (csrc/trajlib.hip): GuSTO is warm-started at its previous iterate (scp_gusto.jl:100-102), so a query that
+ * starts from the solved trajectory of a similar query needs fewer trips than one that starts from the straight line.  A
+ * library keeps solved trajectories on the device; every query of a batch is seeded from its K nearest entries, retargeted to
+ * its own end points.  No counterpart in the reference; the definitions:
+ * Object: a gusto_trajlib is bound to a model, a horizon N, a capacity cap (1 .. GUSTO_TRAJLIB_MAX_CAP entries; the device
+ *   memory for all of them is allocated at creation) and a device.  Entry e stores x_init [x_dim], the goal centre c [x_dim] by
+ *   the straight line's rule ((lo + hi) / 2 where both are finite, else 0), tf, an integer tag, X [N][x_dim], U [N][u_dim] and a
+ *   compact feature row (below).  Entries keep their insertion order; that index is their identity.  A library is not
+ *   thread-safe.  Every call that touches one returns only after its device work is complete.
+ * Distance between query q and entry e, xi = x_init:
+ *     d2(q, e) = sum_i w_init[i] (xi_q[i] - xi_e[i])^2 + sum_i w_goal[i] (c_q[i] - c_e[i])^2 + w_tf (tf_q - tf_e)^2
+ *   accumulated in that order from 0.  The weights are fixed at creation, non-negative and finite (else GUSTO_ERR_ARG); only
+ *   the entries with a positive weight are read, and only they are stored in the feature row: a freeflyerSE2 search reads 96 B
+ *   per entry with the defaults, 32 B with weights on the position alone, not the trajectory.  The default, 1 on the model's
+ *   x_dim entries of both vectors and w_tf = 0, is a PLACEHOLDER: the states have different units, the caller sets it (as dx0
+ *   of gusto_simulate_opts).  The heading is in by default because a DubinsCar seed with another heading is a poor one.
+ * Neighbours: the eligible entries of query q are all entries, or, when the query tags are given, those with tag_e == tag_q.
+ *   Neighbour j of q is the j-th smallest eligible entry in ascending (d2, e): ties go to the lowest entry; an entry whose d2
+ *   is NaN is never a neighbour (+inf is a number).  n_found[q] = min(K, eligible entries whose d2 is a number).
+ * Layout: Bq queries with K neighbours each become the B = Bq K problems of the handle, the layout of
+ *   gusto_set_problems_multistart: problem b = q K + j is seeded from neighbour j of query q, so gusto_select_best with the same
+ *   K and gusto_set_active work on them unchanged.
+ * Retargeting, t_k = k / (N - 1), k = 0 .. N-1, on every state entry i (the quaternion entries of AstrobeeSE3Manifold
+ *   included: the affine correction the straight line gives them):
+ *     X0[k][i] = X_e[k][i] + ((1 - t_k) (xi_q[i] - xi_e[i]) + t_k (c_q[i] - c_e[i])),   U0 = U_e;
+ *   knot 0 is written as xi_q itself.  A query whose x_init and centre equal an entry's gets that entry's X back as numbers:
+ *   only exact zeros are added.  tf is NOT retargeted: an entry solved for another tf is copied as it is.
+ * Starts j >= n_found[q] report entry = -1, dist2 = +inf and are the straight line, bit for bit what gusto_set_problems with
+ *   X0 = NULL writes, U0 = 0: an empty library gives K straight lines.
+ * Out of scope: a diversity rule among the K neighbours, resampling between horizons, eviction, TrajOpt handles, more than one
+ *   device (a library travels by gusto_trajlib_get and gusto_trajlib_add_host).
+ * Search kernel: one wavefront per query; the lanes stride over the feature rows, each keeps its K best in registers, then K
+ *   rounds of two reductions (the smallest d2, then the lowest entry among the lanes that hold it).  Fixed order, no atomics,
+ *   nothing crosses a query: a query's seeds are the same bit for bit in any batch. */
+#define GUSTO_TRAJLIB_MAX_K 8
+#define GUSTO_TRAJLIB_MAX_CAP (1 << 20)
+typedef struct gusto_trajlib_s* gusto_trajlib;
+typedef struct {
+    double w_init[GUSTO_MAXN], w_goal[GUSTO_MAXN];   /* weights on x_init and on the goal centre; the entries behind x_dim are ignored */
+    double w_tf;
+    int lds_tile;   /* 1 (default): the wavefronts of a workgroup share each tile of feature rows through LDS; 0: every wavefront
+                     * reads the rows from global memory.  The same seeds bit for bit; a measurement switch (profiles/trajlib.txt) */
+} gusto_trajlib_opts;
+/* 1 on the model's x_dim entries of w_init and w_goal (0 behind them), w_tf = 0, lds_tile = 1 */
+int gusto_default_trajlib_opts(int model_id, gusto_trajlib_opts* o);
+/* opts = NULL: the defaults.  GUSTO_ERR_ARG: an unknown model, N outside 3 .. 256, cap outside 1 .. GUSTO_TRAJLIB_MAX_CAP, a weight
+ * that is negative or not finite, lds_tile other than 0 / 1; GUSTO_ERR_NO_DEVICE as gusto_create */
+int gusto_trajlib_create(gusto_trajlib* lib, int model_id, int N, int cap, int device, const gusto_trajlib_opts* opts);
+int gusto_trajlib_destroy(gusto_trajlib lib);
+const char* gusto_trajlib_last_error(gusto_trajlib lib);   /* lib = NULL: the last error of a failed creation */
+int gusto_trajlib_size(gusto_trajlib lib, int* count, int* cap);   /* either pointer may be NULL */
+int gusto_trajlib_clear(gusto_trajlib lib);
+/* Appends the problems of handle h whose mask[b] is nonzero, in ascending b, with their current trajectories: a device-to-device
+ * compaction, one kernel, the destination of a problem being the count of the selected problems before it, summed in a fixed
+ * order (no atomics).  mask [B] (HOST), or NULL = converged && successful as gusto_get_status reports them; tag [B] (HOST) the
+ * tags of the problems, or NULL = 0; n_added may be NULL.  The call completes a pending gusto_solve_async on h.
+ * GUSTO_ERR_ARG: a model, N or device that differ, a TrajOpt handle; and a selection that does not fit the remaining
+ * capacity: nothing is appended then and n_added = 0.  GUSTO_ERR_STATE: a handle without problems. */
+int gusto_trajlib_add(gusto_trajlib lib, gusto_handle h, const int* mask, const int* tag, int* n_added);
+/* Appends n entries from HOST arrays: x_init, goal_lo, goal_hi [n][x_dim], tf [n], tag [n] or NULL = 0, X [n][N][x_dim],
+ * U [n][N][u_dim].  A non-finite x_init, tf, X or U and n above the remaining capacity are refused (GUSTO_ERR_ARG, nothing
+ * appended); n = 0 is allowed. */
+int gusto_trajlib_add_host(gusto_trajlib lib, int n, const double* x_init, const double* goal_lo, const double* goal_hi,
+                           const double* tf, const int* tag, const double* X, const double* U);
+/* Copies every entry out, [count] rows each; any pointer may be NULL.  A library written by this call and reloaded by
+ * gusto_trajlib_add_host with goal_lo = goal_hi = goal_c is the same library. */
+int gusto_trajlib_get(gusto_trajlib lib, double* x_init, double* goal_c, double* tf, int* tag, double* X, double* U);
+/* Bq queries seeded from their K nearest entries (definitions above).  x_init, goal_lo, goal_hi [Bq][x_dim], tf [Bq] are HOST
+ * arrays as in gusto_set_problems_multistart; tag [Bq] (HOST), or NULL to ignore the tags.  Afterwards everything
+ * gusto_set_problems does happens unchanged: the history reset, the post-solve stages and the selection invalidated, every
+ * problem active again, the end of a latched scheduler error.
+ * GUSTO_ERR_ARG, nothing launched, the handle left as it was: K outside 1 .. GUSTO_TRAJLIB_MAX_K, Bq < 1, Bq K > batch_cap, a
+ *   null array (tag excepted), a null library, a TrajOpt handle, a library of another model, N or device. */
+int gusto_set_problems_trajlib(gusto_handle h, gusto_trajlib lib, int Bq, int K, const double* x_init, const double* goal_lo,
+                               const double* goal_hi, const double* tf, const int* tag);
+/* The seeds of the last gusto_set_problems_trajlib: entry [B] (-1: the straight line), dist2 [B] (+inf likewise), n_found [Bq];
+ * any pointer may be NULL.  GUSTO_ERR_STATE when the handle's problems were set by another call. */
+int gusto_get_trajlib_seeds(gusto_handle h, int* entry, double* dist2, int* n_found);
+/* GPU time of search plus retargeting of that call, from HIP events on the handle's stream */
+int gusto_last_trajlib_ms(gusto_handle h, double* ms);
+
 /* One convex subproblem per problem (what scp_gusto.jl:82-104 builds and solves in one trip), linearised at
  * (Xp,Up)[b] with the given Delta/omega/obstacle_toggle_distance[b].  Used by the parity tests.
  * Outputs: Xn,Un [B][N][.], obj [B] (JuMP.objective_value), status [B] (GUSTO_SOLVER_*), iters [B]. */
@@ -720,6 +801,9 @@ int gusto_dev_get_prof(gusto_handle h, long long* out);
 /* Development hook: the GPU time of the two launches of the last gusto_tvlqr -- linearise, Riccati -- split by a third event
  * between them (tools/tvlqr_time.py).  Either pointer may be NULL; GUSTO_ERR_STATE before the first gusto_tvlqr. */
 int gusto_dev_tvlqr(gusto_handle h, double* linearise_ms, double* riccati_ms);
+/* Development hook: the GPU time of the two launches of the last gusto_set_problems_trajlib -- search, retargeting -- split by a
+ * third event between them (tools/trajlib_rate.py).  Either pointer may be NULL; GUSTO_ERR_STATE as gusto_last_trajlib_ms. */
+int gusto_dev_trajlib(gusto_handle h, double* search_ms, double* retarget_ms);
 /* Development hook: shape of the last gusto_solve / gusto_subproblem launch -- resident (persistent) workgroups, dynamic
  * LDS bytes per workgroup, workgroups per CU.  GUSTO_ERR_STATE before the first launch.  (The freeflyerSE2 N = 50 kernel
  * is tuned to 4 problems per CU: 40 664 B of the 160 KiB; tests/test_gpu_parity.py guards it.) */
