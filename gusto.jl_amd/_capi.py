@@ -38,6 +38,7 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_default_trajlib_opts", "gusto_trajlib_create", "gusto_trajlib_destroy", "gusto_trajlib_last_error", "gusto_trajlib_size",
            "gusto_trajlib_clear", "gusto_trajlib_add", "gusto_trajlib_add_host", "gusto_trajlib_get", "gusto_set_problems_trajlib",
            "gusto_get_trajlib_seeds", "gusto_last_trajlib_ms",
+           "gusto_set_problems_replan", "gusto_set_problems_replan_knots", "gusto_get_replan", "gusto_last_replan_ms",
            "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr", "gusto_dev_trajlib"]
 
 
@@ -155,6 +156,7 @@ class BestReport(C.Structure):
 
 
 TRAJLIB_MAX_K, TRAJLIB_MAX_CAP = 8, 1 << 20   # GUSTO_TRAJLIB_MAX_K, GUSTO_TRAJLIB_MAX_CAP
+REPLAN_SOURCE = {"traj": 0, "best": 1}        # GUSTO_REPLAN_TRAJ, GUSTO_REPLAN_BEST
 
 
 class TrajLibOpts(C.Structure):
@@ -203,7 +205,7 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(_ROOT, "include"), "-fPIC",
              "-Wno-unused-value", "-Wno-pass-failed"]
-    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "trajlib", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
+    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "trajlib", "replan", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
     bdir = os.path.join(_HERE, "build")
     os.makedirs(bdir, exist_ok=True)
 
@@ -316,6 +318,10 @@ def lib():
         L.gusto_get_trajlib_seeds.argtypes = [vp, vp, vp, vp]
         L.gusto_last_trajlib_ms.argtypes = [vp, C.POINTER(C.c_double)]
         L.gusto_dev_trajlib.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.gusto_set_problems_replan.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp]
+        L.gusto_set_problems_replan_knots.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp]
+        L.gusto_get_replan.argtypes = [vp, vp, vp, vp]
+        L.gusto_last_replan_ms.argtypes = [vp, C.POINTER(C.c_double)]
         L.gusto_default_trajopt_params.argtypes = [ci, C.POINTER(TrajOptParams)]
         L.gusto_create_trajopt.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci]
         L.gusto_set_trajopt_params.argtypes = [vp, C.POINTER(TrajOptParams)]
@@ -492,7 +498,7 @@ class BatchSolver:
         self._chk(self.L.gusto_set_problems(self.h, B, x_init.ctypes.data, goal_lo.ctypes.data, goal_hi.ctypes.data,
                                             tf.ctypes.data, None if X0 is None else self._keep[4].ctypes.data,
                                             None if U0 is None else self._keep[5].ctypes.data), "set_problems")
-        self.B = B
+        self.B, self._tf = B, tf.copy()
 
     def set_problems_multistart(self, x_init, goal_lo, goal_hi, tf, fan, boxes=None, spheres=None):
         """gusto_set_problems_multistart: Bq queries x K = len(fan) starts become the B = Bq K problems of the handle, problem
@@ -506,7 +512,7 @@ class BatchSolver:
         K = fan.shape[0]
         self._chk(self.L.gusto_set_problems_multistart(self.h, Bq, K, x_init.ctypes.data, goal_lo.ctypes.data, goal_hi.ctypes.data,
                                                        tf.ctypes.data, fan.ctypes.data), "set_problems_multistart")
-        self.B = Bq * K
+        self.B, self._tf = Bq * K, np.repeat(tf, K)
         if boxes is not None or spheres is not None:
             rep = lambda tables: None if tables is None else [t for t in tables for _ in range(K)]
             self.set_env_batch(rep(boxes) if boxes is not None else [None] * self.B, rep(spheres))
@@ -519,6 +525,7 @@ class BatchSolver:
         el = None if eligible is None else _arr(np.asarray(eligible).astype(bool), np.int32).reshape(self.B)
         self._chk(self.L.gusto_select_best(self.h, int(K), None if sc is None else sc.ctypes.data,
                                            None if el is None else el.ctypes.data), "select_best")
+        self._select_K = int(K)
         return self.get_best(self.B // int(K))
 
     def get_best(self, Bq):
@@ -548,7 +555,7 @@ class BatchSolver:
         tg = None if tag is None else _arr(tag, np.int32).reshape(Bq)
         self._chk(self.L.gusto_set_problems_trajlib(self.h, lib.h, Bq, K, x_init.ctypes.data, goal_lo.ctypes.data, goal_hi.ctypes.data,
                                                     tf.ctypes.data, None if tg is None else tg.ctypes.data), "set_problems_trajlib")
-        self.B, self._trajlib_K = Bq * K, K
+        self.B, self._trajlib_K, self._tf = Bq * K, K, np.repeat(tf, K)
         if boxes is not None or spheres is not None:
             rep = lambda tables: None if tables is None else [t for t in tables for _ in range(K)]
             self.set_env_batch(rep(boxes) if boxes is not None else [None] * self.B, rep(spheres))
@@ -572,6 +579,82 @@ class BatchSolver:
         a, b = C.c_double(), C.c_double()
         self._chk(self.L.gusto_dev_trajlib(self.h, C.byref(a), C.byref(b)), "dev_trajlib")
         return a.value, b.value
+
+    def _replan_args(self, B, goal_lo, goal_hi, mask):
+        if (goal_lo is None) != (goal_hi is None):
+            raise ValueError("replan: goal_lo and goal_hi are given together or not at all")
+        lo = None if goal_lo is None else _arr(np.broadcast_to(np.asarray(goal_lo, dtype=np.float64), (B, self.n)))
+        hi = None if goal_hi is None else _arr(np.broadcast_to(np.asarray(goal_hi, dtype=np.float64), (B, self.n)))
+        mk = None if mask is None else _arr(np.asarray(mask).astype(bool), np.int32).reshape(B)
+        return lo, hi, mk
+
+    def replan_tf(self, tau, src=None, source="traj"):
+        """tf' [B] = (1 - tau) tf_s of a set_problems_replan* call with these arguments, from the host's record of the source's tf
+        (the arithmetic of the device); None when the source's problems were set from device pointers"""
+        src = self if src is None else src
+        tf_s = getattr(src, "_tf", None)
+        if tf_s is None:
+            return None
+        tau = np.atleast_1d(np.asarray(tau, dtype=np.float64))
+        if source == "best":
+            K = getattr(src, "_select_K", None)
+            if K is None:
+                return None
+            try:
+                wp = src.get_best(src.B // K)["winner_problem"][:len(tau)]
+            except GustoError:      # (no selection: the call itself says so)
+                return None
+            if len(wp) < len(tau):
+                return None
+            tf_s = tf_s[np.where(wp >= 0, wp, np.arange(len(tau)) * K)]
+        return (1 - tau) * tf_s[:len(tau)] if len(tf_s) >= len(tau) else None
+
+    def _replan_env(self, boxes, spheres):
+        if boxes is not None or spheres is not None:
+            self.set_env_batch(boxes if boxes is not None else [None] * self.B, spheres)
+
+    def set_problems_replan(self, tau, x_now, src=None, source="traj", goal_lo=None, goal_hi=None, mask=None, boxes=None, spheres=None):
+        """gusto_set_problems_replan: B = len(x_now) new problems from the states x_now [B, n] to the goals of the source problems
+        (or goal_lo / goal_hi [B, n]) in the time that is left, tf' = (1 - tau) tf_s, every seeded one started from its source
+        trajectory shifted by the fraction tau [B] already flown and bent to x_now (and to a moved goal), the others from the
+        straight line.  src: the BatchSolver that holds the plans (None: this one; its N may differ); source "traj": problem b of
+        src, "best": query b of its last select_best.  mask [B]: which problems are seeded (None: the converged and successful
+        ones / the queries with a winner).  boxes / spheres: one keep-out set per problem into set_env_batch; None leaves the
+        environment as it is.  What was used: replan_info()."""
+        x_now = _arr(x_now).reshape(-1, self.n)
+        B = x_now.shape[0]
+        tau = _arr(np.broadcast_to(np.asarray(tau, dtype=np.float64), (B,)))
+        lo, hi, mk = self._replan_args(B, goal_lo, goal_hi, mask)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        tf_new = self.replan_tf(tau, src, source)
+        self._chk(self.L.gusto_set_problems_replan(self.h, None if src is None else src.h, REPLAN_SOURCE[source], B, tau.ctypes.data,
+                                                   x_now.ctypes.data, ptr(lo), ptr(hi), ptr(mk)), "set_problems_replan")
+        self.B, self._tf = B, tf_new
+        self._replan_env(boxes, spheres)
+
+    def set_problems_replan_knots(self, knot, sample, src=None, B=None, goal_lo=None, goal_hi=None, mask=None, boxes=None, spheres=None):
+        """gusto_set_problems_replan_knots: set_problems_replan with tau = knot / (Ns - 1) and x_now = Xcl[b, knot_b, sample], read on
+        the device from the knots the last simulate() / simulate_disturbed() on src stored (store_knots = 1).  knot: a scalar or
+        [B]; B: None = every problem of src."""
+        B = int((self if src is None else src).B if B is None else B)
+        kn = _arr(np.broadcast_to(np.asarray(knot), (B,)), np.int32)
+        lo, hi, mk = self._replan_args(B, goal_lo, goal_hi, mask)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        tf_new = self.replan_tf(kn / float((self if src is None else src).N - 1), src)
+        self._chk(self.L.gusto_set_problems_replan_knots(self.h, None if src is None else src.h, B, kn.ctypes.data, int(sample), ptr(lo),
+                                                         ptr(hi), ptr(mk)), "set_problems_replan_knots")
+        self.B, self._tf = B, tf_new
+        self._replan_env(boxes, spheres)
+
+    def replan_info(self):
+        """gusto_get_replan: a dict of seeded [B] (bool), tau [B], x_now [B, n] of the last set_problems_replan*"""
+        sd, tau, x = np.zeros(self.B, np.int32), np.zeros(self.B), np.zeros((self.B, self.n))
+        self._chk(self.L.gusto_get_replan(self.h, sd.ctypes.data, tau.ctypes.data, x.ctypes.data), "get_replan")
+        return dict(seeded=sd.astype(bool), tau=tau, x_now=x)
+
+    def last_replan_ms(self):
+        """gusto_last_replan_ms: GPU time of the last set_problems_replan*"""
+        return self._last_ms("last_replan_ms")
 
     def set_trust_state(self, Delta=None, omega=None):
         """gusto_set_trust_state: the caller's own Delta_vec[end] / omega_vec[end] for the next trip of every problem."""
@@ -610,7 +693,7 @@ class BatchSolver:
         """gusto_set_problems_dev: inputs already resident in HBM (raw device pointers)."""
         self._chk(self.L.gusto_set_problems_dev(self.h, int(B), x_init_ptr, goal_lo_ptr, goal_hi_ptr, tf_ptr, X0_ptr,
                                                 U0_ptr), "set_problems_dev")
-        self.B = int(B)
+        self.B, self._tf = int(B), None
 
     def last_solve_ms(self):
         return self._last_ms("last_solve_ms")
@@ -1087,6 +1170,11 @@ class TrajOptSolver(BatchSolver):
 
     def select_best(self, *a, **k):
         raise GustoError("TrajOptSolver: select_best is not supported on TrajOpt handles (gusto_select_best answers GUSTO_ERR_ARG)")
+
+    def set_problems_replan(self, *a, **k):
+        raise GustoError("TrajOptSolver: replanning is not supported on TrajOpt handles (gusto_set_problems_replan answers GUSTO_ERR_ARG)")
+
+    set_problems_replan_knots = set_problems_replan
 
     def set_problems_trajlib(self, *a, **k):
         raise GustoError("TrajOptSolver: library seeds are not supported on TrajOpt handles (gusto_set_problems_trajlib answers GUSTO_ERR_ARG)")

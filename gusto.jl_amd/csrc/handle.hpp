@@ -5,6 +5,7 @@
 
 #include <string>
 #include <utility>
+#include <vector>
 
 #include "common.hpp"
 
@@ -187,6 +188,22 @@ struct __attribute__((visibility("hidden"))) TrajlibState {
     void invalidate() { have = false; }
 };
 
+// Receding-horizon replanning (replan.hip): In the HOST inputs of the call as its kernel reads them (tau [B], x_now [B][n], then
+// the caller's goal_lo, goal_hi [B][n] each when given) and Meta [2][B] seeded and source problem; G (tf [Bs], goal_lo, goal_hi
+// [Bs][n]) and Xs, Us the staging copies of the source's rows when source and destination share memory; Xnow [B][n] the states
+// gusto_set_problems_replan_knots gathers (Meta holds its knots meanwhile).  seeded, tau, x_now: what the last call used, on the
+// host (gusto_get_replan)
+struct __attribute__((visibility("hidden"))) ReplanState {
+    DevBuf<double> In, G, Xs, Us, Xnow;
+    DevBuf<int> Meta;
+    std::vector<int> seeded;
+    std::vector<double> tau, x_now;
+    bool have = false;
+    DevEvent t0, t1;
+    double last_ms = 0.0;
+    void invalidate() { have = false; }
+};
+
 // The library itself: `count` of `cap` entries on `device`, entry e at row e of xi, c [cap][n], tf, tag [cap], X [cap][N][n], U
 // [cap][N][m].  The features are the F positive-weight terms of the distance, in its order of summation: term f has the weight
 // w[f] and reads entry fmap[f] & 15 of x_init (fmap[f] >> 4 == 0), of the goal centre (1) or tf (2).  Feat is feature-major,
@@ -255,6 +272,7 @@ struct gusto_handle_s {
     ShootState shoot; VerifyState verify; TvlqrState tvlqr; SimulateState simulate; LincovState lincov;   // the post-solve stages
     SelectState select;
     TrajlibState trajlib;
+    ReplanState replan;
     std::string err;
 
     // (the buffers and events free themselves; the caller has made `device` current: gusto_destroy)

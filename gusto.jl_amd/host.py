@@ -967,6 +967,90 @@ def solve_SCP_trajlib_batch(TOSs, TOPs, lib, K=1, fallback_fan=None, learn=False
     return out
 
 
+def _check_replan_tf(tf_new, who):
+    """the reference's only row on the final time, Tf >= 0.1 (scp_gusto.jl:248-250), on tf' as TrajectoryOptimizationProblem
+    checks it on tf_guess"""
+    if tf_new is None:
+        raise ValueError(who + ": the tf of the source problems is not known on the host (they were set from device pointers)")
+    if (np.asarray(tf_new) < 0.1).any():
+        bad = int(np.flatnonzero(np.asarray(tf_new) < 0.1)[0])
+        raise ValueError(f"{who}: tf' = (1 - tau) tf of problem {bad} is {float(np.asarray(tf_new)[bad]):g}; the only row on Tf is Tf >= 0.1 "
+                         "(scp_gusto.jl:248-250)")
+
+
+def replan_batch(bs, tau, x_now, src=None, source="traj", goal_lo=None, goal_hi=None, mask=None, boxes=None, spheres=None):
+    """Receding-horizon replanning on a BatchSolver (gusto_set_problems_replan): problem b restarts from the state x_now[b] with
+    the time that is left, tf' = (1 - tau[b]) tf, seeded from its plan on `src` (None: bs itself) shifted by tau and bent to
+    x_now; the arguments are those of BatchSolver.set_problems_replan.  tf' must respect the reference's Tf >= 0.1.  Returns
+    replan_info()."""
+    x_now = np.asarray(x_now, float).reshape(-1, bs.n)
+    tau = np.broadcast_to(np.asarray(tau, float), (len(x_now),))
+    _check_replan_tf(bs.replan_tf(tau, src, source), "replan_batch!")
+    bs.set_problems_replan(tau, x_now, src=src, source=source, goal_lo=goal_lo, goal_hi=goal_hi, mask=mask, boxes=boxes, spheres=spheres)
+    return bs.replan_info()
+
+
+def solve_SCP_receding_batch(TOSs, TOPs, steps, knots_per_step, sim_opts=None, disturb=None, tvlqr_opts=None, max_iter=30, force=False,
+                             device=0):
+    """A receding-horizon loop on one handle.  Per step: gusto_solve, gusto_tvlqr, gusto_simulate_disturbed with store_knots = 1
+    and two samples (sample 0 is the unperturbed one, so sample 1 is the flight), then gusto_set_problems_replan_knots with
+    knot = knots_per_step and sample = 1: the next step plans from where the roll-out is after knots_per_step knots, to the same
+    goals, in the time that is left.  All TOPs share model and N; each may bring its own environment.  sim_opts / disturb /
+    tvlqr_opts: dicts of the fields of gusto_simulate_opts / gusto_disturb_opts / gusto_tvlqr_opts (n_samples and store_knots are
+    set here).
+
+    Returns one dict per step: iterations, converged, successful [B] and solve_ms of the step's solve; x_now [B, n], tau [B],
+    seeded [B] and replan_ms of the replan that ends it (x_now is the x_init of the next step).  TOSs take the last plan."""
+    who = "solve_SCP_receding_batch!"
+    if len(TOSs) != len(TOPs) or not TOPs:
+        raise ValueError(who + ": need as many solutions as problems, at least one")
+    TOP0 = TOPs[0]
+    model, N = TOP0.PD.model, TOP0.N
+    n, B = model.x_dim, len(TOPs)
+    for t in TOPs[1:]:
+        if type(t.PD.model) is not type(model) or t.N != N:
+            raise ValueError(who + ": all problems must share the model type and N")
+    if steps < 1 or not 0 <= knots_per_step <= N - 2:
+        raise ValueError(who + ": need steps >= 1 and 0 <= knots_per_step <= N - 2")
+    same_env = all(np.array_equal(t.PD.env.boxes, TOP0.PD.env.boxes) and np.array_equal(t.PD.env.spheres, TOP0.PD.env.spheres)
+                   for t in TOPs[1:])
+    sp, mp = _capi.default_params(model.model_id)
+    bounds = [_goal_bounds(t.PD.goal_set, n, t.tf_guess) for t in TOPs]
+    sim = dict(sim_opts or {})
+    sim.update(n_samples=2, store_knots=1)
+    bs = BatchSolver(model.model_id, N, B, hist_cap=_hist_cap(max_iter), device=device, boxes=TOP0.PD.env.boxes,
+                     spheres=TOP0.PD.env.spheres, scp_params=sp, model_params=mp)
+    out = []
+    try:
+        if not same_env:
+            bs.set_env_batch([t.PD.env.boxes for t in TOPs], [t.PD.env.spheres for t in TOPs])
+        bs.set_problems(np.stack([t.PD.x_init for t in TOPs]), np.stack([b[0] for b in bounds]), np.stack([b[1] for b in bounds]),
+                        np.array([t.tf_guess for t in TOPs]))
+        for _ in range(steps):
+            tf_now = bs._tf.copy()
+            bs.solve(max_iter, force)
+            snap = _fetch(bs)
+            solve_ms = bs.last_solve_ms()
+            bs.tvlqr(tvlqr_opts or {})
+            bs.simulate_disturbed(sim, disturb)
+            _check_replan_tf(bs.replan_tf(np.full(B, knots_per_step / (N - 1))), who)
+            bs.set_problems_replan_knots(knots_per_step, 1)
+            info = bs.replan_info()
+            out.append(dict(iterations=snap["st"]["iterations"].copy(), converged=snap["st"]["converged"].copy(),
+                            successful=snap["st"]["successful"].copy(), solve_ms=solve_ms, x_now=info["x_now"], tau=info["tau"],
+                            seeded=info["seeded"], replan_ms=bs.last_replan_ms()))
+        for q in range(B):
+            SCPP = SCPProblem(TOPs[q])
+            SCPS = SCPSolution(SCPP, init_traj_straightline(TOPs[q]))
+            _fill_solution(SCPS, SCPP, snap, q, solve_ms * 1e-3 / B)
+            SCPS.traj.Tf = float(tf_now[q])
+            SCPS.traj.dt = SCPS.traj.Tf / (N - 1)
+            TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
+    finally:
+        bs.close()
+    return out
+
+
 def solve_batch_sharded(model_id, N, x_init, goal_lo, goal_hi, tf, world_size, rank, device=0, max_iter=30, boxes=None,
                         spheres=None, group=None, solver=None):
     """The multi-GPU path of SURVEY.md 8(e) in one call (one process per GPU, launched by torch.distributed.run):

@@ -879,3 +879,118 @@ function solve_SCP_trajlib_batch!(TOSs::Vector, TOPs::Vector, lib::TrajLib; K=1,
   end
   result
 end
+
+# ---- receding-horizon replanning: a batch restarted from where each plan is (csrc/replan.hip) -----------------------------------
+# After a few knots of flight the robot is not on its plan: gusto_set_problems_replan makes, of every problem of a handle, a new one
+# from the measured state to the same goals in the time that is left, tf' = (1 - tau) tf, started from the solved plan shifted in
+# time and bent to the new start (include/gusto_hip.h states the definitions, the reference has no counterpart).
+# Mirrors gusto.jl_amd/host.py: replan_batch, solve_SCP_receding_batch.  This wrapper has not been run.
+const GUSTO_REPLAN_TRAJ, GUSTO_REPLAN_BEST = 0, 1
+
+# B problems of handle h (x_dim n) replanned from the states x_now [n,B] after the fractions tau [B] of their time.  src: the handle
+# that holds the plans (C_NULL: h itself; its N may differ); source :traj = problem b of src, :best = query b of its last
+# gusto_select_best.  tf_s [B] or nothing: the tf of the source problems, for the reference's only row on the final time,
+# Tf >= 0.1, checked on tf'.  goal_lo / goal_hi [n,B] or nothing = the source's goals; mask [B] or nothing = the converged and
+# successful plans (the queries with a winner) are seeded, the others start from the straight line.
+# Returns (seeded [B], tau [B], x_now [n,B], ms).
+function replan_batch!(h::Ptr{Cvoid}, B::Integer, n::Integer, tau, x_now; src::Ptr{Cvoid}=Ptr{Cvoid}(C_NULL), source=:traj, tf_s=nothing,
+                       goal_lo=nothing, goal_hi=nothing, mask=nothing)
+  source in (:traj, :best) || error("replan_batch!: source is :traj or :best")
+  (goal_lo === nothing) == (goal_hi === nothing) || error("replan_batch!: goal_lo and goal_hi are given together or not at all")
+  t = tau isa Number ? fill(Float64(tau), B) : Float64.(collect(tau))
+  tf_s === nothing || all((1 .- t) .* tf_s .>= 0.1) ||
+    error("replan_batch!: tf' = (1 - tau) tf violates the only row on Tf, Tf >= 0.1 (scp_gusto.jl:248-250)")
+  x = Matrix{Float64}(x_now)
+  lo = goal_lo === nothing ? nothing : Matrix{Float64}(goal_lo); hi = goal_hi === nothing ? nothing : Matrix{Float64}(goal_hi)
+  mk = mask === nothing ? nothing : Cint.(mask .!= 0)
+  ptr(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+  GC.@preserve t x lo hi mk gusto_check(ccall((:gusto_set_problems_replan, libgusto_hip), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+                    h, src, source == :best ? GUSTO_REPLAN_BEST : GUSTO_REPLAN_TRAJ, B, t, x, ptr(lo), ptr(hi),
+                    mk === nothing ? Ptr{Cint}(C_NULL) : pointer(mk)), h, "set_problems_replan")
+  gusto_replan_info(h, B, n)
+end
+
+function gusto_replan_info(h::Ptr{Cvoid}, B::Integer, n::Integer)
+  seeded, t, x = zeros(Cint, B), zeros(B), zeros(n, B)
+  gusto_check(ccall((:gusto_get_replan, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}), h, seeded, t, x), h, "get_replan")
+  ms = Ref{Cdouble}(0.0)
+  gusto_check(ccall((:gusto_last_replan_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, ms), h, "last_replan_ms")
+  (seeded = seeded .!= 0, tau = t, x_now = x, ms = ms[])
+end
+
+# A receding-horizon loop on one handle.  Per step: gusto_solve, the gains (tvlqr_batch!), the flight (simulate_batch! as
+# gusto_simulate_disturbed with two samples and store_knots: sample 1 of the C ABI is the first perturbed one), then
+# gusto_set_problems_replan_knots with knot = knots_per_step and sample = 1: the next step plans from where the roll-out is, to the
+# same goals, in the time that is left.  All TOPs share model, N and the environment.  Returns one named tuple per step:
+# iterations, converged, successful [B], solve_ms of the step's solve; x_now [n,B], tau [B], seeded [B], replan_ms of the replan
+# that ends it.  TOSs take the last plan.
+function solve_SCP_receding_batch!(TOSs::Vector, TOPs::Vector, steps::Integer, knots_per_step::Integer; plant_rel=0.0, dw=0.0, dx0=0.01,
+                                   Q=1.0, R=1.0, Qf=1.0, max_iter=30, force=false, device=0)
+  length(TOSs) == length(TOPs) && !isempty(TOPs) || error("solve_SCP_receding_batch!: need as many solutions as problems, at least one")
+  TOP0 = TOPs[1]; model, N = TOP0.PD.model, TOP0.N
+  n, m, B = model.x_dim, model.u_dim, length(TOPs)
+  all(T -> typeof(T.PD.model) == typeof(model) && T.N == N && T.PD.env === TOP0.PD.env, TOPs) ||
+    error("solve_SCP_receding_batch!: all problems must share the model type, N and the environment")
+  (steps >= 1 && 0 <= knots_per_step <= N - 2) || error("solve_SCP_receding_batch!: need steps >= 1 and 0 <= knots_per_step <= N - 2")
+  alg0 = SCPParam_GuSTO(model)
+  sp = GustoScpParams(alg0.Δ0, alg0.ω0, alg0.ω_max, alg0.ε, alg0.ρ0, alg0.ρ1, alg0.β_succ, alg0.β_fail, alg0.γ_fail,
+                      SCPParam(model, TOP0.fixed_final_time).convergence_threshold)
+  href = Ref{Ptr{Cvoid}}(C_NULL)
+  gusto_check(ccall((:gusto_create, libgusto_hip), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Cint),
+                    href, gusto_model_id(model), N, B, gusto_hist_cap(max_iter), device), href[], "create")
+  h = href[]
+  gusto_check(ccall((:gusto_set_params, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoScpParams}, Ref{GustoModelParams}),
+                    h, sp, gusto_model_params(TOP0.PD.robot, model)), h, "set_params")
+  boxes, spheres = gusto_env_tables(TOP0.PD.env)
+  gusto_check(ccall((:gusto_set_env, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+                    h, length(boxes) ÷ 6, boxes, length(spheres) ÷ 4, spheres), h, "set_env")
+  x0 = hcat((Float64.(T.PD.x_init) for T in TOPs)...)
+  bounds = [gusto_goal_bounds(T.PD.goal_set, n, T.tf_guess) for T in TOPs]
+  lo, hi = hcat(first.(bounds)...), hcat(last.(bounds)...)
+  tf = Float64[T.tf_guess for T in TOPs]
+  gusto_check(ccall((:gusto_set_problems, libgusto_hip), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    h, B, x0, lo, hi, tf, C_NULL, C_NULL), h, "set_problems")
+  tau = knots_per_step / (N - 1)
+  knot = fill(Cint(knots_per_step), B)
+  out = Vector{Any}(undef, steps)
+  X, U = zeros(n, N, B), zeros(m, N, B)
+  its, conv, succ, stop = zeros(Cint, B), zeros(Cint, B), zeros(Cint, B), zeros(Cint, B)
+  duals = zeros(n, B)
+  msec = Ref{Cdouble}(0.)
+  Hs = nothing
+  tf_plan = copy(tf)
+  for s in 1:steps
+    tf_plan = copy(tf)
+    gusto_check(ccall((:gusto_solve, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Cint), h, max_iter, force), h, "solve")
+    gusto_check(ccall((:gusto_get_traj, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), h, X, U), h, "get_traj")
+    gusto_check(ccall((:gusto_get_status, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ptr{Cvoid}),
+                      h, its, conv, succ, stop, C_NULL), h, "get_status")
+    gusto_check(ccall((:gusto_get_dual, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, duals), h, "get_dual")
+    ccall((:gusto_last_solve_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, msec)
+    Hs = gusto_histories(h, B)
+    tvlqr_batch!(h, B, n, m, N; Q=Q, R=R, Qf=Qf)
+    simulate_batch!(h, B, n, m, N; n_samples=2, dx0=dx0, store_knots=true, plant_rel=plant_rel, dw=dw)
+    tf = (1 - tau) .* tf
+    all(tf .>= 0.1) || error("solve_SCP_receding_batch!: tf' = (1 - tau) tf violates the only row on Tf, Tf >= 0.1 (scp_gusto.jl:248-250)")
+    gusto_check(ccall((:gusto_set_problems_replan_knots, libgusto_hip), Cint,
+                      (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cint}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+                      h, C_NULL, B, knot, 1, C_NULL, C_NULL, C_NULL), h, "set_problems_replan_knots")
+    info = gusto_replan_info(h, B, n)
+    out[s] = (iterations = Int.(its), converged = conv .!= 0, successful = succ .!= 0, solve_ms = msec[], x_now = info.x_now,
+              tau = info.tau, seeded = info.seeded, replan_ms = info.ms)
+  end
+  for q in 1:B
+    SCPP = SCPProblem(TOPs[q])
+    SCPP.param.alg = SCPParam_GuSTO(model)
+    SCPS = SCPSolution(SCPP, Trajectory(X[:, :, q], U[:, :, q], tf_plan[q]))
+    gusto_fill_solution!(SCPS, SCPP.param.alg, Hs, q, its[q], conv[q], succ[q], stop[q], duals[:, q])
+    SCPS.total_time = msec[] / 1e3 / B
+    SCPS.iter_elapsed_times = vcat(0., fill(SCPS.total_time / max(1, its[q]), its[q]))
+    SCPP.param.obstacle_toggle_distance = SCPP.param.alg.Δ_vec[end] / 8 + model.clearance
+    TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
+  end
+  ccall((:gusto_destroy, libgusto_hip), Cint, (Ptr{Cvoid},), h)
+  out
+end

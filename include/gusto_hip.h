@@ -693,8 +693,9 @@ int gusto_get_best_dev(gusto_handle h, const double** X_dev, const double** U_de
  *   only exact zeros are added.  tf is NOT retargeted: an entry solved for another tf is copied as it is.
  * Starts j >= n_found[q] report entry = -1, dist2 = +inf and are the straight line, bit for bit what gusto_set_problems with
  *   X0 = NULL writes, U0 = 0: an empty library gives K straight lines.
- * Out of scope: a diversity rule among the K neighbours, resampling between horizons, eviction, TrajOpt handles, more than one
- *   device (a library travels by gusto_trajlib_get and gusto_trajlib_add_host).
+ * Out of scope: a diversity rule among the K neighbours, resampling between horizons (gusto_set_problems_replan below does it
+ *   for a source handle, Ns != N), eviction, TrajOpt handles, more than one device (a library travels by gusto_trajlib_get and
+ *   gusto_trajlib_add_host).
  * Search kernel: one wavefront per query; the lanes stride over the feature rows, each keeps its K best in registers, then K
  *   rounds of two reductions (the smallest d2, then the lowest entry among the lanes that hold it).  Fixed order, no atomics,
  *   nothing crosses a query: a query's seeds are the same bit for bit in any batch. */
@@ -744,6 +745,60 @@ int gusto_set_problems_trajlib(gusto_handle h, gusto_trajlib lib, int Bq, int K,
 int gusto_get_trajlib_seeds(gusto_handle h, int* entry, double* dist2, int* n_found);
 /* GPU time of search plus retargeting of that call, from HIP events on the handle's stream */
 int gusto_last_trajlib_ms(gusto_handle h, double* ms);
+
+/* Receding-horizon replanning (csrc/replan.hip): after a few knots of flight the robot is not on its plan, and a new plan is
+ * wanted from the measured state to the same goal in the time that is left.  GuSTO is warm-started at its previous iterate
+ * (scp_gusto.jl:100-102), so the solved plan, shifted in time and bent to the new start, is the seed; the trajectory library is
+ * the same idea across queries, this one along time.  No counterpart in the reference; the definitions:
+ * Source handle: src = NULL means h itself; src has the model and the device of h, its horizon Ns may differ from the N of h.
+ * Source rows: GUSTO_REPLAN_TRAJ: source problem b is problem b of src, with its current X [Ns][x_dim], U [Ns][u_dim], tf_s,
+ *   goal_lo and goal_hi; B <= the B of src.  GUSTO_REPLAN_BEST: source b is query b of the last gusto_select_best on src: X and U
+ *   are row b of the compact winner buffers, tf_s and the goals those of problem winner_problem[b]; B <= Bq; src may be h.
+ * Inputs: tau [B] (HOST), the fraction of the source's time already flown, 0 <= tau < 1; x_now [B][x_dim] (HOST), the state to
+ *   start from, finite.
+ * New problem b: x_init = x_now, tf' = (1 - tau) tf_s, and the caller's goal_lo / goal_hi (HOST, [B][x_dim], both or neither);
+ *   NULL: the source problem's goals, copied as they are.
+ * Seeded: seeded[b] = mask[b] != 0 when mask [B] (HOST) is given; without it the source problem is converged && successful as
+ *   gusto_get_status reports them (TRAJ), or the query has a winner (BEST).  A BEST query without a winner is never seeded,
+ *   whatever the mask says; it takes tf_s and its goals from problem b K of src.
+ * Seeded start: t_k = k / (N - 1), k = 0 .. N-1, evaluated in this order:
+ *     sigma_k = (tau (N - 1 - k) + k) (Ns - 1) / (N - 1),   j = min(floor(sigma_k), Ns - 2),   a = sigma_k - j
+ *     S_k = (1 - a) X_s[j] + a X_s[j + 1],   U0[k] = (1 - a) U_s[j] + a U_s[j + 1]
+ *     X0[k][i] = S_k[i] + ((1 - t_k) (x_now[i] - S_0[i]) + t_k (c_new[i] - c_old[i]))
+ *   with c the goal centre by the straight line's rule ((lo + hi) / 2 where both are finite, else 0); the t_k term is skipped
+ *   entirely when no goals are passed.  Knot 0 is written as x_now itself; for knot N - 1, S and U0 are the source's last knot
+ *   itself.  The quaternion entries of AstrobeeSE3Manifold get the same affine treatment as in gusto_set_problems_trajlib.
+ * Identity: with tau = 0, Ns = N, x_now = X_s[0] and no goals the result is the source trajectory as numbers: only exact zeros
+ *   are added.
+ * Unseeded start: the straight line from x_now to the goal centre, U0 = 0: bit for bit what gusto_set_problems with X0 = NULL
+ *   writes for that x_init, goal and tf'.
+ * Afterwards everything gusto_set_problems does happens unchanged: the history reset, the post-solve stages and the selection
+ *   invalidated, every problem active again, the end of a latched scheduler error.  The B of h becomes B.
+ * GUSTO_ERR_ARG: a TrajOpt handle on either side, another model or device, B < 1, B > the batch_cap of h, B above the source's
+ *   count, an unknown source, a null tau or x_now, exactly one goal array, a tau outside [0, 1) or NaN, an x_now that is not
+ *   finite.  GUSTO_ERR_STATE: a source without problems, BEST before a gusto_select_best.  A refused call launches nothing that
+ *   touches the problem arrays of h and leaves h as it was.
+ * Kernel: a thread per (problem, knot), consecutive threads on consecutive knots; no atomics, nothing crosses a problem: a
+ *   problem's start is the same bit for bit in any batch.  When source and destination share memory (src = h) the source rows are
+ *   read from a staging copy made on the stream, device to device.
+ * Out of scope: TrajOpt handles; carrying Delta / omega over (gusto_set_trust_state exists for that); a changed N of h itself;
+ *   more than one device. */
+enum { GUSTO_REPLAN_TRAJ = 0, GUSTO_REPLAN_BEST = 1 };
+int gusto_set_problems_replan(gusto_handle h, gusto_handle src, int source, int B, const double* tau, const double* x_now,
+                              const double* goal_lo, const double* goal_hi, const int* mask);
+/* The same from the stored closed-loop knots of src, GUSTO_REPLAN_TRAJ only: tau_b = knot_b / (Ns - 1) with knot_b in
+ * 0 .. Ns - 2, and x_now[b] = Xcl[b][knot_b][sample][:], read on the device from the knots the last gusto_simulate or
+ * gusto_simulate_disturbed on src stored (store_knots = 1; sample < n_samples): a kernel gathers the B x_dim values into a
+ * staging buffer, which comes to the host in one copy.  An integer knot only: a replan between knots goes through the general
+ * call with any tau.  GUSTO_ERR_ARG also: a null knot, a knot or sample out of range, a stored state that is not finite (a
+ * sample flagged non-finite).  GUSTO_ERR_STATE also: no stored knots on src. */
+int gusto_set_problems_replan_knots(gusto_handle h, gusto_handle src, int B, const int* knot, int sample,
+                                    const double* goal_lo, const double* goal_hi, const int* mask);
+/* What the last of the two calls above used: seeded [B], tau [B], x_now [B][x_dim]; any pointer may be NULL.  GUSTO_ERR_STATE
+ * when the handle's problems were set by another call. */
+int gusto_get_replan(gusto_handle h, int* seeded, double* tau, double* x_now);
+/* GPU time of that call (copies, staging and the kernel), from HIP events on the stream of h; GUSTO_ERR_STATE likewise */
+int gusto_last_replan_ms(gusto_handle h, double* ms);
 
 /* One convex subproblem per problem (what scp_gusto.jl:82-104 builds and solves in one trip), linearised at
  * (Xp,Up)[b] with the given Delta/omega/obstacle_toggle_distance[b].  Used by the parity tests.
