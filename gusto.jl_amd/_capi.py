@@ -39,6 +39,7 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_trajlib_clear", "gusto_trajlib_add", "gusto_trajlib_add_host", "gusto_trajlib_get", "gusto_set_problems_trajlib",
            "gusto_get_trajlib_seeds", "gusto_last_trajlib_ms",
            "gusto_set_problems_replan", "gusto_set_problems_replan_knots", "gusto_get_replan", "gusto_last_replan_ms",
+           "gusto_default_tighten_opts", "gusto_tighten_env", "gusto_get_tighten", "gusto_get_env", "gusto_last_tighten_ms",
            "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr", "gusto_dev_trajlib"]
 
 
@@ -159,6 +160,24 @@ TRAJLIB_MAX_K, TRAJLIB_MAX_CAP = 8, 1 << 20   # GUSTO_TRAJLIB_MAX_K, GUSTO_TRAJL
 REPLAN_SOURCE = {"traj": 0, "best": 1}        # GUSTO_REPLAN_TRAJ, GUSTO_REPLAN_BEST
 
 
+class TightenOpts(C.Structure):
+    """gusto_tighten_opts: the margin in standard deviations and the rules around it"""
+    _fields_ = [("kappa", C.c_double), ("slack", C.c_double), ("margin_cap", C.c_double), ("reach", C.c_double),
+                ("cover_components", C.c_int), ("monotone", C.c_int)]
+
+
+MAX_OBS = 64   # keep-out components per problem
+# gusto_tighten_report in the header's order: (field, dtype, shape as a function of (B, n_obs_max))
+TIGHTEN_FIELDS = tuple((k, np.int32, lambda B, W: (B,)) for k in ("status", "knot", "pair", "n_grown", "blocked")) + \
+                 tuple((k, np.float64, lambda B, W: (B,)) for k in ("min_z_base", "max_margin")) + \
+                 (("margin", np.float64, lambda B, W: (B, W)),)
+
+
+class TightenReport(C.Structure):
+    """gusto_tighten_report: caller-owned arrays"""
+    _fields_ = [(k, C.c_void_p) for k, _, _ in TIGHTEN_FIELDS]
+
+
 class TrajLibOpts(C.Structure):
     """gusto_trajlib_opts"""
     _fields_ = [("w_init", C.c_double * MAXN), ("w_goal", C.c_double * MAXN), ("w_tf", C.c_double), ("lds_tile", C.c_int)]
@@ -205,7 +224,7 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(_ROOT, "include"), "-fPIC",
              "-Wno-unused-value", "-Wno-pass-failed"]
-    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "trajlib", "replan", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
+    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "trajlib", "replan", "tighten", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
     bdir = os.path.join(_HERE, "build")
     os.makedirs(bdir, exist_ok=True)
 
@@ -322,6 +341,11 @@ def lib():
         L.gusto_set_problems_replan_knots.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp]
         L.gusto_get_replan.argtypes = [vp, vp, vp, vp]
         L.gusto_last_replan_ms.argtypes = [vp, C.POINTER(C.c_double)]
+        L.gusto_default_tighten_opts.argtypes = [ci, C.POINTER(TightenOpts)]
+        L.gusto_tighten_env.argtypes = [vp, ci, vp, vp, vp, vp, C.POINTER(TightenOpts)]
+        L.gusto_get_tighten.argtypes = [vp, C.POINTER(TightenReport), C.POINTER(ci)]
+        L.gusto_get_env.argtypes = [vp, C.POINTER(ci), vp, vp, vp, vp]
+        L.gusto_last_tighten_ms.argtypes = [vp, C.POINTER(C.c_double)]
         L.gusto_default_trajopt_params.argtypes = [ci, C.POINTER(TrajOptParams)]
         L.gusto_create_trajopt.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci]
         L.gusto_set_trajopt_params.argtypes = [vp, C.POINTER(TrajOptParams)]
@@ -386,6 +410,14 @@ def default_lincov_opts(model):
     rc = lib().gusto_default_lincov_opts(model, C.byref(o))
     if rc:
         raise ValueError(f"gusto_default_lincov_opts({model}) -> {rc}")
+    return o
+
+
+def default_tighten_opts(model):
+    o = TightenOpts()
+    rc = lib().gusto_default_tighten_opts(model, C.byref(o))
+    if rc:
+        raise ValueError(f"gusto_default_tighten_opts({model}) -> {rc}")
     return o
 
 
@@ -1080,6 +1112,63 @@ class BatchSolver:
     def last_lincov_ms(self):
         return self._last_ms("last_lincov_ms")
 
+    def tighten_opts(self, opts=None, **kw):
+        """a gusto_tighten_opts from None (the defaults), a TightenOpts, or a dict / keywords of its fields"""
+        if isinstance(opts, TightenOpts) and not kw:
+            return opts
+        o = default_tighten_opts(self.model)
+        names = [k for k, _ in TightenOpts._fields_]
+        for k, v in {**(dict(opts) if opts else {}), **kw}.items():
+            if k not in names:
+                raise TypeError(f"unknown tighten option {k!r}")
+            setattr(o, k, int(v) if k in ("cover_components", "monotone") else float(v))
+        return o
+
+    def tighten_env(self, boxes_list, spheres_list=None, **opts):
+        """gusto_tighten_env + gusto_get_tighten: per-problem keep-out tables from the BASE set -- boxes_list / spheres_list as
+        set_env_batch takes them, of length 1 (one set for the batch) or B -- extended over the robot's component offsets and grown
+        by kappa standard deviations of the last lincov(store_S=1); the next solve reads them.  opts: the fields of
+        gusto_tighten_opts (kappa, slack, margin_cap, reach, cover_components, monotone).  Returns get_tighten()."""
+        E = len(boxes_list)
+        bl = [_arr(b if b is not None else np.zeros((0, 6))).reshape(-1, 6) for b in boxes_list]
+        sl = [_arr(s if s is not None else np.zeros((0, 4))).reshape(-1, 4) for s in (spheres_list or [None] * E)]
+        if len(sl) != E:
+            raise ValueError("tighten_env: as many sphere tables as box tables")
+        nb, ns = _arr([len(b) for b in bl], np.int32), _arr([len(s) for s in sl], np.int32)
+        box = _arr(np.concatenate(bl, axis=0)) if bl else np.zeros((0, 6))
+        sph = _arr(np.concatenate(sl, axis=0)) if sl else np.zeros((0, 4))
+        o = self.tighten_opts(opts.pop("opts", None), **opts)
+        self._chk(self.L.gusto_tighten_env(self.h, E, nb.ctypes.data, box.ctypes.data, ns.ctypes.data, sph.ctypes.data, C.byref(o)),
+                  "tighten_env")
+        self.boxes, self.spheres = self.get_env()
+        return self.get_tighten()
+
+    def get_tighten(self):
+        """gusto_get_tighten: the report of the last tighten_env() as a dict of arrays (gusto_tighten_report's fields; margin
+        [B, n_obs_max])"""
+        W = C.c_int()
+        self._chk(self.L.gusto_get_tighten(self.h, None, C.byref(W)), "get_tighten")
+        out = {k: np.zeros(shape(self.B, W.value), dtype=t) for k, t, shape in TIGHTEN_FIELDS}
+        rep = TightenReport(**{k: v.ctypes.data for k, v in out.items()})
+        self._chk(self.L.gusto_get_tighten(self.h, C.byref(rep), None), "get_tighten")
+        return out
+
+    def get_env(self):
+        """gusto_get_env: the handle's current keep-out tables as (boxes_list, spheres_list), lists of [n_box_b, 6] and [n_sph_b, 4]
+        arrays: of length 1 after set_env, else one entry per problem"""
+        E = C.c_int()
+        self._chk(self.L.gusto_get_env(self.h, C.byref(E), None, None, None, None), "get_env")
+        nb, ns = np.zeros(E.value, dtype=np.int32), np.zeros(E.value, dtype=np.int32)
+        self._chk(self.L.gusto_get_env(self.h, None, nb.ctypes.data, None, ns.ctypes.data, None), "get_env")
+        box, sph = np.zeros((int(nb.sum()), 6)), np.zeros((int(ns.sum()), 4))
+        self._chk(self.L.gusto_get_env(self.h, None, None, box.ctypes.data, None, sph.ctypes.data), "get_env")
+        ob, os_ = np.concatenate([[0], np.cumsum(nb)]), np.concatenate([[0], np.cumsum(ns)])
+        return ([box[ob[e]:ob[e + 1]].copy() for e in range(E.value)], [sph[os_[e]:os_[e + 1]].copy() for e in range(E.value)])
+
+    def last_tighten_ms(self):
+        """gusto_last_tighten_ms: GPU time of the last tighten_env()"""
+        return self._last_ms("last_tighten_ms")
+
     def subproblem(self, Xp, Up, Delta, omega, toggle):
         B = self.B
         Xp, Up = _arr(Xp).reshape(B, self.N, self.n), _arr(Up).reshape(B, self.N, self.m)
@@ -1175,6 +1264,9 @@ class TrajOptSolver(BatchSolver):
         raise GustoError("TrajOptSolver: replanning is not supported on TrajOpt handles (gusto_set_problems_replan answers GUSTO_ERR_ARG)")
 
     set_problems_replan_knots = set_problems_replan
+
+    def tighten_env(self, *a, **k):
+        raise GustoError("TrajOptSolver: tighten_env is not supported on TrajOpt handles (gusto_tighten_env answers GUSTO_ERR_ARG)")
 
     def set_problems_trajlib(self, *a, **k):
         raise GustoError("TrajOptSolver: library seeds are not supported on TrajOpt handles (gusto_set_problems_trajlib answers GUSTO_ERR_ARG)")

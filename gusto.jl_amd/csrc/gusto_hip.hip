@@ -201,6 +201,7 @@ int gusto_set_env(gusto_handle h, int n_box, const double* box, int n_sph, const
     { int rc = setter_enter(h); if (rc) return rc; }
     h->d_box.reset(); h->d_sph.reset();
     h->d_env.reset();   // back to one keep-out set for the whole batch
+    h->tighten.forget();
     h->env_B = 0; h->n_obs_max = 0;
     HIPCHK(h, h->d_box.alloc((size_t)6 * n_box)); HIPCHK(h, h->d_sph.alloc((size_t)4 * n_sph));
     if (n_box) HIPCHK(h, hipMemcpy(h->d_box, box, sizeof(double) * 6 * n_box, hipMemcpyHostToDevice));
@@ -233,6 +234,7 @@ int gusto_set_env_batch(gusto_handle h, int B, const int* n_box, const double* b
     if ((tb && !box) || (ts && !sph)) return GUSTO_ERR_ARG;
     { int rc = setter_enter(h); if (rc) return rc; }
     h->d_box.reset(); h->d_sph.reset(); h->d_env.reset();
+    h->tighten.forget();
     h->env_B = 0; h->n_obs_max = 0; h->n_box = 0; h->n_sph = 0;
     HIPCHK(h, h->d_box.alloc(6 * tb)); HIPCHK(h, h->d_sph.alloc(4 * ts)); HIPCHK(h, h->d_env.alloc((size_t)4 * B));
     if (tb) HIPCHK(h, hipMemcpy(h->d_box, box, sizeof(double) * 6 * tb, hipMemcpyHostToDevice));
@@ -290,7 +292,7 @@ int gusto_problems_loaded(gusto_handle h, bool straight) {
     if (rc) return rc;
     h->have_problems = true;
     h->shoot.invalidate(); h->verify.invalidate(); h->tvlqr.invalidate(); h->simulate.invalidate(); h->lincov.invalidate();
-    h->select.invalidate(); h->trajlib.invalidate(); h->replan.invalidate();
+    h->select.invalidate(); h->trajlib.invalidate(); h->replan.invalidate(); h->tighten.invalidate();
     h->n_active = -1;   // (gusto_set_active belongs to the problems it was set for)
     return GUSTO_OK;
 }

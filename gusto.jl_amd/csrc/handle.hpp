@@ -157,6 +157,7 @@ struct __attribute__((visibility("hidden"))) LincovState {
     DevBuf<int> I, Jint, DI, Pd;
     bool have = false, store_S = false, have_Sxx = false, plant = false;
     bool dense = false, store_dense = false, have_dense = false, have_dense_rows = false;
+    bool staged = false;   // the last call read a caller's X, U (the copies in X, U), not the handle's own (gusto_tighten_env)
     size_t dense_rows = 0, dense_nsp = 0;
     DevEvent t0, t1;
     double last_ms = 0.0;
@@ -202,6 +203,23 @@ struct __attribute__((visibility("hidden"))) ReplanState {
     DevEvent t0, t1;
     double last_ms = 0.0;
     void invalidate() { have = false; }
+};
+
+// Risk-tightened keep-out sets (tighten.hip): Bbox, Bsph the caller's base tables of the last call and Rec [2][batch_cap][4] the
+// (box offset, n_box, sphere offset, n_sph) records of every problem, in the base tables and in the tightened ones; M
+// [batch_cap][64] the margins, which outlive gusto_set_problems* (mem: they belong to mem_B problems with the counts cnt
+// [mem_B][2]; gusto_set_env / gusto_set_env_batch end that); the report I [5][batch_cap] status, knot, pair, n_grown, blocked and
+// D [2][batch_cap] min_z_base, max_margin of the last call on these problems (have), n_obs_max its largest component count
+struct __attribute__((visibility("hidden"))) TightenState {
+    DevBuf<double> Bbox, Bsph, M, D;
+    DevBuf<int> Rec, I;
+    std::vector<int> cnt;
+    int mem_B = 0, n_obs_max = 0;
+    bool have = false, mem = false;
+    DevEvent t0, t1;
+    double last_ms = 0.0;
+    void invalidate() { have = false; }
+    void forget() { mem = false; mem_B = 0; cnt.clear(); }
 };
 
 // The library itself: `count` of `cap` entries on `device`, entry e at row e of xi, c [cap][n], tf, tag [cap], X [cap][N][n], U
@@ -273,6 +291,7 @@ struct gusto_handle_s {
     SelectState select;
     TrajlibState trajlib;
     ReplanState replan;
+    TightenState tighten;
     std::string err;
 
     // (the buffers and events free themselves; the caller has made `device` current: gusto_destroy)

@@ -822,6 +822,7 @@ int lincov_host(gusto_handle h, const char* who_c, const double* X, const double
     S.have = true;
     S.store_S = o.store_S != 0;
     S.plant = dist != nullptr;
+    S.staged = X != nullptr;
     S.dense = dense >= 0;
     if (dense >= 0) {
         S.have_dense = true; S.dense_rows = rows; S.dense_nsp = nsp; S.store_dense = dense != 0;

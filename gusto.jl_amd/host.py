@@ -1051,6 +1051,146 @@ def solve_SCP_receding_batch(TOSs, TOPs, steps, knots_per_step, sim_opts=None, d
     return out
 
 
+def solve_SCP_chance_batch(TOSs, TOPs, kappa=3.0, rounds=3, lincov_opts=None, tvlqr_opts=None, disturb=None, tighten_opts=None,
+                           max_iter=30, force=False, device=0):
+    """Plans that keep kappa standard deviations of closed-loop dispersion from every keep-out component, for every robot
+    component, on one handle.  Solve; then per round: gusto_tvlqr and gusto_lincov (store_S = 1; gusto_lincov_disturbed with
+    `disturb`) on the plans, gusto_tighten_env from the BASE keep-out sets for the answered problems still below kappa, and a
+    re-solve of those from their own plan (gusto_set_problems_replan on the handle itself, tau = 0, x_now = x_init); the ones that
+    pass loses go once more from the straight line.  A problem whose start or goal lies inside its own tightened set (blocked) is
+    not re-solved, and one that loses both passes keeps its last answered plan and is left alone afterwards.  At the end the base
+    set is restored and gusto_tvlqr, gusto_lincov and gusto_verify run on it.  All TOPs share model and N; each may bring its own
+    environment.  lincov_opts / tvlqr_opts / disturb / tighten_opts: dicts of the fields of the C structs; kappa overrides
+    tighten_opts' own.  Without actuator noise (du_white) or a plant dispersion the covariance decays to rounding noise along the
+    horizon and a margin built on it means nothing: such options raise ValueError.
+
+    Returns a dict: `answered` [B] (converged and successful, the problems that have a plan), `met_before` and `met` [B]
+    (answered, min_z_obs >= kappa and collision-free on the base set, before the first round and at the end), `min_z_obs` and
+    `collision_free` [B] of the final analysis, `env` (get_env() of the handle at the end: the base set), and `rounds`, one dict per round: `tried` [B] (re-solved), `min_z_base`,
+    `max_margin`, `blocked` [B] of gusto_tighten_env (zeros for the problems it skipped), `lost` [B] (lost both passes),
+    `second_pass` [B], `iterations` [B] of the re-solves, and tighten_ms / lincov_ms / solve_ms.  TOSs take the final plans."""
+    who = "solve_SCP_chance_batch!"
+    if len(TOSs) != len(TOPs) or not TOPs:
+        raise ValueError(who + ": need as many solutions as problems, at least one")
+    lo_ = dict(lincov_opts or {})
+    white = np.asarray(lo_.get("du_white", 0.0), float)
+    noisy = bool((white != 0).any())
+    if disturb is not None:
+        d = dict(disturb)
+        noisy = noisy or bool((np.asarray(d.get("plant_rel", 0.0), float) != 0).any() or (np.asarray(d.get("dw", 0.0), float) != 0).any())
+    if not noisy:
+        raise ValueError(who + ": du_white is all zero and no plant dispersion is given: the covariance decays to rounding noise "
+                         "along the horizon and a margin in its standard deviations means nothing")
+    if not (kappa >= 0 and np.isfinite(kappa)) or rounds < 0:
+        raise ValueError(who + ": need a finite kappa >= 0 and rounds >= 0")
+    TOP0 = TOPs[0]
+    model, N = TOP0.PD.model, TOP0.N
+    n, B = model.x_dim, len(TOPs)
+    for t in TOPs[1:]:
+        if type(t.PD.model) is not type(model) or t.N != N:
+            raise ValueError(who + ": all problems must share the model type and N")
+    lo_["store_S"] = 1
+    to_ = dict(tighten_opts or {})
+    to_["kappa"] = float(kappa)
+    same_env = all(np.array_equal(t.PD.env.boxes, TOP0.PD.env.boxes) and np.array_equal(t.PD.env.spheres, TOP0.PD.env.spheres)
+                   for t in TOPs[1:])
+    base = ([TOP0.PD.env.boxes], [TOP0.PD.env.spheres]) if same_env else ([t.PD.env.boxes for t in TOPs], [t.PD.env.spheres for t in TOPs])
+    sp, mp = _capi.default_params(model.model_id)
+    bounds = [_goal_bounds(t.PD.goal_set, n, t.tf_guess) for t in TOPs]
+    x0 = np.stack([t.PD.x_init for t in TOPs])
+    bs = BatchSolver(model.model_id, N, B, hist_cap=_hist_cap(max_iter), device=device, boxes=TOP0.PD.env.boxes,
+                     spheres=TOP0.PD.env.spheres, scp_params=sp, model_params=mp)
+
+    def restore_base():
+        if same_env:
+            bs.set_env(*[t[0] for t in base])
+        else:
+            bs.set_env_batch(*base)
+
+    def analyse(X, U):
+        bs.tvlqr(tvlqr_opts or {}, X, U)
+        return bs.lincov(lo_, X=X, U=U) if disturb is None else bs.lincov_disturbed(lo_, disturb, X=X, U=U)
+
+    out = dict(rounds=[])
+    try:
+        restore_base()
+        bs.set_problems(x0, np.stack([b[0] for b in bounds]), np.stack([b[1] for b in bounds]), np.array([t.tf_guess for t in TOPs]))
+        bs.solve(max_iter, force)
+        snap = _fetch(bs)
+        per = bs.last_solve_ms() * 1e-3 / B
+        answered = snap["st"]["converged"] & snap["st"]["successful"]
+        keepX, keepU = snap["X"].copy(), snap["U"].copy()
+        src = [(snap, per)] * B                 # where the kept plan of every problem comes from
+        onh = np.ones(B, bool)                  # the handle's trajectory of the problem IS its kept plan
+        done, stuck = np.zeros(B, bool), np.zeros(B, bool)
+        lc = analyse(keepX, keepU)
+        vr = bs.verify(keepX, keepU)
+        out["met_before"] = answered & (lc["min_z_obs"] >= kappa) & vr["collision_free"]
+        done |= answered & (lc["min_z_obs"] >= kappa)
+        tau0 = np.zeros(B)
+
+        def resolve(mask_seed, active):
+            """restart from the kept plans (mask_seed) or the straight line, solve the active ones, keep the winners' plans"""
+            nonlocal keepX, keepU
+            bs.set_problems_replan(tau0, x0, mask=mask_seed)
+            bs.set_active(active)
+            bs.solve(max_iter, force)
+            bs.set_active(None)
+            s = _fetch(bs)
+            win = active & s["st"]["converged"] & s["st"]["successful"]
+            keepX[win], keepU[win] = s["X"][win], s["U"][win]
+            p = bs.last_solve_ms() * 1e-3 / max(1, int(active.sum()))
+            for q in np.flatnonzero(win):
+                src[q] = (s, p)
+            onh[active & ~win] = False
+            return win, s["st"]["iterations"], bs.last_solve_ms()
+
+        for r in range(rounds):
+            open_ = answered & ~done & ~stuck
+            if not open_.any():
+                break
+            if r:
+                lc = analyse(keepX, keepU)
+            lincov_ms = bs.last_lincov_ms()
+            bs.set_active(open_)
+            rep = bs.tighten_env(*base, **to_)
+            bs.set_active(None)
+            done |= open_ & (rep["min_z_base"] >= kappa)
+            blocked = rep["blocked"].astype(bool)
+            todo = open_ & ~done & ~blocked
+            stuck |= open_ & ~done & blocked
+            rd = dict(tried=todo.copy(), min_z_base=rep["min_z_base"], max_margin=rep["max_margin"], blocked=blocked,
+                      lost=np.zeros(B, bool), second_pass=np.zeros(B, bool), iterations=np.zeros(B, dtype=np.int32),
+                      tighten_ms=bs.last_tighten_ms(), lincov_ms=lincov_ms, solve_ms=0.0)
+            if todo.any():
+                win, it, ms = resolve(onh, todo)
+                rd["iterations"][todo] = it[todo]
+                rd["solve_ms"] += ms
+                again = todo & ~win
+                if again.any():
+                    win2, it2, ms2 = resolve(onh, again)
+                    rd["second_pass"] = again
+                    rd["iterations"][again] += it2[again]
+                    rd["solve_ms"] += ms2
+                    rd["lost"] = again & ~win2
+                    stuck |= rd["lost"]
+            out["rounds"].append(rd)
+        restore_base()
+        lc = analyse(keepX, keepU)
+        vr = bs.verify(keepX, keepU)
+        out.update(env=bs.get_env(), answered=answered, min_z_obs=lc["min_z_obs"], collision_free=vr["collision_free"],
+                   met=answered & (lc["min_z_obs"] >= kappa) & vr["collision_free"])
+        for q in range(B):
+            SCPP = SCPProblem(TOPs[q])
+            SCPS = SCPSolution(SCPP, init_traj_straightline(TOPs[q]))
+            _fill_solution(SCPS, SCPP, src[q][0], q, src[q][1])
+            SCPS.traj.X, SCPS.traj.U = keepX[q].T.copy(), keepU[q].T.copy()
+            TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
+    finally:
+        bs.close()
+    return out
+
+
 def solve_batch_sharded(model_id, N, x_init, goal_lo, goal_hi, tf, world_size, rank, device=0, max_iter=30, boxes=None,
                         spheres=None, group=None, solver=None):
     """The multi-GPU path of SURVEY.md 8(e) in one call (one process per GPU, launched by torch.distributed.run):

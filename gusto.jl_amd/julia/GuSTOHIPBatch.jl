@@ -994,3 +994,145 @@ function solve_SCP_receding_batch!(TOSs::Vector, TOPs::Vector, steps::Integer, k
   ccall((:gusto_destroy, libgusto_hip), Cint, (Ptr{Cvoid},), h)
   out
 end
+
+# ---- risk-tightened keep-out sets: plan to a margin in standard deviations (csrc/tighten.hip) ------------------------------------
+# gusto_lincov reports how many standard deviations of closed-loop dispersion lie between a plan and the nearest keep-out
+# component; gusto_tighten_env feeds that back: from the BASE tables and the covariances of the last gusto_lincov (store_S = 1) it
+# writes per-problem tables -- every component extended over the robot's component offsets, then grown by kappa sigma_d -- where
+# gusto_set_env_batch puts its own (include/gusto_hip.h states the definitions, the reference has no counterpart).
+# Mirrors gusto.jl_amd/host.py: BatchSolver.tighten_env, solve_SCP_chance_batch.  This wrapper has not been run.
+struct GustoTightenOpts      # gusto_tighten_opts
+  kappa::Cdouble; slack::Cdouble; margin_cap::Cdouble; reach::Cdouble; cover_components::Cint; monotone::Cint
+end
+mutable struct GustoTightenReport      # gusto_tighten_report
+  status::Ptr{Cint}; knot::Ptr{Cint}; pair::Ptr{Cint}; n_grown::Ptr{Cint}; blocked::Ptr{Cint}
+  min_z_base::Ptr{Cdouble}; max_margin::Ptr{Cdouble}; margin::Ptr{Cdouble}
+end
+
+# boxes / spheres: vectors of [6,n_box] / [4,n_sph] tables, of length 1 (one base set for the batch) or B.
+# Returns (status, knot, pair, n_grown, blocked, min_z_base, max_margin [B], margin [n_obs_max,B], ms).
+function tighten_env!(h::Ptr{Cvoid}, B::Integer, boxes::Vector, spheres::Vector; kappa=3.0, slack=0.0, margin_cap=Inf, reach=Inf,
+                      cover_components=true, monotone=true)
+  length(boxes) == length(spheres) && length(boxes) in (1, B) || error("tighten_env!: one base set, or one per problem")
+  nb, ns = Cint[length(b) ÷ 6 for b in boxes], Cint[length(s) ÷ 4 for s in spheres]
+  box = Float64.(vcat((vec(b) for b in boxes)..., Float64[])); sph = Float64.(vcat((vec(s) for s in spheres)..., Float64[]))
+  o = GustoTightenOpts(kappa, slack, margin_cap, reach, cover_components ? 1 : 0, monotone ? 1 : 0)
+  gusto_check(ccall((:gusto_tighten_env, libgusto_hip), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ref{GustoTightenOpts}),
+                    h, length(boxes), nb, box, ns, sph, o), h, "tighten_env")
+  w = Ref{Cint}(0)
+  gusto_check(ccall((:gusto_get_tighten, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Cint}), h, C_NULL, w), h, "get_tighten")
+  st, kn, pr, ng, bl = (zeros(Cint, B) for _ in 1:5)
+  mz, mm, mg = zeros(B), zeros(B), zeros(Int(w[]), B)
+  GC.@preserve st kn pr ng bl mz mm mg begin
+    rep = GustoTightenReport(pointer(st), pointer(kn), pointer(pr), pointer(ng), pointer(bl), pointer(mz), pointer(mm), pointer(mg))
+    gusto_check(ccall((:gusto_get_tighten, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoTightenReport}, Ptr{Cint}), h, rep, C_NULL), h, "get_tighten")
+  end
+  ms = Ref{Cdouble}(0.0)
+  gusto_check(ccall((:gusto_last_tighten_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, ms), h, "last_tighten_ms")
+  (status = st, knot = kn, pair = pr, n_grown = ng, blocked = bl .!= 0, min_z_base = mz, max_margin = mm, margin = mg, ms = ms[])
+end
+
+# The handle's current keep-out tables: (n_box [n_env], boxes [6, sum n_box], n_sph [n_env], spheres [4, sum n_sph])
+function gusto_env(h::Ptr{Cvoid})
+  ne = Ref{Cint}(0)
+  gusto_check(ccall((:gusto_get_env, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}),
+                    h, ne, C_NULL, C_NULL, C_NULL, C_NULL), h, "get_env")
+  nb, ns = zeros(Cint, ne[]), zeros(Cint, ne[])
+  gusto_check(ccall((:gusto_get_env, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}),
+                    h, C_NULL, nb, C_NULL, ns, C_NULL), h, "get_env")
+  box, sph = zeros(6, sum(nb)), zeros(4, sum(ns))
+  gusto_check(ccall((:gusto_get_env, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}),
+                    h, C_NULL, C_NULL, box, C_NULL, sph), h, "get_env")
+  (n_box = nb, boxes = box, n_sph = ns, spheres = sph)
+end
+
+# Plans that keep kappa standard deviations from every keep-out component, on one handle: solve; per round the gains
+# (tvlqr_batch!), the covariances (lincov_disturbed_batch! with store_S), tighten_env! from the base set for the answered
+# problems below kappa (gusto_set_active), a re-solve of those from their own plan (replan_batch! with tau = 0, x_now = x_init)
+# and once more from the straight line for the ones that pass loses; at the end the base set again and the analysis on it.  All
+# TOPs share model, N and the environment.  A problem that loses both passes keeps its last answered plan.  Returns
+# (answered, met [B], min_z_obs [B], rounds = one named tuple per round).  TOSs take the final trajectories.
+function solve_SCP_chance_batch!(TOSs::Vector, TOPs::Vector; kappa=3.0, rounds=3, dx0=0.01, du_white=0.0, plant_rel=0.0, dw=0.0,
+                                 Q=1.0, R=1.0, Qf=1.0, max_iter=30, force=false, device=0)
+  length(TOSs) == length(TOPs) && !isempty(TOPs) || error("solve_SCP_chance_batch!: need as many solutions as problems, at least one")
+  any(!iszero, du_white) || any(!iszero, plant_rel) || any(!iszero, dw) ||
+    error("solve_SCP_chance_batch!: du_white is all zero and no plant dispersion is given: the covariance decays to rounding noise")
+  TOP0 = TOPs[1]; model, N = TOP0.PD.model, TOP0.N
+  n, m, B = model.x_dim, model.u_dim, length(TOPs)
+  all(T -> typeof(T.PD.model) == typeof(model) && T.N == N && T.PD.env === TOP0.PD.env, TOPs) ||
+    error("solve_SCP_chance_batch!: all problems must share the model type, N and the environment")
+  alg0 = SCPParam_GuSTO(model)
+  sp = GustoScpParams(alg0.Δ0, alg0.ω0, alg0.ω_max, alg0.ε, alg0.ρ0, alg0.ρ1, alg0.β_succ, alg0.β_fail, alg0.γ_fail,
+                      SCPParam(model, TOP0.fixed_final_time).convergence_threshold)
+  href = Ref{Ptr{Cvoid}}(C_NULL)
+  gusto_check(ccall((:gusto_create, libgusto_hip), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Cint),
+                    href, gusto_model_id(model), N, B, gusto_hist_cap(max_iter), device), href[], "create")
+  h = href[]
+  gusto_check(ccall((:gusto_set_params, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoScpParams}, Ref{GustoModelParams}),
+                    h, sp, gusto_model_params(TOP0.PD.robot, model)), h, "set_params")
+  boxes, spheres = gusto_env_tables(TOP0.PD.env)
+  set_base() = gusto_check(ccall((:gusto_set_env, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+                                 h, length(boxes) ÷ 6, boxes, length(spheres) ÷ 4, spheres), h, "set_env")
+  set_base()
+  x0 = hcat((Float64.(T.PD.x_init) for T in TOPs)...)
+  bounds = [gusto_goal_bounds(T.PD.goal_set, n, T.tf_guess) for T in TOPs]
+  lo, hi = hcat(first.(bounds)...), hcat(last.(bounds)...)
+  tf = Float64[T.tf_guess for T in TOPs]
+  gusto_check(ccall((:gusto_set_problems, libgusto_hip), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    h, B, x0, lo, hi, tf, C_NULL, C_NULL), h, "set_problems")
+  X, U = zeros(n, N, B), zeros(m, N, B)
+  its, conv, succ, stop = zeros(Cint, B), zeros(Cint, B), zeros(Cint, B), zeros(Cint, B)
+  function solve_active!(active)
+    mask = active === nothing ? nothing : Cint.(active)
+    gusto_check(ccall((:gusto_set_active, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}), h, mask === nothing ? C_NULL : mask), h, "set_active")
+    gusto_check(ccall((:gusto_solve, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Cint), h, max_iter, force), h, "solve")
+    gusto_check(ccall((:gusto_set_active, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}), h, C_NULL), h, "set_active")
+    gusto_check(ccall((:gusto_get_traj, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), h, X, U), h, "get_traj")
+    gusto_check(ccall((:gusto_get_status, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ptr{Cvoid}),
+                      h, its, conv, succ, stop, C_NULL), h, "get_status")
+    (conv .!= 0) .& (succ .!= 0)
+  end
+  analyse!() = (tvlqr_batch!(h, B, n, m, N, keepX, keepU; Q=Q, R=R, Qf=Qf);
+                lincov_disturbed_batch!(h, B, n, m, N, keepX, keepU; dx0=dx0, du_white=du_white, plant_rel=plant_rel, dw=dw, store_S=true))
+  answered = solve_active!(nothing)
+  keepX, keepU = copy(X), copy(U)
+  onh, done, stuck = trues(B), falses(B), falses(B)
+  out = Any[]
+  for r in 1:rounds
+    open = answered .& .!done .& .!stuck
+    any(open) || break
+    analyse!()
+    gusto_check(ccall((:gusto_set_active, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}), h, Cint.(open)), h, "set_active")
+    rep = tighten_env!(h, B, [boxes], [spheres]; kappa=kappa)
+    gusto_check(ccall((:gusto_set_active, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}), h, C_NULL), h, "set_active")
+    done .|= open .& (rep.min_z_base .>= kappa)
+    todo = open .& .!done .& .!rep.blocked
+    stuck .|= open .& .!done .& rep.blocked
+    lost = falses(B)
+    if any(todo)
+      replan_batch!(h, B, n, 0.0, x0; mask=onh)
+      win = todo .& solve_active!(todo)
+      keepX[:, :, win], keepU[:, :, win] = X[:, :, win], U[:, :, win]
+      again = todo .& .!win
+      onh[again] .= false
+      if any(again)
+        replan_batch!(h, B, n, 0.0, x0; mask=onh)
+        win2 = again .& solve_active!(again)
+        keepX[:, :, win2], keepU[:, :, win2] = X[:, :, win2], U[:, :, win2]
+        onh[win2] .= true
+        lost = again .& .!win2
+        stuck .|= lost
+      end
+    end
+    push!(out, (tried = todo, min_z_base = rep.min_z_base, max_margin = rep.max_margin, blocked = rep.blocked, lost = lost, tighten_ms = rep.ms))
+  end
+  set_base()
+  lc = analyse!()
+  for q in 1:B
+    TOSs[q].traj = Trajectory(keepX[:, :, q], keepU[:, :, q], tf[q])
+  end
+  ccall((:gusto_destroy, libgusto_hip), Cint, (Ptr{Cvoid},), h)
+  (answered = answered, met = answered .& (lc.min_z_obs .>= kappa), min_z_obs = lc.min_z_obs, rounds = out)
+end

@@ -800,6 +800,76 @@ int gusto_get_replan(gusto_handle h, int* seeded, double* tau, double* x_now);
 /* GPU time of that call (copies, staging and the kernel), from HIP events on the stream of h; GUSTO_ERR_STATE likewise */
 int gusto_last_replan_ms(gusto_handle h, double* ms);
 
+/* Risk-tightened keep-out sets (csrc/tighten.hip): gusto_lincov says how many standard deviations of closed-loop dispersion lie
+ * between a plan and the nearest keep-out component; this call feeds that back into planning.  From a caller's BASE keep-out
+ * tables and the covariances of the last gusto_lincov it writes per-problem tables into the handle, where gusto_set_env_batch
+ * puts its own, so that the next gusto_solve plans around them.  The solver's obstacle rows look at robot component 0 only (the
+ * reference does: freeflyer_se2.jl:251,273) while gusto_verify and gusto_lincov look at every component, so every keep-out
+ * component is first extended over the component offsets, then grown.  No counterpart in the reference; the definitions, for one
+ * problem, WS = 2 in the plane and 3 in space:
+ * Base set: n_box / box_min_max / n_sph / sph_c_r in the form of gusto_set_env_batch.  n_env = 1: one set for all B problems;
+ *   n_env = B: one per problem; at most 64 components per problem.  The handle's current tables are NOT read: a caller that
+ *   passes the same base every time never compounds margins.
+ * Inputs from the handle: the last gusto_lincov, gusto_lincov_disturbed or gusto_lincov_dense since gusto_set_problems*, which
+ *   must have run with store_S = 1 (else GUSTO_ERR_STATE): its Sxx [N][x_dim][x_dim], its per-problem status, and the X that call
+ *   saw (its copy of a caller's X, or the handle's own trajectories).
+ * Per pair: for robot component c, base component i and knot k, the signed distance d at X[:,k] and its outward normal nh, and
+ *     sigma_d = sqrt(max(0, nh' Sxx_k[0:WS, 0:WS] nh)),   z = d / sigma_d   (sigma_d == 0: the sign of d decides, +-inf)
+ *   exactly as gusto_lincov defines them.
+ * Margin of base component i:
+ *     m_i = min(margin_cap, max over the (c, k) with d - kappa sigma_d <= reach of max(0, kappa sigma_d - slack))
+ *   (0 when no pair counts).  With monotone = 1, m_i = max(m_i, previous m_i).  A NaN never wins a maximum.
+ * Previous margins: those the last gusto_tighten_env on this handle wrote for this problem, if that call had the same B and the
+ *   problem the same n_box and n_sph; zeros otherwise.  gusto_set_env and gusto_set_env_batch drop them; gusto_set_problems*
+ *   does not (a driver sets problems again between two calls).
+ * Cover (cover_components = 1): omax_j, omin_j = the largest and smallest of comp_off[c][j] - comp_off[0][j] over the robot's
+ *   components, j < WS (component 0 contributes 0).  A box becomes [lo - omax, hi - omin]; a sphere gets the centre
+ *   c - (omax + omin) / 2 and the radius R + |(omax - omin) / 2|.  cover_components = 0: omax = omin = 0.
+ * Grow: a box becomes [(lo - omax) - m_i, (hi - omin) + m_i] in the first WS coordinates, the others are copied; a sphere's
+ *   radius becomes (R + |(omax - omin) / 2|) + m_i.  With cover off and m_i = 0 the component is the base one bit for bit.
+ * Guarantee (cover on): for every location q and component c, the signed distance of component 0 at q to the tightened component
+ *   is at most the signed distance of component c at q to the base component, minus m_i (up to rounding).
+ * Report, per problem [B]: min_z_base, knot, pair -- gusto_lincov's min_z_obs, obs_knot (1-based; 0: +inf) and obs_pair (ordinal
+ *   c n_obs + i; -1: +inf) with its tie rules, but on the BASE set: independent of cover and margins.  max_margin the largest
+ *   m_i, n_grown the number of components with m_i > 0, blocked = 1 when x_init, or the goal centre (goal_lo + goal_hi) / 2
+ *   where its first WS entries are finite, has a negative component-0 signed distance to a component of the problem's own
+ *   tightened set.  margin [B][n_obs_max], n_obs_max the largest component count of the call: zeros behind a problem's own count.
+ * Skipped problems: inactive under gusto_set_active, or gusto_lincov status 0.  status = 0 (else 1), min_z_base, knot and pair
+ *   zero; the margins are the previous ones, and the problem's tables are still written, as cover plus those margins, so the
+ *   handle's set is whole; max_margin, n_grown and blocked describe those tables.
+ * Afterwards the handle holds per-problem tables for B problems (as after gusto_set_env_batch) and the next gusto_solve reads
+ *   them.  Trajectories, status, histories and the results of the post-solve stages are untouched.
+ * GUSTO_ERR_ARG: a TrajOpt handle, DubinsCar, n_env neither 1 nor B, more than 64 components or a negative count, a null or
+ *   non-finite table, kappa or slack negative or not finite, margin_cap negative or NaN, reach NaN, a flag other than 0 / 1.
+ *   GUSTO_ERR_STATE: a handle without problems, no covariances.  A refused call leaves the handle as it was.
+ * Kernel: one wave per problem, a lane per keep-out component, the knots in sequence; reductions in a fixed order, no atomics:
+ *   a problem's outputs are the same bit for bit in any batch.  The call runs on the handle's stream after any pending
+ *   gusto_solve_async and is timed with events of its own.
+ * Out of scope: margins on the controls, per-knot margins, margins from the dense samples, TrajOpt handles. */
+typedef struct {
+    double kappa;          /* margin in standard deviations; finite, >= 0; default 3 */
+    double slack;          /* m = max(0, kappa sigma_d - slack); finite, >= 0; default 0 */
+    double margin_cap;     /* upper bound of a component's margin; >= 0, may be +inf; default +inf */
+    double reach;          /* a (component, obstacle) pair counts at knot k only if d - kappa sigma_d <= reach; default +inf */
+    int cover_components;  /* 1: extend every obstacle over the robot's component offsets first; default 1 */
+    int monotone;          /* 1: a margin never falls below the one the previous call wrote for this problem; default 1 */
+} gusto_tighten_opts;
+int gusto_default_tighten_opts(int model_id, gusto_tighten_opts* o);
+int gusto_tighten_env(gusto_handle h, int n_env, const int* n_box, const double* box_min_max, const int* n_sph,
+                      const double* sph_c_r, const gusto_tighten_opts* o);
+typedef struct {
+    int *status, *knot, *pair, *n_grown, *blocked;   /* [B] */
+    double *min_z_base, *max_margin;                 /* [B] */
+    double *margin;                                  /* [B][n_obs_max] */
+} gusto_tighten_report;                              /* caller-owned, any pointer may be NULL */
+/* The report of the last gusto_tighten_env since gusto_set_problems* (none: GUSTO_ERR_STATE); out = NULL: n_obs_max alone */
+int gusto_get_tighten(gusto_handle h, gusto_tighten_report* out, int* n_obs_max);
+/* The handle's current keep-out tables in the form of gusto_set_env_batch: *n_env = 1 after gusto_set_env (or before any), else
+ * the number of problems; n_box, n_sph [n_env]; the tables.  Any pointer may be NULL: a size query passes the arrays as NULL. */
+int gusto_get_env(gusto_handle h, int* n_env, int* n_box, double* box_min_max, int* n_sph, double* sph_c_r);
+/* GPU time of the last gusto_tighten_env (copies and the kernel), from HIP events on the handle's stream */
+int gusto_last_tighten_ms(gusto_handle h, double* ms);
+
 /* One convex subproblem per problem (what scp_gusto.jl:82-104 builds and solves in one trip), linearised at
  * (Xp,Up)[b] with the given Delta/omega/obstacle_toggle_distance[b].  Used by the parity tests.
  * Outputs: Xn,Un [B][N][.], obj [B] (JuMP.objective_value), status [B] (GUSTO_SOLVER_*), iters [B]. */
