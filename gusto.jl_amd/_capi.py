@@ -40,6 +40,7 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_get_trajlib_seeds", "gusto_last_trajlib_ms",
            "gusto_set_problems_replan", "gusto_set_problems_replan_knots", "gusto_get_replan", "gusto_last_replan_ms",
            "gusto_default_tighten_opts", "gusto_tighten_env", "gusto_get_tighten", "gusto_get_env", "gusto_last_tighten_ms",
+           "gusto_default_roadmap_opts", "gusto_set_problems_roadmap", "gusto_get_roadmap", "gusto_last_roadmap_ms",
            "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr", "gusto_dev_trajlib"]
 
 
@@ -178,6 +179,24 @@ class TightenReport(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in TIGHTEN_FIELDS]
 
 
+class RoadmapOpts(C.Structure):
+    """gusto_roadmap_opts: the growth of the keep-out components, the stand-off of the corner nodes, the straight line first"""
+    _fields_ = [("inflate", C.c_double), ("pad", C.c_double), ("straight_first", C.c_int)]
+
+
+ROADMAP_MAX_K, ROADMAP_MAX_VIA = 8, 16   # GUSTO_ROADMAP_MAX_K, GUSTO_ROADMAP_MAX_VIA
+ROADMAP_STATUS = {0: "DIRECT", 1: "PATH", 2: "END_BLOCKED", 3: "NO_PATH", 4: "TOO_LONG", 5: "STRAIGHT"}
+# gusto_roadmap_report in the header's order: (field, dtype, shape as a function of B)
+ROADMAP_FIELDS = (("status", np.int32, lambda B: (B,)), ("n_via", np.int32, lambda B: (B,)),
+                  ("via", np.int32, lambda B: (B, ROADMAP_MAX_VIA)), ("length", np.float64, lambda B: (B,)),
+                  ("banned", np.int32, lambda B: (B, ROADMAP_MAX_K)), ("stage_ms", np.float64, lambda B: (3,)))
+
+
+class RoadmapReport(C.Structure):
+    """gusto_roadmap_report: caller-owned arrays"""
+    _fields_ = [(k, C.c_void_p) for k, _, _ in ROADMAP_FIELDS]
+
+
 class TrajLibOpts(C.Structure):
     """gusto_trajlib_opts"""
     _fields_ = [("w_init", C.c_double * MAXN), ("w_goal", C.c_double * MAXN), ("w_tf", C.c_double), ("lds_tile", C.c_int)]
@@ -224,7 +243,7 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(_ROOT, "include"), "-fPIC",
              "-Wno-unused-value", "-Wno-pass-failed"]
-    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "trajlib", "replan", "tighten", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
+    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "trajlib", "replan", "tighten", "roadmap", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
     bdir = os.path.join(_HERE, "build")
     os.makedirs(bdir, exist_ok=True)
 
@@ -346,6 +365,10 @@ def lib():
         L.gusto_get_tighten.argtypes = [vp, C.POINTER(TightenReport), C.POINTER(ci)]
         L.gusto_get_env.argtypes = [vp, C.POINTER(ci), vp, vp, vp, vp]
         L.gusto_last_tighten_ms.argtypes = [vp, C.POINTER(C.c_double)]
+        L.gusto_default_roadmap_opts.argtypes = [ci, C.POINTER(RoadmapOpts)]
+        L.gusto_set_problems_roadmap.argtypes = [vp, ci, ci, vp, vp, vp, vp, C.POINTER(RoadmapOpts)]
+        L.gusto_get_roadmap.argtypes = [vp, C.POINTER(RoadmapReport)]
+        L.gusto_last_roadmap_ms.argtypes = [vp, C.POINTER(C.c_double)]
         L.gusto_default_trajopt_params.argtypes = [ci, C.POINTER(TrajOptParams)]
         L.gusto_create_trajopt.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci]
         L.gusto_set_trajopt_params.argtypes = [vp, C.POINTER(TrajOptParams)]
@@ -418,6 +441,14 @@ def default_tighten_opts(model):
     rc = lib().gusto_default_tighten_opts(model, C.byref(o))
     if rc:
         raise ValueError(f"gusto_default_tighten_opts({model}) -> {rc}")
+    return o
+
+
+def default_roadmap_opts(model):
+    o = RoadmapOpts()
+    rc = lib().gusto_default_roadmap_opts(model, C.byref(o))
+    if rc:
+        raise ValueError(f"gusto_default_roadmap_opts({model}) -> {rc}")
     return o
 
 
@@ -574,6 +605,39 @@ class BatchSolver:
         self._chk(self.L.gusto_get_best_dev(self.h, C.byref(px), C.byref(pu), C.byref(pw)), "get_best_dev")
         return (_dev_view(px.value, (Bq, self.N, self.n), self.device), _dev_view(pu.value, (Bq, self.N, self.m), self.device),
                 _dev_view(pw.value, (Bq,), self.device, "<i4"))
+
+    def set_problems_roadmap(self, x_init, goal_lo, goal_hi, tf, K=1, opts=None, **kw):
+        """gusto_set_problems_roadmap: Bq queries x K alternates become the B = Bq K problems of the handle, problem q K + j =
+        alternate j of query q, each seeded from a shortest collision-free polyline through the corners of the handle's current
+        keep-out set (set_env: shared; set_env_batch / tighten_env: Bq K sets, query q uses that of problem q K).  opts: None (the
+        defaults on the handle's radius), a RoadmapOpts, or keywords of its fields (inflate, pad, straight_first) over the model's
+        defaults.  The report: roadmap_info()."""
+        x_init, goal_lo, goal_hi = _arr(x_init).reshape(-1, self.n), _arr(goal_lo).reshape(-1, self.n), \
+            _arr(goal_hi).reshape(-1, self.n)
+        Bq, K = x_init.shape[0], int(K)
+        tf = _arr(np.broadcast_to(np.asarray(tf, dtype=np.float64), (Bq,)))
+        if kw:   # (a caller's RoadmapOpts is not written to)
+            opts = default_roadmap_opts(self.model) if opts is None else RoadmapOpts(opts.inflate, opts.pad, opts.straight_first)
+        for k, v in kw.items():
+            if k not in [f for f, _ in RoadmapOpts._fields_]:
+                raise TypeError(f"unknown roadmap option {k!r}")
+            setattr(opts, k, v)
+        self._chk(self.L.gusto_set_problems_roadmap(self.h, Bq, K, x_init.ctypes.data, goal_lo.ctypes.data, goal_hi.ctypes.data,
+                                                    tf.ctypes.data, None if opts is None else C.byref(opts)), "set_problems_roadmap")
+        self.B, self._tf = Bq * K, np.repeat(tf, K)
+
+    def roadmap_info(self):
+        """gusto_get_roadmap: the report of the last set_problems_roadmap as a dict of arrays over the B problems -- status
+        (ROADMAP_STATUS), n_via, via [B, 16] (node indices, -1 behind n_via), length, banned [B, 8] (component indices, -1 behind
+        the count) -- and stage_ms [3], the GPU time of graph, search and seed"""
+        out = {k: np.zeros(shape(self.B), dtype=t) for k, t, shape in ROADMAP_FIELDS}
+        rep = RoadmapReport(**{k: v.ctypes.data for k, v in out.items()})
+        self._chk(self.L.gusto_get_roadmap(self.h, C.byref(rep)), "get_roadmap")
+        return out
+
+    def last_roadmap_ms(self):
+        """gusto_last_roadmap_ms: GPU time of the last set_problems_roadmap (copies, graph, search, seed)"""
+        return self._last_ms("last_roadmap_ms")
 
     def set_problems_trajlib(self, lib, x_init, goal_lo, goal_hi, tf, K=1, tag=None, boxes=None, spheres=None):
         """gusto_set_problems_trajlib: Bq queries seeded from their K nearest entries of the TrajLib `lib` become the B = Bq K problems
@@ -1267,6 +1331,9 @@ class TrajOptSolver(BatchSolver):
 
     def tighten_env(self, *a, **k):
         raise GustoError("TrajOptSolver: tighten_env is not supported on TrajOpt handles (gusto_tighten_env answers GUSTO_ERR_ARG)")
+
+    def set_problems_roadmap(self, *a, **k):
+        raise GustoError("TrajOptSolver: roadmap seeds are not supported on TrajOpt handles (gusto_set_problems_roadmap answers GUSTO_ERR_ARG)")
 
     def set_problems_trajlib(self, *a, **k):
         raise GustoError("TrajOptSolver: library seeds are not supported on TrajOpt handles (gusto_set_problems_trajlib answers GUSTO_ERR_ARG)")

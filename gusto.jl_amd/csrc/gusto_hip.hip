@@ -292,7 +292,7 @@ int gusto_problems_loaded(gusto_handle h, bool straight) {
     if (rc) return rc;
     h->have_problems = true;
     h->shoot.invalidate(); h->verify.invalidate(); h->tvlqr.invalidate(); h->simulate.invalidate(); h->lincov.invalidate();
-    h->select.invalidate(); h->trajlib.invalidate(); h->replan.invalidate(); h->tighten.invalidate();
+    h->select.invalidate(); h->trajlib.invalidate(); h->replan.invalidate(); h->tighten.invalidate(); h->roadmap.invalidate();
     h->n_active = -1;   // (gusto_set_active belongs to the problems it was set for)
     return GUSTO_OK;
 }

@@ -222,6 +222,22 @@ struct __attribute__((visibility("hidden"))) TightenState {
     void forget() { mem = false; mem_B = 0; cnt.clear(); }
 };
 
+// Roadmap seeds (roadmap.hip): In the [Bq] inputs of gusto_set_problems_roadmap as its kernels read them (x_init, goal_lo,
+// goal_hi [Bq][n] each, tf [Bq]) and Rec [n_env][4] the (box offset, n_box, sphere offset, n_sph) record of every query's set in
+// the handle's tables; the graph of every set, Ve rows sized from the call's largest component count: Nodes [n_env][Ve][WS], Dead
+// [n_env][Ve], Vis [n_env][Ve][ceil(Ve / 64)]; the report I ([B] status, [B] n_via, [B][16] via, [B][8] banned), Len [B] and the
+// polylines Pts [B][18][3] the seed kernel resamples.  stage_ms: graph (with the copies), search, seed
+struct __attribute__((visibility("hidden"))) RoadmapState {
+    DevBuf<double> In, Nodes, Len, Pts;
+    DevBuf<int> Rec, Dead, I;
+    DevBuf<unsigned long long> Vis;
+    int K = 0, Bq = 0;
+    bool have = false;
+    DevEvent t0, t1, t2, t3;
+    double last_ms = 0.0, stage_ms[3] = {0.0, 0.0, 0.0};
+    void invalidate() { have = false; }
+};
+
 // The library itself: `count` of `cap` entries on `device`, entry e at row e of xi, c [cap][n], tf, tag [cap], X [cap][N][n], U
 // [cap][N][m].  The features are the F positive-weight terms of the distance, in its order of summation: term f has the weight
 // w[f] and reads entry fmap[f] & 15 of x_init (fmap[f] >> 4 == 0), of the goal centre (1) or tf (2).  Feat is feature-major,
@@ -292,6 +308,7 @@ struct gusto_handle_s {
     TrajlibState trajlib;
     ReplanState replan;
     TightenState tighten;
+    RoadmapState roadmap;
     std::string err;
 
     // (the buffers and events free themselves; the caller has made `device` current: gusto_destroy)

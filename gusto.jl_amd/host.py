@@ -967,6 +967,88 @@ def solve_SCP_trajlib_batch(TOSs, TOPs, lib, K=1, fallback_fan=None, learn=False
     return out
 
 
+def solve_SCP_roadmap_batch(TOSs, TOPs, K=1, fallback_fan=None, straight_first=False, roadmap_opts=None, solver="hip", max_iter=30,
+                            force=False, device=0):
+    """Every TOP is one planning QUERY, seeded from a shortest collision-free polyline through the corners of its inflated
+    keep-out set (gusto_set_problems_roadmap: K alternates of other homotopy classes; a query with an unblocked line, or without
+    a path, is the straight line), solved in one launch of len(TOPs) K problems and answered with the best alternate that is
+    converged and successful (gusto_select_best on the last true cost).  All TOPs share model and N; each may bring its own
+    environment.  straight_first: alternate 0 is the straight line and the paths follow.  roadmap_opts: a dict of inflate / pad
+    over the model's defaults.
+
+    fallback_fan: the queries without a winner go through the multi-start path afterwards (gusto_set_problems_multistart with this
+    fan [Kf, 2]; True = default_fan), on the same handle -- the retry of solve_SCP_multistart_batch(policy="retry").
+
+    Returns one dict per query: `winner` (the alternate's index, -1 when none qualified), `cost` (its last J_true, +inf
+    likewise), `source` ("roadmap", "fan", or None without a winner), `status` (the ROADMAP_STATUS code of the winning alternate's
+    seed, of alternate 0 without a roadmap winner) and `SCPS`, the filled SCPSolution of the winner -- without one, of alternate 0.
+    `roadmap_ms` is the GPU time of the seeding call.  TOSs[q].traj and TOSs[q].SCPS are set as by solve_SCP_batch."""
+    if len(TOSs) != len(TOPs) or not TOPs:
+        raise ValueError("solve_SCP_roadmap_batch!: need as many solutions as problems, at least one")
+    TOP0 = TOPs[0]
+    model, N = TOP0.PD.model, TOP0.N
+    n = model.x_dim
+    Q, K = len(TOPs), int(K)
+    for t in TOPs[1:]:
+        if type(t.PD.model) is not type(model) or t.N != N:
+            raise ValueError("solve_SCP_roadmap_batch!: all problems must share the model type and N")
+    fan = None
+    if fallback_fan is not None and fallback_fan is not False:
+        fan = default_fan(model.model_id) if fallback_fan is True else np.asarray(fallback_fan, float).reshape(-1, 2)
+    same_env = all(np.array_equal(t.PD.env.boxes, TOP0.PD.env.boxes) and np.array_equal(t.PD.env.spheres, TOP0.PD.env.spheres)
+                   for t in TOPs[1:])
+    sp, mp = _capi.default_params(model.model_id)
+    x0 = np.stack([t.PD.x_init for t in TOPs])
+    bounds = [_goal_bounds(t.PD.goal_set, n, t.tf_guess) for t in TOPs]
+    lo, hi = np.stack([b[0] for b in bounds]), np.stack([b[1] for b in bounds])
+    tf = np.array([t.tf_guess for t in TOPs])
+    cap = Q * K if fan is None else max(Q * K, len(fan))
+    bs = BatchSolver(model.model_id, N, cap, hist_cap=_hist_cap(max_iter), device=device, boxes=TOP0.PD.env.boxes,
+                     spheres=TOP0.PD.env.spheres, scp_params=sp, model_params=mp)
+    out = [None] * Q
+
+    def take(q, snap, b, per, winner, cost, source, status, ms):
+        SCPP = SCPProblem(TOPs[q])
+        SCPS = SCPSolution(SCPP, init_traj_straightline(TOPs[q]))
+        _fill_solution(SCPS, SCPP, snap, b, per)
+        TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
+        out[q] = dict(winner=int(winner), cost=float(cost), source=source, status=int(status), roadmap_ms=float(ms), SCPS=SCPS)
+
+    try:
+        if not same_env:   # one set per query, repeated K times: query q reads that of problem q K
+            bs.set_env_batch([t.PD.env.boxes for t in TOPs for _ in range(K)], [t.PD.env.spheres for t in TOPs for _ in range(K)])
+        opts = dict(roadmap_opts or {}, straight_first=int(bool(straight_first)))
+        bs.set_problems_roadmap(x0, lo, hi, tf, K, **opts)
+        info, ms = bs.roadmap_info(), bs.last_roadmap_ms()
+        bs.solve(max_iter, force)
+        best = bs.select_best(K)
+        snap = _fetch(bs)
+        per = bs.last_solve_ms() * 1e-3 / Q
+        for q in range(Q):
+            w = best["winner"][q]
+            if w >= 0:
+                take(q, snap, best["winner_problem"][q], per, w, best["best_score"][q], "roadmap", info["status"][q * K + w], ms)
+            else:
+                take(q, snap, q * K, per, -1, np.inf, None, info["status"][q * K], ms)
+        again = np.flatnonzero(best["winner"] < 0)
+        if fan is not None:
+            Kf = len(fan)
+            for c in range(0, len(again), cap // Kf):
+                qs = again[c:c + cap // Kf]
+                env = {} if same_env else dict(boxes=[TOPs[q].PD.env.boxes for q in qs], spheres=[TOPs[q].PD.env.spheres for q in qs])
+                bs.set_problems_multistart(x0[qs], lo[qs], hi[qs], tf[qs], fan, **env)
+                bs.solve(max_iter, force)
+                best = bs.select_best(Kf)
+                snap = _fetch(bs)
+                per = bs.last_solve_ms() * 1e-3 / len(qs)
+                for i, q in enumerate(qs):
+                    if best["winner"][i] >= 0:
+                        take(q, snap, best["winner_problem"][i], per, best["winner"][i], best["best_score"][i], "fan", out[q]["status"], ms)
+    finally:
+        bs.close()
+    return out
+
+
 def _check_replan_tf(tf_new, who):
     """the reference's only row on the final time, Tf >= 0.1 (scp_gusto.jl:248-250), on tf' as TrajectoryOptimizationProblem
     checks it on tf_guess"""

@@ -1136,3 +1136,119 @@ function solve_SCP_chance_batch!(TOSs::Vector, TOPs::Vector; kappa=3.0, rounds=3
   ccall((:gusto_destroy, libgusto_hip), Cint, (Ptr{Cvoid},), h)
   (answered = answered, met = answered .& (lc.min_z_obs .>= kappa), min_z_obs = lc.min_z_obs, rounds = out)
 end
+
+# ---- roadmap seeds: every query starts from a shortest collision-free polyline (csrc/roadmap.hip) -------------------------------
+# None of the fan, the library and replanning looks at the keep-out set before the first solve; gusto_set_problems_roadmap does:
+# a visibility graph over the corners of the inflated keep-out components, per query the shortest path and, as alternates, the
+# shortest paths that avoid the corners of one more component each; the polyline resampled by arc length is the initial
+# trajectory (a query with an unblocked line, or without a path, is the straight line).  include/gusto_hip.h states the
+# definitions; the reference has no counterpart.  Mirrors gusto.jl_amd/host.py: BatchSolver.set_problems_roadmap,
+# solve_SCP_roadmap_batch.  This wrapper has not been run.
+const GUSTO_ROADMAP_MAX_K = 8
+const GUSTO_ROADMAP_MAX_VIA = 16
+struct GustoRoadmapOpts      # gusto_roadmap_opts
+  inflate::Cdouble; pad::Cdouble
+  straight_first::Cint
+end
+mutable struct GustoRoadmapReport      # gusto_roadmap_report
+  status::Ptr{Cint}; n_via::Ptr{Cint}
+  via::Ptr{Cint}
+  length::Ptr{Cdouble}
+  banned::Ptr{Cint}
+  stage_ms::Ptr{Cdouble}
+end
+
+# Bq queries (columns of x0, lo, hi; tf [Bq]) x K alternates become the B = Bq K problems of the handle h, problem (q - 1) K + j
+# = alternate j of query q, from the handle's current keep-out tables.  inflate / pad = nothing: the model's defaults.  Returns
+# (status, n_via, via [16, B], length, banned [8, B], stage_ms = (graph, search, seed), ms)
+function set_problems_roadmap!(h::Ptr{Cvoid}, model_id::Integer, x0::Matrix{Float64}, lo::Matrix{Float64}, hi::Matrix{Float64}, tf::Vector{Float64};
+                               K=1, inflate=nothing, pad=nothing, straight_first=false)
+  Bq = size(x0, 2); B = Bq * K
+  d = Ref(GustoRoadmapOpts(0., 0., 0))
+  gusto_check(ccall((:gusto_default_roadmap_opts, libgusto_hip), Cint, (Cint, Ref{GustoRoadmapOpts}), model_id, d), h, "default_roadmap_opts")
+  o = GustoRoadmapOpts(inflate === nothing ? d[].inflate : inflate, pad === nothing ? d[].pad : pad, straight_first ? 1 : 0)
+  gusto_check(ccall((:gusto_set_problems_roadmap, libgusto_hip), Cint,
+                    (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{GustoRoadmapOpts}),
+                    h, Bq, K, x0, lo, hi, tf, o), h, "set_problems_roadmap")
+  status, n_via, via, len = zeros(Cint, B), zeros(Cint, B), zeros(Cint, GUSTO_ROADMAP_MAX_VIA, B), zeros(B)
+  banned, stage = zeros(Cint, GUSTO_ROADMAP_MAX_K, B), zeros(3)
+  GC.@preserve status n_via via len banned stage begin
+    rep = GustoRoadmapReport(pointer(status), pointer(n_via), pointer(via), pointer(len), pointer(banned), pointer(stage))
+    gusto_check(ccall((:gusto_get_roadmap, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoRoadmapReport}), h, rep), h, "get_roadmap")
+  end
+  ms = Ref{Cdouble}(0.)
+  gusto_check(ccall((:gusto_last_roadmap_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, ms), h, "last_roadmap_ms")
+  (status = status, n_via = n_via, via = via, length = len, banned = banned, stage_ms = stage, ms = ms[])
+end
+
+# Every TOP is one planning QUERY, seeded by set_problems_roadmap! with K alternates, solved in one launch of Q K problems and
+# answered with the best alternate that is converged and successful (gusto_select_best on the last true cost).  fallback_fan: the
+# queries without a winner go through solve_SCP_multistart_batch!'s fan afterwards (true = gusto_default_fan).  Returns per query
+# (winner, cost, source, status): the winning alternate (1-based; 0 = none qualified), its cost (Inf likewise), :roadmap, :fan or
+# :none, and the roadmap status of the winning alternate's seed (of alternate 1 without a roadmap winner).  All TOPs share model, N
+# and the environment.
+function solve_SCP_roadmap_batch!(TOSs::Vector, TOPs::Vector; K=1, fallback_fan=nothing, straight_first=false, inflate=nothing, pad=nothing,
+                                  max_iter=30, force=false, device=0)
+  TOP0 = TOPs[1]; model, N = TOP0.PD.model, TOP0.N
+  n, m, Q = model.x_dim, model.u_dim, length(TOPs)
+  all(T -> typeof(T.PD.model) == typeof(model) && T.N == N && T.PD.env === TOP0.PD.env, TOPs) ||
+    error("solve_SCP_roadmap_batch!: all problems must share the model type, N and the environment")
+  alg0 = SCPParam_GuSTO(model)
+  sp = GustoScpParams(alg0.Δ0, alg0.ω0, alg0.ω_max, alg0.ε, alg0.ρ0, alg0.ρ1, alg0.β_succ, alg0.β_fail, alg0.γ_fail,
+                      SCPParam(model, TOP0.fixed_final_time).convergence_threshold)
+  href = Ref{Ptr{Cvoid}}(C_NULL)
+  gusto_check(ccall((:gusto_create, libgusto_hip), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Cint),
+                    href, gusto_model_id(model), N, Q * K, gusto_hist_cap(max_iter), device), href[], "create")
+  h = href[]
+  gusto_check(ccall((:gusto_set_params, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoScpParams}, Ref{GustoModelParams}),
+                    h, sp, gusto_model_params(TOP0.PD.robot, model)), h, "set_params")
+  boxes, spheres = gusto_env_tables(TOP0.PD.env)
+  gusto_check(ccall((:gusto_set_env, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+                    h, length(boxes) ÷ 6, boxes, length(spheres) ÷ 4, spheres), h, "set_env")
+  x0 = hcat((Float64.(T.PD.x_init) for T in TOPs)...)
+  bounds = [gusto_goal_bounds(T.PD.goal_set, n, T.tf_guess) for T in TOPs]
+  lo, hi = hcat(first.(bounds)...), hcat(last.(bounds)...)
+  tf = Float64[T.tf_guess for T in TOPs]
+  info = set_problems_roadmap!(h, gusto_model_id(model), x0, lo, hi, tf; K=K, inflate=inflate, pad=pad, straight_first=straight_first)
+  B = Q * K
+  gusto_check(ccall((:gusto_solve, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Cint), h, max_iter, force), h, "solve")
+  X, U = zeros(n, N, B), zeros(m, N, B)
+  gusto_check(ccall((:gusto_get_traj, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), h, X, U), h, "get_traj")
+  its, conv, succ, stop = zeros(Cint, B), zeros(Cint, B), zeros(Cint, B), zeros(Cint, B)
+  gusto_check(ccall((:gusto_get_status, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ptr{Cvoid}),
+                    h, its, conv, succ, stop, C_NULL), h, "get_status")
+  duals = zeros(n, B)
+  gusto_check(ccall((:gusto_get_dual, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, duals), h, "get_dual")
+  msec = Ref{Cdouble}(0.)
+  ccall((:gusto_last_solve_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, msec)
+  Hs = gusto_histories(h, B)
+  gusto_check(ccall((:gusto_select_best, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cint}), h, K, C_NULL, C_NULL), h, "select_best")
+  win, wp, best = zeros(Cint, Q), zeros(Cint, Q), zeros(Q)
+  GC.@preserve win wp best begin
+    rep = GustoBestReport(pointer(win), pointer(wp), C_NULL, pointer(best), C_NULL, C_NULL)
+    gusto_check(ccall((:gusto_get_best, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoBestReport}), h, rep), h, "get_best")
+  end
+  result = Vector{Any}(undef, Q)
+  for q in 1:Q
+    j = win[q] >= 0 ? wp[q] + 1 : (q - 1) * K + 1
+    SCPP = SCPProblem(TOPs[q])
+    SCPP.param.alg = SCPParam_GuSTO(model)
+    SCPS = SCPSolution(SCPP, Trajectory(X[:, :, j], U[:, :, j], TOPs[q].tf_guess))
+    gusto_fill_solution!(SCPS, SCPP.param.alg, Hs, j, its[j], conv[j], succ[j], stop[j], duals[:, j])
+    SCPS.total_time = msec[] / 1e3 / B
+    SCPS.iter_elapsed_times = vcat(0., fill(SCPS.total_time / max(1, its[j]), its[j]))
+    SCPP.param.obstacle_toggle_distance = SCPP.param.alg.Δ_vec[end] / 8 + model.clearance
+    TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
+    result[q] = (winner = win[q] + 1, cost = win[q] >= 0 ? best[q] : Inf, source = win[q] >= 0 ? :roadmap : :none, status = info.status[j])
+  end
+  ccall((:gusto_destroy, libgusto_hip), Cint, (Ptr{Cvoid},), h)
+  lost = findall(r -> r.winner == 0, result)
+  if fallback_fan !== nothing && fallback_fan !== false && !isempty(lost)
+    fan = fallback_fan === true ? nothing : fallback_fan
+    again = solve_SCP_multistart_batch!(TOSs[lost], TOPs[lost]; fan=fan, policy=:all, max_iter=max_iter, force=force, device=device)
+    for (i, q) in enumerate(lost)
+      again[i][1] > 0 && (result[q] = (winner = again[i][1], cost = again[i][2], source = :fan, status = result[q].status))
+    end
+  end
+  result
+end

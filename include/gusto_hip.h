@@ -870,6 +870,81 @@ int gusto_get_env(gusto_handle h, int* n_env, int* n_box, double* box_min_max, i
 /* GPU time of the last gusto_tighten_env (copies and the kernel), from HIP events on the handle's stream */
 int gusto_last_tighten_ms(gusto_handle h, double* ms);
 
+/* Roadmap seeds (csrc/roadmap.hip): GuSTO is a local method, and the fan, the library and replanning all start from the straight
+ * line or from earlier plans; none looks at the keep-out set before the first solve.  This call does: every query starts from a
+ * shortest collision-free polyline through the corners of its inflated keep-out set (a visibility graph), its alternates from
+ * the shortest paths that avoid the corners of one more component each.  No counterpart in the reference, whose
+ * init_traj_straightline is what a query with an unblocked line gets.  The definitions, WS = 2 in the plane and 3 in space:
+ * Layout: that of gusto_set_problems_multistart.  Bq queries with K alternates each, 1 <= K <= GUSTO_ROADMAP_MAX_K, become the
+ *   B = Bq K problems of the handle; problem b = q K + j is alternate j of query q.  x_init, goal_lo, goal_hi [Bq][x_dim] and tf
+ *   [Bq] are HOST arrays; everything gusto_set_problems does afterwards happens unchanged.
+ * Keep-out set: the handle's current tables.  After gusto_set_env the set is shared by the batch; after gusto_set_env_batch or
+ *   gusto_tighten_env the handle must hold Bq K sets (else GUSTO_ERR_STATE) and query q uses the set of problem q K.  Components
+ *   come in table order, boxes then spheres, C <= 64; without components every query is DIRECT.  Coordinates are the first WS of
+ *   min, max and centre: the planar reading the solver has for WS = 2.
+ * Blocking sets: box i blocks the open box (lo - inflate, hi + inflate), the L-infinity inflation, a superset of the disc's;
+ *   sphere i blocks the open ball of radius R + inflate.
+ * Nodes: node 0 is x_init[0:WS]; node 1 the goal centre on those entries by the straight line's rule; node 2 + 2^WS i + c is
+ *   corner c of component i, bit j of c choosing the low or the high side: (lo_j - inflate) - pad or (hi_j + inflate) + pad for
+ *   a box, c_j -+ ((R + inflate) + pad) for a sphere.  A node strictly inside any blocking set is dead; so are the nodes of a
+ *   banned component (the component itself still blocks).
+ * Edges: two live nodes see each other when the segment between them meets no blocking set; the length of an edge is
+ *   sqrt(sum d_j^2) in coordinate order.
+ * Status of a search: GUSTO_ROADMAP_END_BLOCKED node 0 or node 1 is dead, else GUSTO_ROADMAP_DIRECT 0 sees 1, else
+ *   GUSTO_ROADMAP_PATH a path was found, GUSTO_ROADMAP_NO_PATH none exists, GUSTO_ROADMAP_TOO_LONG the shortest one has more than
+ *   GUSTO_ROADMAP_MAX_VIA interior nodes.
+ * Shortest path: Dijkstra from node 0 -- the unsettled node of smallest distance goes next, ties to the lowest index; a
+ *   predecessor changes on a strict `<` only; the search stops when node 1 is settled.
+ * Alternates: alternate 0 has no ban.  After alternate j - 1 the component that owns its first interior node joins the ban list;
+ *   alternate j is the shortest path under that list.  Once an alternate is not PATH, it and all later ones are the straight
+ *   line with the status, length and ban list of that alternate and n_via = 0.
+ * straight_first = 1: problem q K is the straight line and the alternates follow, problem q K + 1 + j is alternate j; with K >= 2
+ *   that is the pair a gusto_select_best decides.  The row of problem q K is that of alternate 0 when it is not PATH, else
+ *   status GUSTO_ROADMAP_STRAIGHT, n_via = 0, length +inf and an empty ban list.
+ * Seed of a PATH alternate: Lp the length of the polyline node 0, interior nodes, node 1, summed from node 0; t_k = k / (N - 1).
+ *   The first WS entries of X0[k] are the point at arc length t_k Lp on the polyline: on the first segment i whose end lies beyond
+ *   that length (the last one otherwise), P_i + ((t_k Lp - cum_i) / len_i) (P_{i+1} - P_i).  Knot 0 is written as x_init's own
+ *   entries and knot N - 1 as the goal centre's.  Every other entry is the straight line's expression, as the fan writes it;
+ *   U0 = 0.  Any other status is the straight line, bit for bit what gusto_set_problems with X0 = NULL writes.
+ * Options: inflate and pad default to radius + 0.02 and 0.03 -- placeholders taken from the table study of profiles/roadmap.txt
+ *   (the planar obstacle table, N = 50), not tuned for anything else.
+ * Report: all arrays [Bq K], caller-owned, any pointer may be NULL.  via: node indices, -1 behind n_via; length: Lp for PATH, the
+ *   distance from node 0 to node 1 for DIRECT, +inf otherwise; banned: the ban list the alternate was searched under, component
+ *   indices, -1 behind the count; stage_ms [3]: GPU time of the graph kernel (with the copies), the search and the seed kernel.
+ * GUSTO_ERR_ARG, nothing launched, the handle left as it was: K outside 1 .. GUSTO_ROADMAP_MAX_K, Bq < 1, Bq K > batch_cap, a
+ *   null array, options that are not finite or out of range, a TrajOpt handle.  All four models, one device.
+ * Kernels: the graph once per keep-out set (a wave per node and block of 64 nodes, the visibility matrix as a bit mask), the
+ *   search with one wavefront per query, the seed with a thread per knot; they run on the handle's stream and are timed together
+ *   with events.  No atomics, reductions in a fixed order: a query's outputs are the same bit for bit in any batch, and for a
+ *   shared set or the same set passed per problem. */
+#define GUSTO_ROADMAP_MAX_K 8
+#define GUSTO_ROADMAP_MAX_VIA 16
+#define GUSTO_ROADMAP_DIRECT 0
+#define GUSTO_ROADMAP_PATH 1
+#define GUSTO_ROADMAP_END_BLOCKED 2
+#define GUSTO_ROADMAP_NO_PATH 3
+#define GUSTO_ROADMAP_TOO_LONG 4
+#define GUSTO_ROADMAP_STRAIGHT 5
+typedef struct {
+    double inflate;       /* growth of every component before it blocks; finite, >= 0; default radius + 0.02 (placeholder) */
+    double pad;           /* distance of the corner nodes from the blocking sets; finite, > 0; default 0.03 (placeholder) */
+    int straight_first;   /* 1: problem q K is the straight line, the alternates follow; default 0 */
+} gusto_roadmap_opts;
+int gusto_default_roadmap_opts(int model_id, gusto_roadmap_opts* o);
+int gusto_set_problems_roadmap(gusto_handle h, int Bq, int K, const double* x_init, const double* goal_lo,
+                               const double* goal_hi, const double* tf, const gusto_roadmap_opts* o /* NULL: the defaults */);
+typedef struct {
+    int *status, *n_via;   /* [Bq K] */
+    int *via;              /* [Bq K][GUSTO_ROADMAP_MAX_VIA] */
+    double *length;        /* [Bq K] */
+    int *banned;           /* [Bq K][GUSTO_ROADMAP_MAX_K] */
+    double *stage_ms;      /* [3] graph, search, seed */
+} gusto_roadmap_report;    /* caller-owned, any pointer may be NULL */
+/* The report of the last gusto_set_problems_roadmap since the problems were set (none: GUSTO_ERR_STATE) */
+int gusto_get_roadmap(gusto_handle h, gusto_roadmap_report* out);
+/* GPU time of the last gusto_set_problems_roadmap (copies and the three kernels), from HIP events on the handle's stream */
+int gusto_last_roadmap_ms(gusto_handle h, double* ms);
+
 /* One convex subproblem per problem (what scp_gusto.jl:82-104 builds and solves in one trip), linearised at
  * (Xp,Up)[b] with the given Delta/omega/obstacle_toggle_distance[b].  Used by the parity tests.
  * Outputs: Xn,Un [B][N][.], obj [B] (JuMP.objective_value), status [B] (GUSTO_SOLVER_*), iters [B]. */
