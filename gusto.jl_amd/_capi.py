@@ -41,6 +41,8 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_set_problems_replan", "gusto_set_problems_replan_knots", "gusto_get_replan", "gusto_last_replan_ms",
            "gusto_default_tighten_opts", "gusto_tighten_env", "gusto_get_tighten", "gusto_get_env", "gusto_last_tighten_ms",
            "gusto_default_roadmap_opts", "gusto_set_problems_roadmap", "gusto_get_roadmap", "gusto_last_roadmap_ms",
+           "gusto_default_tfsearch_opts", "gusto_tfsearch_begin", "gusto_tfsearch_update", "gusto_get_tfsearch", "gusto_get_tfsearch_dev",
+           "gusto_last_tfsearch_ms",
            "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr", "gusto_dev_trajlib"]
 
 
@@ -197,6 +199,25 @@ class RoadmapReport(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in ROADMAP_FIELDS]
 
 
+class TfsearchOpts(C.Structure):
+    """gusto_tfsearch_opts: the range used where the per-query arrays are None, the relative width that ends a query, the seed"""
+    _fields_ = [("tf_lo", C.c_double), ("tf_hi", C.c_double), ("rtol", C.c_double), ("seed", C.c_int)]
+
+
+TFSEARCH_SEED = {"line": 0, "incumbent": 1}   # GUSTO_TFSEARCH_SEED_LINE, GUSTO_TFSEARCH_SEED_INCUMBENT
+TFSEARCH_NONE, TFSEARCH_DONE, TFSEARCH_FLOOR, TFSEARCH_NONMONOTONE = 1, 2, 4, 8   # bits of the status word
+# gusto_tfsearch_report in the header's order: (field, dtype, shape as a function of (Bq, K, N, n, m))
+TFSEARCH_FIELDS = tuple((k, np.int32, lambda Q, K, N, n, m: (Q,)) for k in ("status", "round_found", "n_eligible")) + \
+                  tuple((k, np.float64, lambda Q, K, N, n, m: (Q,)) for k in ("lo", "hi", "tf_best", "J_best")) + \
+                  (("cand", np.float64, lambda Q, K, N, n, m: (Q, K)), ("X", np.float64, lambda Q, K, N, n, m: (Q, N, n)),
+                   ("U", np.float64, lambda Q, K, N, n, m: (Q, N, m)))
+
+
+class TfsearchReport(C.Structure):
+    """gusto_tfsearch_report: caller-owned arrays"""
+    _fields_ = [(k, C.c_void_p) for k, _, _ in TFSEARCH_FIELDS]
+
+
 class TrajLibOpts(C.Structure):
     """gusto_trajlib_opts"""
     _fields_ = [("w_init", C.c_double * MAXN), ("w_goal", C.c_double * MAXN), ("w_tf", C.c_double), ("lds_tile", C.c_int)]
@@ -243,7 +264,7 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(_ROOT, "include"), "-fPIC",
              "-Wno-unused-value", "-Wno-pass-failed"]
-    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "trajlib", "replan", "tighten", "roadmap", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
+    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "trajlib", "replan", "tighten", "roadmap", "tfsearch", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
     bdir = os.path.join(_HERE, "build")
     os.makedirs(bdir, exist_ok=True)
 
@@ -369,6 +390,12 @@ def lib():
         L.gusto_set_problems_roadmap.argtypes = [vp, ci, ci, vp, vp, vp, vp, C.POINTER(RoadmapOpts)]
         L.gusto_get_roadmap.argtypes = [vp, C.POINTER(RoadmapReport)]
         L.gusto_last_roadmap_ms.argtypes = [vp, C.POINTER(C.c_double)]
+        L.gusto_default_tfsearch_opts.argtypes = [ci, C.POINTER(TfsearchOpts)]
+        L.gusto_tfsearch_begin.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, C.POINTER(TfsearchOpts)]
+        L.gusto_tfsearch_update.argtypes = [vp, vp]
+        L.gusto_get_tfsearch.argtypes = [vp, C.POINTER(TfsearchReport), C.POINTER(ci), C.POINTER(ci)]
+        L.gusto_get_tfsearch_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.gusto_last_tfsearch_ms.argtypes = [vp, C.POINTER(C.c_double)]
         L.gusto_default_trajopt_params.argtypes = [ci, C.POINTER(TrajOptParams)]
         L.gusto_create_trajopt.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci]
         L.gusto_set_trajopt_params.argtypes = [vp, C.POINTER(TrajOptParams)]
@@ -449,6 +476,14 @@ def default_roadmap_opts(model):
     rc = lib().gusto_default_roadmap_opts(model, C.byref(o))
     if rc:
         raise ValueError(f"gusto_default_roadmap_opts({model}) -> {rc}")
+    return o
+
+
+def default_tfsearch_opts(model):
+    o = TfsearchOpts()
+    rc = lib().gusto_default_tfsearch_opts(model, C.byref(o))
+    if rc:
+        raise ValueError(f"gusto_default_tfsearch_opts({model}) -> {rc}")
     return o
 
 
@@ -638,6 +673,66 @@ class BatchSolver:
     def last_roadmap_ms(self):
         """gusto_last_roadmap_ms: GPU time of the last set_problems_roadmap (copies, graph, search, seed)"""
         return self._last_ms("last_roadmap_ms")
+
+    def tfsearch_begin(self, x_init, goal_lo, goal_hi, tf_lo=None, tf_hi=None, K=8, rtol=None, seed=None, boxes=None, spheres=None):
+        """gusto_tfsearch_begin: Bq queries x K candidate final times become the B = Bq K problems of the handle, problem q K + j =
+        candidate j of query q, each started from the straight line.  tf_lo, tf_hi: a scalar or [Bq], the range searched (None: the
+        library's default); rtol: a query is done when hi - lo <= rtol hi; seed "incumbent" (later candidates start from the
+        query's retimed incumbent) or "line".  boxes / spheres: one keep-out set PER QUERY, repeated K times into set_env_batch;
+        None leaves the environment as it is.  Then: solve(); tfsearch_update(); ... while it returns queries still searching."""
+        x_init, goal_lo, goal_hi = _arr(x_init).reshape(-1, self.n), _arr(goal_lo).reshape(-1, self.n), \
+            _arr(goal_hi).reshape(-1, self.n)
+        Bq, K = x_init.shape[0], int(K)
+        o = default_tfsearch_opts(self.model)
+        if rtol is not None:
+            o.rtol = float(rtol)
+        if seed is not None:
+            if seed not in TFSEARCH_SEED and seed not in TFSEARCH_SEED.values():
+                raise ValueError(f"tfsearch_begin: seed is 'line' or 'incumbent', not {seed!r}")
+            o.seed = TFSEARCH_SEED.get(seed, seed)
+        lo = None if tf_lo is None else _arr(np.broadcast_to(np.asarray(tf_lo, dtype=np.float64), (Bq,)))
+        hi = None if tf_hi is None else _arr(np.broadcast_to(np.asarray(tf_hi, dtype=np.float64), (Bq,)))
+        self._chk(self.L.gusto_tfsearch_begin(self.h, Bq, K, x_init.ctypes.data, goal_lo.ctypes.data, goal_hi.ctypes.data,
+                                              None if lo is None else lo.ctypes.data, None if hi is None else hi.ctypes.data,
+                                              C.byref(o)), "tfsearch_begin")
+        self.B, self._tf, self._tfsearch = Bq * K, None, (Bq, K)
+        if boxes is not None or spheres is not None:
+            rep = lambda tables: None if tables is None else [t for t in tables for _ in range(K)]
+            self.set_env_batch(rep(boxes) if boxes is not None else [None] * self.B, rep(spheres))
+
+    def tfsearch_update(self, eligible=None):
+        """gusto_tfsearch_update, after a solve of the round's problems: incumbents, brackets and status words, the next round's
+        candidates and seeds; the problems of the queries that are done become inactive.  eligible [B]: which problems count
+        (None: the converged and successful ones).  Returns the number of queries still searching."""
+        el = None if eligible is None else _arr(np.asarray(eligible).astype(bool), np.int32).reshape(self.B)
+        self._chk(self.L.gusto_tfsearch_update(self.h, None if el is None else el.ctypes.data), "tfsearch_update")
+        ns = C.c_int()
+        self._chk(self.L.gusto_get_tfsearch(self.h, None, None, C.byref(ns)), "get_tfsearch")
+        return ns.value
+
+    def tfsearch_info(self):
+        """gusto_get_tfsearch: a dict over the Bq queries of status (bits TFSEARCH_NONE / DONE / FLOOR / NONMONOTONE), round_found
+        (-1: no incumbent), n_eligible, lo, hi, tf_best (NaN: no incumbent), J_best, cand [Bq, K], the incumbents X [Bq, N, n] and
+        U [Bq, N, m], and the scalars round (updates so far) and n_searching"""
+        Bq, K = self._tfsearch
+        out = {k: np.zeros(shape(Bq, K, self.N, self.n, self.m), dtype=t) for k, t, shape in TFSEARCH_FIELDS}
+        rep = TfsearchReport(**{k: v.ctypes.data for k, v in out.items()})
+        rd, ns = C.c_int(), C.c_int()
+        self._chk(self.L.gusto_get_tfsearch(self.h, C.byref(rep), C.byref(rd), C.byref(ns)), "get_tfsearch")
+        out["round"], out["n_searching"] = rd.value, ns.value
+        return out
+
+    def tfsearch_dev(self):
+        """gusto_get_tfsearch_dev as zero-copy torch views: the incumbents X [Bq, N, n], U [Bq, N, m] and tf_best [Bq]"""
+        Bq, _ = self._tfsearch
+        px, pu, pt = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._chk(self.L.gusto_get_tfsearch_dev(self.h, C.byref(px), C.byref(pu), C.byref(pt)), "get_tfsearch_dev")
+        return (_dev_view(px.value, (Bq, self.N, self.n), self.device), _dev_view(pu.value, (Bq, self.N, self.m), self.device),
+                _dev_view(pt.value, (Bq,), self.device))
+
+    def last_tfsearch_ms(self):
+        """gusto_last_tfsearch_ms: GPU time of the last tfsearch_begin / tfsearch_update (copies and kernels)"""
+        return self._last_ms("last_tfsearch_ms")
 
     def set_problems_trajlib(self, lib, x_init, goal_lo, goal_hi, tf, K=1, tag=None, boxes=None, spheres=None):
         """gusto_set_problems_trajlib: Bq queries seeded from their K nearest entries of the TrajLib `lib` become the B = Bq K problems

@@ -293,6 +293,7 @@ int gusto_problems_loaded(gusto_handle h, bool straight) {
     h->have_problems = true;
     h->shoot.invalidate(); h->verify.invalidate(); h->tvlqr.invalidate(); h->simulate.invalidate(); h->lincov.invalidate();
     h->select.invalidate(); h->trajlib.invalidate(); h->replan.invalidate(); h->tighten.invalidate(); h->roadmap.invalidate();
+    h->tfsearch.invalidate();   // (tfsearch.hip sets it again behind its own call)
     h->n_active = -1;   // (gusto_set_active belongs to the problems it was set for)
     return GUSTO_OK;
 }
@@ -337,6 +338,7 @@ int gusto_solve(gusto_handle h, int max_iter, int force) {
     int rc = gusto_finish(h);   // (a batch that lost a problem to a scheduler error is not resumed: gusto_set_problems first)
     if (rc) return rc;
     rc = do_scp(h, 0, max_iter, force ? 1 : 0);
+    if (!rc) h->solves++;
     return rc ? rc : gusto_finish(h);
 }
 
@@ -346,7 +348,9 @@ int gusto_solve_async(gusto_handle h, int max_iter, int force) {
     HIPCHK(h, hipSetDevice(h->device));
     int rc = gusto_finish(h);
     if (rc) return rc;
-    return do_scp(h, 0, max_iter, force ? 1 : 0);
+    rc = do_scp(h, 0, max_iter, force ? 1 : 0);
+    if (!rc) h->solves++;
+    return rc;
 }
 
 // Which problems of the batch the following gusto_solve / gusto_solve_async / gusto_shoot calls work on.  The reference's

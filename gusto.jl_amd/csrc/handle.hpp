@@ -238,6 +238,24 @@ struct __attribute__((visibility("hidden"))) RoadmapState {
     void invalidate() { have = false; }
 };
 
+// Final-time search (tfsearch.hip), Bq queries x K candidates: In the queries as the seed kernel reads them (x_init, goal_lo,
+// goal_hi [Bq][n] each); D [6][Bq] lo, hi, lo0, hi0, tf_best, J_best; I [4][Bq] status, round_found, n_eligible, parked (the
+// query was done before the last update: its problems are left alone); Cand [Bq][K]; X [Bq][N][n], U [Bq][N][m] the incumbents;
+// Elig [B] the copy of a caller's eligibility.  round: updates so far; n_searching: queries neither NONE nor DONE; solves_at: the
+// handle's count of solve calls at the last begin or update.  have: gusto_problems_loaded ends it, tfsearch.hip sets it again
+// behind its own call
+struct __attribute__((visibility("hidden"))) TfsearchState {
+    DevBuf<double> In, D, Cand, X, U;
+    DevBuf<int> I, Elig;
+    int K = 0, Bq = 0, round = 0, n_searching = 0, seed = 0;
+    double rtol = 0.0;
+    unsigned long long solves_at = 0;
+    bool have = false;
+    DevEvent t0, t1;
+    double last_ms = 0.0;
+    void invalidate() { have = false; }
+};
+
 // The library itself: `count` of `cap` entries on `device`, entry e at row e of xi, c [cap][n], tf, tag [cap], X [cap][N][n], U
 // [cap][N][m].  The features are the F positive-weight terms of the distance, in its order of summation: term f has the weight
 // w[f] and reads entry fmap[f] & 15 of x_init (fmap[f] >> 4 == 0), of the goal centre (1) or tf (2).  Feat is feature-major,
@@ -309,6 +327,8 @@ struct gusto_handle_s {
     ReplanState replan;
     TightenState tighten;
     RoadmapState roadmap;
+    TfsearchState tfsearch;
+    unsigned long long solves = 0;   // gusto_solve / gusto_solve_async calls that enqueued a launch (gusto_tfsearch_update asks for one)
     std::string err;
 
     // (the buffers and events free themselves; the caller has made `device` current: gusto_destroy)

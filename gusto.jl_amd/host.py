@@ -876,6 +876,77 @@ def solve_SCP_multistart_batch(TOSs, TOPs, fan=None, policy="all", solver="hip",
     return out
 
 
+def solve_SCP_min_time_batch(TOSs, TOPs, tf_lo, tf_hi, K=8, rounds=3, rtol=0.01, seed="incumbent", eligible=None, solver="hip",
+                             max_iter=30, force=False, device=0):
+    """Every TOP is one planning QUERY, answered with the shortest final time in [tf_lo, tf_hi] (scalars or one per query) whose
+    solve is eligible: a K-section search over solves (gusto_tfsearch_begin / gusto_tfsearch_update), K candidate final times per
+    query and round, at most `rounds` rounds, a query done once hi - lo <= rtol hi.  TOP.tf_guess is not read but for the goals'
+    times; TrajectoryOptimizationProblem(fixed_final_time=False) stays as inert as in the reference -- the search is this call.
+    All TOPs share model and N; each may bring its own environment.
+
+    seed: "incumbent" starts the later candidates from the query's retimed incumbent, "line" from the straight line.  eligible:
+    None (converged and successful) or a callable bs -> boolean mask [B] over the BatchSolver's problems after a round's solve --
+    "that also passes verify", "with min_z_obs >= kappa", "with J <= budget" are the same call.
+
+    Returns one dict per query: `tf` (NaN without an incumbent), `lo`, `hi`, `status` (bits _capi.TFSEARCH_NONE / DONE / FLOOR /
+    NONMONOTONE), `J` (the incumbent's last J_true) and `SCPS`, the filled SCPSolution of the solve that found the incumbent -- for
+    a NONE query of the straight line's solve at tf_hi.  TOSs[q].traj is the incumbent with Tf = tf, TOSs[q].SCPS that SCPS."""
+    if len(TOSs) != len(TOPs) or not TOPs:
+        raise ValueError("solve_SCP_min_time_batch!: need as many solutions as problems, at least one")
+    if rounds < 1:
+        raise ValueError("solve_SCP_min_time_batch!: need at least one round")
+    TOP0 = TOPs[0]
+    model, N = TOP0.PD.model, TOP0.N
+    n, Q, K = model.x_dim, len(TOPs), int(K)
+    for t in TOPs[1:]:
+        if type(t.PD.model) is not type(model) or t.N != N:
+            raise ValueError("solve_SCP_min_time_batch!: all problems must share the model type and N")
+    same_env = all(np.array_equal(t.PD.env.boxes, TOP0.PD.env.boxes) and np.array_equal(t.PD.env.spheres, TOP0.PD.env.spheres)
+                   for t in TOPs[1:])
+    sp, mp = _capi.default_params(model.model_id)
+    x0 = np.stack([t.PD.x_init for t in TOPs])
+    bounds = [_goal_bounds(t.PD.goal_set, n, t.tf_guess) for t in TOPs]
+    lo, hi = np.stack([b[0] for b in bounds]), np.stack([b[1] for b in bounds])
+    bs = BatchSolver(model.model_id, N, Q * K, hist_cap=_hist_cap(max_iter), device=device, boxes=TOP0.PD.env.boxes,
+                     spheres=TOP0.PD.env.spheres, scp_params=sp, model_params=mp)
+    out = [None] * Q
+
+    def take(q, snap, b, per, tf, info):
+        SCPP = SCPProblem(TOPs[q])
+        SCPP.tf_guess = float(tf)
+        SCPS = SCPSolution(SCPP, Trajectory(np.zeros((n, N)), np.zeros((model.u_dim, N)), tf))
+        _fill_solution(SCPS, SCPP, snap, b, per)
+        TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
+        out[q] = dict(tf=float(info["tf_best"][q]), lo=float(info["lo"][q]), hi=float(info["hi"][q]), status=int(info["status"][q]),
+                      J=float(info["J_best"][q]), SCPS=SCPS)
+
+    try:
+        env = {} if same_env else dict(boxes=[t.PD.env.boxes for t in TOPs], spheres=[t.PD.env.spheres for t in TOPs])
+        bs.tfsearch_begin(x0, lo, hi, tf_lo, tf_hi, K=K, rtol=rtol, seed=seed, **env)
+        cand = bs.tfsearch_info()["cand"]
+        for r in range(rounds):
+            bs.solve(max_iter, force)
+            snap = _fetch(bs)
+            per = bs.last_solve_ms() * 1e-3 / Q
+            ok = np.asarray(eligible(bs)).astype(bool) if eligible is not None else snap["st"]["converged"] & snap["st"]["successful"]
+            searching = bs.tfsearch_update(ok if eligible is not None else None)
+            info = bs.tfsearch_info()
+            for q in range(Q):
+                if info["round_found"][q] == r:      # the incumbent of this round: the lowest candidate at tf_best that counts
+                    j = int(np.flatnonzero(ok[q * K:(q + 1) * K] & (cand[q] == info["tf_best"][q]))[0])
+                    take(q, snap, q * K + j, per, cand[q, j], info)
+                elif out[q] is None and info["round_found"][q] < 0:
+                    take(q, snap, q * K + K - 1, per, cand[q, K - 1], info)   # (round 0, no incumbent: the line at tf_hi)
+                else:
+                    out[q].update(lo=float(info["lo"][q]), hi=float(info["hi"][q]), status=int(info["status"][q]))
+            cand = info["cand"]
+            if searching == 0:
+                break
+    finally:
+        bs.close()
+    return out
+
+
 class TrajLib(_capi.TrajLib):
     """A device-resident library of solved trajectories (gusto_trajlib): TrajLib(model_id, N, cap, device=0, w_init=None,
     w_goal=None, w_tf=None).  add_from(solver, mask=None, tag=None) appends the converged and successful (or the masked) problems

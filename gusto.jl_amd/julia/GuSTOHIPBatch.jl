@@ -1252,3 +1252,152 @@ function solve_SCP_roadmap_batch!(TOSs::Vector, TOPs::Vector; K=1, fallback_fan=
   end
   result
 end
+
+# ---- final-time search: per query the shortest final time whose solve is eligible (csrc/tfsearch.hip) --------------------------
+# fixed_final_time = false is inert in the reference: Tf is a variable with the single row Tf >= 0.1 and every solve runs at the
+# caller's guess.  The search runs around gusto_solve: K candidate final times per query and round, the bracket, the incumbent
+# plans, the next candidates and their seeds kept on the device.  include/gusto_hip.h states the definitions.  Mirrors
+# gusto.jl_amd/host.py: BatchSolver.tfsearch_begin / tfsearch_update / tfsearch_info, solve_SCP_min_time_batch.  This wrapper has
+# not been run.
+const GUSTO_TFSEARCH_SEED_LINE = 0
+const GUSTO_TFSEARCH_SEED_INCUMBENT = 1
+const GUSTO_TFSEARCH_NONE = 1
+const GUSTO_TFSEARCH_DONE = 2
+const GUSTO_TFSEARCH_FLOOR = 4
+const GUSTO_TFSEARCH_NONMONOTONE = 8
+struct GustoTfsearchOpts      # gusto_tfsearch_opts
+  tf_lo::Cdouble; tf_hi::Cdouble
+  rtol::Cdouble
+  seed::Cint
+end
+mutable struct GustoTfsearchReport      # gusto_tfsearch_report
+  status::Ptr{Cint}; round_found::Ptr{Cint}; n_eligible::Ptr{Cint}
+  lo::Ptr{Cdouble}; hi::Ptr{Cdouble}; tf_best::Ptr{Cdouble}; J_best::Ptr{Cdouble}
+  cand::Ptr{Cdouble}
+  X::Ptr{Cdouble}; U::Ptr{Cdouble}
+end
+
+# Bq queries (columns of x0, lo, hi) x K candidate final times in [tf_lo[q], tf_hi[q]] become the B = Bq K problems of the handle
+# h, problem (q - 1) K + j = candidate j of query q, each started from the straight line.  seed: :incumbent or :line.
+function tfsearch_begin!(h::Ptr{Cvoid}, model_id::Integer, x0::Matrix{Float64}, lo::Matrix{Float64}, hi::Matrix{Float64},
+                         tf_lo::Vector{Float64}, tf_hi::Vector{Float64}; K=8, rtol=0.01, seed=:incumbent)
+  Bq = size(x0, 2)
+  d = Ref(GustoTfsearchOpts(0., 0., 0., 0))
+  gusto_check(ccall((:gusto_default_tfsearch_opts, libgusto_hip), Cint, (Cint, Ref{GustoTfsearchOpts}), model_id, d), h, "default_tfsearch_opts")
+  o = GustoTfsearchOpts(d[].tf_lo, d[].tf_hi, rtol, seed == :line ? GUSTO_TFSEARCH_SEED_LINE : GUSTO_TFSEARCH_SEED_INCUMBENT)
+  gusto_check(ccall((:gusto_tfsearch_begin, libgusto_hip), Cint,
+                    (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{GustoTfsearchOpts}),
+                    h, Bq, K, x0, lo, hi, tf_lo, tf_hi, o), h, "tfsearch_begin")
+  nothing
+end
+
+# The report of the search on h: (status, round_found, n_eligible, lo, hi, tf_best, J_best, cand [K, Bq], X [n, N, Bq], U [m, N, Bq],
+# round, n_searching, ms)
+function tfsearch_info(h::Ptr{Cvoid}, Bq::Integer, K::Integer, N::Integer, n::Integer, m::Integer)
+  status, found, ne = zeros(Cint, Bq), zeros(Cint, Bq), zeros(Cint, Bq)
+  lo, hi, tfb, Jb, cand = zeros(Bq), zeros(Bq), zeros(Bq), zeros(Bq), zeros(K, Bq)
+  X, U = zeros(n, N, Bq), zeros(m, N, Bq)
+  rd, ns = Ref{Cint}(0), Ref{Cint}(0)
+  GC.@preserve status found ne lo hi tfb Jb cand X U begin
+    rep = GustoTfsearchReport(pointer(status), pointer(found), pointer(ne), pointer(lo), pointer(hi), pointer(tfb), pointer(Jb),
+                              pointer(cand), pointer(X), pointer(U))
+    gusto_check(ccall((:gusto_get_tfsearch, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoTfsearchReport}, Ref{Cint}, Ref{Cint}), h, rep, rd, ns),
+                h, "get_tfsearch")
+  end
+  ms = Ref{Cdouble}(0.)
+  gusto_check(ccall((:gusto_last_tfsearch_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, ms), h, "last_tfsearch_ms")
+  (status = status, round_found = found, n_eligible = ne, lo = lo, hi = hi, tf_best = tfb, J_best = Jb, cand = cand, X = X, U = U,
+   round = Int(rd[]), n_searching = Int(ns[]), ms = ms[])
+end
+
+# After a solve of the round's problems: incumbents, brackets, status words, the next candidates and seeds; the problems of the
+# queries that are done become inactive.  eligible: nothing (converged and successful) or a Bool / integer vector [B].  Returns
+# the number of queries still searching.
+function tfsearch_update!(h::Ptr{Cvoid}; eligible=nothing)
+  el = eligible === nothing ? C_NULL : Cint.(eligible .!= 0)
+  gusto_check(ccall((:gusto_tfsearch_update, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}), h, el), h, "tfsearch_update")
+  ns = Ref{Cint}(0)
+  gusto_check(ccall((:gusto_get_tfsearch, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cint}, Ref{Cint}), h, C_NULL, C_NULL, ns),
+              h, "get_tfsearch")
+  Int(ns[])
+end
+
+# Device pointers to the incumbents [n, N, Bq], [m, N, Bq] and tf_best [Bq]
+function tfsearch_dev(h::Ptr{Cvoid})
+  px, pu, pt = Ref{Ptr{Cdouble}}(C_NULL), Ref{Ptr{Cdouble}}(C_NULL), Ref{Ptr{Cdouble}}(C_NULL)
+  gusto_check(ccall((:gusto_get_tfsearch_dev, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Ptr{Cdouble}}, Ref{Ptr{Cdouble}}, Ref{Ptr{Cdouble}}),
+                    h, px, pu, pt), h, "get_tfsearch_dev")
+  (X = px[], U = pu[], tf_best = pt[])
+end
+
+# Every TOP is one planning QUERY, answered with the shortest final time in [tf_lo, tf_hi] (numbers or one per query) whose solve
+# is eligible: at most `rounds` rounds of K candidates.  eligible: nothing, or a function of (h, B) that returns the mask [B]
+# after a round's solve.  Returns per query (tf, lo, hi, status, J); TOSs[q].traj is the incumbent with Tf = tf, TOSs[q].SCPS the
+# solution of the solve that found it (without an incumbent: of the straight line's solve at tf_hi).  All TOPs share model, N and
+# the environment.  TrajectoryOptimizationProblem(...; fixed_final_time=false) stays as inert as in the reference.
+function solve_SCP_min_time_batch!(TOSs::Vector, TOPs::Vector, tf_lo, tf_hi; K=8, rounds=3, rtol=0.01, seed=:incumbent, eligible=nothing,
+                                   max_iter=30, force=false, device=0)
+  TOP0 = TOPs[1]; model, N = TOP0.PD.model, TOP0.N
+  n, m, Q = model.x_dim, model.u_dim, length(TOPs)
+  all(T -> typeof(T.PD.model) == typeof(model) && T.N == N && T.PD.env === TOP0.PD.env, TOPs) ||
+    error("solve_SCP_min_time_batch!: all problems must share the model type, N and the environment")
+  alg0 = SCPParam_GuSTO(model)
+  sp = GustoScpParams(alg0.Δ0, alg0.ω0, alg0.ω_max, alg0.ε, alg0.ρ0, alg0.ρ1, alg0.β_succ, alg0.β_fail, alg0.γ_fail,
+                      SCPParam(model, TOP0.fixed_final_time).convergence_threshold)
+  href = Ref{Ptr{Cvoid}}(C_NULL)
+  gusto_check(ccall((:gusto_create, libgusto_hip), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Cint),
+                    href, gusto_model_id(model), N, Q * K, gusto_hist_cap(max_iter), device), href[], "create")
+  h = href[]
+  gusto_check(ccall((:gusto_set_params, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoScpParams}, Ref{GustoModelParams}),
+                    h, sp, gusto_model_params(TOP0.PD.robot, model)), h, "set_params")
+  boxes, spheres = gusto_env_tables(TOP0.PD.env)
+  gusto_check(ccall((:gusto_set_env, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+                    h, length(boxes) ÷ 6, boxes, length(spheres) ÷ 4, spheres), h, "set_env")
+  x0 = hcat((Float64.(T.PD.x_init) for T in TOPs)...)
+  bounds = [gusto_goal_bounds(T.PD.goal_set, n, T.tf_guess) for T in TOPs]
+  lo, hi = hcat(first.(bounds)...), hcat(last.(bounds)...)
+  tlo = tf_lo isa Number ? fill(Float64(tf_lo), Q) : Float64.(tf_lo)
+  thi = tf_hi isa Number ? fill(Float64(tf_hi), Q) : Float64.(tf_hi)
+  tfsearch_begin!(h, gusto_model_id(model), x0, lo, hi, tlo, thi; K=K, rtol=rtol, seed=seed)
+  B = Q * K
+  info = tfsearch_info(h, Q, K, N, n, m)
+  taken = falses(Q)
+  for r in 0:rounds-1
+    cand = info.cand
+    gusto_check(ccall((:gusto_solve, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Cint), h, max_iter, force), h, "solve")
+    X, U = zeros(n, N, B), zeros(m, N, B)
+    gusto_check(ccall((:gusto_get_traj, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), h, X, U), h, "get_traj")
+    its, conv, succ, stop = zeros(Cint, B), zeros(Cint, B), zeros(Cint, B), zeros(Cint, B)
+    gusto_check(ccall((:gusto_get_status, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ptr{Cvoid}),
+                      h, its, conv, succ, stop, C_NULL), h, "get_status")
+    duals = zeros(n, B)
+    gusto_check(ccall((:gusto_get_dual, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, duals), h, "get_dual")
+    msec = Ref{Cdouble}(0.)
+    ccall((:gusto_last_solve_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, msec)
+    Hs = gusto_histories(h, B)
+    ok = eligible === nothing ? (conv .!= 0) .& (succ .!= 0) : Bool.(eligible(h, B) .!= 0)
+    searching = tfsearch_update!(h; eligible = eligible === nothing ? nothing : ok)
+    info = tfsearch_info(h, Q, K, N, n, m)
+    for q in 1:Q
+      j = 0
+      if info.round_found[q] == r         # the incumbent of this round: the lowest candidate at tf_best that counts
+        j = (q - 1) * K + findfirst(i -> ok[(q - 1) * K + i] && cand[i, q] == info.tf_best[q], 1:K)
+      elseif !taken[q] && info.round_found[q] < 0
+        j = q * K                         # (round 0, no incumbent: the line at tf_hi)
+      end
+      j == 0 && continue
+      taken[q] = true
+      SCPP = SCPProblem(TOPs[q])
+      SCPP.param.alg = SCPParam_GuSTO(model)
+      SCPS = SCPSolution(SCPP, Trajectory(X[:, :, j], U[:, :, j], cand[(j - 1) % K + 1, q]))
+      gusto_fill_solution!(SCPS, SCPP.param.alg, Hs, j, its[j], conv[j], succ[j], stop[j], duals[:, j])
+      SCPS.total_time = msec[] / 1e3 / B
+      SCPS.iter_elapsed_times = vcat(0., fill(SCPS.total_time / max(1, its[j]), its[j]))
+      SCPP.param.obstacle_toggle_distance = SCPP.param.alg.Δ_vec[end] / 8 + model.clearance
+      TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
+    end
+    searching == 0 && break
+  end
+  ccall((:gusto_destroy, libgusto_hip), Cint, (Ptr{Cvoid},), h)
+  [(tf = info.tf_best[q], lo = info.lo[q], hi = info.hi[q], status = Int(info.status[q]), J = info.J_best[q]) for q in 1:Q]
+end

@@ -945,6 +945,80 @@ int gusto_get_roadmap(gusto_handle h, gusto_roadmap_report* out);
 /* GPU time of the last gusto_set_problems_roadmap (copies and the three kernels), from HIP events on the handle's stream */
 int gusto_last_roadmap_ms(gusto_handle h, double* ms);
 
+/* Final-time search (csrc/tfsearch.hip): per query the shortest final time whose solve is eligible, found by K-section over
+ * solves.  The reference's free final time is a variable with the single row Tf >= 0.1 that nothing moves, so every solve runs at
+ * the caller's guess; Tf does not become a variable of the subproblem here either -- the search runs around gusto_solve:
+ *     gusto_tfsearch_begin; repeat { gusto_solve; gusto_tfsearch_update; } while queries are searching; gusto_get_tfsearch.
+ * Bracket, incumbent plans, candidates and seeds stay on the device between the launches.  The definitions:
+ * Layout: that of gusto_set_problems_multistart.  Bq queries with K candidate final times each, 1 <= K <= GUSTO_MAX_STARTS, are
+ *   the B = Bq K problems of the handle; problem b = q K + j is candidate j of query q and its tf is the candidate T_j.  x_init,
+ *   goal_lo, goal_hi [Bq][x_dim] and the range tf_lo, tf_hi [Bq] (NULL: the options' value for every query) are HOST arrays;
+ *   gusto_set_env_batch needs B sets, as for multi-start.  After begin, and after every update, everything gusto_set_problems
+ *   does has happened: history reset, stages and selection invalidated, every problem active (but those of a done query, below).
+ * Per query: the bracket lo, hi and the caller's lo0, hi0; the incumbent -- tf_best, its X [N][x_dim] and U [N][u_dim] as the
+ *   solve left them, J_best its last J_true (NaN when it has none), round_found (-1: no incumbent, tf_best NaN) --; the status
+ *   word; the current candidates.
+ * Candidates: w = hi - lo.  Round 0 (no incumbent): T_j = lo + (j + 1) (w / K) for j < K - 1 and T_{K-1} = hi itself.  With an
+ *   incumbent hi is known good: T_j = lo + (j + 1) (w / (K + 1)), j = 0 .. K - 1.  One rounded difference, division, product and
+ *   sum in IEEE double, nothing fused.  K = 1 is bisection after the first round.
+ * Seeds.  GUSTO_TFSEARCH_SEED_LINE, or a query without an incumbent: the straight line and U0 = 0, bit for bit what
+ *   gusto_set_problems with X0 = NULL writes for that x_init, goal and tf.  GUSTO_TFSEARCH_SEED_INCUMBENT with an incumbent: the
+ *   incumbent retimed, s = tf_best / T_j: X0[k][i] = X_inc[k][i] outside the rate entries R, s X_inc[k][i] + (1 - s) L_k[i] on
+ *   them (L_k the straight line's knot), U0[k] = (s s) U_inc[k], knot 0 x_init itself.  R: FreeflyerSE2 {3, 4, 5}, AstrobeeSE3
+ *   {3, 4, 5, 9, 10, 11}, AstrobeeSE3Manifold {3, 4, 5, 10, 11, 12}.  Time scaling is an exact symmetry of these models (double
+ *   integrator, attitude kinematics, Euler's equations) and of their trapezoid rows: the position and attitude rows of the
+ *   collocation defect are unchanged, the rate rows multiplied by s; the (1 - s) L term only restores non-zero end rates.  The
+ *   speed of DubinsCar is a constant of the model, nothing retimes: GUSTO_TFSEARCH_SEED_INCUMBENT is GUSTO_ERR_ARG there.
+ * Update, after a solve of the round's problems.  T_j is the problem's tf on the device; ok_j is eligible[q K + j] != 0 (a HOST
+ *   array [B]) or, for NULL, converged && successful.
+ *   1. F' = the smallest T_j with ok_j, ties to the lowest j.  If it exists and there is no incumbent or F' < tf_best (strict),
+ *      that problem becomes the incumbent; round_found = the number of updates before this one.  n_eligible = |{j : ok_j}|.
+ *   2. F = tf_best.  With an incumbent hi = F and lo = max({lo0}, {lo_old if lo_old < F}, {T_j : !ok_j, T_j < F}); without one
+ *      lo = max_j T_j and hi = hi0.
+ *   3. Status bits: GUSTO_TFSEARCH_NONE no incumbent after a round; GUSTO_TFSEARCH_DONE hi - lo <= rtol hi (a rounded difference
+ *      and product); GUSTO_TFSEARCH_FLOOR lo == lo0, the lower end was never refuted and the answer may lie below the range;
+ *      GUSTO_TFSEARCH_NONMONOTONE some i < j with ok_i && !ok_j, or lo_old >= F, in this or an earlier round.  NONE or DONE: the
+ *      query is done.
+ *   4. A searching query gets the next candidates and their seeds.  A done query is not touched by later updates; its K
+ *      problems become the straight line at tf = hi (so do its candidates) and are inactive (gusto_set_active) in later solves.
+ *   No rule assumes that the verdicts are monotone in tf.  After round 0 hi - lo <= w0 / K, and after every further round the
+ *   width is at most the previous one divided by K + 1, up to the roundings of the candidates.
+ * GUSTO_ERR_ARG, nothing launched, the handle left as it was: a TrajOpt handle, K outside 1 .. GUSTO_MAX_STARTS, Bq < 1,
+ *   Bq K > batch_cap, a null x_init or goal array, a query whose range is not 0 < tf_lo < tf_hi < inf, rtol outside [1e-6, 1),
+ *   an unknown seed, DubinsCar with GUSTO_TFSEARCH_SEED_INCUMBENT.  GUSTO_ERR_STATE: update or a getter before begin or after any
+ *   other gusto_set_problems* call on the handle; update when no query is searching; update with eligible = NULL and no
+ *   gusto_solve / gusto_solve_async since the last begin or update.
+ * Kernels: begin with a thread per candidate, update with one wavefront per query (lane j = candidate j), seed with a thread
+ *   per (problem, knot); on the handle's stream, timed with events.  An update reads the Bq status words back, nothing else.
+ *   No atomics, nothing crosses a query: a query's report and seeds are the same bit for bit in any batch. */
+enum { GUSTO_TFSEARCH_SEED_LINE = 0, GUSTO_TFSEARCH_SEED_INCUMBENT = 1 };
+#define GUSTO_TFSEARCH_NONE 1
+#define GUSTO_TFSEARCH_DONE 2
+#define GUSTO_TFSEARCH_FLOOR 4
+#define GUSTO_TFSEARCH_NONMONOTONE 8
+typedef struct {
+    double tf_lo, tf_hi;   /* used where the per-query arrays are NULL; 0 < tf_lo < tf_hi, finite; default 1, 100 (placeholders) */
+    double rtol;           /* a query is done when hi - lo <= rtol * hi; in [1e-6, 1); default 0.01 */
+    int seed;              /* GUSTO_TFSEARCH_SEED_*; default INCUMBENT (DubinsCar: LINE) */
+} gusto_tfsearch_opts;
+int gusto_default_tfsearch_opts(int model_id, gusto_tfsearch_opts* o);
+int gusto_tfsearch_begin(gusto_handle h, int Bq, int K, const double* x_init, const double* goal_lo, const double* goal_hi,
+                         const double* tf_lo /* [Bq] or NULL */, const double* tf_hi /* [Bq] or NULL */,
+                         const gusto_tfsearch_opts* o /* NULL: the defaults */);
+int gusto_tfsearch_update(gusto_handle h, const int* eligible /* [B] HOST, or NULL = converged && successful */);
+typedef struct {
+    int *status, *round_found, *n_eligible;   /* [Bq]; n_eligible: of the query's last round */
+    double *lo, *hi, *tf_best, *J_best;       /* [Bq] */
+    double *cand;                             /* [Bq][K] */
+    double *X, *U;                            /* [Bq][N][x_dim], [Bq][N][u_dim]: the incumbents (zeros before the first) */
+} gusto_tfsearch_report;                      /* caller-owned, any pointer may be NULL */
+/* The search's report; *round the number of updates so far, *n_searching the queries neither NONE nor DONE (either may be NULL) */
+int gusto_get_tfsearch(gusto_handle h, gusto_tfsearch_report* out, int* round, int* n_searching);
+/* Device pointers to the incumbents [Bq][N][x_dim], [Bq][N][u_dim] and tf_best [Bq], valid until the next begin */
+int gusto_get_tfsearch_dev(gusto_handle h, const double** X_dev, const double** U_dev, const double** tf_best_dev);
+/* GPU time of the last begin or update (copies and kernels), from HIP events on the handle's stream */
+int gusto_last_tfsearch_ms(gusto_handle h, double* ms);
+
 /* One convex subproblem per problem (what scp_gusto.jl:82-104 builds and solves in one trip), linearised at
  * (Xp,Up)[b] with the given Delta/omega/obstacle_toggle_distance[b].  Used by the parity tests.
  * Outputs: Xn,Un [B][N][.], obj [B] (JuMP.objective_value), status [B] (GUSTO_SOLVER_*), iters [B]. */
