@@ -598,22 +598,30 @@ class BatchSolver:
                                             None if U0 is None else self._keep[5].ctypes.data), "set_problems")
         self.B, self._tf = B, tf.copy()
 
+    def _query_arrays(self, x_init, goal_lo, goal_hi, tf=None):
+        """the [Bq] inputs of a query entry as the C ABI reads them: x_init, goal_lo, goal_hi [Bq, n], tf [Bq] (a scalar is
+        broadcast; None stays None), and Bq"""
+        x_init, goal_lo, goal_hi = (_arr(a).reshape(-1, self.n) for a in (x_init, goal_lo, goal_hi))
+        Bq = x_init.shape[0]
+        return x_init, goal_lo, goal_hi, None if tf is None else _arr(np.broadcast_to(np.asarray(tf, dtype=np.float64), (Bq,))), Bq
+
+    def _env_per_query(self, K, boxes, spheres):
+        """one keep-out set per query, repeated K times into set_env_batch; None for both leaves the environment as it is"""
+        if boxes is not None or spheres is not None:
+            rep = lambda tables: None if tables is None else [t for t in tables for _ in range(K)]
+            self.set_env_batch(rep(boxes) if boxes is not None else [None] * self.B, rep(spheres))
+
     def set_problems_multistart(self, x_init, goal_lo, goal_hi, tf, fan, boxes=None, spheres=None):
         """gusto_set_problems_multistart: Bq queries x K = len(fan) starts become the B = Bq K problems of the handle, problem
         q K + j = start j of query q; fan [K, 2] the lateral offsets (a2, a3) in metres, (0, 0) the straight line.  boxes / spheres:
         one keep-out set PER QUERY (lists of Bq tables), repeated K times into set_env_batch; None leaves the environment as it is."""
-        x_init, goal_lo, goal_hi = _arr(x_init).reshape(-1, self.n), _arr(goal_lo).reshape(-1, self.n), \
-            _arr(goal_hi).reshape(-1, self.n)
-        Bq = x_init.shape[0]
-        tf = _arr(np.broadcast_to(np.asarray(tf, dtype=np.float64), (Bq,)))
+        x_init, goal_lo, goal_hi, tf, Bq = self._query_arrays(x_init, goal_lo, goal_hi, tf)
         fan = _arr(fan).reshape(-1, 2)
         K = fan.shape[0]
         self._chk(self.L.gusto_set_problems_multistart(self.h, Bq, K, x_init.ctypes.data, goal_lo.ctypes.data, goal_hi.ctypes.data,
                                                        tf.ctypes.data, fan.ctypes.data), "set_problems_multistart")
         self.B, self._tf = Bq * K, np.repeat(tf, K)
-        if boxes is not None or spheres is not None:
-            rep = lambda tables: None if tables is None else [t for t in tables for _ in range(K)]
-            self.set_env_batch(rep(boxes) if boxes is not None else [None] * self.B, rep(spheres))
+        self._env_per_query(K, boxes, spheres)
 
     def select_best(self, K, score=None, eligible=None):
         """gusto_select_best + gusto_get_best: per group of K consecutive problems the eligible one with the smallest score (ties:
@@ -647,10 +655,8 @@ class BatchSolver:
         keep-out set (set_env: shared; set_env_batch / tighten_env: Bq K sets, query q uses that of problem q K).  opts: None (the
         defaults on the handle's radius), a RoadmapOpts, or keywords of its fields (inflate, pad, straight_first) over the model's
         defaults.  The report: roadmap_info()."""
-        x_init, goal_lo, goal_hi = _arr(x_init).reshape(-1, self.n), _arr(goal_lo).reshape(-1, self.n), \
-            _arr(goal_hi).reshape(-1, self.n)
-        Bq, K = x_init.shape[0], int(K)
-        tf = _arr(np.broadcast_to(np.asarray(tf, dtype=np.float64), (Bq,)))
+        x_init, goal_lo, goal_hi, tf, Bq = self._query_arrays(x_init, goal_lo, goal_hi, tf)
+        K = int(K)
         if kw:   # (a caller's RoadmapOpts is not written to)
             opts = default_roadmap_opts(self.model) if opts is None else RoadmapOpts(opts.inflate, opts.pad, opts.straight_first)
         for k, v in kw.items():
@@ -680,9 +686,8 @@ class BatchSolver:
         library's default); rtol: a query is done when hi - lo <= rtol hi; seed "incumbent" (later candidates start from the
         query's retimed incumbent) or "line".  boxes / spheres: one keep-out set PER QUERY, repeated K times into set_env_batch;
         None leaves the environment as it is.  Then: solve(); tfsearch_update(); ... while it returns queries still searching."""
-        x_init, goal_lo, goal_hi = _arr(x_init).reshape(-1, self.n), _arr(goal_lo).reshape(-1, self.n), \
-            _arr(goal_hi).reshape(-1, self.n)
-        Bq, K = x_init.shape[0], int(K)
+        x_init, goal_lo, goal_hi, _, Bq = self._query_arrays(x_init, goal_lo, goal_hi)
+        K = int(K)
         o = default_tfsearch_opts(self.model)
         if rtol is not None:
             o.rtol = float(rtol)
@@ -690,15 +695,12 @@ class BatchSolver:
             if seed not in TFSEARCH_SEED and seed not in TFSEARCH_SEED.values():
                 raise ValueError(f"tfsearch_begin: seed is 'line' or 'incumbent', not {seed!r}")
             o.seed = TFSEARCH_SEED.get(seed, seed)
-        lo = None if tf_lo is None else _arr(np.broadcast_to(np.asarray(tf_lo, dtype=np.float64), (Bq,)))
-        hi = None if tf_hi is None else _arr(np.broadcast_to(np.asarray(tf_hi, dtype=np.float64), (Bq,)))
+        lo, hi = (None if v is None else _arr(np.broadcast_to(np.asarray(v, dtype=np.float64), (Bq,))) for v in (tf_lo, tf_hi))
         self._chk(self.L.gusto_tfsearch_begin(self.h, Bq, K, x_init.ctypes.data, goal_lo.ctypes.data, goal_hi.ctypes.data,
                                               None if lo is None else lo.ctypes.data, None if hi is None else hi.ctypes.data,
                                               C.byref(o)), "tfsearch_begin")
         self.B, self._tf, self._tfsearch = Bq * K, None, (Bq, K)
-        if boxes is not None or spheres is not None:
-            rep = lambda tables: None if tables is None else [t for t in tables for _ in range(K)]
-            self.set_env_batch(rep(boxes) if boxes is not None else [None] * self.B, rep(spheres))
+        self._env_per_query(K, boxes, spheres)
 
     def tfsearch_update(self, eligible=None):
         """gusto_tfsearch_update, after a solve of the round's problems: incumbents, brackets and status words, the next round's
@@ -739,17 +741,13 @@ class BatchSolver:
         of the handle, problem q K + j = neighbour j of query q (a start without a neighbour is the straight line).  tag [Bq]: only
         the entries with the query's tag are eligible (None: all).  boxes / spheres: one keep-out set PER QUERY, repeated K times
         into set_env_batch; None leaves the environment as it is.  The seeds: trajlib_seeds()."""
-        x_init, goal_lo, goal_hi = _arr(x_init).reshape(-1, self.n), _arr(goal_lo).reshape(-1, self.n), \
-            _arr(goal_hi).reshape(-1, self.n)
-        Bq, K = x_init.shape[0], int(K)
-        tf = _arr(np.broadcast_to(np.asarray(tf, dtype=np.float64), (Bq,)))
+        x_init, goal_lo, goal_hi, tf, Bq = self._query_arrays(x_init, goal_lo, goal_hi, tf)
+        K = int(K)
         tg = None if tag is None else _arr(tag, np.int32).reshape(Bq)
         self._chk(self.L.gusto_set_problems_trajlib(self.h, lib.h, Bq, K, x_init.ctypes.data, goal_lo.ctypes.data, goal_hi.ctypes.data,
                                                     tf.ctypes.data, None if tg is None else tg.ctypes.data), "set_problems_trajlib")
         self.B, self._trajlib_K, self._tf = Bq * K, K, np.repeat(tf, K)
-        if boxes is not None or spheres is not None:
-            rep = lambda tables: None if tables is None else [t for t in tables for _ in range(K)]
-            self.set_env_batch(rep(boxes) if boxes is not None else [None] * self.B, rep(spheres))
+        self._env_per_query(K, boxes, spheres)
 
     def trajlib_seeds(self):
         """gusto_get_trajlib_seeds: a dict of entry [Bq, K] (-1: the straight line), dist2 [Bq, K] (+inf likewise), n_found [Bq]"""
@@ -761,9 +759,7 @@ class BatchSolver:
 
     def last_trajlib_ms(self):
         """gusto_last_trajlib_ms: GPU time of search plus retargeting of the last set_problems_trajlib"""
-        ms = C.c_double()
-        self._chk(self.L.gusto_last_trajlib_ms(self.h, C.byref(ms)), "last_trajlib_ms")
-        return ms.value
+        return self._last_ms("last_trajlib_ms")
 
     def trajlib_phase_ms(self):
         """gusto_dev_trajlib: (search_ms, retarget_ms) of the last set_problems_trajlib"""

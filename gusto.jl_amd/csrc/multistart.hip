@@ -7,8 +7,8 @@
 // Fan kernel: a thread per (problem, knot), the shape of init_straightline_kernel (scp.hpp).  A thread derives its query's
 // frame from the [Bq] inputs -- a handful of flops, cheaper than a second launch and a frame buffer -- and writes its knot's n
 // states and m controls; the thread of knot 1 also writes the problem's replicated x_init, goal_lo, goal_hi and tf.
-// Consecutive threads write consecutive knots, so a wavefront covers one contiguous range of X and of U.  The straight-line
-// expression is the one of init_straightline_kernel, written the same way: a start with a zero offset is that kernel's output
+// Consecutive threads write consecutive knots, so a wavefront covers one contiguous range of X and of U.  The straight line
+// is straight_line() of seed.hpp, the one init_straightline_kernel evaluates: a start with a zero offset is that kernel's output
 // bit for bit, and so are the entries behind the workspace of every start.
 // Select kernel: one wavefront per query, lane j = start j (K <= 64).  A wave_reduce minimum over the eligible scores, a
 // second one over the lanes that hold it picks the lowest lane (the idiom of obstacle_margin in lincov.hip), then the whole
@@ -16,34 +16,36 @@
 // nothing crosses a query: a query's report is the same bit for bit in any batch.
 #include <hip/hip_runtime.h>
 
-#include "post.hpp"
+#include "seed.hpp"
 
 using namespace gusto;
 
 namespace {
 
 struct FanArgs {
-    const double *xi, *glo, *ghi, *tf, *fan;             // the queries: [Bq][n] each, [Bq]; the offsets [K][2]
-    double *X, *U, *x_init, *goal_lo, *goal_hi, *tf_b;   // the handle's [B] arrays
-    int B, K, N;
+    QueryDev Q;   // the queries; extra: tf [Bq], then the offsets [K][2]
+    SeedOut out;
+    int B, Bq, K, N;
 };
 
 template <int MODEL> __global__ void fan_kernel(const FanArgs A) {
     using T = MT<MODEL>;
     constexpr int n = T::n, m = T::m, WS = T::WS;
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= A.B * A.N) return;
-    const int b = gid / A.N, k = gid % A.N, q = b / A.K, j = b % A.K;
-    const double t = (double)k / (double)(A.N - 1);  // LinRange element: (1-t)*a + t*b
-    double x[n], pi[WS], pg[WS];
+    KnotId id;
+    if (!knot_id(A.B, A.K, A.N, id)) return;
+    const int b = id.b, k = id.k, j = id.j;
+    const double t = id.t;
+    const size_t qn = (size_t)id.q * n;   // the query's row of xi, glo, ghi
+    const double *tf = A.Q.extra, *fan = tf + A.Bq;
+    double* Xo = A.out.X + ((size_t)b * A.N + k) * n;
+    double x[WS], pi[WS], pg[WS];   // the workspace entries; the others are the line's and go out at once
 #pragma unroll
     for (int i = 0; i < n; i++) {
-        const double lo = A.glo[(size_t)q * n + i], hi = A.ghi[(size_t)q * n + i];
-        const double xg = (isfinite(lo) && isfinite(hi)) ? 0.5 * (lo + hi) : 0.0;  // center(goal), zeros elsewhere
-        x[i] = (1 - t) * A.xi[(size_t)q * n + i] + t * xg;
-        if (i < WS) { pi[i] = A.xi[(size_t)q * n + i]; pg[i] = xg; }
+        const double xl = straight_line(t, A.Q.xi[qn + i], A.Q.glo[qn + i], A.Q.ghi[qn + i]);
+        if (i < WS) { x[i] = xl; pi[i] = A.Q.xi[qn + i]; pg[i] = goal_centre(A.Q.glo[qn + i], A.Q.ghi[qn + i]); }
+        else Xo[i] = xl;
     }
-    const double a2 = A.fan[2 * j], a3 = WS == 3 ? A.fan[2 * j + 1] : 0.0;   // (a3 is ignored in the plane)
+    const double a2 = fan[2 * j], a3 = WS == 3 ? fan[2 * j + 1] : 0.0;   // (a3 is ignored in the plane)
     if (a2 != 0.0 || a3 != 0.0) {
         double d[WS], e1[WS], w[WS];
 #pragma unroll
@@ -68,18 +70,10 @@ template <int MODEL> __global__ void fan_kernel(const FanArgs A) {
         for (int i = 0; i < WS; i++) x[i] += tent * w[i];
     }
 #pragma unroll
-    for (int i = 0; i < n; i++) A.X[((size_t)b * A.N + k) * n + i] = x[i];
+    for (int i = 0; i < WS; i++) Xo[i] = x[i];
 #pragma unroll
-    for (int i = 0; i < m; i++) A.U[((size_t)b * A.N + k) * m + i] = 0.0;
-    if (k == 0) {
-#pragma unroll
-        for (int i = 0; i < n; i++) {
-            A.x_init[(size_t)b * n + i] = A.xi[(size_t)q * n + i];
-            A.goal_lo[(size_t)b * n + i] = A.glo[(size_t)q * n + i];
-            A.goal_hi[(size_t)b * n + i] = A.ghi[(size_t)q * n + i];
-        }
-        A.tf_b[b] = A.tf[q];
-    }
+    for (int i = 0; i < m; i++) A.out.U[((size_t)b * A.N + k) * m + i] = 0.0;
+    if (k == 0) seed_problem_tail<MODEL>(A.out, b, A.Q.xi + qn, A.Q.glo + qn, A.Q.ghi + qn, tf[id.q]);
 }
 
 struct SelectArgs {
@@ -122,11 +116,6 @@ __global__ void __launch_bounds__(64) select_kernel(const SelectArgs A) {
     for (int e = lane; e < A.nu; e += 64) A.Ub[(size_t)q * A.nu + e] = won ? Uw[e] : 0.0;
 }
 
-int refuse(gusto_handle h, const char* who, const char* what) {
-    h->err = std::string(who) + ": " + what;
-    return GUSTO_ERR_ARG;
-}
-
 // the refusals of the two getters, then the handle's device and its enqueued solve
 int best_enter(gusto_handle h, const char* who) {
     if (int rc = post_enter(h, who, nullptr, nullptr)) return rc;
@@ -141,37 +130,19 @@ extern "C" {
 int gusto_set_problems_multistart(gusto_handle h, int Bq, int K, const double* x_init, const double* glo, const double* ghi,
                                   const double* tf, const double* fan) {
     const char* who = "gusto_set_problems_multistart";
-    if (!h) return GUSTO_ERR_ARG;
-    if (h->trajopt) return refuse(h, who, "TrajOpt handle (not supported)");
-    if (K < 1 || K > GUSTO_MAX_STARTS) return refuse(h, who, "K outside 1 .. GUSTO_MAX_STARTS");
-    if (Bq < 1 || (long long)Bq * K > h->batch_cap) return refuse(h, who, "need Bq >= 1 and Bq K <= batch_cap");
-    if (!x_init || !glo || !ghi || !tf || !fan) return refuse(h, who, "a null array");
-    for (int i = 0; i < 2 * K; i++)
-        if (!(fabs(fan[i]) < INFINITY)) return refuse(h, who, ("fan must be finite (start " + std::to_string(i / 2) + ")").c_str());
-    HIPCHK(h, hipSetDevice(h->device));
-    if (int rc = gusto_complete(h)) return rc;
-    const size_t n = h->n, q = Bq;
-    std::vector<double> in(q * (3 * n + 1) + 2 * (size_t)K);   // x_init | goal_lo | goal_hi | tf | fan: one copy
-    double* at = in.data();
-    for (const double* src : {x_init, glo, ghi}) { memcpy(at, src, sizeof(double) * q * n); at += q * n; }
-    memcpy(at, tf, sizeof(double) * q);
-    memcpy(at + q, fan, sizeof(double) * 2 * K);
-    SelectState& S = h->select;
-    HIPCHK(h, S.In.ensure(in.size()));
-    h->sched_err = 0;   // (a latched scheduler error ends here: every problem is set again)
-    h->B = Bq * K;
-    HIPCHK(h, hipMemcpyAsync(S.In, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, h->stream));
-    FanArgs A;
-    A.xi = S.In; A.glo = A.xi + q * n; A.ghi = A.glo + q * n; A.tf = A.ghi + q * n; A.fan = A.tf + q;
-    A.X = h->d_X; A.U = h->d_U; A.x_init = h->d_xinit; A.goal_lo = h->d_glo; A.goal_hi = h->d_ghi; A.tf_b = h->d_tf;
-    A.B = h->B; A.K = K; A.N = h->N;
-    const int tot = h->B * h->N;
-    if (int rc = for_model(h->model_pub, [&](auto M) -> int {
-            hipLaunchKernelGGL(fan_kernel<decltype(M)::value>, dim3((tot + 255) / 256), dim3(256), 0, h->stream, A);
-            HIPCHK(h, hipGetLastError());
+    if (int rc = seed_enter(h, who, Bq, K, GUSTO_MAX_STARTS, "GUSTO_MAX_STARTS", {x_init, glo, ghi, tf, fan}, [&]() -> int {
+            for (int i = 0; i < 2 * K; i++)
+                if (!(fabs(fan[i]) < INFINITY)) return refuse(h, who, "fan must be finite (start " + std::to_string(i / 2) + ")");
             return GUSTO_OK;
         }))
         return rc;
+    const std::vector<double> in = pack_queries(Bq, h->n, x_init, glo, ghi, {{tf, (size_t)Bq}, {fan, 2 * (size_t)K}});
+    SelectState& S = h->select;
+    HIPCHK(h, S.In.ensure(in.size()));
+    seed_set_B(h, (size_t)Bq * K);
+    HIPCHK(h, hipMemcpyAsync(S.In, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, h->stream));
+    const FanArgs A{query_dev(S.In, Bq, h->n), seed_out(h), h->B, Bq, K, h->N};
+    if (int rc = launch_per_knot(h, A, [](auto M) { return fan_kernel<decltype(M)::value>; })) return rc;
     return gusto_problems_loaded(h, false);   // (waits for the stream: `in` is read by then)
 }
 

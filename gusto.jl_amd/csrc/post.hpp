@@ -1,4 +1,5 @@
-// post.hpp -- the host path of the post-solve stages (shoot.hip, verify.hip, tvlqr.hip, simulate.hip, lincov.hip) and of multistart.hip; nothing else includes it.  Plain
+// post.hpp -- the host path of the post-solve stages (shoot.hip, verify.hip, tvlqr.hip, simulate.hip, lincov.hip, tighten.hip);
+// seed.hpp, the host path of the seeding stages, builds on it, and nothing else includes it.  Plain
 // functions that answer a GUSTO_* code and leave the text in h->err: `if (int rc = ...) return rc;` at the call site.  A new
 // stage starts from these, from a struct of its own next to ShootState / VerifyState / TvlqrState / SimulateState / LincovState
 // (handle.hpp) and, on the device, from rollout.hpp: the roll-out every stage but shoot.hip shares.
@@ -11,6 +12,12 @@
 #include <vector>
 
 #include "handle.hpp"
+
+// a refusal: "<who>: <what>" in h->err, and the code
+static inline int refuse(gusto_handle h, const std::string& who, const std::string& what, int rc = GUSTO_ERR_ARG) {
+    h->err = who + ": " + what;
+    return rc;
+}
 
 // the refusals every stage begins with (a stage without X, U passes nulls), then the handle's device and its enqueued solve
 static inline int post_enter(gusto_handle h, const char* who, const double* X, const double* U) {

@@ -9,12 +9,12 @@
 // consecutive threads write consecutive knots.  The thread of knot 0 also writes the problem's x_init, goal_lo, goal_hi and tf.
 // A thread of knot k reads the source knots j and j + 1 (and those of knot 0), which other threads may be writing when source
 // and destination are the same handle: the source rows are then read from a staging copy made on the stream, device to
-// device.  An unseeded problem evaluates the expression of init_straightline_kernel (scp.hpp), written the same way: that
+// device.  An unseeded problem evaluates straight_line() of seed.hpp, as init_straightline_kernel (scp.hpp) does: that
 // kernel's output bit for bit.  No atomics, nothing crosses a problem: a problem's output is the same bit for bit in any batch.
 // Gather kernel: a thread per (problem, state entry) copies x_now out of Xcl [B][Ns][S][n].
 #include <hip/hip_runtime.h>
 
-#include "post.hpp"
+#include "seed.hpp"
 
 using namespace gusto;
 
@@ -26,34 +26,28 @@ struct ReplanArgs {
     const int *seeded, *sp;                              // [B]: seeded, the source problem (tf and goals)
     const double *Xs, *Us;                               // the source rows, row b [Ns][n], [Ns][m]
     const double *stf, *sglo, *sghi;                     // the source's problems
-    double *X, *U, *x_init, *goal_lo, *goal_hi, *tf_b;   // the handle's [B] arrays
+    SeedOut out;
     int B, N, Ns;
 };
-
-GD double centre_of(double lo, double hi) { return (isfinite(lo) && isfinite(hi)) ? 0.5 * (lo + hi) : 0.0; }   // center(goal), zeros elsewhere
 
 template <int MODEL> __global__ void replan_kernel(const ReplanArgs A) {
     using T = MT<MODEL>;
     constexpr int n = T::n, m = T::m;
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= A.B * A.N) return;
-    const int b = gid / A.N, k = gid % A.N, s = A.sp[b];
-    const double t = (double)k / (double)(A.N - 1);  // LinRange element: (1-t)*a + t*b
+    KnotId id;
+    if (!knot_id(A.B, 1, A.N, id)) return;
+    const int b = id.b, k = id.k, s = A.sp[b];
+    const double t = id.t;
     const double* xn = A.xnow + (size_t)b * n;
     const double* lo_p = A.nlo ? A.nlo + (size_t)b * n : A.sglo + (size_t)s * n;
     const double* hi_p = A.nlo ? A.nhi + (size_t)b * n : A.sghi + (size_t)s * n;
-    double* Xo = A.X + ((size_t)b * A.N + k) * n;
-    double* Uo = A.U + ((size_t)b * A.N + k) * m;
+    double* Xo = A.out.X + ((size_t)b * A.N + k) * n;
+    double* Uo = A.out.U + ((size_t)b * A.N + k) * m;
     double glo[n], ghi[n];
 #pragma unroll
     for (int i = 0; i < n; i++) { glo[i] = lo_p[i]; ghi[i] = hi_p[i]; }
     if (!A.seeded[b]) {
 #pragma unroll
-        for (int i = 0; i < n; i++) {
-            const double lo = glo[i], hi = ghi[i];
-            const double xg = (isfinite(lo) && isfinite(hi)) ? 0.5 * (lo + hi) : 0.0;  // center(goal), zeros elsewhere
-            Xo[i] = (1 - t) * xn[i] + t * xg;
-        }
+        for (int i = 0; i < n; i++) Xo[i] = straight_line(t, xn[i], glo[i], ghi[i]);
 #pragma unroll
         for (int i = 0; i < m; i++) Uo[i] = 0.0;
     } else {
@@ -70,22 +64,14 @@ template <int MODEL> __global__ void replan_kernel(const ReplanArgs A) {
             const double S = last ? Xr[(size_t)(A.Ns - 1) * n + i] : (1 - a) * Xr[(size_t)j * n + i] + a * Xr[(size_t)(j + 1) * n + i];
             const double S0 = (1 - a0) * Xr[(size_t)j0 * n + i] + a0 * Xr[(size_t)(j0 + 1) * n + i];
             double d = (1 - t) * (xn[i] - S0);
-            if (A.nlo) d = d + t * (centre_of(glo[i], ghi[i]) - centre_of(A.sglo[(size_t)s * n + i], A.sghi[(size_t)s * n + i]));
+            if (A.nlo) d = d + t * (goal_centre(glo[i], ghi[i]) - goal_centre(A.sglo[(size_t)s * n + i], A.sghi[(size_t)s * n + i]));
             Xo[i] = k == 0 ? xn[i] : S + d;
         }
 #pragma unroll
         for (int i = 0; i < m; i++)
             Uo[i] = last ? Ur[(size_t)(A.Ns - 1) * m + i] : (1 - a) * Ur[(size_t)j * m + i] + a * Ur[(size_t)(j + 1) * m + i];
     }
-    if (k == 0) {
-#pragma unroll
-        for (int i = 0; i < n; i++) {
-            A.x_init[(size_t)b * n + i] = xn[i];
-            A.goal_lo[(size_t)b * n + i] = glo[i];
-            A.goal_hi[(size_t)b * n + i] = ghi[i];
-        }
-        A.tf_b[b] = (1 - A.tau[b]) * A.stf[s];
-    }
+    if (k == 0) seed_problem_tail<MODEL>(A.out, b, xn, glo, ghi, (1 - A.tau[b]) * A.stf[s]);
 }
 
 // x_now[b][i] = Xcl[b][knot[b]][sample][i]
@@ -94,11 +80,6 @@ __global__ void gather_knots_kernel(const double* Xcl, const int* knot, double* 
     if (gid >= B * n) return;
     const int b = gid / n, i = gid % n;
     xnow[gid] = Xcl[(((size_t)b * Ns + knot[b]) * S + sample) * n + i];
-}
-
-int refuse(gusto_handle h, const char* who, const std::string& what, int rc = GUSTO_ERR_ARG) {
-    h->err = std::string(who) + ": " + what;
-    return rc;
 }
 
 // the refusals both entry points share, up to the source's problems; *src becomes h for a null source.  Afterwards both
@@ -168,8 +149,7 @@ int replan_impl(gusto_handle h, gusto_handle src, int source, int B, const doubl
     A.stf = src->d_tf; A.sglo = src->d_glo; A.sghi = src->d_ghi;
     A.Xs = best ? src->select.X.get() : src->d_X.get();
     A.Us = best ? src->select.U.get() : src->d_U.get();
-    h->sched_err = 0;   // (a latched scheduler error ends here: every problem is set again)
-    h->B = B;
+    seed_set_B(h, B);
     HIPCHK(h, R.t0.record(h->stream));
     HIPCHK(h, hipMemcpyAsync(R.In, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(R.Meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, h->stream));
@@ -188,15 +168,9 @@ int replan_impl(gusto_handle h, gusto_handle src, int source, int B, const doubl
     A.tau = R.In; A.xnow = A.tau + nb;
     A.nlo = glo ? A.xnow + nb * n : nullptr; A.nhi = glo ? A.nlo + nb * n : nullptr;
     A.seeded = R.Meta; A.sp = R.Meta + nb;
-    A.X = h->d_X; A.U = h->d_U; A.x_init = h->d_xinit; A.goal_lo = h->d_glo; A.goal_hi = h->d_ghi; A.tf_b = h->d_tf;
+    A.out = seed_out(h);
     A.B = B; A.N = h->N; A.Ns = (int)Ns;
-    const int tot = B * h->N;
-    if (int rc = for_model(h->model_pub, [&](auto M) -> int {
-            hipLaunchKernelGGL(replan_kernel<decltype(M)::value>, dim3((tot + 255) / 256), dim3(256), 0, h->stream, A);
-            HIPCHK(h, hipGetLastError());
-            return GUSTO_OK;
-        }))
-        return rc;
+    if (int rc = launch_per_knot(h, A, [](auto M) { return replan_kernel<decltype(M)::value>; })) return rc;
     HIPCHK(h, R.t1.record(h->stream));
     if (int rc = gusto_problems_loaded(h, false)) return rc;   // (waits for the stream: `in` and `meta` are read by then)
     HIPCHK(h, event_ms(R.t0, R.t1, &R.last_ms));
@@ -260,10 +234,7 @@ int gusto_get_replan(gusto_handle h, int* seeded, double* tau, double* x_now) {
 }
 
 int gusto_last_replan_ms(gusto_handle h, double* ms) {
-    if (!h || !ms) return GUSTO_ERR_ARG;
-    if (!h->replan.have) { h->err = "gusto_last_replan_ms: the handle's problems were not set by gusto_set_problems_replan"; return GUSTO_ERR_STATE; }
-    *ms = h->replan.last_ms;
-    return GUSTO_OK;
+    return stage_last_ms(h, &gusto_handle_s::replan, ms, "gusto_last_replan_ms", "the handle's problems were not set by gusto_set_problems_replan");
 }
 
 }  // extern "C"

@@ -14,11 +14,11 @@
 // holders: the idiom of select_kernel in multistart.hip), then every lane relaxes its nodes against the bit row of the settled
 // node, the edge length recomputed from the coordinates.  Lane 0 walks the predecessors back and writes the path as points.
 // Seed kernel: a thread per (problem, knot), the shape of fan_kernel (multistart.hip): the polyline resampled by arc length on
-// the workspace entries, the straight line's expression elsewhere, and the [Bq] inputs replicated into the handle's [B] arrays.
+// the workspace entries, straight_line() of seed.hpp elsewhere, and the [Bq] inputs replicated into the handle's [B] arrays.
 // No atomics, every reduction in a fixed order, nothing crosses a query: a query's outputs are the same bit for bit in any batch.
 #include <hip/hip_runtime.h>
 
-#include "post.hpp"
+#include "seed.hpp"
 
 using namespace gusto;
 
@@ -195,10 +195,8 @@ template <int MODEL> __global__ void __launch_bounds__(64) search_kernel(const S
         for (int j = 0; j < WS; j++) {
             double x;
             if (idx == 0) x = A.xi[q * n + j];
-            else if (idx == 1) {
-                const double lo = A.glo[q * n + j], hi = A.ghi[q * n + j];
-                x = (isfinite(lo) && isfinite(hi)) ? 0.5 * (lo + hi) : 0.0;   // center(goal), zeros elsewhere
-            } else x = A.nodes[(e * A.VeMax + (idx - 2)) * WS + j];
+            else if (idx == 1) x = goal_centre(A.glo[q * n + j], A.ghi[q * n + j]);
+            else x = A.nodes[(e * A.VeMax + (idx - 2)) * WS + j];
             P[idx * WS + j] = x;
         }
     }
@@ -350,26 +348,28 @@ template <int MODEL> __global__ void __launch_bounds__(64) search_kernel(const S
 }
 
 struct SeedArgs {
-    const double *xi, *glo, *ghi, *tf;                   // the queries: [Bq][n] each, [Bq]
-    const int *status, *n_via;                           // [B]
-    const double *length, *pts;                          // [B], [B][RM_PTS][3]
-    double *X, *U, *x_init, *goal_lo, *goal_hi, *tf_b;   // the handle's [B] arrays
+    QueryDev Q;                    // the queries; extra: tf [Bq]
+    const int *status, *n_via;     // [B]
+    const double *length, *pts;    // [B], [B][RM_PTS][3]
+    SeedOut out;
     int B, K, N;
 };
 
 template <int MODEL> __global__ void seed_kernel(const SeedArgs A) {
     using T = MT<MODEL>;
     constexpr int n = T::n, m = T::m, WS = T::WS;
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= A.B * A.N) return;
-    const int b = gid / A.N, k = gid % A.N, q = b / A.K;
-    const double t = (double)k / (double)(A.N - 1);  // LinRange element: (1-t)*a + t*b
-    double x[n];
+    KnotId id;
+    if (!knot_id(A.B, A.K, A.N, id)) return;
+    const int b = id.b, k = id.k;
+    const double t = id.t;
+    const size_t qn = (size_t)id.q * n;   // the query's row of xi, glo, ghi
+    double* Xo = A.out.X + ((size_t)b * A.N + k) * n;
+    double x[WS];   // the workspace entries; the others are the line's and go out at once
 #pragma unroll
     for (int i = 0; i < n; i++) {
-        const double lo = A.glo[(size_t)q * n + i], hi = A.ghi[(size_t)q * n + i];
-        const double xg = (isfinite(lo) && isfinite(hi)) ? 0.5 * (lo + hi) : 0.0;  // center(goal), zeros elsewhere
-        x[i] = (1 - t) * A.xi[(size_t)q * n + i] + t * xg;
+        const double xl = straight_line(t, A.Q.xi[qn + i], A.Q.glo[qn + i], A.Q.ghi[qn + i]);
+        if (i < WS) x[i] = xl;
+        else Xo[i] = xl;
     }
     if (A.status[b] == GUSTO_ROADMAP_PATH && k > 0 && k < A.N - 1) {
         // the point at arc length t Lp: the first segment whose end lies beyond it (the last one otherwise)
@@ -388,23 +388,10 @@ template <int MODEL> __global__ void seed_kernel(const SeedArgs A) {
         for (int j = 0; j < WS; j++) x[j] = pt[3 * i + j] + f * (pt[3 * i + 3 + j] - pt[3 * i + j]);
     }
 #pragma unroll
-    for (int i = 0; i < n; i++) A.X[((size_t)b * A.N + k) * n + i] = x[i];
+    for (int i = 0; i < WS; i++) Xo[i] = x[i];
 #pragma unroll
-    for (int i = 0; i < m; i++) A.U[((size_t)b * A.N + k) * m + i] = 0.0;
-    if (k == 0) {
-#pragma unroll
-        for (int i = 0; i < n; i++) {
-            A.x_init[(size_t)b * n + i] = A.xi[(size_t)q * n + i];
-            A.goal_lo[(size_t)b * n + i] = A.glo[(size_t)q * n + i];
-            A.goal_hi[(size_t)b * n + i] = A.ghi[(size_t)q * n + i];
-        }
-        A.tf_b[b] = A.tf[q];
-    }
-}
-
-int refuse(gusto_handle h, const char* what, int rc = GUSTO_ERR_ARG) {
-    h->err = std::string("gusto_set_problems_roadmap: ") + what;
-    return rc;
+    for (int i = 0; i < m; i++) A.out.U[((size_t)b * A.N + k) * m + i] = 0.0;
+    if (k == 0) seed_problem_tail<MODEL>(A.out, b, A.Q.xi + qn, A.Q.glo + qn, A.Q.ghi + qn, A.Q.extra[id.q]);
 }
 
 }  // namespace
@@ -425,21 +412,19 @@ int gusto_default_roadmap_opts(int model_id, gusto_roadmap_opts* o) {
 
 int gusto_set_problems_roadmap(gusto_handle h, int Bq, int K, const double* x_init, const double* glo, const double* ghi,
                                const double* tf, const gusto_roadmap_opts* opts) {
-    if (!h) return GUSTO_ERR_ARG;
-    if (h->trajopt) return refuse(h, "TrajOpt handle (not supported)");
-    if (K < 1 || K > GUSTO_ROADMAP_MAX_K) return refuse(h, "K outside 1 .. GUSTO_ROADMAP_MAX_K");
-    if (Bq < 1 || (long long)Bq * K > h->batch_cap) return refuse(h, "need Bq >= 1 and Bq K <= batch_cap");
-    if (!x_init || !glo || !ghi || !tf) return refuse(h, "a null array");
+    const char* who = "gusto_set_problems_roadmap";
     gusto_roadmap_opts o;
-    if (opts) o = *opts;
-    else {
-        o.inflate = h->mp.radius + 0.02; o.pad = 0.03; o.straight_first = 0;   // the defaults, on the handle's own radius
-    }
-    if (!(o.inflate >= 0 && o.inflate < INFINITY)) return refuse(h, "inflate must be finite and >= 0");
-    if (!(o.pad > 0 && o.pad < INFINITY)) return refuse(h, "pad must be finite and > 0");
-    if (o.straight_first != 0 && o.straight_first != 1) return refuse(h, "straight_first must be 0 or 1");
-    HIPCHK(h, hipSetDevice(h->device));
-    if (int rc = gusto_complete(h)) return rc;
+    if (int rc = seed_enter(h, who, Bq, K, GUSTO_ROADMAP_MAX_K, "GUSTO_ROADMAP_MAX_K", {x_init, glo, ghi, tf}, [&]() -> int {
+            if (opts) o = *opts;
+            else {
+                o.inflate = h->mp.radius + 0.02; o.pad = 0.03; o.straight_first = 0;   // the defaults, on the handle's own radius
+            }
+            if (!(o.inflate >= 0 && o.inflate < INFINITY)) return refuse(h, who, "inflate must be finite and >= 0");
+            if (!(o.pad > 0 && o.pad < INFINITY)) return refuse(h, who, "pad must be finite and > 0");
+            if (o.straight_first != 0 && o.straight_first != 1) return refuse(h, who, "straight_first must be 0 or 1");
+            return GUSTO_OK;
+        }))
+        return rc;
 
     // the keep-out set of every query: the shared one, or the set of problem q K
     const size_t n = h->n, q = Bq, B = q * K;
@@ -447,7 +432,7 @@ int gusto_set_problems_roadmap(gusto_handle h, int Bq, int K, const double* x_in
     std::vector<int> rec(4 * (size_t)n_env);
     int Cmax = 0;
     if (h->d_env) {
-        if ((size_t)h->env_B != B) return refuse(h, "the handle holds per-problem keep-out sets for another number of problems than Bq K", GUSTO_ERR_STATE);
+        if ((size_t)h->env_B != B) return refuse(h, who, "the handle holds per-problem keep-out sets for another number of problems than Bq K", GUSTO_ERR_STATE);
         std::vector<int> all(4 * B);
         HIPCHK(h, hipMemcpy(all.data(), h->d_env, sizeof(int) * all.size(), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < q; i++) memcpy(&rec[4 * i], &all[4 * i * K], sizeof(int) * 4);
@@ -456,7 +441,7 @@ int gusto_set_problems_roadmap(gusto_handle h, int Bq, int K, const double* x_in
     }
     for (int e = 0; e < n_env; e++) {
         if (rec[4 * e + 1] < 0 || rec[4 * e + 3] < 0 || rec[4 * e + 1] + rec[4 * e + 3] > RM_MAXC)
-            return refuse(h, "more than 64 keep-out components in a set", GUSTO_ERR_STATE);
+            return refuse(h, who, "more than 64 keep-out components in a set", GUSTO_ERR_STATE);
         Cmax = std::max(Cmax, rec[4 * e + 1] + rec[4 * e + 3]);
     }
     int WS = 0;
@@ -464,19 +449,15 @@ int gusto_set_problems_roadmap(gusto_handle h, int Bq, int K, const double* x_in
     const size_t VeMax = (size_t)Cmax << WS, W = (VeMax + 63) / 64;
 
     RoadmapState& S = h->roadmap;
-    std::vector<double> in(q * (3 * n + 1));   // x_init | goal_lo | goal_hi | tf: one copy
-    double* at = in.data();
-    for (const double* src : {x_init, glo, ghi}) { memcpy(at, src, sizeof(double) * q * n); at += q * n; }
-    memcpy(at, tf, sizeof(double) * q);
+    const std::vector<double> in = pack_queries(q, n, x_init, glo, ghi, {{tf, q}});
     HIPCHK(h, S.In.ensure(in.size())); HIPCHK(h, S.Rec.ensure(rec.size()));
     HIPCHK(h, S.Nodes.ensure((size_t)n_env * VeMax * WS)); HIPCHK(h, S.Dead.ensure((size_t)n_env * VeMax));
     HIPCHK(h, S.Vis.ensure((size_t)n_env * VeMax * W));
     HIPCHK(h, S.I.ensure(B * (2 + RM_VIA + RM_BAN))); HIPCHK(h, S.Len.ensure(B)); HIPCHK(h, S.Pts.ensure(B * RM_PTS * 3));
-    if ((size_t)n_env * VeMax * W > (size_t)INT_MAX) return refuse(h, "keep-out sets too large");
+    if ((size_t)n_env * VeMax * W > (size_t)INT_MAX) return refuse(h, who, "keep-out sets too large");
 
     S.have = false;
-    h->sched_err = 0;   // (a latched scheduler error ends here: every problem is set again)
-    h->B = (int)B;
+    seed_set_B(h, B);
     HIPCHK(h, S.t0.record(h->stream));
     HIPCHK(h, hipMemcpyAsync(S.In, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(S.Rec, rec.data(), sizeof(int) * rec.size(), hipMemcpyHostToDevice, h->stream));
@@ -485,18 +466,14 @@ int gusto_set_problems_roadmap(gusto_handle h, int Bq, int K, const double* x_in
     G.rec = S.Rec; G.box = h->d_box; G.sph = h->d_sph; G.inflate = o.inflate; G.pad = o.pad;
     G.VeMax = (int)VeMax; G.W = (int)W; G.nodes = S.Nodes; G.dead = S.Dead; G.vis = S.Vis;
     SearchArgs Q{};
-    Q.xi = S.In; Q.glo = Q.xi + q * n; Q.ghi = Q.glo + q * n;
+    const QueryDev D = query_dev(S.In, q, n);
+    Q.xi = D.xi; Q.glo = D.glo; Q.ghi = D.ghi;
     Q.rec = S.Rec; Q.box = h->d_box; Q.sph = h->d_sph; Q.inflate = o.inflate;
     Q.n_env = n_env; Q.VeMax = (int)VeMax; Q.W = (int)W; Q.K = K; Q.straight_first = o.straight_first;
     Q.nodes = S.Nodes; Q.dead = S.Dead; Q.vis = S.Vis;
     Q.status = S.I; Q.n_via = S.I + B; Q.via = S.I + 2 * B; Q.banned = S.I + (2 + RM_VIA) * B;
     Q.length = S.Len; Q.pts = S.Pts;
-    SeedArgs A{};
-    A.xi = Q.xi; A.glo = Q.glo; A.ghi = Q.ghi; A.tf = Q.ghi + q * n;
-    A.status = Q.status; A.n_via = Q.n_via; A.length = S.Len; A.pts = S.Pts;
-    A.X = h->d_X; A.U = h->d_U; A.x_init = h->d_xinit; A.goal_lo = h->d_glo; A.goal_hi = h->d_ghi; A.tf_b = h->d_tf;
-    A.B = (int)B; A.K = K; A.N = h->N;
-    const int tot = (int)B * h->N;
+    const SeedArgs A{D, Q.status, Q.n_via, S.Len, S.Pts, seed_out(h), h->B, K, h->N};
     if (int rc = for_model(h->model_pub, [&](auto M) -> int {
             constexpr int MODEL = decltype(M)::value, WSM = MT<MODEL>::WS;
             if (VeMax) {
@@ -507,12 +484,11 @@ int gusto_set_problems_roadmap(gusto_handle h, int Bq, int K, const double* x_in
             hipLaunchKernelGGL(search_kernel<MODEL>, dim3((unsigned)q), dim3(64), 0, h->stream, Q);
             HIPCHK(h, hipGetLastError());
             HIPCHK(h, S.t2.record(h->stream));
-            hipLaunchKernelGGL(seed_kernel<MODEL>, dim3((tot + 255) / 256), dim3(256), 0, h->stream, A);
-            HIPCHK(h, hipGetLastError());
-            HIPCHK(h, S.t3.record(h->stream));
             return GUSTO_OK;
         }))
         return rc;
+    if (int rc = launch_per_knot(h, A, [](auto M) { return seed_kernel<decltype(M)::value>; })) return rc;
+    HIPCHK(h, S.t3.record(h->stream));
     if (int rc = gusto_problems_loaded(h, false)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));   // (`in` and `rec` are read by then)
     HIPCHK(h, event_ms(S.t0, S.t3, &S.last_ms));
@@ -540,10 +516,7 @@ int gusto_get_roadmap(gusto_handle h, gusto_roadmap_report* out) {
 }
 
 int gusto_last_roadmap_ms(gusto_handle h, double* ms) {
-    if (!h || !ms) return GUSTO_ERR_ARG;
-    if (!h->roadmap.have) { h->err = "gusto_last_roadmap_ms: call gusto_set_problems_roadmap first"; return GUSTO_ERR_STATE; }
-    *ms = h->roadmap.last_ms;
-    return GUSTO_OK;
+    return stage_last_ms(h, &gusto_handle_s::roadmap, ms, "gusto_last_roadmap_ms", "call gusto_set_problems_roadmap first");
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // synchronisation and the hardware dispatcher load-balances problems with different iteration counts.
 #pragma once
 #include "ipm.hpp"
+#include "seed.hpp"   // the straight line of init_straightline_kernel, which every seeding stage shares
 
 #ifndef GUSTO_WAVES_PER_EU
 #define GUSTO_WAVES_PER_EU 1
@@ -679,16 +680,12 @@ static __global__ void sched_order_kernel(int B, const int* bucket, int* order) 
 template <int MODEL> __global__ void init_straightline_kernel(const KParams P) {
     using T = MT<MODEL>;
     constexpr int n = T::n, m = T::m;
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= P.B * P.N) return;
-    const int b = gid / P.N, k = gid % P.N;
-    const double t = (double)k / (double)(P.N - 1);  // LinRange element: (1-t)*a + t*b
+    KnotId id;
+    if (!knot_id(P.B, 1, P.N, id)) return;
+    const int b = id.b, k = id.k;
 #pragma unroll
-    for (int i = 0; i < n; i++) {
-        const double lo = P.goal_lo[(size_t)b * n + i], hi = P.goal_hi[(size_t)b * n + i];
-        const double xg = (isfinite(lo) && isfinite(hi)) ? 0.5 * (lo + hi) : 0.0;  // center(goal), zeros elsewhere
-        P.X[((size_t)b * P.N + k) * n + i] = (1 - t) * P.x_init[(size_t)b * n + i] + t * xg;
-    }
+    for (int i = 0; i < n; i++)
+        P.X[((size_t)b * P.N + k) * n + i] = straight_line(id.t, P.x_init[(size_t)b * n + i], P.goal_lo[(size_t)b * n + i], P.goal_hi[(size_t)b * n + i]);
 #pragma unroll
     for (int i = 0; i < m; i++) P.U[((size_t)b * P.N + k) * m + i] = 0.0;
 }

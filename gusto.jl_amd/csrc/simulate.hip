@@ -290,11 +290,6 @@ template <int MODEL> int launch_simulate(gusto_handle h, const KParams& P, const
     return GUSTO_OK;
 }
 
-int refuse(gusto_handle h, const std::string& who, const std::string& text) {
-    h->err = who + ": " + text;
-    return GUSTO_ERR_ARG;
-}
-
 // The arguments of gusto_simulate_disturbed that gusto_simulate does not have: GUSTO_ERR_ARG and the text, which names the
 // offending problem, sample and entry (plant_entry_read: post.hpp).  No device
 int disturb_args_host(gusto_handle h, const std::string& who, size_t B, size_t Ns, const gusto_disturb_opts& d, const double* plant,

@@ -13,14 +13,14 @@
 // wave_reduce minimum over the eligible final times, a second one over the lanes that hold it picks the lowest lane; the whole
 // wave gathers that problem's X and U, lane-consecutive, into the incumbent buffers.
 // Seed kernel: a thread per (problem, knot), the shape of fan_kernel (multistart.hip); consecutive threads write consecutive
-// knots, the thread of knot 0 also writes the problem's x_init, goal_lo, goal_hi and tf.  The straight-line expression is the
-// one of init_straightline_kernel (scp.hpp), written the same way: that kernel's output bit for bit.  The incumbent is read from
+// knots, the thread of knot 0 also writes the problem's x_init, goal_lo, goal_hi and tf.  The straight line is straight_line()
+// of seed.hpp, the one init_straightline_kernel (scp.hpp) evaluates: that kernel's output bit for bit.  The incumbent is read from
 // the search's own buffers, never from the rows the kernel writes.
 // The candidates are one rounded difference, division, product and sum each (contraction switched off where they are formed).  No atomics,
 // nothing crosses a query: a query's report and seeds are the same bit for bit in any batch.
 #include <hip/hip_runtime.h>
 
-#include "post.hpp"
+#include "seed.hpp"
 
 using namespace gusto;
 
@@ -146,33 +146,30 @@ __global__ void __launch_bounds__(64) update_kernel(const UpdateArgs A) {
 }
 
 struct SeedArgs {
-    const double *xi, *glo, *ghi;                        // the queries: [Bq][n] each
-    const double *D, *cand, *Xb, *Ub;                    // the search's state
+    QueryDev Q;                         // the queries (extra: the bracket of gusto_tfsearch_begin, not read here)
+    const double *D, *cand, *Xb, *Ub;   // the search's state
     const int* I;
-    double *X, *U, *x_init, *goal_lo, *goal_hi, *tf_b;   // the handle's [B] arrays
+    SeedOut out;
     int B, Bq, K, N, seed;
 };
 
 template <int MODEL> __global__ void seed_kernel(const SeedArgs A) {
     using T = MT<MODEL>;
     constexpr int n = T::n, m = T::m;
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= A.B * A.N) return;
-    const int b = gid / A.N, k = gid % A.N, q = b / A.K;
+    KnotId id;
+    if (!knot_id(A.B, A.K, A.N, id)) return;
+    const int b = id.b, k = id.k, q = id.q;
     if (A.I[TI_PARKED * A.Bq + q]) return;   // done before the last update: its problems stay as they are
-    const double t = (double)k / (double)(A.N - 1);  // LinRange element: (1-t)*a + t*b
+    const double t = id.t;
+    const size_t qn = (size_t)q * n;   // the query's row of xi, glo, ghi
     const double Tj = A.cand[b];
     const bool retime = A.seed == GUSTO_TFSEARCH_SEED_INCUMBENT && A.I[TI_FOUND * A.Bq + q] >= 0 &&
                         !(A.I[TI_STATUS * A.Bq + q] & TF_FINISHED);
-    double* Xo = A.X + ((size_t)b * A.N + k) * n;
-    double* Uo = A.U + ((size_t)b * A.N + k) * m;
+    double* Xo = A.out.X + ((size_t)b * A.N + k) * n;
+    double* Uo = A.out.U + ((size_t)b * A.N + k) * m;
     double x[n];
 #pragma unroll
-    for (int i = 0; i < n; i++) {
-        const double lo = A.glo[(size_t)q * n + i], hi = A.ghi[(size_t)q * n + i];
-        const double xg = (isfinite(lo) && isfinite(hi)) ? 0.5 * (lo + hi) : 0.0;  // center(goal), zeros elsewhere
-        x[i] = (1 - t) * A.xi[(size_t)q * n + i] + t * xg;
-    }
+    for (int i = 0; i < n; i++) x[i] = straight_line(t, A.Q.xi[qn + i], A.Q.glo[qn + i], A.Q.ghi[qn + i]);
     if (!retime) {
 #pragma unroll
         for (int i = 0; i < n; i++) Xo[i] = x[i];
@@ -184,44 +181,22 @@ template <int MODEL> __global__ void seed_kernel(const SeedArgs A) {
         const double* Ur = A.Ub + ((size_t)q * A.N + k) * m;
 #pragma unroll
         for (int i = 0; i < n; i++) {
-            const double v = rate_entry<MODEL>(i) ? s * Xr[i] + (1 - s) * x[i] : Xr[i];
-            Xo[i] = k == 0 ? A.xi[(size_t)q * n + i] : v;
+            // s Xr + (1 - s) x, the second product fused as it always was (straight_line in seed.hpp: why it is written out)
+            const double v = rate_entry<MODEL>(i) ? fma(1 - s, x[i], s * Xr[i]) : Xr[i];
+            Xo[i] = k == 0 ? A.Q.xi[qn + i] : v;
         }
 #pragma unroll
         for (int i = 0; i < m; i++) Uo[i] = s2 * Ur[i];
     }
-    if (k == 0) {
-#pragma unroll
-        for (int i = 0; i < n; i++) {
-            A.x_init[(size_t)b * n + i] = A.xi[(size_t)q * n + i];
-            A.goal_lo[(size_t)b * n + i] = A.glo[(size_t)q * n + i];
-            A.goal_hi[(size_t)b * n + i] = A.ghi[(size_t)q * n + i];
-        }
-        A.tf_b[b] = Tj;
-    }
-}
-
-int refuse(gusto_handle h, const char* who, const std::string& what, int rc = GUSTO_ERR_ARG) {
-    h->err = std::string(who) + ": " + what;
-    return rc;
+    if (k == 0) seed_problem_tail<MODEL>(A.out, b, A.Q.xi + qn, A.Q.glo + qn, A.Q.ghi + qn, Tj);
 }
 
 bool bracket_ok(double lo, double hi) { return lo > 0 && lo < hi && hi < INFINITY; }
 
 int launch_seed(gusto_handle h) {
-    TfsearchState& S = h->tfsearch;
-    const size_t n = h->n, q = S.Bq;
-    SeedArgs A;
-    A.xi = S.In; A.glo = A.xi + q * n; A.ghi = A.glo + q * n;
-    A.D = S.D; A.cand = S.Cand; A.Xb = S.X; A.Ub = S.U; A.I = S.I;
-    A.X = h->d_X; A.U = h->d_U; A.x_init = h->d_xinit; A.goal_lo = h->d_glo; A.goal_hi = h->d_ghi; A.tf_b = h->d_tf;
-    A.B = h->B; A.Bq = S.Bq; A.K = S.K; A.N = h->N; A.seed = S.seed;
-    const int tot = h->B * h->N;
-    return for_model(h->model_pub, [&](auto M) -> int {
-        hipLaunchKernelGGL(seed_kernel<decltype(M)::value>, dim3((tot + 255) / 256), dim3(256), 0, h->stream, A);
-        HIPCHK(h, hipGetLastError());
-        return GUSTO_OK;
-    });
+    const TfsearchState& S = h->tfsearch;
+    const SeedArgs A{query_dev(S.In, S.Bq, h->n), S.D, S.Cand, S.X, S.U, S.I, seed_out(h), h->B, S.Bq, S.K, h->N, S.seed};
+    return launch_per_knot(h, A, [](auto M) { return seed_kernel<decltype(M)::value>; });
 }
 
 // the refusals of update and the getters, then the handle's device and its enqueued solve
@@ -247,41 +222,37 @@ int gusto_default_tfsearch_opts(int model_id, gusto_tfsearch_opts* o) {
 int gusto_tfsearch_begin(gusto_handle h, int Bq, int K, const double* x_init, const double* glo, const double* ghi,
                          const double* tf_lo, const double* tf_hi, const gusto_tfsearch_opts* o) {
     const char* who = "gusto_tfsearch_begin";
-    if (!h) return GUSTO_ERR_ARG;
-    if (h->trajopt) return refuse(h, who, "TrajOpt handle (not supported)");
-    if (K < 1 || K > GUSTO_MAX_STARTS) return refuse(h, who, "K outside 1 .. GUSTO_MAX_STARTS");
-    if (Bq < 1 || (long long)Bq * K > h->batch_cap) return refuse(h, who, "need Bq >= 1 and Bq K <= batch_cap");
-    if (!x_init || !glo || !ghi) return refuse(h, who, "a null array");
     gusto_tfsearch_opts opts;
-    if (o) opts = *o;
-    else gusto_default_tfsearch_opts(h->model_pub, &opts);
-    if (!(opts.rtol >= 1e-6 && opts.rtol < 1)) return refuse(h, who, "rtol must lie in [1e-6, 1)");
-    if (opts.seed != GUSTO_TFSEARCH_SEED_LINE && opts.seed != GUSTO_TFSEARCH_SEED_INCUMBENT) return refuse(h, who, "unknown seed");
-    if (opts.seed == GUSTO_TFSEARCH_SEED_INCUMBENT && h->model_pub == GUSTO_DUBINS_CAR)
-        return refuse(h, who, "DubinsCar: the speed is a constant of the model, nothing retimes (GUSTO_TFSEARCH_SEED_LINE)");
+    std::vector<double> br;   // lo0 | hi0
+    if (int rc = seed_enter(h, who, Bq, K, GUSTO_MAX_STARTS, "GUSTO_MAX_STARTS", {x_init, glo, ghi}, [&]() -> int {
+            if (o) opts = *o;
+            else gusto_default_tfsearch_opts(h->model_pub, &opts);
+            if (!(opts.rtol >= 1e-6 && opts.rtol < 1)) return refuse(h, who, "rtol must lie in [1e-6, 1)");
+            if (opts.seed != GUSTO_TFSEARCH_SEED_LINE && opts.seed != GUSTO_TFSEARCH_SEED_INCUMBENT) return refuse(h, who, "unknown seed");
+            if (opts.seed == GUSTO_TFSEARCH_SEED_INCUMBENT && h->model_pub == GUSTO_DUBINS_CAR)
+                return refuse(h, who, "DubinsCar: the speed is a constant of the model, nothing retimes (GUSTO_TFSEARCH_SEED_LINE)");
+            br.resize(2 * (size_t)Bq);
+            for (size_t i = 0, q = Bq; i < q; i++) {
+                br[i] = tf_lo ? tf_lo[i] : opts.tf_lo;
+                br[q + i] = tf_hi ? tf_hi[i] : opts.tf_hi;
+                if (!bracket_ok(br[i], br[q + i])) return refuse(h, who, "need 0 < tf_lo < tf_hi < inf (query " + std::to_string(i) + ")");
+            }
+            return GUSTO_OK;
+        }))
+        return rc;
     const size_t n = h->n, m = h->m, N = h->N, q = Bq;
-    std::vector<double> in(q * (3 * n + 2));   // x_init | goal_lo | goal_hi | lo0 | hi0: one copy
-    double* at = in.data();
-    for (const double* src : {x_init, glo, ghi}) { memcpy(at, src, sizeof(double) * q * n); at += q * n; }
-    for (size_t i = 0; i < q; i++) {
-        at[i] = tf_lo ? tf_lo[i] : opts.tf_lo;
-        at[q + i] = tf_hi ? tf_hi[i] : opts.tf_hi;
-        if (!bracket_ok(at[i], at[q + i])) return refuse(h, who, "need 0 < tf_lo < tf_hi < inf (query " + std::to_string(i) + ")");
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    if (int rc = gusto_complete(h)) return rc;
+    const std::vector<double> in = pack_queries(q, n, x_init, glo, ghi, {{br.data(), 2 * q}});
     TfsearchState& S = h->tfsearch;
     S.have = false;
     HIPCHK(h, S.In.ensure(in.size())); HIPCHK(h, S.D.ensure(TF_ND * q)); HIPCHK(h, S.I.ensure(TI_NI * q));
     HIPCHK(h, S.Cand.ensure(q * K)); HIPCHK(h, S.X.ensure(q * N * n)); HIPCHK(h, S.U.ensure(q * N * m));
     HIPCHK(h, hipMemsetAsync(S.X, 0, sizeof(double) * q * N * n, h->stream));   // (the report's X, U before the first incumbent)
     HIPCHK(h, hipMemsetAsync(S.U, 0, sizeof(double) * q * N * m, h->stream));
-    h->sched_err = 0;   // (a latched scheduler error ends here: every problem is set again)
-    h->B = Bq * K;
+    seed_set_B(h, q * K);
     S.K = K; S.Bq = Bq; S.round = 0; S.n_searching = Bq; S.seed = opts.seed; S.rtol = opts.rtol;
     HIPCHK(h, S.t0.record(h->stream));
     HIPCHK(h, hipMemcpyAsync(S.In, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, h->stream));
-    const double* lo0 = S.In + 3 * q * n;
+    const double* lo0 = query_dev(S.In, q, n).extra;
     hipLaunchKernelGGL(begin_kernel, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, lo0, lo0 + q, S.D.get(), S.I.get(), S.Cand.get(), Bq, K);
     HIPCHK(h, hipGetLastError());
     if (int rc = launch_seed(h)) return rc;
@@ -363,10 +334,7 @@ int gusto_get_tfsearch_dev(gusto_handle h, const double** X_dev, const double** 
 }
 
 int gusto_last_tfsearch_ms(gusto_handle h, double* ms) {
-    if (!h || !ms) return GUSTO_ERR_ARG;
-    if (!h->tfsearch.have) return refuse(h, "gusto_last_tfsearch_ms", "the handle's problems were not set by gusto_tfsearch_begin", GUSTO_ERR_STATE);
-    *ms = h->tfsearch.last_ms;
-    return GUSTO_OK;
+    return stage_last_ms(h, &gusto_handle_s::tfsearch, ms, "gusto_last_tfsearch_ms", "the handle's problems were not set by gusto_tfsearch_begin");
 }
 
 }  // extern "C"

@@ -211,11 +211,6 @@ template <int MODEL> __global__ void __launch_bounds__(TG_WAVES * 64) tighten_ke
     }
 }
 
-int refuse(gusto_handle h, const std::string& what, int rc = GUSTO_ERR_ARG) {
-    h->err = "gusto_tighten_env: " + what;
-    return rc;
-}
-
 }  // namespace
 
 extern "C" {
@@ -230,34 +225,35 @@ int gusto_default_tighten_opts(int model_id, gusto_tighten_opts* o) {
 
 int gusto_tighten_env(gusto_handle h, int n_env, const int* n_box, const double* box, const int* n_sph, const double* sph,
                       const gusto_tighten_opts* opts) {
-    if (int rc = post_enter(h, "gusto_tighten_env", nullptr, nullptr)) return rc;
-    if (!model_info(h->model)->has_obs) return refuse(h, "the model has no keep-out sets");
+    const char* who = "gusto_tighten_env";
+    if (int rc = post_enter(h, who, nullptr, nullptr)) return rc;
+    if (!model_info(h->model)->has_obs) return refuse(h, who, "the model has no keep-out sets");
     gusto_tighten_opts o;
     gusto_default_tighten_opts(h->model, &o);
     if (opts) o = *opts;
-    if (!(o.kappa >= 0 && o.kappa < INFINITY)) return refuse(h, "kappa must be finite and >= 0");
-    if (!(o.slack >= 0 && o.slack < INFINITY)) return refuse(h, "slack must be finite and >= 0");
-    if (!(o.margin_cap >= 0)) return refuse(h, "margin_cap must be >= 0 (it may be +inf)");
-    if (o.reach != o.reach) return refuse(h, "reach is a NaN");
+    if (!(o.kappa >= 0 && o.kappa < INFINITY)) return refuse(h, who, "kappa must be finite and >= 0");
+    if (!(o.slack >= 0 && o.slack < INFINITY)) return refuse(h, who, "slack must be finite and >= 0");
+    if (!(o.margin_cap >= 0)) return refuse(h, who, "margin_cap must be >= 0 (it may be +inf)");
+    if (o.reach != o.reach) return refuse(h, who, "reach is a NaN");
     if ((o.cover_components != 0 && o.cover_components != 1) || (o.monotone != 0 && o.monotone != 1))
-        return refuse(h, "cover_components and monotone must be 0 or 1");
+        return refuse(h, who, "cover_components and monotone must be 0 or 1");
     const size_t B = h->B, Bc = h->batch_cap;
-    if (n_env != 1 && n_env != (int)B) return refuse(h, "n_env must be 1 or the B of gusto_set_problems");
-    if (!n_box || !n_sph) return refuse(h, "a null n_box or n_sph");
+    if (n_env != 1 && n_env != (int)B) return refuse(h, who, "n_env must be 1 or the B of gusto_set_problems");
+    if (!n_box || !n_sph) return refuse(h, who, "a null n_box or n_sph");
     size_t tb = 0, ts = 0;
     for (int e = 0; e < n_env; e++) {
         if (n_box[e] < 0 || n_sph[e] < 0 || n_box[e] + n_sph[e] > TG_LANES)
-            return refuse(h, "between 0 and 64 keep-out components per problem (set " + std::to_string(e) + ")");
+            return refuse(h, who, "between 0 and 64 keep-out components per problem (set " + std::to_string(e) + ")");
         tb += n_box[e]; ts += n_sph[e];
     }
-    if ((tb && !box) || (ts && !sph)) return refuse(h, "a null table");
+    if ((tb && !box) || (ts && !sph)) return refuse(h, who, "a null table");
     for (size_t i = 0; i < 6 * tb; i++)
-        if (!(fabs(box[i]) < INFINITY)) return refuse(h, "box_min_max must be finite (box " + std::to_string(i / 6) + ")");
+        if (!(fabs(box[i]) < INFINITY)) return refuse(h, who, "box_min_max must be finite (box " + std::to_string(i / 6) + ")");
     for (size_t i = 0; i < 4 * ts; i++)
-        if (!(fabs(sph[i]) < INFINITY)) return refuse(h, "sph_c_r must be finite (sphere " + std::to_string(i / 4) + ")");
+        if (!(fabs(sph[i]) < INFINITY)) return refuse(h, who, "sph_c_r must be finite (sphere " + std::to_string(i / 4) + ")");
     const LincovState& L = h->lincov;
     if (!L.have || !L.store_S || !L.have_Sxx)
-        return refuse(h, "no covariances: call gusto_lincov with store_S = 1 first", GUSTO_ERR_STATE);
+        return refuse(h, who, "no covariances: call gusto_lincov with store_S = 1 first", GUSTO_ERR_STATE);
 
     // the records of every problem in the base tables and in the tightened ones, and whether its remembered margins hold
     TightenState& S = h->tighten;
@@ -275,7 +271,7 @@ int gusto_tighten_env(gusto_handle h, int n_env, const int* n_box, const double*
         cnt[2 * b] = n_box[e]; cnt[2 * b + 1] = n_sph[e];
         keep[b] = S.mem && S.mem_B == (int)B && S.cnt[2 * b] == n_box[e] && S.cnt[2 * b + 1] == n_sph[e];
     }
-    if (ob > (size_t)INT_MAX / 8 || os > (size_t)INT_MAX / 8) return refuse(h, "tables too large");
+    if (ob > (size_t)INT_MAX / 8 || os > (size_t)INT_MAX / 8) return refuse(h, who, "tables too large");
 
     // the tightened tables are built beside the handle's and take their place once the launch is through
     DevBuf<double> nbox, nsph;

@@ -15,14 +15,14 @@
 // wavefronts of a workgroup stage a tile of TL_TILE entries in LDS ([F][TL_TILE], lane-consecutive: no bank conflicts) and all
 // read it there: a quarter of the L2 reads; without, every wavefront reads the rows from global memory.  The arithmetic is the
 // same function of the same numbers.  Measured: profiles/trajlib.txt.
-// Retarget kernel: a thread per (problem, knot), the shape of fan_kernel.  A start without a neighbour evaluates the expression
-// of init_straightline_kernel (scp.hpp), written the same way: that kernel's output bit for bit.
+// Retarget kernel: a thread per (problem, knot), the shape of fan_kernel.  A start without a neighbour evaluates straight_line()
+// of seed.hpp, as init_straightline_kernel (scp.hpp) does: that kernel's output bit for bit.
 // Compaction kernel (gusto_trajlib_add): a wavefront per problem.  Its lanes count the selected problems before it (integers: any
 // order gives the same sum), which is its row behind the library's count; a selected problem's wavefront then copies its
 // trajectory lane-consecutively and writes centre and features.
 #include <hip/hip_runtime.h>
 
-#include "post.hpp"
+#include "seed.hpp"
 
 using namespace gusto;
 
@@ -36,10 +36,8 @@ struct FeatMap {
     double w[TRAJLIB_MAX_F];
 };
 
-GD double centre_of(double lo, double hi) { return (isfinite(lo) && isfinite(hi)) ? 0.5 * (lo + hi) : 0.0; }   // center(goal), zeros elsewhere
-
 struct SearchArgs {
-    const double *xi, *glo, *ghi, *tf;   // the queries: [Bq][n] each, [Bq]
+    QueryDev Q;                          // the queries; extra: tf [Bq]
     const int* qtag;                     // [Bq], null: tags ignored
     const double* feat;                  // [F][cap]
     const int* etag;                     // [cap]
@@ -59,7 +57,7 @@ template <int K, bool TILED> __global__ void __launch_bounds__(64 * TL_WAVES) se
     if (valid && lane < F) {
         const int kind = A.M.fmap[lane] >> 4, i = A.M.fmap[lane] & 15;
         const size_t at = (size_t)q * A.n + i;
-        qf[lane] = kind == 0 ? A.xi[at] : (kind == 1 ? centre_of(A.glo[at], A.ghi[at]) : A.tf[q]);
+        qf[lane] = kind == 0 ? A.Q.xi[at] : (kind == 1 ? goal_centre(A.Q.glo[at], A.Q.ghi[at]) : A.Q.extra[q]);
     }
     const int tq = (valid && A.qtag) ? A.qtag[q] : 0;
     double bd[K];
@@ -120,30 +118,27 @@ template <int K, bool TILED> __global__ void __launch_bounds__(64 * TL_WAVES) se
 }
 
 struct RetargetArgs {
-    const double *xi, *glo, *ghi, *tf;                   // the queries
-    const int* entry;                                    // [B]
-    const double *lxi, *lc, *lX, *lU;                    // the library's rows
-    double *X, *U, *x_init, *goal_lo, *goal_hi, *tf_b;   // the handle's [B] arrays
+    QueryDev Q;                         // the queries; extra: tf [Bq]
+    const int* entry;                   // [B]
+    const double *lxi, *lc, *lX, *lU;   // the library's rows
+    SeedOut out;
     int B, K, N;
 };
 
 template <int MODEL> __global__ void retarget_kernel(const RetargetArgs A) {
     using T = MT<MODEL>;
     constexpr int n = T::n, m = T::m;
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= A.B * A.N) return;
-    const int b = gid / A.N, k = gid % A.N, q = b / A.K;
+    KnotId id;
+    if (!knot_id(A.B, A.K, A.N, id)) return;
+    const int b = id.b, k = id.k;
+    const double t = id.t;
+    const double *xi = A.Q.xi + (size_t)id.q * n, *glo = A.Q.glo + (size_t)id.q * n, *ghi = A.Q.ghi + (size_t)id.q * n;   // the query's rows
     const int e = A.entry[b];
-    const double t = (double)k / (double)(A.N - 1);  // LinRange element: (1-t)*a + t*b
-    double* Xo = A.X + ((size_t)b * A.N + k) * n;
-    double* Uo = A.U + ((size_t)b * A.N + k) * m;
+    double* Xo = A.out.X + ((size_t)b * A.N + k) * n;
+    double* Uo = A.out.U + ((size_t)b * A.N + k) * m;
     if (e < 0) {
 #pragma unroll
-        for (int i = 0; i < n; i++) {
-            const double lo = A.glo[(size_t)q * n + i], hi = A.ghi[(size_t)q * n + i];
-            const double xg = (isfinite(lo) && isfinite(hi)) ? 0.5 * (lo + hi) : 0.0;  // center(goal), zeros elsewhere
-            Xo[i] = (1 - t) * A.xi[(size_t)q * n + i] + t * xg;
-        }
+        for (int i = 0; i < n; i++) Xo[i] = straight_line(t, xi[i], glo[i], ghi[i]);
 #pragma unroll
         for (int i = 0; i < m; i++) Uo[i] = 0.0;
     } else {
@@ -151,23 +146,15 @@ template <int MODEL> __global__ void retarget_kernel(const RetargetArgs A) {
         const double* Ue = A.lU + ((size_t)e * A.N + k) * m;
 #pragma unroll
         for (int i = 0; i < n; i++) {
-            const double xq = A.xi[(size_t)q * n + i];
-            const double cq = centre_of(A.glo[(size_t)q * n + i], A.ghi[(size_t)q * n + i]);
+            const double xq = xi[i];
+            const double cq = goal_centre(glo[i], ghi[i]);
             const double dxi = xq - A.lxi[(size_t)e * n + i], dc = cq - A.lc[(size_t)e * n + i];
             Xo[i] = k == 0 ? xq : Xe[i] + ((1 - t) * dxi + t * dc);
         }
 #pragma unroll
         for (int i = 0; i < m; i++) Uo[i] = Ue[i];
     }
-    if (k == 0) {
-#pragma unroll
-        for (int i = 0; i < n; i++) {
-            A.x_init[(size_t)b * n + i] = A.xi[(size_t)q * n + i];
-            A.goal_lo[(size_t)b * n + i] = A.glo[(size_t)q * n + i];
-            A.goal_hi[(size_t)b * n + i] = A.ghi[(size_t)q * n + i];
-        }
-        A.tf_b[b] = A.tf[q];
-    }
+    if (k == 0) seed_problem_tail<MODEL>(A.out, b, xi, glo, ghi, A.Q.extra[id.q]);
 }
 
 struct CompactArgs {
@@ -191,12 +178,12 @@ __global__ void __launch_bounds__(64) compact_kernel(const CompactArgs A) {
     if (lane < A.n) {
         const size_t at = (size_t)b * A.n + lane;
         A.lxi[e * A.n + lane] = A.x_init[at];
-        A.lc[e * A.n + lane] = centre_of(A.goal_lo[at], A.goal_hi[at]);
+        A.lc[e * A.n + lane] = goal_centre(A.goal_lo[at], A.goal_hi[at]);
     }
     if (lane < A.M.F) {
         const int kind = A.M.fmap[lane] >> 4, i = A.M.fmap[lane] & 15;
         const size_t at = (size_t)b * A.n + i;
-        A.feat[(size_t)lane * A.cap + e] = kind == 0 ? A.x_init[at] : (kind == 1 ? centre_of(A.goal_lo[at], A.goal_hi[at]) : A.tf[b]);
+        A.feat[(size_t)lane * A.cap + e] = kind == 0 ? A.x_init[at] : (kind == 1 ? goal_centre(A.goal_lo[at], A.goal_hi[at]) : A.tf[b]);
     }
     if (lane == 0) { A.ltf[e] = A.tf[b]; A.ltag[e] = A.tag[b]; }
 }
@@ -205,10 +192,6 @@ thread_local std::string g_lib_err;   // a failed gusto_trajlib_create
 
 int lib_refuse(gusto_trajlib lib, const char* who, const std::string& what) {
     lib->err = std::string(who) + ": " + what;
-    return GUSTO_ERR_ARG;
-}
-int refuse(gusto_handle h, const char* who, const char* what) {
-    h->err = std::string(who) + ": " + what;
     return GUSTO_ERR_ARG;
 }
 
@@ -416,30 +399,23 @@ int gusto_trajlib_get(gusto_trajlib lib, double* x_init, double* goal_c, double*
 int gusto_set_problems_trajlib(gusto_handle h, gusto_trajlib lib, int Bq, int K, const double* x_init, const double* glo,
                                const double* ghi, const double* tf, const int* tag) {
     const char* who = "gusto_set_problems_trajlib";
-    if (!h) return GUSTO_ERR_ARG;
-    if (h->trajopt) return refuse(h, who, "TrajOpt handle (not supported)");
-    if (K < 1 || K > GUSTO_TRAJLIB_MAX_K) return refuse(h, who, "K outside 1 .. GUSTO_TRAJLIB_MAX_K");
-    if (Bq < 1 || (long long)Bq * K > h->batch_cap) return refuse(h, who, "need Bq >= 1 and Bq K <= batch_cap");
-    if (!x_init || !glo || !ghi || !tf) return refuse(h, who, "a null array");
-    if (!lib) return refuse(h, who, "a null library");
-    if (lib->model != h->model_pub || lib->N != h->N || lib->device != h->device)
-        return refuse(h, who, "the library's model, N or device differ from the handle's");
-    HIPCHK(h, hipSetDevice(h->device));
-    if (int rc = gusto_complete(h)) return rc;
+    if (int rc = seed_enter(h, who, Bq, K, GUSTO_TRAJLIB_MAX_K, "GUSTO_TRAJLIB_MAX_K", {x_init, glo, ghi, tf}, [&]() -> int {
+            if (!lib) return refuse(h, who, "a null library");
+            if (lib->model != h->model_pub || lib->N != h->N || lib->device != h->device)
+                return refuse(h, who, "the library's model, N or device differ from the handle's");
+            return GUSTO_OK;
+        }))
+        return rc;
     const size_t n = h->n, q = Bq, B = q * K;
-    std::vector<double> in(q * (3 * n + 1));   // x_init | goal_lo | goal_hi | tf: one copy
-    double* at = in.data();
-    for (const double* src : {x_init, glo, ghi}) { memcpy(at, src, sizeof(double) * q * n); at += q * n; }
-    memcpy(at, tf, sizeof(double) * q);
+    const std::vector<double> in = pack_queries(q, n, x_init, glo, ghi, {{tf, q}});
     TrajlibState& S = h->trajlib;
     HIPCHK(h, S.In.ensure(in.size())); HIPCHK(h, S.Tag.ensure(q));
     HIPCHK(h, S.Entry.ensure(B)); HIPCHK(h, S.Dist.ensure(B)); HIPCHK(h, S.Found.ensure(q));
-    h->sched_err = 0;   // (a latched scheduler error ends here: every problem is set again)
-    h->B = (int)B;
+    seed_set_B(h, B);
     HIPCHK(h, hipMemcpyAsync(S.In, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, h->stream));
     if (tag) HIPCHK(h, hipMemcpyAsync(S.Tag, tag, sizeof(int) * q, hipMemcpyHostToDevice, h->stream));
     SearchArgs A;
-    A.xi = S.In; A.glo = A.xi + q * n; A.ghi = A.glo + q * n; A.tf = A.ghi + q * n;
+    A.Q = query_dev(S.In, q, n);
     A.qtag = tag ? S.Tag.get() : nullptr;
     A.feat = lib->Feat; A.etag = lib->tag; A.cap = lib->cap; A.L = lib->count; A.Bq = Bq; A.n = (int)n;
     A.M = feat_map(lib);
@@ -458,18 +434,8 @@ int gusto_set_problems_trajlib(gusto_handle h, gusto_trajlib lib, int Bq, int K,
     }
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, S.mid.record(h->stream));
-    RetargetArgs R;
-    R.xi = A.xi; R.glo = A.glo; R.ghi = A.ghi; R.tf = A.tf; R.entry = S.Entry;
-    R.lxi = lib->xi; R.lc = lib->c; R.lX = lib->X; R.lU = lib->U;
-    R.X = h->d_X; R.U = h->d_U; R.x_init = h->d_xinit; R.goal_lo = h->d_glo; R.goal_hi = h->d_ghi; R.tf_b = h->d_tf;
-    R.B = h->B; R.K = K; R.N = h->N;
-    const int tot = h->B * h->N;
-    if (int rc = for_model(h->model_pub, [&](auto M) -> int {
-            hipLaunchKernelGGL(retarget_kernel<decltype(M)::value>, dim3((tot + 255) / 256), dim3(256), 0, h->stream, R);
-            HIPCHK(h, hipGetLastError());
-            return GUSTO_OK;
-        }))
-        return rc;
+    const RetargetArgs R{A.Q, S.Entry, lib->xi, lib->c, lib->X, lib->U, seed_out(h), h->B, K, h->N};
+    if (int rc = launch_per_knot(h, R, [](auto M) { return retarget_kernel<decltype(M)::value>; })) return rc;
     HIPCHK(h, S.t1.record(h->stream));
     if (int rc = gusto_problems_loaded(h, false)) return rc;   // (waits for the stream: `in` and `tag` are read by then)
     HIPCHK(h, event_ms(S.t0, S.t1, &S.last_ms));
@@ -489,10 +455,7 @@ int gusto_get_trajlib_seeds(gusto_handle h, int* entry, double* dist2, int* n_fo
 }
 
 int gusto_last_trajlib_ms(gusto_handle h, double* ms) {
-    if (!h || !ms) return GUSTO_ERR_ARG;
-    if (!h->trajlib.have) { h->err = "gusto_last_trajlib_ms: call gusto_set_problems_trajlib first"; return GUSTO_ERR_STATE; }
-    *ms = h->trajlib.last_ms;
-    return GUSTO_OK;
+    return stage_last_ms(h, &gusto_handle_s::trajlib, ms, "gusto_last_trajlib_ms", "call gusto_set_problems_trajlib first");
 }
 
 int gusto_dev_trajlib(gusto_handle h, double* search_ms, double* retarget_ms) {

@@ -795,6 +795,88 @@ def default_fan(model_id):
     return np.array([(0.0, 0.0), (0.5, 0.0), (-0.5, 0.0), (0.0, 0.5), (0.0, -0.5)])
 
 
+class _QueryBatch:
+    """What the query drivers share (solve_SCP_multistart_batch, solve_SCP_min_time_batch, solve_SCP_trajlib_batch,
+    solve_SCP_roadmap_batch): every TOP is one planning query, all of one model and N, each with its own environment or all with
+    the same.  The checks (in the driver's name `who`), the stacked inputs x0, lo, hi [Q, n] and tf [Q], the BatchSolver, the
+    environment of a subset of the queries, the filling of a query's solution and report, and the fanned launches of the queries
+    that are left without a winner.  out[q] is the driver's report of query q."""
+
+    def __init__(self, who, TOSs, TOPs, early=None):
+        """early: the text of a refusal of the driver's own that comes before the model check (None: there is none)"""
+        if len(TOSs) != len(TOPs) or not TOPs:
+            raise ValueError(f"{who}!: need as many solutions as problems, at least one")
+        if early is not None:
+            raise ValueError(f"{who}!: {early}")
+        TOP0 = TOPs[0]
+        self.TOSs, self.TOPs, self.model, self.N, self.Q = TOSs, TOPs, TOP0.PD.model, TOP0.N, len(TOPs)
+        for t in TOPs[1:]:
+            if type(t.PD.model) is not type(self.model) or t.N != self.N:
+                raise ValueError(f"{who}!: all problems must share the model type and N")
+        self.same_env = all(np.array_equal(t.PD.env.boxes, TOP0.PD.env.boxes) and np.array_equal(t.PD.env.spheres, TOP0.PD.env.spheres)
+                            for t in TOPs[1:])
+        self.x0 = np.stack([t.PD.x_init for t in TOPs])
+        bounds = [_goal_bounds(t.PD.goal_set, self.model.x_dim, t.tf_guess) for t in TOPs]
+        self.lo, self.hi = np.stack([b[0] for b in bounds]), np.stack([b[1] for b in bounds])
+        self.tf = np.array([t.tf_guess for t in TOPs])
+        self.out = [None] * self.Q
+
+    def solver(self, cap, max_iter, force, device):
+        """the BatchSolver of the call, for cap problems, on the first query's environment"""
+        sp, mp = _capi.default_params(self.model.model_id)
+        env = self.TOPs[0].PD.env
+        self.cap, self.max_iter, self.force = cap, max_iter, force
+        self.bs = BatchSolver(self.model.model_id, self.N, cap, hist_cap=_hist_cap(max_iter), device=device, boxes=env.boxes,
+                              spheres=env.spheres, scp_params=sp, model_params=mp)
+        return self.bs
+
+    def env(self, qs=None):
+        """boxes / spheres of the queries qs (None: all), one set per query, for a set_problems_* call; {} when all share one"""
+        if self.same_env:
+            return {}
+        tops = self.TOPs if qs is None else [self.TOPs[q] for q in qs]
+        return dict(boxes=[t.PD.env.boxes for t in tops], spheres=[t.PD.env.spheres for t in tops])
+
+    def take(self, q, snap, b, per, solved_tf=None, **report):
+        """problem b of the snapshot is query q's answer: TOSs[q] and out[q] = report + SCPS.  tf: the final time it was solved
+        with (solved_tf) when that is not the query's tf_guess"""
+        TOP = self.TOPs[q]
+        SCPP = SCPProblem(TOP)
+        if solved_tf is None:
+            init = init_traj_straightline(TOP)
+        else:
+            SCPP.tf_guess = float(solved_tf)
+            init = Trajectory(np.zeros((self.model.x_dim, self.N)), np.zeros((self.model.u_dim, self.N)), solved_tf)
+        SCPS = SCPSolution(SCPP, init)
+        _fill_solution(SCPS, SCPP, snap, b, per)
+        self.TOSs[q].traj, self.TOSs[q].SCPS = SCPS.traj, SCPS
+        self.out[q] = dict(report, SCPS=SCPS)
+
+    def solved(self, K, nq):
+        """solve what is set, nq queries of K starts, and select: (best, snapshot, seconds per query)"""
+        self.bs.solve(self.max_iter, self.force)
+        best = self.bs.select_best(K)
+        return best, _fetch(self.bs), self.bs.last_solve_ms() * 1e-3 / nq
+
+    def fanned(self, qs, fan):
+        """the queries qs through one launch of the multi-start fan"""
+        qs = np.asarray(qs)
+        self.bs.set_problems_multistart(self.x0[qs], self.lo[qs], self.hi[qs], self.tf[qs], fan, **self.env(qs))
+        return self.solved(len(fan), len(qs))
+
+    def chunks(self, again, K):
+        """the queries `again` in as many pieces as K starts each need on this handle"""
+        step = self.cap // K
+        return [again[c:c + step] for c in range(0, len(again), step)]
+
+
+def _fallback_fan(model_id, fallback_fan):
+    """fallback_fan of a driver: None / False (none), True (default_fan) or the offsets [Kf, 2]"""
+    if fallback_fan is None or fallback_fan is False:
+        return None
+    return default_fan(model_id) if fallback_fan is True else np.asarray(fallback_fan, float).reshape(-1, 2)
+
+
 def solve_SCP_multistart_batch(TOSs, TOPs, fan=None, policy="all", solver="hip", max_iter=30, force=False, device=0):
     """Every TOP is one planning QUERY, started from a fan of K initial trajectories (gusto_set_problems_multistart: the straight
     line bent sideways by fan[j] = (a2, a3) metres; None = default_fan) and answered with the best start that is converged and
@@ -809,56 +891,26 @@ def solve_SCP_multistart_batch(TOSs, TOPs, fan=None, policy="all", solver="hip",
     and TOSs[q].SCPS are set as by solve_SCP_batch."""
     if policy not in ("all", "retry"):
         raise ValueError("solve_SCP_multistart_batch!: policy is 'all' or 'retry'")
-    if len(TOSs) != len(TOPs) or not TOPs:
-        raise ValueError("solve_SCP_multistart_batch!: need as many solutions as problems, at least one")
-    TOP0 = TOPs[0]
-    model, N = TOP0.PD.model, TOP0.N
-    n = model.x_dim
-    Q = len(TOPs)
-    for t in TOPs[1:]:
-        if type(t.PD.model) is not type(model) or t.N != N:
-            raise ValueError("solve_SCP_multistart_batch!: all problems must share the model type and N")
-    fan = default_fan(model.model_id) if fan is None else np.asarray(fan, float).reshape(-1, 2)
+    qb = _QueryBatch("solve_SCP_multistart_batch", TOSs, TOPs)
+    Q, x0, lo, hi, tf = qb.Q, qb.x0, qb.lo, qb.hi, qb.tf
+    fan = default_fan(qb.model.model_id) if fan is None else np.asarray(fan, float).reshape(-1, 2)
     K = len(fan)
-    same_env = all(np.array_equal(t.PD.env.boxes, TOP0.PD.env.boxes) and np.array_equal(t.PD.env.spheres, TOP0.PD.env.spheres)
-                   for t in TOPs[1:])
-    sp, mp = _capi.default_params(model.model_id)
-    x0 = np.stack([t.PD.x_init for t in TOPs])
-    bounds = [_goal_bounds(t.PD.goal_set, n, t.tf_guess) for t in TOPs]
-    lo, hi = np.stack([b[0] for b in bounds]), np.stack([b[1] for b in bounds])
-    tf = np.array([t.tf_guess for t in TOPs])
-    cap = Q * K if policy == "all" else max(Q, K)
-    bs = BatchSolver(model.model_id, N, cap, hist_cap=_hist_cap(max_iter), device=device, boxes=TOP0.PD.env.boxes,
-                     spheres=TOP0.PD.env.spheres, scp_params=sp, model_params=mp)
-    out = [None] * Q
-
-    def take(q, snap, b, per, winner, cost):
-        SCPP = SCPProblem(TOPs[q])
-        SCPS = SCPSolution(SCPP, init_traj_straightline(TOPs[q]))
-        _fill_solution(SCPS, SCPP, snap, b, per)
-        TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
-        out[q] = dict(winner=int(winner), cost=float(cost), SCPS=SCPS)
+    bs = qb.solver(Q * K if policy == "all" else max(Q, K), max_iter, force, device)
 
     def fanned(qs, keep_loser):
         """the queries qs through one fanned launch; a query without a winner is taken from start 0 when keep_loser"""
-        qs = np.asarray(qs)
-        env = {} if same_env else dict(boxes=[TOPs[q].PD.env.boxes for q in qs], spheres=[TOPs[q].PD.env.spheres for q in qs])
-        bs.set_problems_multistart(x0[qs], lo[qs], hi[qs], tf[qs], fan, **env)
-        bs.solve(max_iter, force)
-        best = bs.select_best(K)
-        snap = _fetch(bs)
-        per = bs.last_solve_ms() * 1e-3 / len(qs)
+        best, snap, per = qb.fanned(qs, fan)
         for i, q in enumerate(qs):
             if best["winner"][i] >= 0:
-                take(q, snap, best["winner_problem"][i], per, best["winner"][i], best["best_score"][i])
+                qb.take(q, snap, best["winner_problem"][i], per, winner=int(best["winner"][i]), cost=float(best["best_score"][i]))
             elif keep_loser:
-                take(q, snap, i * K, per, -1, np.inf)
+                qb.take(q, snap, i * K, per, winner=-1, cost=float(np.inf))
 
     try:
         if policy == "all":
             fanned(np.arange(Q), True)
         else:
-            if not same_env:
+            if not qb.same_env:
                 bs.set_env_batch([t.PD.env.boxes for t in TOPs], [t.PD.env.spheres for t in TOPs])
             bs.set_problems(x0, lo, hi, tf)
             bs.solve(max_iter, force)
@@ -867,13 +919,12 @@ def solve_SCP_multistart_batch(TOSs, TOPs, fan=None, policy="all", solver="hip",
             ok = snap["st"]["converged"] & snap["st"]["successful"]
             for q in range(Q):
                 last = snap["h"]["J_true"][q, snap["h"]["nJ"][q] - 1]
-                take(q, snap, q, per, 0 if ok[q] else -1, last if ok[q] else np.inf)
-            again = np.flatnonzero(~ok)
-            for c in range(0, len(again), cap // K):
-                fanned(again[c:c + cap // K], False)
+                qb.take(q, snap, q, per, winner=0 if ok[q] else -1, cost=float(last if ok[q] else np.inf))
+            for qs in qb.chunks(np.flatnonzero(~ok), K):
+                fanned(qs, False)
     finally:
         bs.close()
-    return out
+    return qb.out
 
 
 def solve_SCP_min_time_batch(TOSs, TOPs, tf_lo, tf_hi, K=8, rounds=3, rtol=0.01, seed="incumbent", eligible=None, solver="hip",
@@ -891,38 +942,17 @@ def solve_SCP_min_time_batch(TOSs, TOPs, tf_lo, tf_hi, K=8, rounds=3, rtol=0.01,
     Returns one dict per query: `tf` (NaN without an incumbent), `lo`, `hi`, `status` (bits _capi.TFSEARCH_NONE / DONE / FLOOR /
     NONMONOTONE), `J` (the incumbent's last J_true) and `SCPS`, the filled SCPSolution of the solve that found the incumbent -- for
     a NONE query of the straight line's solve at tf_hi.  TOSs[q].traj is the incumbent with Tf = tf, TOSs[q].SCPS that SCPS."""
-    if len(TOSs) != len(TOPs) or not TOPs:
-        raise ValueError("solve_SCP_min_time_batch!: need as many solutions as problems, at least one")
-    if rounds < 1:
-        raise ValueError("solve_SCP_min_time_batch!: need at least one round")
-    TOP0 = TOPs[0]
-    model, N = TOP0.PD.model, TOP0.N
-    n, Q, K = model.x_dim, len(TOPs), int(K)
-    for t in TOPs[1:]:
-        if type(t.PD.model) is not type(model) or t.N != N:
-            raise ValueError("solve_SCP_min_time_batch!: all problems must share the model type and N")
-    same_env = all(np.array_equal(t.PD.env.boxes, TOP0.PD.env.boxes) and np.array_equal(t.PD.env.spheres, TOP0.PD.env.spheres)
-                   for t in TOPs[1:])
-    sp, mp = _capi.default_params(model.model_id)
-    x0 = np.stack([t.PD.x_init for t in TOPs])
-    bounds = [_goal_bounds(t.PD.goal_set, n, t.tf_guess) for t in TOPs]
-    lo, hi = np.stack([b[0] for b in bounds]), np.stack([b[1] for b in bounds])
-    bs = BatchSolver(model.model_id, N, Q * K, hist_cap=_hist_cap(max_iter), device=device, boxes=TOP0.PD.env.boxes,
-                     spheres=TOP0.PD.env.spheres, scp_params=sp, model_params=mp)
-    out = [None] * Q
+    qb = _QueryBatch("solve_SCP_min_time_batch", TOSs, TOPs, early="need at least one round" if rounds < 1 else None)
+    Q, K = qb.Q, int(K)
+    bs = qb.solver(Q * K, max_iter, force, device)
+    out = qb.out
 
     def take(q, snap, b, per, tf, info):
-        SCPP = SCPProblem(TOPs[q])
-        SCPP.tf_guess = float(tf)
-        SCPS = SCPSolution(SCPP, Trajectory(np.zeros((n, N)), np.zeros((model.u_dim, N)), tf))
-        _fill_solution(SCPS, SCPP, snap, b, per)
-        TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
-        out[q] = dict(tf=float(info["tf_best"][q]), lo=float(info["lo"][q]), hi=float(info["hi"][q]), status=int(info["status"][q]),
-                      J=float(info["J_best"][q]), SCPS=SCPS)
+        qb.take(q, snap, b, per, solved_tf=tf, tf=float(info["tf_best"][q]), lo=float(info["lo"][q]), hi=float(info["hi"][q]),
+                status=int(info["status"][q]), J=float(info["J_best"][q]))
 
     try:
-        env = {} if same_env else dict(boxes=[t.PD.env.boxes for t in TOPs], spheres=[t.PD.env.spheres for t in TOPs])
-        bs.tfsearch_begin(x0, lo, hi, tf_lo, tf_hi, K=K, rtol=rtol, seed=seed, **env)
+        bs.tfsearch_begin(qb.x0, qb.lo, qb.hi, tf_lo, tf_hi, K=K, rtol=rtol, seed=seed, **qb.env())
         cand = bs.tfsearch_info()["cand"]
         for r in range(rounds):
             bs.solve(max_iter, force)
@@ -968,54 +998,26 @@ def solve_SCP_trajlib_batch(TOSs, TOPs, lib, K=1, fallback_fan=None, learn=False
     likewise), `source` ("library", "fan", or None without a winner), `entry` (the library entry the winning start was seeded
     from; -1 for a straight line or a fan start) and `SCPS`, the filled SCPSolution of the winner -- without one, of start 0.
     TOSs[q].traj and TOSs[q].SCPS are set as by solve_SCP_batch."""
-    if len(TOSs) != len(TOPs) or not TOPs:
-        raise ValueError("solve_SCP_trajlib_batch!: need as many solutions as problems, at least one")
-    TOP0 = TOPs[0]
-    model, N = TOP0.PD.model, TOP0.N
-    n = model.x_dim
-    Q, K = len(TOPs), int(K)
-    for t in TOPs[1:]:
-        if type(t.PD.model) is not type(model) or t.N != N:
-            raise ValueError("solve_SCP_trajlib_batch!: all problems must share the model type and N")
-    if lib.model != model.model_id or lib.N != N:
+    qb = _QueryBatch("solve_SCP_trajlib_batch", TOSs, TOPs)
+    Q, K = qb.Q, int(K)
+    if lib.model != qb.model.model_id or lib.N != qb.N:
         raise ValueError("solve_SCP_trajlib_batch!: the library belongs to another model or N")
-    fan = None
-    if fallback_fan is not None and fallback_fan is not False:
-        fan = default_fan(model.model_id) if fallback_fan is True else np.asarray(fallback_fan, float).reshape(-1, 2)
-    same_env = all(np.array_equal(t.PD.env.boxes, TOP0.PD.env.boxes) and np.array_equal(t.PD.env.spheres, TOP0.PD.env.spheres)
-                   for t in TOPs[1:])
-    sp, mp = _capi.default_params(model.model_id)
-    x0 = np.stack([t.PD.x_init for t in TOPs])
-    bounds = [_goal_bounds(t.PD.goal_set, n, t.tf_guess) for t in TOPs]
-    lo, hi = np.stack([b[0] for b in bounds]), np.stack([b[1] for b in bounds])
-    tf = np.array([t.tf_guess for t in TOPs])
-    cap = Q * K if fan is None else max(Q * K, len(fan))
-    bs = BatchSolver(model.model_id, N, cap, hist_cap=_hist_cap(max_iter), device=lib.device, boxes=TOP0.PD.env.boxes,
-                     spheres=TOP0.PD.env.spheres, scp_params=sp, model_params=mp)
-    out = [None] * Q
-
-    def take(q, snap, b, per, winner, cost, source, entry):
-        SCPP = SCPProblem(TOPs[q])
-        SCPS = SCPSolution(SCPP, init_traj_straightline(TOPs[q]))
-        _fill_solution(SCPS, SCPP, snap, b, per)
-        TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
-        out[q] = dict(winner=int(winner), cost=float(cost), source=source, entry=int(entry), SCPS=SCPS)
+    fan = _fallback_fan(qb.model.model_id, fallback_fan)
+    bs = qb.solver(Q * K if fan is None else max(Q * K, len(fan)), max_iter, force, lib.device)
 
     def finish(qs, Ks, source, entries, keep_loser):
         """solve what is set, select, fill the queries qs; with learn the winners join the library.  Returns the losers"""
-        bs.solve(max_iter, force)
-        best = bs.select_best(Ks)
-        snap = _fetch(bs)
-        per = bs.last_solve_ms() * 1e-3 / len(qs)
+        best, snap, per = qb.solved(Ks, len(qs))
         lost = []
         for i, q in enumerate(qs):
             w = best["winner"][i]
             if w >= 0:
-                take(q, snap, best["winner_problem"][i], per, w, best["best_score"][i], source, -1 if entries is None else entries[i, w])
+                qb.take(q, snap, best["winner_problem"][i], per, winner=int(w), cost=float(best["best_score"][i]), source=source,
+                        entry=int(-1 if entries is None else entries[i, w]))
             else:
                 lost.append(q)
                 if keep_loser:
-                    take(q, snap, i * Ks, per, -1, np.inf, None, -1)
+                    qb.take(q, snap, i * Ks, per, winner=-1, cost=float(np.inf), source=None, entry=-1)
         if learn and (best["winner"] >= 0).any():
             mask = np.zeros(bs.B, bool)
             mask[best["winner_problem"][best["winner"] >= 0]] = True
@@ -1023,19 +1025,15 @@ def solve_SCP_trajlib_batch(TOSs, TOPs, lib, K=1, fallback_fan=None, learn=False
         return np.array(lost, dtype=int)
 
     try:
-        env = {} if same_env else dict(boxes=[t.PD.env.boxes for t in TOPs], spheres=[t.PD.env.spheres for t in TOPs])
-        bs.set_problems_trajlib(lib, x0, lo, hi, tf, K, **env)
+        bs.set_problems_trajlib(lib, qb.x0, qb.lo, qb.hi, qb.tf, K, **qb.env())
         again = finish(np.arange(Q), K, "library", bs.trajlib_seeds()["entry"], True)
         if fan is not None:
-            Kf = len(fan)
-            for c in range(0, len(again), cap // Kf):
-                qs = again[c:c + cap // Kf]
-                env = {} if same_env else dict(boxes=[TOPs[q].PD.env.boxes for q in qs], spheres=[TOPs[q].PD.env.spheres for q in qs])
-                bs.set_problems_multistart(x0[qs], lo[qs], hi[qs], tf[qs], fan, **env)
-                finish(qs, Kf, "fan", None, False)
+            for qs in qb.chunks(again, len(fan)):
+                bs.set_problems_multistart(qb.x0[qs], qb.lo[qs], qb.hi[qs], qb.tf[qs], fan, **qb.env(qs))
+                finish(qs, len(fan), "fan", None, False)
     finally:
         bs.close()
-    return out
+    return qb.out
 
 
 def solve_SCP_roadmap_batch(TOSs, TOPs, K=1, fallback_fan=None, straight_first=False, roadmap_opts=None, solver="hip", max_iter=30,
@@ -1054,64 +1052,30 @@ def solve_SCP_roadmap_batch(TOSs, TOPs, K=1, fallback_fan=None, straight_first=F
     likewise), `source` ("roadmap", "fan", or None without a winner), `status` (the ROADMAP_STATUS code of the winning alternate's
     seed, of alternate 0 without a roadmap winner) and `SCPS`, the filled SCPSolution of the winner -- without one, of alternate 0.
     `roadmap_ms` is the GPU time of the seeding call.  TOSs[q].traj and TOSs[q].SCPS are set as by solve_SCP_batch."""
-    if len(TOSs) != len(TOPs) or not TOPs:
-        raise ValueError("solve_SCP_roadmap_batch!: need as many solutions as problems, at least one")
-    TOP0 = TOPs[0]
-    model, N = TOP0.PD.model, TOP0.N
-    n = model.x_dim
-    Q, K = len(TOPs), int(K)
-    for t in TOPs[1:]:
-        if type(t.PD.model) is not type(model) or t.N != N:
-            raise ValueError("solve_SCP_roadmap_batch!: all problems must share the model type and N")
-    fan = None
-    if fallback_fan is not None and fallback_fan is not False:
-        fan = default_fan(model.model_id) if fallback_fan is True else np.asarray(fallback_fan, float).reshape(-1, 2)
-    same_env = all(np.array_equal(t.PD.env.boxes, TOP0.PD.env.boxes) and np.array_equal(t.PD.env.spheres, TOP0.PD.env.spheres)
-                   for t in TOPs[1:])
-    sp, mp = _capi.default_params(model.model_id)
-    x0 = np.stack([t.PD.x_init for t in TOPs])
-    bounds = [_goal_bounds(t.PD.goal_set, n, t.tf_guess) for t in TOPs]
-    lo, hi = np.stack([b[0] for b in bounds]), np.stack([b[1] for b in bounds])
-    tf = np.array([t.tf_guess for t in TOPs])
-    cap = Q * K if fan is None else max(Q * K, len(fan))
-    bs = BatchSolver(model.model_id, N, cap, hist_cap=_hist_cap(max_iter), device=device, boxes=TOP0.PD.env.boxes,
-                     spheres=TOP0.PD.env.spheres, scp_params=sp, model_params=mp)
-    out = [None] * Q
+    qb = _QueryBatch("solve_SCP_roadmap_batch", TOSs, TOPs)
+    Q, K, out = qb.Q, int(K), qb.out
+    fan = _fallback_fan(qb.model.model_id, fallback_fan)
+    bs = qb.solver(Q * K if fan is None else max(Q * K, len(fan)), max_iter, force, device)
 
     def take(q, snap, b, per, winner, cost, source, status, ms):
-        SCPP = SCPProblem(TOPs[q])
-        SCPS = SCPSolution(SCPP, init_traj_straightline(TOPs[q]))
-        _fill_solution(SCPS, SCPP, snap, b, per)
-        TOSs[q].traj, TOSs[q].SCPS = SCPS.traj, SCPS
-        out[q] = dict(winner=int(winner), cost=float(cost), source=source, status=int(status), roadmap_ms=float(ms), SCPS=SCPS)
+        qb.take(q, snap, b, per, winner=int(winner), cost=float(cost), source=source, status=int(status), roadmap_ms=float(ms))
 
     try:
-        if not same_env:   # one set per query, repeated K times: query q reads that of problem q K
+        if not qb.same_env:   # one set per query, repeated K times: query q reads that of problem q K
             bs.set_env_batch([t.PD.env.boxes for t in TOPs for _ in range(K)], [t.PD.env.spheres for t in TOPs for _ in range(K)])
         opts = dict(roadmap_opts or {}, straight_first=int(bool(straight_first)))
-        bs.set_problems_roadmap(x0, lo, hi, tf, K, **opts)
+        bs.set_problems_roadmap(qb.x0, qb.lo, qb.hi, qb.tf, K, **opts)
         info, ms = bs.roadmap_info(), bs.last_roadmap_ms()
-        bs.solve(max_iter, force)
-        best = bs.select_best(K)
-        snap = _fetch(bs)
-        per = bs.last_solve_ms() * 1e-3 / Q
+        best, snap, per = qb.solved(K, Q)
         for q in range(Q):
             w = best["winner"][q]
             if w >= 0:
                 take(q, snap, best["winner_problem"][q], per, w, best["best_score"][q], "roadmap", info["status"][q * K + w], ms)
             else:
                 take(q, snap, q * K, per, -1, np.inf, None, info["status"][q * K], ms)
-        again = np.flatnonzero(best["winner"] < 0)
         if fan is not None:
-            Kf = len(fan)
-            for c in range(0, len(again), cap // Kf):
-                qs = again[c:c + cap // Kf]
-                env = {} if same_env else dict(boxes=[TOPs[q].PD.env.boxes for q in qs], spheres=[TOPs[q].PD.env.spheres for q in qs])
-                bs.set_problems_multistart(x0[qs], lo[qs], hi[qs], tf[qs], fan, **env)
-                bs.solve(max_iter, force)
-                best = bs.select_best(Kf)
-                snap = _fetch(bs)
-                per = bs.last_solve_ms() * 1e-3 / len(qs)
+            for qs in qb.chunks(np.flatnonzero(best["winner"] < 0), len(fan)):
+                best, snap, per = qb.fanned(qs, fan)
                 for i, q in enumerate(qs):
                     if best["winner"][i] >= 0:
                         take(q, snap, best["winner_problem"][i], per, best["winner"][i], best["best_score"][i], "fan", out[q]["status"], ms)
