@@ -22,7 +22,7 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_last_error", "gusto_set_params", "gusto_set_ipm_opts", "gusto_set_env", "gusto_set_env_batch", "gusto_set_schedule", "gusto_set_decomposition", "gusto_dev_workspace_bytes",
            "gusto_set_stream",
            "gusto_set_problems", "gusto_set_problems_dev", "gusto_solve", "gusto_solve_async", "gusto_set_active", "gusto_wait",
-           "gusto_last_solve_ms", "gusto_get_traj",
+           "gusto_last_solve_ms", "gusto_get_traj", "gusto_get_problems",
            "gusto_get_traj_dev", "gusto_gather_peer", "gusto_get_status", "gusto_get_dual", "gusto_get_history", "gusto_get_hist_cap",
            "gusto_set_trust_state", "gusto_subproblem", "gusto_default_shoot_opts", "gusto_shoot", "gusto_get_shoot",
            "gusto_default_trajopt_params", "gusto_create_trajopt", "gusto_set_trajopt_params", "gusto_solve_trajopt", "gusto_solve_trajopt_async",
@@ -43,6 +43,7 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_default_roadmap_opts", "gusto_set_problems_roadmap", "gusto_get_roadmap", "gusto_last_roadmap_ms",
            "gusto_default_tfsearch_opts", "gusto_tfsearch_begin", "gusto_tfsearch_update", "gusto_get_tfsearch", "gusto_get_tfsearch_dev",
            "gusto_last_tfsearch_ms",
+           "gusto_default_legs_opts", "gusto_legs_begin", "gusto_legs_advance", "gusto_get_legs", "gusto_get_legs_dev", "gusto_last_legs_ms",
            "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr", "gusto_dev_trajlib"]
 
 
@@ -218,6 +219,27 @@ class TfsearchReport(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in TFSEARCH_FIELDS]
 
 
+class LegsOpts(C.Structure):
+    """gusto_legs_opts: the mode"""
+    _fields_ = [("mode", C.c_int)]
+
+
+LEGS_MODE = {"auto": 0, "sequential": 1, "parallel": 2}   # GUSTO_LEGS_AUTO, GUSTO_LEGS_SEQUENTIAL, GUSTO_LEGS_PARALLEL
+LEGS_FLYING, LEGS_DONE, LEGS_FAILED = 1, 2, 4             # the status word
+# gusto_legs_report in the header's order: (field, dtype, shape as a function of (Bq, L, Nj, n, m))
+LEGS_FIELDS = tuple((k, np.int32, lambda Q, L, Nj, n, m: (Q,)) for k in ("status", "failed_leg", "n_done")) + \
+              (("J_total", np.float64, lambda Q, L, Nj, n, m: (Q,)),) + \
+              tuple((k, np.int32, lambda Q, L, Nj, n, m: (Q, L)) for k in ("iterations", "converged", "successful", "stop_reason")) + \
+              tuple((k, np.float64, lambda Q, L, Nj, n, m: (Q, L)) for k in ("J", "gap", "arrive")) + \
+              (("X", np.float64, lambda Q, L, Nj, n, m: (Q, Nj, n)), ("U", np.float64, lambda Q, L, Nj, n, m: (Q, Nj, m)),
+               ("t", np.float64, lambda Q, L, Nj, n, m: (Q, Nj)))
+
+
+class LegsReport(C.Structure):
+    """gusto_legs_report: caller-owned arrays"""
+    _fields_ = [(k, C.c_void_p) for k, _, _ in LEGS_FIELDS]
+
+
 class TrajLibOpts(C.Structure):
     """gusto_trajlib_opts"""
     _fields_ = [("w_init", C.c_double * MAXN), ("w_goal", C.c_double * MAXN), ("w_tf", C.c_double), ("lds_tile", C.c_int)]
@@ -264,7 +286,7 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(_ROOT, "include"), "-fPIC",
              "-Wno-unused-value", "-Wno-pass-failed"]
-    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "trajlib", "replan", "tighten", "roadmap", "tfsearch", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
+    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "trajlib", "replan", "tighten", "roadmap", "tfsearch", "legs", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
     bdir = os.path.join(_HERE, "build")
     os.makedirs(bdir, exist_ok=True)
 
@@ -321,6 +343,7 @@ def lib():
         L.gusto_set_active.argtypes = [vp, vp]
         L.gusto_last_solve_ms.argtypes = [vp, C.POINTER(C.c_double)]
         L.gusto_get_traj.argtypes = [vp, vp, vp]
+        L.gusto_get_problems.argtypes = [vp, vp, vp, vp, vp]
         L.gusto_get_traj_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         L.gusto_get_status.argtypes = [vp, vp, vp, vp, vp, vp]
         L.gusto_gather_peer.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, C.POINTER(ci)]
@@ -396,6 +419,12 @@ def lib():
         L.gusto_get_tfsearch.argtypes = [vp, C.POINTER(TfsearchReport), C.POINTER(ci), C.POINTER(ci)]
         L.gusto_get_tfsearch_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.gusto_last_tfsearch_ms.argtypes = [vp, C.POINTER(C.c_double)]
+        L.gusto_default_legs_opts.argtypes = [ci, C.POINTER(LegsOpts)]
+        L.gusto_legs_begin.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, C.POINTER(LegsOpts)]
+        L.gusto_legs_advance.argtypes = [vp, vp]
+        L.gusto_get_legs.argtypes = [vp, C.POINTER(LegsReport), C.POINTER(ci), C.POINTER(ci)]
+        L.gusto_get_legs_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.gusto_last_legs_ms.argtypes = [vp, C.POINTER(C.c_double)]
         L.gusto_default_trajopt_params.argtypes = [ci, C.POINTER(TrajOptParams)]
         L.gusto_create_trajopt.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci]
         L.gusto_set_trajopt_params.argtypes = [vp, C.POINTER(TrajOptParams)]
@@ -485,6 +514,27 @@ def default_tfsearch_opts(model):
     if rc:
         raise ValueError(f"gusto_default_tfsearch_opts({model}) -> {rc}")
     return o
+
+
+def default_legs_opts(model):
+    o = LegsOpts()
+    rc = lib().gusto_default_legs_opts(model, C.byref(o))
+    if rc:
+        raise ValueError(f"gusto_default_legs_opts({model}) -> {rc}")
+    return o
+
+
+def legs_mode(goal_lo, goal_hi, n_legs=None, mode="auto"):
+    """The mode a timeline is flown in, as LEGS_MODE names it: `mode` itself unless "auto", then "parallel" where every goal
+    before a query's last pins every entry (lo == hi, finite), else "sequential".  goal_lo, goal_hi [Bq, L, n]; n_legs [Bq]"""
+    if mode not in LEGS_MODE:
+        raise ValueError(f"legs: mode is 'auto', 'sequential' or 'parallel', not {mode!r}")
+    if mode != "auto":
+        return mode
+    lo, hi = np.asarray(goal_lo, float), np.asarray(goal_hi, float)
+    Bq, L = lo.shape[:2]
+    inner = np.arange(L)[None, :] < (np.full(Bq, L) if n_legs is None else np.asarray(n_legs).reshape(Bq))[:, None] - 1
+    return "parallel" if ((lo == hi) & np.isfinite(lo)).all(axis=2)[inner].all() else "sequential"
 
 
 def default_trajlib_opts(model):
@@ -736,6 +786,60 @@ class BatchSolver:
         """gusto_last_tfsearch_ms: GPU time of the last tfsearch_begin / tfsearch_update (copies and kernels)"""
         return self._last_ms("last_tfsearch_ms")
 
+    def legs_begin(self, x_init, goal_lo, goal_hi, t_goal, n_legs=None, mode="auto", boxes=None, spheres=None):
+        """gusto_legs_begin: Bq queries with a timeline of L goals each, goal_lo / goal_hi [Bq, L, n] at the times t_goal [Bq, L]
+        (n_legs [Bq]: the goals a query has, None = L), flown as legs.  mode "sequential": B = Bq, problem q is the query's current
+        leg; "parallel" (every interior goal a full point): B = Bq L, problem q L + l = leg l; "auto": legs_mode() decides here.
+        boxes / spheres: one keep-out set PER QUERY, repeated once per problem of the query into set_env_batch; None leaves the
+        environment as it is.  Then: solve(); legs_advance(); ... while it returns queries still flying.  Returns the mode taken."""
+        x_init, lo, hi, _, Bq = self._query_arrays(x_init, goal_lo, goal_hi)      # (the goals: [Bq L, n])
+        L = lo.shape[0] // Bq
+        t_goal = _arr(np.broadcast_to(np.asarray(t_goal, dtype=np.float64), (Bq, L)))
+        nl = None if n_legs is None else _arr(n_legs, np.int32).reshape(Bq)
+        mode = legs_mode(lo.reshape(Bq, L, self.n), hi.reshape(Bq, L, self.n), nl, mode)      # (never "auto": the library checks it)
+        o = LegsOpts(LEGS_MODE[mode])
+        self._chk(self.L.gusto_legs_begin(self.h, Bq, L, None if nl is None else nl.ctypes.data, x_init.ctypes.data, lo.ctypes.data,
+                                          hi.ctypes.data, t_goal.ctypes.data, C.byref(o)), "legs_begin")
+        K = L if mode == "parallel" else 1
+        self.B, self._tf, self._legs = Bq * K, None, (Bq, L)
+        self._env_per_query(K, boxes, spheres)
+        return mode
+
+    def legs_advance(self, eligible=None):
+        """gusto_legs_advance, after a solve: the solved legs into the joined buffers and the report, the next legs' seeds; the
+        problems of the finished queries become inactive.  eligible [B]: which problems count (None: the converged and successful
+        ones).  Returns the number of queries still flying."""
+        el = None if eligible is None else _arr(np.asarray(eligible).astype(bool), np.int32).reshape(self.B)
+        self._chk(self.L.gusto_legs_advance(self.h, None if el is None else el.ctypes.data), "legs_advance")
+        nf = C.c_int()
+        self._chk(self.L.gusto_get_legs(self.h, None, None, C.byref(nf)), "get_legs")
+        return nf.value
+
+    def legs_info(self):
+        """gusto_get_legs: a dict over the Bq queries of status (LEGS_FLYING / DONE / FAILED), failed_leg (-1: none), n_done,
+        J_total; over queries and legs [Bq, L] of iterations, converged, successful, stop_reason, J, gap, arrive; the joined X
+        [Bq, Nj, n], U [Bq, Nj, m], t [Bq, Nj] with Nj = L (N - 1) + 1; and the scalars round (advances so far) and n_flying"""
+        Bq, L = self._legs
+        out = {k: np.zeros(shape(Bq, L, L * (self.N - 1) + 1, self.n, self.m), dtype=t) for k, t, shape in LEGS_FIELDS}
+        rep = LegsReport(**{k: v.ctypes.data for k, v in out.items()})
+        rd, nf = C.c_int(), C.c_int()
+        self._chk(self.L.gusto_get_legs(self.h, C.byref(rep), C.byref(rd), C.byref(nf)), "get_legs")
+        out["round"], out["n_flying"] = rd.value, nf.value
+        return out
+
+    def legs_dev(self):
+        """gusto_get_legs_dev as zero-copy torch views: the joined X [Bq, Nj, n], U [Bq, Nj, m] and t [Bq, Nj]"""
+        Bq, L = self._legs
+        Nj = L * (self.N - 1) + 1
+        px, pu, pt = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._chk(self.L.gusto_get_legs_dev(self.h, C.byref(px), C.byref(pu), C.byref(pt)), "get_legs_dev")
+        return (_dev_view(px.value, (Bq, Nj, self.n), self.device), _dev_view(pu.value, (Bq, Nj, self.m), self.device),
+                _dev_view(pt.value, (Bq, Nj), self.device))
+
+    def last_legs_ms(self):
+        """gusto_last_legs_ms: GPU time of the last legs_begin / legs_advance (copies and kernels)"""
+        return self._last_ms("last_legs_ms")
+
     def set_problems_trajlib(self, lib, x_init, goal_lo, goal_hi, tf, K=1, tag=None, boxes=None, spheres=None):
         """gusto_set_problems_trajlib: Bq queries seeded from their K nearest entries of the TrajLib `lib` become the B = Bq K problems
         of the handle, problem q K + j = neighbour j of query q (a start without a neighbour is the straight line).  tag [Bq]: only
@@ -889,6 +993,12 @@ class BatchSolver:
         X, U = np.zeros((self.B, self.N, self.n)), np.zeros((self.B, self.N, self.m))
         self._chk(self.L.gusto_get_traj(self.h, X.ctypes.data, U.ctypes.data), "get_traj")
         return X, U
+
+    def problems(self):
+        """gusto_get_problems: (x_init, goal_lo, goal_hi [B, n], tf [B]) as the handle holds them"""
+        xi, lo, hi, tf = np.zeros((self.B, self.n)), np.zeros((self.B, self.n)), np.zeros((self.B, self.n)), np.zeros(self.B)
+        self._chk(self.L.gusto_get_problems(self.h, xi.ctypes.data, lo.ctypes.data, hi.ctypes.data, tf.ctypes.data), "get_problems")
+        return xi, lo, hi, tf
 
     def traj_dev(self):
         """gusto_get_traj_dev as zero-copy torch views of the handle's HBM buffers: X [B,N,n], U [B,N,m] (valid until

@@ -294,6 +294,7 @@ int gusto_problems_loaded(gusto_handle h, bool straight) {
     h->shoot.invalidate(); h->verify.invalidate(); h->tvlqr.invalidate(); h->simulate.invalidate(); h->lincov.invalidate();
     h->select.invalidate(); h->trajlib.invalidate(); h->replan.invalidate(); h->tighten.invalidate(); h->roadmap.invalidate();
     h->tfsearch.invalidate();   // (tfsearch.hip sets it again behind its own call)
+    h->legs.invalidate();       // (legs.hip likewise)
     h->n_active = -1;   // (gusto_set_active belongs to the problems it was set for)
     return GUSTO_OK;
 }
@@ -519,6 +520,17 @@ int gusto_get_status(gusto_handle h, int* iterations, int* converged, int* succe
         if (stop) stop[b] = st[(size_t)b * ST_NI + ST_STOP];
         if (ipm) ipm[b] = st[(size_t)b * ST_NI + ST_IPM];
     }
+    return GUSTO_OK;
+}
+
+// the problems the handle holds, as gusto_set_problems or a seeding stage left them (any pointer may be null)
+int gusto_get_problems(gusto_handle h, double* x_init, double* glo, double* ghi, double* tf) {
+    if (int rc = getter_enter(h, true)) return rc;
+    const size_t B = h->B, n = h->n;
+    if (x_init) HIPCHK(h, hipMemcpy(x_init, h->d_xinit, sizeof(double) * B * n, hipMemcpyDeviceToHost));
+    if (glo) HIPCHK(h, hipMemcpy(glo, h->d_glo, sizeof(double) * B * n, hipMemcpyDeviceToHost));
+    if (ghi) HIPCHK(h, hipMemcpy(ghi, h->d_ghi, sizeof(double) * B * n, hipMemcpyDeviceToHost));
+    if (tf) HIPCHK(h, hipMemcpy(tf, h->d_tf, sizeof(double) * B, hipMemcpyDeviceToHost));
     return GUSTO_OK;
 }
 

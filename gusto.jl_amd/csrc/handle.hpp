@@ -256,6 +256,24 @@ struct __attribute__((visibility("hidden"))) TfsearchState {
     void invalidate() { have = false; }
 };
 
+// Goal timeline (legs.hip), Bq queries x L legs: In the timeline as the kernels read it (x_init [Bq][n], goal_lo, goal_hi
+// [Bq][L][n], t_goal [Bq][L]) and NL the leg counts [Bq]; I: [4][Bq] status, failed_leg, n_done and the copy of the status words
+// an advance reads (it writes the others), then [4][Bq][L] iterations, converged, successful, stop_reason; D: [Bq] J_total, then
+// [3][Bq][L] J, gap, arrive; the joined X [Bq][Nj][n], U [Bq][Nj][m], T [Bq][Nj], Nj = L (N - 1) + 1; Xs the staging copy of the
+// handle's X a SEQUENTIAL advance reads; Elig [B] the copy of a caller's eligibility.  mode: SEQUENTIAL or PARALLEL, never AUTO;
+// round: advances so far; n_flying; solves_at: the handle's count of solve calls at the last begin or advance.  have:
+// gusto_problems_loaded ends it, legs.hip sets it again behind its own call
+struct __attribute__((visibility("hidden"))) LegsState {
+    DevBuf<double> In, D, X, U, T, Xs;
+    DevBuf<int> NL, I, Elig;
+    int Bq = 0, L = 0, mode = 0, round = 0, n_flying = 0;
+    unsigned long long solves_at = 0;
+    bool have = false;
+    DevEvent t0, t1;
+    double last_ms = 0.0;
+    void invalidate() { have = false; }
+};
+
 // The library itself: `count` of `cap` entries on `device`, entry e at row e of xi, c [cap][n], tf, tag [cap], X [cap][N][n], U
 // [cap][N][m].  The features are the F positive-weight terms of the distance, in its order of summation: term f has the weight
 // w[f] and reads entry fmap[f] & 15 of x_init (fmap[f] >> 4 == 0), of the goal centre (1) or tf (2).  Feat is feature-major,
@@ -328,7 +346,8 @@ struct gusto_handle_s {
     TightenState tighten;
     RoadmapState roadmap;
     TfsearchState tfsearch;
-    unsigned long long solves = 0;   // gusto_solve / gusto_solve_async calls that enqueued a launch (gusto_tfsearch_update asks for one)
+    LegsState legs;
+    unsigned long long solves = 0;   // gusto_solve / gusto_solve_async calls that enqueued a launch (gusto_tfsearch_update, gusto_legs_advance ask for one)
     std::string err;
 
     // (the buffers and events free themselves; the caller has made `device` current: gusto_destroy)

@@ -1,5 +1,5 @@
 // seed.hpp -- what a seeding stage starts from: the stages that turn Bq queries x K starts into the handle's B = Bq K problems
-// (multistart.hip, trajlib.hip, replan.hip, roadmap.hip, tfsearch.hip).  On the device: the straight line of
+// (multistart.hip, trajlib.hip, replan.hip, roadmap.hip, tfsearch.hip, legs.hip).  On the device: the straight line of
 // init_straightline_kernel (scp.hpp, which includes this header for it) as ONE expression, so that an unseeded start of every
 // stage is that kernel's output bit for bit, the decode of a thread into (problem, knot, query, start), and the knot-0 tail
 // that replicates a query into the handle's [B] arrays.  On the host, in the manner of post.hpp: the refusals every query entry
@@ -66,11 +66,17 @@ static inline gusto::SeedOut seed_out(gusto_handle h) { return {h->d_X, h->d_U, 
 
 // The arguments every query entry has: K in 1 .. k_max (k_name: the limit's name in the text), Bq >= 1 with Bq K problems that
 // fit the handle, no null array.  GUSTO_ERR_ARG and the text in *err, the first of these that applies.  No device, no handle.
+// cap_K > 0: an entry whose problems per query its own refusals decide (gusto_legs_begin: 1 or K) names the least count here,
+// Bq cap_K problems must fit, and checks the count it takes itself.
 static inline int query_args_host(int Bq, int K, int k_max, const char* k_name, int batch_cap, std::initializer_list<const void*> arrays,
-                                  const char* who, std::string* err) {
+                                  const char* who, std::string* err, int cap_K = 0) {
     const std::string w = std::string(who) + ": ";
     if (K < 1 || K > k_max) { *err = w + "K outside 1 .. " + k_name; return GUSTO_ERR_ARG; }
-    if (Bq < 1 || (long long)Bq * K > batch_cap) { *err = w + "need Bq >= 1 and Bq K <= batch_cap"; return GUSTO_ERR_ARG; }
+    if (cap_K > 0 && (Bq < 1 || (long long)Bq * cap_K > batch_cap)) {
+        *err = w + "need Bq >= 1 and at least " + std::to_string(cap_K) + " problem(s) per query within batch_cap";
+        return GUSTO_ERR_ARG;
+    }
+    if (cap_K <= 0 && (Bq < 1 || (long long)Bq * K > batch_cap)) { *err = w + "need Bq >= 1 and Bq K <= batch_cap"; return GUSTO_ERR_ARG; }
     for (const void* a : arrays)
         if (!a) { *err = w + "a null array"; return GUSTO_ERR_ARG; }
     return GUSTO_OK;
@@ -78,10 +84,10 @@ static inline int query_args_host(int Bq, int K, int k_max, const char* k_name, 
 // ... behind the handle's own refusals; then `own()`, the refusals of the entry itself (it answers a GUSTO_* code), and only
 // then the handle's device and its enqueued solve: nothing on the handle changes when a call is refused
 template <class Own> static int seed_enter(gusto_handle h, const char* who, int Bq, int K, int k_max, const char* k_name,
-                                           std::initializer_list<const void*> arrays, Own&& own) {
+                                           std::initializer_list<const void*> arrays, Own&& own, int cap_K = 0) {
     if (!h) return GUSTO_ERR_ARG;
     if (h->trajopt) return refuse(h, who, "TrajOpt handle (not supported)");
-    if (int rc = query_args_host(Bq, K, k_max, k_name, h->batch_cap, arrays, who, &h->err)) return rc;
+    if (int rc = query_args_host(Bq, K, k_max, k_name, h->batch_cap, arrays, who, &h->err, cap_K)) return rc;
     if (int rc = own()) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     return gusto_complete(h);

@@ -24,14 +24,19 @@ INDEX_MAPS = {
 }
 
 
-def _tree(model_id, X, U, tf, extra=None, column_major_reader=False, K=None, sigma=None):
+def _tree(model_id, X, U, tf, extra=None, column_major_reader=False, K=None, sigma=None, t=None):
     """X [.., N, n], U [.., N, m] in the C ABI layout -> the notebook's layout (state index first, knot second).
     column_major_reader: keep the C layout [.., N, n] -- HDF5 dimensions are row-major, so HDF5.jl / MATLAB present such
     a data set as n x N (x B), exactly the matrix the notebook wrote."""
     X, U = np.asarray(X, float), np.asarray(U, float)
     N = X.shape[-2]
     tf = np.asarray(tf, float)
-    t = np.linspace(0.0, 1.0, N) * tf[..., None] if tf.ndim else np.linspace(0.0, float(tf), N)
+    if t is not None:       # a joined goal timeline (host.solve_SCP_timeline_batch): the knot times, uniform per leg only
+        t = np.asarray(t, float)
+        if t.shape != X.shape[:-1]:
+            raise ValueError("export: t must be [.., N], the knots of X")
+    else:
+        t = np.linspace(0.0, 1.0, N) * tf[..., None] if tf.ndim else np.linspace(0.0, float(tf), N)
     names_x, names_u = INDEX_MAPS[model_id]
     sw = (lambda a: a) if column_major_reader else (lambda a: np.swapaxes(a, -1, -2))
     out = {"traj": {"x_traj": sw(X), "u_traj": sw(U), "t_traj": t},
@@ -62,12 +67,13 @@ def _flatten(tree, prefix=""):
     return flat
 
 
-def write(path, model_id, X, U, tf, status=None, K=None, sigma=None):
+def write(path, model_id, X, U, tf, status=None, K=None, sigma=None, t=None):
     """path ending in .h5 -> HDF5 (the notebook's container); .mat -> MATLAB v5 with nested structs; .npz -> flat keys
     'traj/x_traj', ...  K (optional): the tracking gains of BatchSolver.tvlqr, written as traj/k_traj [N-1][u_dim][x_dim] per
     trajectory next to x_traj, u_traj and t_traj.  sigma (optional): the standard deviations sigma_x of BatchSolver.lincov,
-    written as traj/sigma_traj [N][x_dim] next to k_traj.  Returns the tree that was written."""
-    tree = _tree(model_id, X, U, tf, status, column_major_reader=path.endswith((".h5", ".hdf5")), K=K, sigma=sigma)
+    written as traj/sigma_traj [N][x_dim] next to k_traj.  t (optional): the knot times [N] of a joined goal timeline, written as
+    traj/t_traj instead of the uniform grid 0 .. tf.  Returns the tree that was written."""
+    tree = _tree(model_id, X, U, tf, status, column_major_reader=path.endswith((".h5", ".hdf5")), K=K, sigma=sigma, t=t)
     if path.endswith((".h5", ".hdf5")):
         from . import h5lite
         h5lite.write_h5(path, tree)

@@ -977,6 +977,83 @@ def solve_SCP_min_time_batch(TOSs, TOPs, tf_lo, tf_hi, K=8, rounds=3, rtol=0.01,
     return out
 
 
+def _timeline_of(TOP):
+    """The goal timeline of a problem: every goal of its GoalSet with 0 < t_guess <= tf_guess, grouped by time into a list of
+    (T, lo, hi) in the order of time, lo / hi by the rules of _goal_bounds at that time (two goals at one time are one entry; a
+    coordinate no goal of that time names is +-inf).  Goals behind tf_guess are left out, as the plain solve leaves out all but
+    those at tf_guess.  The last entry must be at tf_guess itself: a final time without a goal is an error."""
+    gs, n, tf = TOP.PD.goal_set, TOP.PD.model.x_dim, TOP.tf_guess
+    times = sorted({g.t_guess for g in gs.goals if 0 < g.t_guess <= tf})
+    if not times or times[-1] != tf:
+        raise ValueError("_timeline_of: no goal at the final time tf_guess")
+    return [(T,) + _goal_bounds(gs, n, T) for T in times]
+
+
+def solve_SCP_timeline_batch(TOSs, TOPs, mode="auto", verify=False, solver="hip", max_iter=30, force=False, device=0):
+    """Every TOP is one planning QUERY whose GoalSet is flown as a timeline (gusto_legs_begin / gusto_legs_advance): every goal
+    time in (0, tf_guess] ends a LEG, an ordinary GuSTO problem from the previous junction to that goal in the time between the
+    two, and the solved legs are joined on the device.  solve_SCP and the other drivers ignore the goals before tf_guess, as the
+    reference does; this call is the one that flies them.  All TOPs share model and N; each may bring its own environment and its
+    own number of goals.
+
+    mode "sequential": one leg per query and round, the state a leg arrives in is the next leg's start (goals that leave a
+    junction partly free); "parallel": every leg of every query in one launch (every goal before the last must pin every
+    coordinate); "auto": parallel where allowed.  verify=True: BatchSolver.verify runs per round and a leg counts only if it is
+    also collision-free.
+
+    Returns one dict per query, also TOSs[q].timeline: status (_capi.LEGS_DONE / LEGS_FAILED), failed_leg (-1: none), n_done,
+    J_total, T [L_q] and per leg iterations, converged, successful, stop_reason, J, gap, arrive [L_q].  TOSs[q].traj is the joined
+    trajectory, X [n, L_q (N - 1) + 1] and U with the knot times in traj.t and Tf the last goal's time (rows behind a failed leg
+    are zeros); TOSs[q].SCPS the list of the filled SCPSolutions of the legs that were flown."""
+    qb = _QueryBatch("solve_SCP_timeline_batch", TOSs, TOPs)
+    Q, N, n = qb.Q, qb.N, qb.model.x_dim
+    lines = [_timeline_of(t) for t in TOPs]
+    nl = np.array([len(tl) for tl in lines], np.int32)
+    L = int(nl.max())
+    T, lo, hi = np.zeros((Q, L)), np.full((Q, L, n), -np.inf), np.full((Q, L, n), np.inf)
+    for q, tl in enumerate(lines):
+        for l, (t, a, b) in enumerate(tl):
+            T[q, l], lo[q, l], hi[q, l] = t, a, b
+    mode = _capi.legs_mode(lo, hi, nl, mode)
+    K = L if mode == "parallel" else 1
+    bs = qb.solver(Q * K, max_iter, force, device)
+    scps = [[] for _ in range(Q)]
+    try:
+        bs.legs_begin(qb.x0, lo, hi, T, n_legs=nl, mode=mode, **qb.env())
+        flying = np.ones(Q, bool)
+        rnd = 0
+        while flying.any():
+            bs.solve(max_iter, force)
+            snap = _fetch(bs)
+            per = bs.last_solve_ms() * 1e-3 / (int(flying.sum()) if K == 1 else int(nl.sum()))   # (seconds per leg solved)
+            ok = None
+            if verify:
+                ok = snap["st"]["converged"] & snap["st"]["successful"] & (bs.verify()["collision_free"] != 0)
+            for q in np.flatnonzero(flying):
+                for l in (range(nl[q]) if K > 1 else [rnd]):
+                    SCPP = SCPProblem(TOPs[q])
+                    SCPP.tf_guess = float(T[q, l] - (T[q, l - 1] if l else 0.0))
+                    SCPS = SCPSolution(SCPP, Trajectory(np.zeros((n, N)), np.zeros((qb.model.u_dim, N)), SCPP.tf_guess))
+                    _fill_solution(SCPS, SCPP, snap, q * K + (l if K > 1 else 0), per)
+                    scps[q].append(SCPS)
+            bs.legs_advance(ok)
+            info = bs.legs_info()
+            flying = info["status"] == _capi.LEGS_FLYING
+            rnd += 1
+        for q in range(Q):
+            Lq, Nq = int(nl[q]), int(nl[q]) * (N - 1) + 1
+            traj = Trajectory(info["X"][q, :Nq].T.copy(), info["U"][q, :Nq].T.copy(), T[q, Lq - 1])
+            traj.t = info["t"][q, :Nq].copy()
+            rep = {k: (int if k != "J_total" else float)(info[k][q]) for k in ("status", "failed_leg", "n_done", "J_total")}
+            rep.update({k: info[k][q, :Lq].copy() for k in ("iterations", "converged", "successful", "stop_reason", "J", "gap", "arrive")})
+            rep["T"] = T[q, :Lq].copy()
+            TOSs[q].traj, TOSs[q].SCPS, TOSs[q].timeline = traj, scps[q], rep
+            qb.out[q] = rep
+    finally:
+        bs.close()
+    return qb.out
+
+
 class TrajLib(_capi.TrajLib):
     """A device-resident library of solved trajectories (gusto_trajlib): TrajLib(model_id, N, cap, device=0, w_init=None,
     w_goal=None, w_tf=None).  add_from(solver, mask=None, tag=None) appends the converged and successful (or the masked) problems

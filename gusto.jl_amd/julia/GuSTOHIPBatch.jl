@@ -1401,3 +1401,134 @@ function solve_SCP_min_time_batch!(TOSs::Vector, TOPs::Vector, tf_lo, tf_hi; K=8
   ccall((:gusto_destroy, libgusto_hip), Cint, (Ptr{Cvoid},), h)
   [(tf = info.tf_best[q], lo = info.lo[q], hi = info.hi[q], status = Int(info.status[q]), J = info.J_best[q]) for q in 1:Q]
 end
+
+# ---- goal timeline: the goals of a query before its final time, flown as legs and joined on the device (csrc/legs.hip) ---------
+# A GoalSet is keyed by time, but every goal row function hard-codes knot N: a goal before the final time is carried and ignored
+# by the solve.  The timeline runs around gusto_solve: every goal interval is a leg, an ordinary problem from the previous
+# junction to that goal in the time between the two; the report and the joined trajectories stay on the device.
+# include/gusto_hip.h states the definitions.  Mirrors gusto.jl_amd/host.py: BatchSolver.legs_begin / legs_advance / legs_info,
+# solve_SCP_timeline_batch.  This wrapper has not been run.
+const GUSTO_LEGS_AUTO = 0
+const GUSTO_LEGS_SEQUENTIAL = 1
+const GUSTO_LEGS_PARALLEL = 2
+const GUSTO_LEGS_FLYING = 1
+const GUSTO_LEGS_DONE = 2
+const GUSTO_LEGS_FAILED = 4
+struct GustoLegsOpts      # gusto_legs_opts
+  mode::Cint
+end
+mutable struct GustoLegsReport      # gusto_legs_report
+  status::Ptr{Cint}; failed_leg::Ptr{Cint}; n_done::Ptr{Cint}
+  J_total::Ptr{Cdouble}
+  iterations::Ptr{Cint}; converged::Ptr{Cint}; successful::Ptr{Cint}; stop_reason::Ptr{Cint}
+  J::Ptr{Cdouble}; gap::Ptr{Cdouble}; arrive::Ptr{Cdouble}
+  X::Ptr{Cdouble}; U::Ptr{Cdouble}; t::Ptr{Cdouble}
+end
+
+# every goal of the GoalSet with 0 < t_guess <= tf_guess, grouped by time: [(T, lo, hi)] in the order of time, lo / hi by the rules
+# of gusto_goal_bounds at that time.  A final time without a goal is an error.
+function gusto_timeline_of(TOP)
+  n, tf = TOP.PD.model.x_dim, TOP.tf_guess
+  times = sort(unique([t for t in keys(TOP.PD.goal_set.goals) if 0 < t <= tf]))
+  (isempty(times) || times[end] != tf) && error("gusto_timeline_of: no goal at the final time tf_guess")
+  [(T, gusto_goal_bounds(TOP.PD.goal_set, n, T)...) for T in times]
+end
+
+# Bq queries (columns of x0) with L goals each -- lo, hi [n, L, Bq] at the times T [L, Bq], n_legs [Bq] of them per query -- are
+# flown as legs on the handle h.  mode: :auto, :sequential (B = Bq, problem q is the query's current leg) or :parallel (B = Bq L,
+# problem (q - 1) L + l = leg l of query q; every goal before the last must pin every coordinate).
+function legs_begin!(h::Ptr{Cvoid}, model_id::Integer, x0::Matrix{Float64}, lo::Array{Float64,3}, hi::Array{Float64,3}, T::Matrix{Float64};
+                     n_legs=nothing, mode=:auto)
+  Bq, L = size(x0, 2), size(T, 1)
+  d = Ref(GustoLegsOpts(0))
+  gusto_check(ccall((:gusto_default_legs_opts, libgusto_hip), Cint, (Cint, Ref{GustoLegsOpts}), model_id, d), h, "default_legs_opts")
+  o = GustoLegsOpts(mode == :sequential ? GUSTO_LEGS_SEQUENTIAL : mode == :parallel ? GUSTO_LEGS_PARALLEL : d[].mode)
+  nl = n_legs === nothing ? C_NULL : Cint.(n_legs)
+  gusto_check(ccall((:gusto_legs_begin, libgusto_hip), Cint,
+                    (Ptr{Cvoid}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{GustoLegsOpts}),
+                    h, Bq, L, nl, x0, lo, hi, T, o), h, "legs_begin")
+  nothing
+end
+
+# After a solve: the solved legs into the joined buffers and the report, the next legs' seeds; the problems of the finished
+# queries become inactive.  eligible: nothing (converged and successful) or a Bool / integer vector [B].  Returns the number of
+# queries still flying.
+function legs_advance!(h::Ptr{Cvoid}; eligible=nothing)
+  el = eligible === nothing ? C_NULL : Cint.(eligible .!= 0)
+  gusto_check(ccall((:gusto_legs_advance, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}), h, el), h, "legs_advance")
+  nf = Ref{Cint}(0)
+  gusto_check(ccall((:gusto_get_legs, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cint}, Ref{Cint}), h, C_NULL, C_NULL, nf), h, "get_legs")
+  Int(nf[])
+end
+
+# The report of the timeline on h: per query status, failed_leg, n_done, J_total; per leg [L, Bq] iterations, converged,
+# successful, stop_reason, J, gap, arrive; the joined X [n, Nj, Bq], U [m, Nj, Bq], t [Nj, Bq] with Nj = L (N - 1) + 1; round,
+# n_flying and the GPU time of the last begin or advance
+function legs_info(h::Ptr{Cvoid}, Bq::Integer, L::Integer, N::Integer, n::Integer, m::Integer)
+  Nj = L * (N - 1) + 1
+  status, failed, ndone, Jt = zeros(Cint, Bq), zeros(Cint, Bq), zeros(Cint, Bq), zeros(Bq)
+  its, conv, succ, stop = zeros(Cint, L, Bq), zeros(Cint, L, Bq), zeros(Cint, L, Bq), zeros(Cint, L, Bq)
+  J, gap, arrive = zeros(L, Bq), zeros(L, Bq), zeros(L, Bq)
+  X, U, t = zeros(n, Nj, Bq), zeros(m, Nj, Bq), zeros(Nj, Bq)
+  rd, nf = Ref{Cint}(0), Ref{Cint}(0)
+  GC.@preserve status failed ndone Jt its conv succ stop J gap arrive X U t begin
+    rep = GustoLegsReport(pointer(status), pointer(failed), pointer(ndone), pointer(Jt), pointer(its), pointer(conv), pointer(succ),
+                          pointer(stop), pointer(J), pointer(gap), pointer(arrive), pointer(X), pointer(U), pointer(t))
+    gusto_check(ccall((:gusto_get_legs, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoLegsReport}, Ref{Cint}, Ref{Cint}), h, rep, rd, nf), h, "get_legs")
+  end
+  ms = Ref{Cdouble}(0.)
+  gusto_check(ccall((:gusto_last_legs_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, ms), h, "last_legs_ms")
+  (status = status, failed_leg = failed, n_done = ndone, J_total = Jt, iterations = its, converged = conv, successful = succ,
+   stop_reason = stop, J = J, gap = gap, arrive = arrive, X = X, U = U, t = t, round = Int(rd[]), n_flying = Int(nf[]), ms = ms[])
+end
+
+# Device pointers to the joined X [n, Nj, Bq], U [m, Nj, Bq] and t [Nj, Bq]
+function legs_dev(h::Ptr{Cvoid})
+  px, pu, pt = Ref{Ptr{Cdouble}}(C_NULL), Ref{Ptr{Cdouble}}(C_NULL), Ref{Ptr{Cdouble}}(C_NULL)
+  gusto_check(ccall((:gusto_get_legs_dev, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Ptr{Cdouble}}, Ref{Ptr{Cdouble}}, Ref{Ptr{Cdouble}}),
+                    h, px, pu, pt), h, "get_legs_dev")
+  (X = px[], U = pu[], t = pt[])
+end
+
+# Every TOP is one planning QUERY whose GoalSet is flown as a timeline: every goal time in (0, tf_guess] ends a leg.  mode as
+# legs_begin!.  Returns per query (status, failed_leg, n_done, J_total, T, gap, arrive); TOSs[q].traj is the joined trajectory with
+# Tf the last goal's time; its knot times are the `t` of the returned tuple.  All TOPs share model, N and the environment.  solve_SCP! keeps ignoring the goals before tf_guess, as the reference does.
+function solve_SCP_timeline_batch!(TOSs::Vector, TOPs::Vector; mode=:auto, max_iter=30, force=false, device=0)
+  TOP0 = TOPs[1]; model, N = TOP0.PD.model, TOP0.N
+  n, m, Q = model.x_dim, model.u_dim, length(TOPs)
+  all(T -> typeof(T.PD.model) == typeof(model) && T.N == N && T.PD.env === TOP0.PD.env, TOPs) ||
+    error("solve_SCP_timeline_batch!: all problems must share the model type, N and the environment")
+  lines = [gusto_timeline_of(T) for T in TOPs]
+  nl = length.(lines); L = maximum(nl)
+  T, lo, hi = zeros(L, Q), fill(-Inf, n, L, Q), fill(Inf, n, L, Q)
+  for q in 1:Q, (l, (t, a, b)) in enumerate(lines[q])
+    T[l, q] = t; lo[:, l, q] = a; hi[:, l, q] = b
+  end
+  alg0 = SCPParam_GuSTO(model)
+  sp = GustoScpParams(alg0.Δ0, alg0.ω0, alg0.ω_max, alg0.ε, alg0.ρ0, alg0.ρ1, alg0.β_succ, alg0.β_fail, alg0.γ_fail,
+                      SCPParam(model, TOP0.fixed_final_time).convergence_threshold)
+  href = Ref{Ptr{Cvoid}}(C_NULL)
+  gusto_check(ccall((:gusto_create, libgusto_hip), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Cint),
+                    href, gusto_model_id(model), N, Q * L, gusto_hist_cap(max_iter), device), href[], "create")
+  h = href[]
+  gusto_check(ccall((:gusto_set_params, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoScpParams}, Ref{GustoModelParams}),
+                    h, sp, gusto_model_params(TOP0.PD.robot, model)), h, "set_params")
+  boxes, spheres = gusto_env_tables(TOP0.PD.env)
+  gusto_check(ccall((:gusto_set_env, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+                    h, length(boxes) ÷ 6, boxes, length(spheres) ÷ 4, spheres), h, "set_env")
+  x0 = hcat((Float64.(T.PD.x_init) for T in TOPs)...)
+  legs_begin!(h, gusto_model_id(model), x0, lo, hi, T; n_legs=nl, mode=mode)
+  flying = Q
+  while flying > 0
+    gusto_check(ccall((:gusto_solve, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Cint), h, max_iter, force), h, "solve")
+    flying = legs_advance!(h)
+  end
+  info = legs_info(h, Q, L, N, n, m)
+  ccall((:gusto_destroy, libgusto_hip), Cint, (Ptr{Cvoid},), h)
+  for q in 1:Q
+    Nq = nl[q] * (N - 1) + 1
+    TOSs[q].traj = Trajectory(info.X[:, 1:Nq, q], info.U[:, 1:Nq, q], T[nl[q], q])
+  end
+  [(status = Int(info.status[q]), failed_leg = Int(info.failed_leg[q]), n_done = Int(info.n_done[q]), J_total = info.J_total[q],
+    T = T[1:nl[q], q], t = info.t[1:nl[q] * (N - 1) + 1, q], gap = info.gap[1:nl[q], q], arrive = info.arrive[1:nl[q], q]) for q in 1:Q]
+end

@@ -182,6 +182,9 @@ int gusto_last_solve_ms(gusto_handle h, double* ms);
 
 /* SCPS.traj (X,U) -- TOS.traj aliases it (traj_opt.jl:58) */
 int gusto_get_traj(gusto_handle h, double* X, double* U);
+/* The problems the handle holds, as gusto_set_problems* or a seeding stage left them: x_init, goal_lo, goal_hi [B][x_dim], tf [B]
+ * (any pointer may be NULL) */
+int gusto_get_problems(gusto_handle h, double* x_init, double* goal_lo, double* goal_hi, double* tf);
 int gusto_get_traj_dev(gusto_handle h, const double** X_dev, const double** U_dev);
 /* Final gather of a multi-GPU run from ONE host process (one handle per GPU, shards enqueued with gusto_solve_async): completes
  * every source's solve and copies the shards, in the order of `src`, into buffers on the GPU of `dst` -- one direct peer copy
@@ -1018,6 +1021,87 @@ int gusto_get_tfsearch(gusto_handle h, gusto_tfsearch_report* out, int* round, i
 int gusto_get_tfsearch_dev(gusto_handle h, const double** X_dev, const double** U_dev, const double** tf_best_dev);
 /* GPU time of the last begin or update (copies and kernels), from HIP events on the handle's stream */
 int gusto_last_tfsearch_ms(gusto_handle h, double* ms);
+
+/* Goal timeline (csrc/legs.hip): the goals of a query before its final time, flown as legs and joined on the device.  A GoalSet
+ * of the reference is keyed by time and Goal(params, t_guess, ...) may sit at any t_guess (src/goals.jl:18-30), but every goal
+ * row function hard-codes knot N, so a goal before the final time is carried and ignored by the solve -- there and in
+ * gusto_solve.  No solve kernel changes here either: the timeline runs around gusto_solve,
+ *     gusto_legs_begin; repeat { gusto_solve; gusto_legs_advance; } while n_flying > 0; gusto_get_legs.
+ * Every goal interval is a LEG, an ordinary problem: start at the previous junction, goal rows of that goal, tf the interval.
+ * The definitions:
+ * Timeline.  Query q has L_q = n_legs[q] goals (NULL: L for every query), 1 <= L_q <= L <= GUSTO_MAX_STARTS, at the times
+ *   T_0 < T_1 < ... < T_{L_q - 1}, finite, T_0 > 0 (t_goal [Bq][L]; entries behind L_q are not read).  Goal l is goal_lo/hi[q][l]
+ *   ([Bq][L][x_dim]) under the rules of gusto_set_problems: lo == hi a point row, lo != hi a box row on every finite side, +-Inf
+ *   no goal on that side.  Leg l has tf_l = T_l - T_{l-1}, one rounded difference, and tf_0 = T_0 itself.  All arrays are HOST.
+ * Modes (gusto_legs_opts.mode).  GUSTO_LEGS_SEQUENTIAL: the handle holds B = Bq problems, problem q is the query's current leg;
+ *   round r (the number of advances so far) solves leg r of every query that still flies.  The state a leg arrives in is the
+ *   state the next leg starts from: the mode for junctions a goal leaves partly free (position-only waypoints).  It is greedy:
+ *   leg l arrives as is cheapest for itself, the state at a partly free junction is not optimised across legs.
+ *   GUSTO_LEGS_PARALLEL: the multi-start layout, B = Bq L, problem b = q L + l is leg l; one launch solves all legs and one
+ *   advance joins them.  Refused (GUSTO_ERR_ARG) unless every interior goal (l < L_q - 1) of every query pins every entry, lo ==
+ *   hi finite: leg l + 1 then starts from that point.  Problems l >= L_q of a ragged query are the straight line of the query's
+ *   last leg, and inactive (gusto_set_active).  GUSTO_LEGS_AUTO (the default): PARALLEL where allowed, else SEQUENTIAL.
+ *   gusto_set_env_batch needs B sets as laid out: Bq for SEQUENTIAL, Bq L for PARALLEL.
+ * Leg problem: x_init the junction (x_init[q] for leg 0), the goal goal l, tf = tf_l.  Its seed is the straight line with U0 =
+ *   0, bit for bit what gusto_set_problems with X0 = NULL writes for those inputs.  After begin, and after every advance,
+ *   everything gusto_set_problems does has happened: history reset, stages and selection invalidated, every problem active but
+ *   those named inactive here.
+ * Advance, SEQUENTIAL, after a solve of round r.  ok_q is eligible[q] != 0 (a HOST array [B]) or, for NULL, converged &&
+ *   successful as gusto_get_status reports them.  For every flying query: (1) leg r is STORED: its X, U go to the joined
+ *   buffers, its iterations, converged, successful, stop reason and last J_true (NaN when it has none) to the report; (2) ok_q
+ *   and r + 1 < L_q: the junction is X_r[N-1] as stored, copied not recomputed; it becomes x_init of leg r + 1, whose seed is
+ *   written, and the query keeps flying; (3) ok_q and r + 1 == L_q: status DONE; (4) !ok_q: status FAILED, failed_leg = r, no
+ *   later leg is run.  A finished query's problem becomes the straight line of the leg it flew last and is inactive in later
+ *   solves; later advances do not touch its report.
+ * Advance, PARALLEL: once, eligible [B] over the problems.  Every leg l < L_q is stored; failed_leg is the first leg that is
+ *   not ok, else the status is DONE.  Every problem becomes the straight line of its own leg and is inactive afterwards.
+ * Join.  Nj = L (N - 1) + 1 knots per query; rows behind the last stored leg are zeros.  Stored leg l fills the knots l (N - 1)
+ *   ... (l + 1)(N - 1).  X at a junction knot is leg l's last knot; U there is leg l + 1's U[0] -- leg l's U[N-1] is the
+ *   reference's free u_N and is dropped --, and the last knot of the last stored leg takes that leg's U[N-1].
+ *   t[l (N - 1) + k] = T_{l-1} + k (tf_l / (N - 1)) with T_{-1} = 0: one division, product and sum in IEEE double, nothing fused,
+ *   and T_l itself for k = N - 1.  Everything else is copies.
+ * Report, per query: status (one of the bits GUSTO_LEGS_FLYING / DONE / FAILED), failed_leg (-1: none), n_done (the legs that
+ *   arrived: stored and ok, before the first that is not), J_total (the sum of the stored legs' J, in leg order).  Per query and
+ *   leg [Bq][L] (zeros where no leg is stored): iterations, converged, successful, stop_reason, J; gap = max_i |X_l[0][i] -
+ *   junction[i]|, the residual of the hard init row as the solve left it, and 0 for leg 0; arrive = the largest violation of goal
+ *   l's rows at the leg's last knot: |x - lo| on point entries, max(lo - x, x - hi, 0) on the others.  And the joined X, U, t.
+ * GUSTO_ERR_ARG, nothing launched, the handle left as it was: a TrajOpt handle, L outside 1 .. GUSTO_MAX_STARTS, an n_legs[q]
+ *   outside 1 .. L, Bq < 1, B > batch_cap, a null x_init, goal or t_goal, times not finite or not strictly increasing from > 0, a
+ *   non-finite x_init, an unknown mode, PARALLEL with an interior goal that is not a full point.  GUSTO_ERR_STATE: advance or a
+ *   getter before begin or after any other gusto_set_problems* call on the handle; advance with n_flying == 0; advance with
+ *   eligible = NULL and no gusto_solve / gusto_solve_async since the last begin or advance.
+ * Kernels: begin with a thread per (problem, knot); advance with a thread per (leg in flight, knot), which copies the knot into
+ *   the joined buffers and writes the next leg's seed knot -- the thread of knot 0 also the leg's report row and the problem's
+ *   inputs --, behind one wavefront per leg that forms gap and arrive; on the handle's stream, timed with events.  The rows a
+ *   SEQUENTIAL advance reads are a staging copy: it writes the problem it reads.  An advance reads the Bq status words back,
+ *   nothing else.  No atomics, nothing crosses a query: a query's report, joined buffers and seeds are the same bit for bit in
+ *   any batch.  Out of scope: TrajOpt handles, a different N per leg, post-solve stages on the joined trajectory (they run per
+ *   leg on the handle). */
+enum { GUSTO_LEGS_AUTO = 0, GUSTO_LEGS_SEQUENTIAL = 1, GUSTO_LEGS_PARALLEL = 2 };
+#define GUSTO_LEGS_FLYING 1
+#define GUSTO_LEGS_DONE 2
+#define GUSTO_LEGS_FAILED 4
+typedef struct {
+    int mode;              /* GUSTO_LEGS_*; default AUTO */
+} gusto_legs_opts;
+int gusto_default_legs_opts(int model_id, gusto_legs_opts* o);
+int gusto_legs_begin(gusto_handle h, int Bq, int L, const int* n_legs /* [Bq] or NULL = L */, const double* x_init /* [Bq][x_dim] */,
+                     const double* goal_lo, const double* goal_hi /* [Bq][L][x_dim] */, const double* t_goal /* [Bq][L] */,
+                     const gusto_legs_opts* o /* NULL: the defaults */);
+int gusto_legs_advance(gusto_handle h, const int* eligible /* [B] HOST, or NULL = converged && successful */);
+typedef struct {
+    int *status, *failed_leg, *n_done;                        /* [Bq] */
+    double *J_total;                                          /* [Bq] */
+    int *iterations, *converged, *successful, *stop_reason;   /* [Bq][L] */
+    double *J, *gap, *arrive;                                 /* [Bq][L] */
+    double *X, *U, *t;                                        /* [Bq][Nj][x_dim], [Bq][Nj][u_dim], [Bq][Nj], Nj = L (N - 1) + 1 */
+} gusto_legs_report;                                          /* caller-owned, any pointer may be NULL */
+/* The timeline's report; *round the number of advances so far, *n_flying the queries still flying (either may be NULL) */
+int gusto_get_legs(gusto_handle h, gusto_legs_report* out, int* round, int* n_flying);
+/* Device pointers to the joined X [Bq][Nj][x_dim], U [Bq][Nj][u_dim] and t [Bq][Nj], valid until the next begin */
+int gusto_get_legs_dev(gusto_handle h, const double** X_dev, const double** U_dev, const double** t_dev);
+/* GPU time of the last begin or advance (copies and kernels), from HIP events on the handle's stream */
+int gusto_last_legs_ms(gusto_handle h, double* ms);
 
 /* One convex subproblem per problem (what scp_gusto.jl:82-104 builds and solves in one trip), linearised at
  * (Xp,Up)[b] with the given Delta/omega/obstacle_toggle_distance[b].  Used by the parity tests.
