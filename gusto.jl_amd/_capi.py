@@ -44,6 +44,8 @@ SYMBOLS = ["gusto_default_params", "gusto_default_ipm_opts", "gusto_model_dims",
            "gusto_default_tfsearch_opts", "gusto_tfsearch_begin", "gusto_tfsearch_update", "gusto_get_tfsearch", "gusto_get_tfsearch_dev",
            "gusto_last_tfsearch_ms",
            "gusto_default_legs_opts", "gusto_legs_begin", "gusto_legs_advance", "gusto_get_legs", "gusto_get_legs_dev", "gusto_last_legs_ms",
+           "gusto_default_fleet_opts", "gusto_fleet_schedule", "gusto_fleet_separation", "gusto_get_fleet", "gusto_get_fleet_tracks",
+           "gusto_last_fleet_ms",
            "gusto_dev_get_prof", "gusto_dev_launch_info", "gusto_dev_tvlqr", "gusto_dev_trajlib"]
 
 
@@ -255,6 +257,29 @@ class VerifyReport(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _ in VERIFY_FIELDS]
 
 
+class FleetOpts(C.Structure):
+    """gusto_fleet_opts: the fleet clock, the margin, the candidate delays, the clock cap, component pairs, pruning"""
+    _fields_ = [("dt_clock", C.c_double), ("margin", C.c_double), ("n_delays", C.c_int), ("delay_stride", C.c_int),
+                ("clock_cap", C.c_int), ("components", C.c_int), ("prune", C.c_int)]
+
+
+FLEET_NO_PLAN, FLEET_SCHEDULED, FLEET_BLOCKED = 0, 1, 2   # GUSTO_FLEET_*
+# gusto_fleet_report in the header's order: (field, dtype, shape as a function of (F, R))
+FLEET_FIELDS = (("status", np.int32, lambda F, R: (F * R,)), ("delay_steps", np.int32, lambda F, R: (F * R,)),
+                ("delay", np.float64, lambda F, R: (F * R,)), ("blocker", np.int32, lambda F, R: (F * R,)),
+                ("min_sep", np.float64, lambda F, R: (F * R,)), ("partner", np.int32, lambda F, R: (F * R,)),
+                ("step", np.int32, lambda F, R: (F * R,)), ("pair_min_sep", np.float64, lambda F, R: (F, R, R)),
+                ("pair_step", np.int32, lambda F, R: (F, R, R)), ("n_scheduled", np.int32, lambda F, R: (F,)),
+                ("n_blocked", np.int32, lambda F, R: (F,)), ("n_conflicts", np.int32, lambda F, R: (F,)),
+                ("fleet_min_sep", np.float64, lambda F, R: (F,)), ("makespan_steps", np.int32, lambda F, R: (F,)),
+                ("stage_ms", np.float64, lambda F, R: (3,)))
+
+
+class FleetReport(C.Structure):
+    """gusto_fleet_report: caller-owned arrays"""
+    _fields_ = [(k, C.c_void_p) for k, _, _ in FLEET_FIELDS]
+
+
 class TrajOptParams(C.Structure):
     """gusto_trajopt_params = SCPParam_TrajOpt (scp_trajopt.jl:3-30)"""
     _fields_ = [(k, C.c_double) for k in ("mu0", "s0", "c", "tau_plus", "tau_minus", "k", "ftol", "xtol", "ctol")] + \
@@ -286,7 +311,7 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(_ROOT, "include"), "-fPIC",
              "-Wno-unused-value", "-Wno-pass-failed"]
-    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "trajlib", "replan", "tighten", "roadmap", "tfsearch", "legs", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
+    units = ["gusto_hip", "shoot", "verify", "tvlqr", "simulate", "lincov", "multistart", "trajlib", "replan", "tighten", "roadmap", "tfsearch", "legs", "fleet", "model_0", "model_1", "model_2", "model_3", "model_4", "model_5", "model_6"]
     bdir = os.path.join(_HERE, "build")
     os.makedirs(bdir, exist_ok=True)
 
@@ -425,6 +450,12 @@ def lib():
         L.gusto_get_legs.argtypes = [vp, C.POINTER(LegsReport), C.POINTER(ci), C.POINTER(ci)]
         L.gusto_get_legs_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.gusto_last_legs_ms.argtypes = [vp, C.POINTER(C.c_double)]
+        L.gusto_default_fleet_opts.argtypes = [ci, C.POINTER(FleetOpts)]
+        L.gusto_fleet_schedule.argtypes = [vp, ci, vp, vp, C.POINTER(FleetOpts)]
+        L.gusto_fleet_separation.argtypes = [vp, ci, vp, C.POINTER(FleetOpts)]
+        L.gusto_get_fleet.argtypes = [vp, C.POINTER(FleetReport), C.POINTER(ci), C.POINTER(ci)]
+        L.gusto_get_fleet_tracks.argtypes = [vp, vp, vp, C.POINTER(ci)]
+        L.gusto_last_fleet_ms.argtypes = [vp, C.POINTER(C.c_double)]
         L.gusto_default_trajopt_params.argtypes = [ci, C.POINTER(TrajOptParams)]
         L.gusto_create_trajopt.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci]
         L.gusto_set_trajopt_params.argtypes = [vp, C.POINTER(TrajOptParams)]
@@ -524,6 +555,14 @@ def default_legs_opts(model):
     return o
 
 
+def default_fleet_opts(model):
+    o = FleetOpts()
+    rc = lib().gusto_default_fleet_opts(model, C.byref(o))
+    if rc:
+        raise ValueError(f"gusto_default_fleet_opts({model}) -> {rc}")
+    return o
+
+
 def legs_mode(goal_lo, goal_hi, n_legs=None, mode="auto"):
     """The mode a timeline is flown in, as LEGS_MODE names it: `mode` itself unless "auto", then "parallel" where every goal
     before a query's last pins every entry (lo == hi, finite), else "sequential".  goal_lo, goal_hi [Bq, L, n]; n_legs [Bq]"""
@@ -604,6 +643,8 @@ class BatchSolver:
         """gusto_set_params: the SCP and / or the robot and model parameters of every later call on this handle (None: kept)"""
         self._chk(self.L.gusto_set_params(self.h, C.byref(scp_params) if scp_params is not None else None,
                                           C.byref(model_params) if model_params is not None else None), "set_params")
+        if model_params is not None:
+            self._model_params = model_params   # (fleet_opts: the default margin is the handle's clearance)
 
     def close(self):
         if getattr(self, "h", None) and self.h:
@@ -839,6 +880,69 @@ class BatchSolver:
     def last_legs_ms(self):
         """gusto_last_legs_ms: GPU time of the last legs_begin / legs_advance (copies and kernels)"""
         return self._last_ms("last_legs_ms")
+
+    def fleet_opts(self, opts=None, **kw):
+        """a gusto_fleet_opts from None (the library's defaults on the handle's clearance: a null pointer unless keywords are
+        given), a FleetOpts, or keywords of its fields (dt_clock, margin, n_delays, delay_stride, clock_cap, components, prune)"""
+        if opts is None and not kw:
+            return None
+        if opts is None:
+            o = default_fleet_opts(self.model)
+            mp = getattr(self, "_model_params", None)
+            if mp is not None:
+                o.margin = mp.clearance
+        else:   # (a caller's FleetOpts is not written to)
+            o = FleetOpts(*(getattr(opts, f) for f, _ in FleetOpts._fields_))
+        for k, v in kw.items():
+            if k not in [f for f, _ in FleetOpts._fields_]:
+                raise TypeError(f"unknown fleet option {k!r}")
+            setattr(o, k, float(v) if k in ("dt_clock", "margin") else int(v))
+        return o
+
+    def fleet_schedule(self, R, order=None, eligible=None, opts=None, **kw):
+        """gusto_fleet_schedule + gusto_get_fleet, after interpolate(): the B problems are F = B / R fleets of R robots, problem
+        f R + i robot i of fleet f.  Robots are placed in the order order [F, R] (None: index order); a robot departs by the
+        smallest candidate delay that keeps it `margin` away from every robot placed before it.  eligible [B]: which robots have
+        a plan (None: converged and successful).  Returns fleet_info()."""
+        o = self.fleet_opts(opts, **kw)
+        od = None if order is None else _arr(order, np.int32).reshape(self.B)
+        el = None if eligible is None else _arr(np.asarray(eligible).astype(bool), np.int32).reshape(self.B)
+        self._chk(self.L.gusto_fleet_schedule(self.h, int(R), None if od is None else od.ctypes.data,
+                                              None if el is None else el.ctypes.data, None if o is None else C.byref(o)), "fleet_schedule")
+        return self.fleet_info()
+
+    def fleet_separation(self, R, delay_steps=None, opts=None, **kw):
+        """gusto_fleet_separation + gusto_get_fleet: the pairwise separation report for the last schedule's shifts (None) or for
+        delay_steps [B] in clock steps, -1 = the robot never departs.  Returns fleet_info()."""
+        o = self.fleet_opts(opts, **kw)
+        ds = None if delay_steps is None else _arr(delay_steps, np.int32).reshape(self.B)
+        self._chk(self.L.gusto_fleet_separation(self.h, int(R), None if ds is None else ds.ctypes.data,
+                                                None if o is None else C.byref(o)), "fleet_separation")
+        return self.fleet_info()
+
+    def fleet_info(self):
+        """gusto_get_fleet: a dict over the B robots of status (FLEET_NO_PLAN / SCHEDULED / BLOCKED), delay_steps, delay, blocker,
+        min_sep, partner, step; over pairs [F, R, R] of pair_min_sep, pair_step; over the F fleets of n_scheduled, n_blocked,
+        n_conflicts, fleet_min_sep, makespan_steps; stage_ms [3] (track, schedule, separation) and the scalars F, R"""
+        F, R = C.c_int(), C.c_int()
+        self._chk(self.L.gusto_get_fleet(self.h, None, C.byref(F), C.byref(R)), "get_fleet")
+        out = {k: np.zeros(shape(F.value, R.value), dtype=t) for k, t, shape in FLEET_FIELDS}
+        rep = FleetReport(**{k: v.ctypes.data for k, v in out.items()})
+        self._chk(self.L.gusto_get_fleet(self.h, C.byref(rep), None, None), "get_fleet")
+        out["F"], out["R"] = F.value, R.value
+        return out
+
+    def fleet_tracks(self):
+        """gusto_get_fleet_tracks: (J [B], Q [B, J_max, WS]) of the last fleet call; rows behind J[b] are zeros"""
+        jm = C.c_int()
+        self._chk(self.L.gusto_get_fleet_tracks(self.h, None, None, C.byref(jm)), "get_fleet_tracks")
+        J, Q = np.zeros(self.B, dtype=np.int32), np.zeros((self.B, jm.value, WS_DIM[self.model]))
+        self._chk(self.L.gusto_get_fleet_tracks(self.h, J.ctypes.data, Q.ctypes.data, None), "get_fleet_tracks")
+        return J, Q
+
+    def last_fleet_ms(self):
+        """gusto_last_fleet_ms: GPU time of the last fleet_schedule / fleet_separation (copies and kernels)"""
+        return self._last_ms("last_fleet_ms")
 
     def set_problems_trajlib(self, lib, x_init, goal_lo, goal_hi, tf, K=1, tag=None, boxes=None, spheres=None):
         """gusto_set_problems_trajlib: Bq queries seeded from their K nearest entries of the TrajLib `lib` become the B = Bq K problems

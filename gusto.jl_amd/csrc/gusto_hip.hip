@@ -295,6 +295,7 @@ int gusto_problems_loaded(gusto_handle h, bool straight) {
     h->select.invalidate(); h->trajlib.invalidate(); h->replan.invalidate(); h->tighten.invalidate(); h->roadmap.invalidate();
     h->tfsearch.invalidate();   // (tfsearch.hip sets it again behind its own call)
     h->legs.invalidate();       // (legs.hip likewise)
+    h->fleet.invalidate();
     h->n_active = -1;   // (gusto_set_active belongs to the problems it was set for)
     return GUSTO_OK;
 }

@@ -274,6 +274,23 @@ struct __attribute__((visibility("hidden"))) LegsState {
     void invalidate() { have = false; }
 };
 
+// Fleet coordination (fleet.hip), F fleets x R robots of the last call: Q [B][Jmax][WS] the tracks on the fleet clock, Box [B][2 WS]
+// their bounding boxes (lo, hi), J [B] the sample counts and Fin [B] whether a track is finite; Ord, Elig, Sig [B] the copies of a
+// caller's order, eligibility and shifts; Sch the last schedule's rows ([3][B] status, sigma, blocker); the report I ([5][B] status,
+// delay_steps, blocker, partner, step; [F][R][R] pair_step; [4][F] n_scheduled, n_blocked, n_conflicts, makespan_steps) and D ([2][B]
+// delay, min_sep; [F][R][R] pair_min_sep; [F] fleet_min_sep).  have: a report belongs to these problems; have_sched: so does Sch,
+// made on the clock step sched_dt.  stage_ms: track, schedule, separation
+struct __attribute__((visibility("hidden"))) FleetState {
+    DevBuf<double> Q, Box, D;
+    DevBuf<int> J, Fin, Ord, Elig, Sig, Sch, I;
+    int F = 0, R = 0, Jmax = 0, ws = 0;
+    double sched_dt = 0.0;
+    bool have = false, have_sched = false;
+    DevEvent t0, t1, t2, t3, t4;
+    double last_ms = 0.0, stage_ms[3] = {0.0, 0.0, 0.0};
+    void invalidate() { have = false; have_sched = false; }
+};
+
 // The library itself: `count` of `cap` entries on `device`, entry e at row e of xi, c [cap][n], tf, tag [cap], X [cap][N][n], U
 // [cap][N][m].  The features are the F positive-weight terms of the distance, in its order of summation: term f has the weight
 // w[f] and reads entry fmap[f] & 15 of x_init (fmap[f] >> 4 == 0), of the goal centre (1) or tf (2).  Feat is feature-major,
@@ -347,6 +364,7 @@ struct gusto_handle_s {
     RoadmapState roadmap;
     TfsearchState tfsearch;
     LegsState legs;
+    FleetState fleet;
     unsigned long long solves = 0;   // gusto_solve / gusto_solve_async calls that enqueued a launch (gusto_tfsearch_update, gusto_legs_advance ask for one)
     std::string err;
 

@@ -1054,6 +1054,97 @@ def solve_SCP_timeline_batch(TOSs, TOPs, mode="auto", verify=False, solver="hip"
     return qb.out
 
 
+def fleet_park_spheres(start, goal, R, radius, margin, comp_off, n_base=None):
+    """The parking keep-outs of fleets of R consecutive robots: robot b plans around one sphere at the start and one at the goal
+    centre of every other robot of its fleet.  start, goal [B, WS]; comp_off [n_comp, >= WS] the robot's component offsets;
+    n_base [B] the components robot b's base set has already (None: none).
+
+    Sphere radius: radius + margin + 2 omax, omax = max_c |comp_off[c] - comp_off[0]| over the first WS entries: clearing the
+    sphere with component 0 keeps every component pair `margin` apart from a robot parked there.  A sphere that would contain
+    the robot's own start or goal is left out and listed.  More than 64 components for one robot: ValueError.
+
+    Returns (spheres, skipped): spheres[b] is [k_b, 4] rows (x, y, z, r), skipped a list of (robot, other, "start" / "goal")."""
+    start, goal = np.asarray(start, float), np.asarray(goal, float)
+    B, ws = start.shape
+    if R < 1 or B % R:
+        raise ValueError("fleet_park_spheres!: R must divide the number of robots")
+    off = np.asarray(comp_off, float)[:, :ws]
+    omax = float(np.max(np.sqrt(np.sum((off - off[0]) ** 2, axis=1))))
+    rad = radius + margin + 2 * omax
+    spheres, skipped = [], []
+    for b in range(B):
+        rows = []
+        for o in range(b - b % R, b - b % R + R):
+            for what, c in (("start", start[o]), ("goal", goal[o])):
+                if o == b:
+                    continue
+                if min(np.linalg.norm(start[b] - c), np.linalg.norm(goal[b] - c)) < rad:
+                    skipped.append((b, o, what))
+                    continue
+                rows.append(list(c) + [0.0] * (3 - ws) + [rad])
+        if (0 if n_base is None else int(n_base[b])) + len(rows) > 64:
+            raise ValueError(f"fleet_park_spheres!: robot {b} would have more than 64 keep-out components")
+        spheres.append(np.asarray(rows, float).reshape(-1, 4))
+    return spheres, skipped
+
+
+def solve_SCP_fleet_batch(TOSs, TOPs, R, margin=None, order=None, park_keepouts=True, fleet_opts=None, solver="hip", max_iter=30,
+                          force=False, device=0):
+    """Every TOP is one ROBOT, R consecutive TOPs one fleet that shares a workspace: solve, interpolate, gusto_fleet_schedule,
+    gusto_fleet_separation.  Prioritised planning on fixed paths: every robot keeps its solved path, a robot of lower priority
+    (order [F, R], None: index order) departs later, by the smallest candidate delay that keeps it `margin` (None: the model's
+    clearance) away from every robot placed before it.  Robots hold at their start before they depart and stay parked at their
+    goal: whether they can is the caller's business.  All TOPs share model and N; each may bring its own environment.
+
+    park_keepouts: every robot plans around a sphere at the start and at the goal centre of every other robot of its fleet
+    (fleet_park_spheres), on top of its own environment, so that a parked robot is never flown through.
+
+    fleet_opts: a dict of gusto_fleet_opts fields (dt_clock, n_delays, delay_stride, clock_cap, components).
+
+    Every TOS is filled as by solve_SCP_batch, plus TOS.fleet_status (_capi.FLEET_*), TOS.delay and the time grid TOS.traj.t =
+    delay + k dt (export.write(..., t=) takes it).  Returns the fleet report of BatchSolver.fleet_info() as a dict, with
+    `park_skipped` (fleet_park_spheres), `robots`, one dict per robot (status, delay, blocker, min_sep, SCPS), and `dense`, the
+    (nfull [B], positions [B, nfull_max, WS]) of gusto_interpolate that the stage read."""
+    who = "solve_SCP_fleet_batch"
+    qb = _QueryBatch(who, TOSs, TOPs, early=None if R >= 1 and len(TOPs) % max(R, 1) == 0 else "R must divide the number of problems")
+    Q, N, mid = qb.Q, qb.N, qb.model.model_id
+    _, mp = _capi.default_params(mid)
+    margin = float(mp.clearance if margin is None else margin)
+    ws = _capi.WS_DIM[mid]
+    skipped = []
+    boxes = [t.PD.env.boxes for t in TOPs]
+    spheres = [np.asarray(t.PD.env.spheres, float).reshape(-1, 4) for t in TOPs]
+    if park_keepouts:
+        centre = np.where(np.isfinite(qb.lo) & np.isfinite(qb.hi), 0.5 * (qb.lo + qb.hi), 0.0)
+        off = np.array([list(mp.comp_off[c]) for c in range(max(1, mp.n_robot_comp))])
+        park, skipped = fleet_park_spheres(qb.x0[:, :ws], centre[:, :ws], R, mp.radius, margin, off,
+                                           [len(b) + len(s) for b, s in zip(boxes, spheres)])
+        spheres = [np.concatenate([s, p], axis=0) for s, p in zip(spheres, park)]
+    bs = qb.solver(Q, max_iter, force, device)
+    try:
+        if park_keepouts or not qb.same_env:
+            bs.set_env_batch(boxes, spheres)
+        bs.set_problems(qb.x0, qb.lo, qb.hi, qb.tf)
+        bs.solve(max_iter, force)
+        snap = _fetch(bs)
+        per = bs.last_solve_ms() * 1e-3 / Q
+        nfull, Xfull, _ = bs.interpolate()
+        kw = dict(fleet_opts or {}, margin=margin)
+        bs.fleet_schedule(R, order=order, **kw)
+        rep = bs.fleet_separation(R, **kw)
+        for q in range(Q):
+            qb.take(q, snap, q, per, status=int(rep["status"][q]), delay=float(rep["delay"][q]), blocker=int(rep["blocker"][q]),
+                    min_sep=float(rep["min_sep"][q]))
+            TOS = TOSs[q]
+            TOS.fleet_status, TOS.delay = int(rep["status"][q]), float(rep["delay"][q])
+            TOS.traj.t = TOS.delay + np.arange(N) * (qb.tf[q] / (N - 1))
+    finally:
+        bs.close()
+    rep["park_skipped"], rep["robots"] = skipped, qb.out
+    rep["dense"] = (nfull, Xfull[:, :, :ws].copy())   # the dense positions the stage read
+    return rep
+
+
 class TrajLib(_capi.TrajLib):
     """A device-resident library of solved trajectories (gusto_trajlib): TrajLib(model_id, N, cap, device=0, w_init=None,
     w_goal=None, w_tf=None).  add_from(solver, mask=None, tag=None) appends the converged and successful (or the masked) problems

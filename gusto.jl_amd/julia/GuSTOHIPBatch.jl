@@ -1532,3 +1532,134 @@ function solve_SCP_timeline_batch!(TOSs::Vector, TOPs::Vector; mode=:auto, max_i
   [(status = Int(info.status[q]), failed_leg = Int(info.failed_leg[q]), n_done = Int(info.n_done[q]), J_total = info.J_total[q],
     T = T[1:nl[q], q], t = info.t[1:nl[q] * (N - 1) + 1, q], gap = info.gap[1:nl[q], q], arrive = info.arrive[1:nl[q], q]) for q in 1:Q]
 end
+
+# ---- fleet coordination (gusto_fleet_schedule / gusto_fleet_separation, csrc/fleet.hip) ---------------------------------------
+# R consecutive problems of the handle are the robots of one fleet; every robot keeps its solved path and departs by the smallest
+# candidate delay that keeps it `margin` away from every robot placed before it (include/gusto_hip.h states the definitions, the
+# reference has no counterpart).  The call sequences are those of gusto.jl_amd/_capi.py and host.py.  This wrapper has not been run.
+const GUSTO_FLEET_NO_PLAN = 0
+const GUSTO_FLEET_SCHEDULED = 1
+const GUSTO_FLEET_BLOCKED = 2
+struct GustoFleetOpts      # gusto_fleet_opts
+  dt_clock::Cdouble; margin::Cdouble
+  n_delays::Cint; delay_stride::Cint; clock_cap::Cint; components::Cint; prune::Cint
+end
+mutable struct GustoFleetReport      # gusto_fleet_report
+  status::Ptr{Cint}; delay_steps::Ptr{Cint}
+  delay::Ptr{Cdouble}
+  blocker::Ptr{Cint}
+  min_sep::Ptr{Cdouble}
+  partner::Ptr{Cint}; step::Ptr{Cint}
+  pair_min_sep::Ptr{Cdouble}
+  pair_step::Ptr{Cint}
+  n_scheduled::Ptr{Cint}; n_blocked::Ptr{Cint}; n_conflicts::Ptr{Cint}
+  fleet_min_sep::Ptr{Cdouble}
+  makespan_steps::Ptr{Cint}
+  stage_ms::Ptr{Cdouble}
+end
+
+# the library's defaults for the model, with the keywords over them
+function gusto_fleet_opts(model_id::Integer; margin=nothing, dt_clock=nothing, n_delays=nothing, delay_stride=nothing, clock_cap=nothing,
+                          components=nothing)
+  d = Ref(GustoFleetOpts(0., 0., 0, 0, 0, 0, 0))
+  gusto_check(ccall((:gusto_default_fleet_opts, libgusto_hip), Cint, (Cint, Ref{GustoFleetOpts}), model_id, d), C_NULL, "default_fleet_opts")
+  pick(v, dflt) = v === nothing ? dflt : v
+  GustoFleetOpts(pick(dt_clock, d[].dt_clock), pick(margin, d[].margin), pick(n_delays, d[].n_delays), pick(delay_stride, d[].delay_stride),
+                 pick(clock_cap, d[].clock_cap), pick(components, d[].components), d[].prune)
+end
+
+# The report of the last fleet call on h, B = F R robots: per robot status, delay_steps, delay, blocker, min_sep, partner, step; per
+# pair [R, R, F] pair_min_sep, pair_step; per fleet n_scheduled, n_blocked, n_conflicts, fleet_min_sep, makespan_steps; stage_ms
+function fleet_info(h::Ptr{Cvoid})
+  Fr, Rr = Ref{Cint}(0), Ref{Cint}(0)
+  gusto_check(ccall((:gusto_get_fleet, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Cint}, Ref{Cint}), h, C_NULL, Fr, Rr), h, "get_fleet")
+  F, R = Int(Fr[]), Int(Rr[]); B = F * R
+  status, steps, blocker, partner, step = zeros(Cint, B), zeros(Cint, B), zeros(Cint, B), zeros(Cint, B), zeros(Cint, B)
+  delay, min_sep, pair_sep, pair_step = zeros(B), zeros(B), zeros(R, R, F), zeros(Cint, R, R, F)
+  ns, nb, nc, span, fsep, ms = zeros(Cint, F), zeros(Cint, F), zeros(Cint, F), zeros(Cint, F), zeros(F), zeros(3)
+  GC.@preserve status steps blocker partner step delay min_sep pair_sep pair_step ns nb nc span fsep ms begin
+    rep = GustoFleetReport(pointer(status), pointer(steps), pointer(delay), pointer(blocker), pointer(min_sep), pointer(partner),
+                           pointer(step), pointer(pair_sep), pointer(pair_step), pointer(ns), pointer(nb), pointer(nc), pointer(fsep),
+                           pointer(span), pointer(ms))
+    gusto_check(ccall((:gusto_get_fleet, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoFleetReport}, Ptr{Cint}, Ptr{Cint}), h, rep, C_NULL, C_NULL),
+                h, "get_fleet")
+  end
+  total = Ref{Cdouble}(0.)
+  gusto_check(ccall((:gusto_last_fleet_ms, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{Cdouble}), h, total), h, "last_fleet_ms")
+  (status = status, delay_steps = steps, delay = delay, blocker = blocker, min_sep = min_sep, partner = partner, step = step,
+   pair_min_sep = pair_sep, pair_step = pair_step, n_scheduled = ns, n_blocked = nb, n_conflicts = nc, fleet_min_sep = fsep,
+   makespan_steps = span, stage_ms = ms, ms = total[], F = F, R = R)
+end
+
+# After gusto_interpolate: the departure schedule of fleets of R robots.  order: nothing (index order) or [R, F], 0-based robot
+# indices in placement order; eligible: nothing (converged and successful) or a Bool / integer vector [B].  Returns fleet_info.
+function fleet_schedule!(h::Ptr{Cvoid}, R::Integer, opts::GustoFleetOpts; order=nothing, eligible=nothing)
+  od = order === nothing ? C_NULL : Cint.(vec(order))
+  el = eligible === nothing ? C_NULL : Cint.(eligible .!= 0)
+  gusto_check(ccall((:gusto_fleet_schedule, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Cint}, Ref{GustoFleetOpts}), h, R, od, el, opts),
+              h, "fleet_schedule")
+  fleet_info(h)
+end
+
+# The pairwise separation report for the last schedule's shifts (delay_steps = nothing) or for delay_steps [B] in clock steps,
+# -1 = the robot never departs.  Returns fleet_info.
+function fleet_separation!(h::Ptr{Cvoid}, R::Integer, opts::GustoFleetOpts; delay_steps=nothing)
+  ds = delay_steps === nothing ? C_NULL : Cint.(delay_steps)
+  gusto_check(ccall((:gusto_fleet_separation, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}, Ref{GustoFleetOpts}), h, R, ds, opts),
+              h, "fleet_separation")
+  fleet_info(h)
+end
+
+# The clock tracks of the last fleet call: (J [B], Q [WS, J_max, B])
+function fleet_tracks(h::Ptr{Cvoid}, B::Integer, ws::Integer)
+  jm = Ref{Cint}(0)
+  gusto_check(ccall((:gusto_get_fleet_tracks, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cdouble}, Ref{Cint}), h, C_NULL, C_NULL, jm), h, "get_fleet_tracks")
+  J, Q = zeros(Cint, B), zeros(ws, Int(jm[]), B)
+  gusto_check(ccall((:gusto_get_fleet_tracks, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}), h, J, Q, C_NULL), h, "get_fleet_tracks")
+  (J, Q)
+end
+
+# Every TOP is one ROBOT, R consecutive TOPs one fleet: solve, interpolate, fleet_schedule!, fleet_separation!.  All TOPs share
+# model, N and the environment; whether a robot can hold at its start and park at its goal is the caller's business.  The parking
+# keep-outs of the Python driver (host.fleet_park_spheres) are not built here: pass environments that hold them.  Returns
+# fleet_info; TOSs[q].traj is robot q's trajectory, its departure delay is the report's delay[q].
+function solve_SCP_fleet_batch!(TOSs::Vector, TOPs::Vector, R::Integer; margin=nothing, order=nothing, fleet_opts=(;), max_iter=30,
+                                force=false, device=0)
+  TOP0 = TOPs[1]; model, N = TOP0.PD.model, TOP0.N
+  n, m, Q = model.x_dim, model.u_dim, length(TOPs)
+  (R >= 1 && Q % R == 0) || error("solve_SCP_fleet_batch!: R must divide the number of problems")
+  all(T -> typeof(T.PD.model) == typeof(model) && T.N == N && T.PD.env === TOP0.PD.env, TOPs) ||
+    error("solve_SCP_fleet_batch!: all problems must share the model type, N and the environment")
+  alg0 = SCPParam_GuSTO(model)
+  sp = GustoScpParams(alg0.Δ0, alg0.ω0, alg0.ω_max, alg0.ε, alg0.ρ0, alg0.ρ1, alg0.β_succ, alg0.β_fail, alg0.γ_fail,
+                      SCPParam(model, TOP0.fixed_final_time).convergence_threshold)
+  href = Ref{Ptr{Cvoid}}(C_NULL)
+  gusto_check(ccall((:gusto_create, libgusto_hip), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Cint),
+                    href, gusto_model_id(model), N, Q, gusto_hist_cap(max_iter), device), href[], "create")
+  h = href[]
+  gusto_check(ccall((:gusto_set_params, libgusto_hip), Cint, (Ptr{Cvoid}, Ref{GustoScpParams}, Ref{GustoModelParams}),
+                    h, sp, gusto_model_params(TOP0.PD.robot, model)), h, "set_params")
+  boxes, spheres = gusto_env_tables(TOP0.PD.env)
+  gusto_check(ccall((:gusto_set_env, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+                    h, length(boxes) ÷ 6, boxes, length(spheres) ÷ 4, spheres), h, "set_env")
+  x0 = hcat((Float64.(T.PD.x_init) for T in TOPs)...)
+  bounds = [gusto_goal_bounds(T.PD.goal_set, n, T.tf_guess) for T in TOPs]
+  lo, hi = hcat((b[1] for b in bounds)...), hcat((b[2] for b in bounds)...)
+  tf = Float64[T.tf_guess for T in TOPs]
+  gusto_check(ccall((:gusto_set_problems, libgusto_hip), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    h, Q, x0, lo, hi, tf, C_NULL, C_NULL), h, "set_problems")
+  gusto_check(ccall((:gusto_solve, libgusto_hip), Cint, (Ptr{Cvoid}, Cint, Cint), h, max_iter, force), h, "solve")
+  X, U = zeros(n, N, Q), zeros(m, N, Q)
+  gusto_check(ccall((:gusto_get_traj, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), h, X, U), h, "get_traj")
+  gusto_check(ccall((:gusto_interpolate, libgusto_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}, Ptr{Cint}),
+                    h, C_NULL, C_NULL, C_NULL, C_NULL), h, "interpolate")
+  o = gusto_fleet_opts(gusto_model_id(model); margin=margin, fleet_opts...)
+  fleet_schedule!(h, R, o; order=order)
+  info = fleet_separation!(h, R, o)
+  ccall((:gusto_destroy, libgusto_hip), Cint, (Ptr{Cvoid},), h)
+  for q in 1:Q
+    TOSs[q].traj = Trajectory(X[:, :, q], U[:, :, q], tf[q])
+  end
+  info
+end

@@ -1103,6 +1103,98 @@ int gusto_get_legs_dev(gusto_handle h, const double** X_dev, const double** U_de
 /* GPU time of the last begin or advance (copies and kernels), from HIP events on the handle's stream */
 int gusto_last_legs_ms(gusto_handle h, double* ms);
 
+/* Fleet coordination (csrc/fleet.hip): robot-to-robot separation and departure delays.  Every other stage treats a problem as
+ * if it were alone in the workspace; this one holds the robots of a fleet against each other.  It is prioritised planning on
+ * fixed paths: every robot keeps its solved path, a robot of lower priority departs later, by the smallest delay out of a set
+ * of candidates that keeps it `margin` away from every robot ranked above it, for all time.  Robots hold at their start before
+ * they depart and stay parked at their goal after they arrive.  No counterpart in the reference (it plans one robot, once);
+ * the definitions are therefore stated here.
+ *     gusto_solve; gusto_interpolate; gusto_fleet_schedule; gusto_get_fleet.
+ * WHETHER A ROBOT CAN HOLD AT ITS START OR PARK AT ITS GOAL IS THE CALLER'S BUSINESS: the stage does not look at velocities.  (The
+ * table and ISS problem generators start and end at rest.)
+ * Layout: that of gusto_set_problems_multistart with K = R.  A fleet is R consecutive problems of the handle, problem f R + i is
+ *   robot i of fleet f; 1 <= R <= GUSTO_MAX_STARTS and R divides B, F = B / R.  GuSTO handles of FreeflyerSE2, AstrobeeSE3 and
+ *   AstrobeeSE3Manifold; DubinsCar cannot hold at its start and has no robot geometry: GUSTO_ERR_ARG.
+ * Inputs: the dense trajectories of the last gusto_interpolate since gusto_set_problems* (without them GUSTO_ERR_STATE): nfull[b],
+ *   the first WS entries P_s of Xfull[b][s] (WS = 2 in the plane, 3 in space), and tf[b].  The stage writes none of the handle's
+ *   trajectories, status, histories, keep-out tables or dense buffers.  gusto_set_active is not consulted: `eligible` says which
+ *   robots have a plan.  A problem gusto_interpolate left out (nfull[b] < 2) has a track of NaN.
+ * Track on the fleet clock: the clock step is h = dt_clock.  Robot b has J_b = (int)ceil(tf_b / h) + 1 clock samples; a J_b
+ *   above clock_cap (or a tf_b that is not positive and finite) is GUSTO_ERR_ARG for the whole call, the text names the first
+ *   such problem, nothing is clamped.  With h_b = tf_b / (double)(nfull_b - 1), for j < J_b - 1:
+ *       tau = (double)j * h;  s = tau / h_b;  i = min((int)floor(s), nfull_b - 2);  w = s - (double)i;
+ *       Q_b[j] = (1 - w) * P_i + w * P_{i+1}
+ *   and Q_b[J_b - 1] = P_{nfull_b - 1} exactly.  Every operation is rounded on its own (no fused multiply-add).
+ * Position: with a departure shift sigma >= 0 in clock steps, p_b(j; sigma) = Q_b[clamp(j - sigma, 0, J_b - 1)]; sigma = -1: the
+ *   robot never departs, p_b = Q_b[0] for all j.  end_b = sigma + J_b - 1, and 0 for sigma = -1: nothing moves behind it.
+ * Separation: the robot's components are spheres of `radius` at p + comp_off[c], as everywhere.  For robots a, b at step j and
+ *   the component pair (ca, cb), ca outer and cb inner: delta_x = (pa_x - pb_x) + (comp_off[ca][x] - comp_off[cb][x]), x < WS;
+ *   d2 = sum_x delta_x^2 in coordinate order, every operation rounded on its own.  D2(a, b, j): the smallest d2 over the component
+ *   pairs, fmin from +inf (a NaN never wins); components = 0: pair (0, 0) only.  thr = 2 radius + margin, thr2 = thr * thr.  A
+ *   conflict is D2 < thr2: no square root enters a decision.  The reported separation is sqrt(D2) - 2 radius.
+ * Schedule: robots are placed in the order order[f][0 .. R - 1], a permutation of 0 .. R - 1 per fleet (NULL: index order).  A
+ *   robot that is not eligible gets GUSTO_FLEET_NO_PLAN and is placed with sigma = -1: it still blocks a path through its
+ *   start.  Eligible: eligible[b] != 0, or with NULL converged and successful from the status words; a robot whose track has a
+ *   non-finite entry is never eligible.  An eligible robot i has the candidates sigma_d = d * delay_stride, d = 0 .. n_delays - 1.
+ *   Candidate d is feasible when for every robot k placed before i and every j = 0 .. max(end_i, end_k): D2(i, k, j) >= thr2 at
+ *   p_i(j; sigma_d), p_k(j; sigma_k).  The robot takes the smallest feasible candidate: GUSTO_FLEET_SCHEDULED; with none it is
+ *   GUSTO_FLEET_BLOCKED and placed with sigma = -1.  blocker: the first robot in placement order that refutes candidate 0 (its
+ *   index in the fleet), -1 when candidate 0 is feasible or the robot is NO_PLAN.  delay = (double)sigma * h, 0 for sigma = -1.
+ * Separation report, for given shifts -- gusto_fleet_schedule reports it for the shifts it chose; gusto_fleet_separation for the
+ *   last schedule's (delay_steps = NULL; dt_clock must be the schedule's) or for a caller's delay_steps [B], in which -1 is allowed:
+ *   then status is SCHEDULED where delay_steps >= 0 and NO_PLAN elsewhere, blocker -1, and the last schedule's stay what NULL means.
+ *   Per pair a != b: the smallest D2 over j = 0 .. max(end_a, end_b) as a separation, and the first step where it occurs;
+ *   [F][R][R], symmetric, the diagonal (and a pair without a finite D2) +inf / -1.  Per robot: the smallest entry of its row of the
+ *   pair table, the partner (the lowest index on a tie, -1: none below +inf) and that pair's step.  Per fleet: n_conflicts, the
+ *   pairs a < b with min D2 < thr2; the smallest separation; makespan_steps, the largest end over SCHEDULED robots (0: none);
+ *   n_scheduled and n_blocked.
+ * Runs on the handle's stream, after any pending gusto_solve_async; timed with events of its own.  No atomics, nothing crosses a
+ *   fleet: a fleet's outputs are the same bit for bit whatever else is in the batch and wherever the fleet sits in it.
+ * GUSTO_ERR_ARG, nothing launched, the handle and the stage's state left as they were, in this order: a TrajOpt handle; DubinsCar;
+ *   R outside 1 .. GUSTO_MAX_STARTS or not dividing B; bad options; `order` not a permutation (the text names the fleet); a
+ *   delay_steps entry outside -1 .. GUSTO_FLEET_MAX_SHIFT (it names the problem); a J_b above clock_cap (likewise).
+ * GUSTO_ERR_STATE: no problems; no dense trajectories; gusto_fleet_separation with delay_steps = NULL before any schedule; the
+ *   getters before any call.  gusto_set_problems* ends the stage's state. */
+#define GUSTO_FLEET_NO_PLAN 0
+#define GUSTO_FLEET_SCHEDULED 1
+#define GUSTO_FLEET_BLOCKED 2
+#define GUSTO_FLEET_MAX_SHIFT (1 << 24)
+typedef struct {
+    double dt_clock;       /* clock step, > 0 and finite; default 0.1, the default dt_min of gusto_verify_opts */
+    double margin;         /* finite, >= 0; default the model's clearance, the distance the solver keeps from keep-out components */
+    int n_delays;          /* 1 .. 64; default 64 */
+    int delay_stride;      /* clock steps between candidates, 1 .. GUSTO_FLEET_MAX_SHIFT / 64; default 10 */
+    int clock_cap;         /* largest J_b allowed, 2 .. GUSTO_FLEET_MAX_SHIFT; default 8192 */
+    int components;        /* 0: component pair (0, 0) only; 1 (default): every pair */
+    int prune;             /* development: 1 (default) skips a placed robot whose track's bounding box lies further from the
+                              candidate's than thr plus the component offsets; 0 tests it.  The results are the same bit for bit */
+} gusto_fleet_opts;
+int gusto_default_fleet_opts(int model_id, gusto_fleet_opts* o);
+int gusto_fleet_schedule(gusto_handle h, int R, const int* order /* [B] HOST: order[f R + p] = the robot placed p-th, or NULL */,
+                         const int* eligible /* [B] HOST, or NULL = converged && successful */, const gusto_fleet_opts* o /* NULL: defaults */);
+int gusto_fleet_separation(gusto_handle h, int R, const int* delay_steps /* [B] HOST, or NULL = the last schedule's */,
+                           const gusto_fleet_opts* o);
+typedef struct {
+    int *status, *delay_steps;                 /* [B]: GUSTO_FLEET_*, sigma */
+    double *delay;                             /* [B] */
+    int *blocker;                              /* [B] */
+    double *min_sep;                           /* [B] */
+    int *partner, *step;                       /* [B] */
+    double *pair_min_sep;                      /* [F][R][R] */
+    int *pair_step;                            /* [F][R][R] */
+    int *n_scheduled, *n_blocked, *n_conflicts;   /* [F] */
+    double *fleet_min_sep;                     /* [F] */
+    int *makespan_steps;                       /* [F] */
+    double *stage_ms;                          /* [3]: GPU time of the track, schedule and separation kernels of the last call (0: not run) */
+} gusto_fleet_report;                          /* caller-owned, any pointer may be NULL */
+/* The report of the last gusto_fleet_schedule / gusto_fleet_separation; *F and *R its shape (out, F, R may be NULL) */
+int gusto_get_fleet(gusto_handle h, gusto_fleet_report* out, int* F, int* R);
+/* The tracks of that call: J [B], Q [B][J_max][WS] (rows behind J[b] are zeros), *J_max the largest J_b.  A size query passes
+ * the arrays as NULL. */
+int gusto_get_fleet_tracks(gusto_handle h, int* J, double* Q, int* J_max);
+/* GPU time of the last gusto_fleet_schedule / gusto_fleet_separation (copies and kernels), from HIP events on the handle's stream */
+int gusto_last_fleet_ms(gusto_handle h, double* ms);
+
 /* One convex subproblem per problem (what scp_gusto.jl:82-104 builds and solves in one trip), linearised at
  * (Xp,Up)[b] with the given Delta/omega/obstacle_toggle_distance[b].  Used by the parity tests.
  * Outputs: Xn,Un [B][N][.], obj [B] (JuMP.objective_value), status [B] (GUSTO_SOLVER_*), iters [B]. */
